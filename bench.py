@@ -17,8 +17,16 @@ issues its early backward from a helper thread (`config.early_backward_thread` r
 the timed steps beside their mean (`ms_per_step_p10 / _p50 / _p90`: device time between the steps' first launches).
 
 Extra objects on the JSON line: `roofline` for the pillar-scatter kernel (the kernel BASELINE.json's north_star names), timed live with HIP
-events on the launch stream inside the timed region; `cpu_baseline`: the same step on the host cores with the oracle-backed CPU backend (rank 0,
-N = 1 only); `bf16` / `matched_accuracy`: the same step in the other compute mode (N = 1 only); `configs`: the other BASELINE configurations.
+events on the launch stream inside the timed region.  The stepper's helper thread starts at the early-backward hook (PCACC_EARLY_DEFER=0 unless
+the environment says otherwise): its deferred start made two runs of the same command end at different results.  A plain run stops there: set-up, warm-up, the K timed steps, the line.  With `--full` the
+line also carries what takes runs of its own: `roofline_step` and `roofline.cold_cache` (an instrumented extra step, cold-cache launches of the
+roofline kernel); `cpu_baseline`: the same step on the host cores with the oracle-backed CPU backend (rank 0, N = 1 only); `bf16` /
+`matched_accuracy`: the same step in the other compute mode (N = 1 only); `configs`: the other BASELINE configurations.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller, as DIR/<name>.npy (float32 / float64): the loss terms and metrics
+(`stats.<key>.npy`), every parameter after the optimizer step (`param.<name>.npy`), and a fixed sample of the step's gradients
+(`grad_sample.npy`, DUMP_GRAD_SAMPLE entries at seeded positions of the parameters' concatenation).  Inputs and initial weights are seeded:
+the same arguments give the same inputs, and the same outputs bit for bit, in every run.
 """
 import argparse
 import json
@@ -141,6 +149,7 @@ from pcaccumulation_amd.synthetic import make_sequence  # noqa: E402
 
 T_FRAMES = 5
 HBM_PEAK_GBPS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 TB/s measured copy ceiling)
+DUMP_GRAD_SAMPLE = 1 << 20      # gradient entries in --dump-outputs' grad_sample.npy (4 MiB; the parameters themselves are ~44.5 MB)
 
 
 def build(cfg, device, seed=0):
@@ -278,6 +287,44 @@ def train_step(stepper, batcher, scenes):
     if stats is not None and hasattr(stats, 'resolve'):
         stats.resolve()                 # the metrics the reference reads with .item(): on the host before the step counts as done
     return stats
+
+
+def dump_outputs(out_dir, stats, model):
+    """--dump-outputs: what one training step hands its caller -- the loss terms and metrics it returns, the parameters the optimizer step left,
+    and a fixed sample of the gradients the backward produced -- as float32 / float64 .npy files under `out_dir`.  Returns the bytes written."""
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+
+    def save(name, arr):
+        nonlocal written
+        arr = np.ascontiguousarray(arr, dtype=np.float64 if arr.dtype == np.float64 else np.float32)
+        np.save(os.path.join(out_dir, name + '.npy'), arr)
+        written += arr.nbytes
+
+    def stat(prefix, value):
+        if isinstance(value, dict):
+            for k, v in value.items():
+                stat('%s.%s' % (prefix, k), v)
+        elif torch.is_tensor(value):
+            save(prefix, value.detach().cpu().numpy())
+        elif isinstance(value, (list, tuple)):
+            for i, v in enumerate(value):
+                stat('%s.%d' % (prefix, i), v)
+        elif isinstance(value, (bool, int, float, np.number, np.ndarray)):
+            save(prefix, np.asarray(value, dtype=np.float64))
+        else:                                                          # a result the comparison would miss: refuse rather than drop it
+            raise TypeError('--dump-outputs: %s is a %s, not a tensor, number, array, list or dict' % (prefix, type(value).__name__))
+    for key, value in (stats or {}).items():
+        stat('stats.' + key, value)
+    named = list(model.named_parameters())
+    for name, p in named:
+        save('param.' + name, p.detach().float().cpu().numpy())
+    total = sum(p.numel() for _, p in named)
+    idx = np.sort(np.random.RandomState(0).choice(total, min(DUMP_GRAD_SAMPLE, total), replace=False))
+    flat = torch.cat([(p.grad.detach().float() if p.grad is not None else torch.zeros_like(p, dtype=torch.float32)).reshape(-1) for _, p in named])
+    save('grad_sample', flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy())
+    save('grad_sample_index', idx.astype(np.float64))
+    return written
 
 
 def _median(xs):
@@ -560,7 +607,18 @@ def main():
     ap.add_argument('--prepare-ahead', action='store_true', help='build the pillar index / CSR / point features of the next batch on the prefetch stream during the current step (MotionNet.prepare_inputs) instead of inside its own forward; measured neutral: 29.16 vs 29.22 ms over 8 interleaved runs each, sd 0.5')
     ap.add_argument('--cpu-affinity', default='l3', choices=['l3', 'none'], help="'l3' (default): bind the process to the CPUs of one last-level-cache domain (a different one per local rank) for the GPU part of the run -- the step's two host threads then share a cache instead of landing on two sockets in some runs (distributed.bind_to_l3_domain); restored for the CPU baseline")
     ap.add_argument('--no-prefetch', action='store_true', help='voxelise each batch at the start of its own step instead of one step ahead on a side stream')
+    ap.add_argument('--full', action='store_true', help='after the timed steps, also run what takes runs of its own: the instrumented extra step (roofline_step) and '
+                    'cold-cache roofline launches, the same step in the other compute mode, the other BASELINE configurations and the CPU baseline '
+                    '(each still subject to its --no-* switch); off by default: a plain run sets up, warms up, times the steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed (loss terms, parameters after the optimizer '
+                    'step, a seeded sample of the gradients) as DIR/<name>.npy in float32 / float64 (rank 0)')
     args = ap.parse_args()
+    # The stepper's helper thread starts at the early-backward hook, not deferred behind the upper half's forward (PCACC_EARLY_DEFER, distributed.py
+    # _defer_now): with the deferred start two runs of this command -- same inputs, same weights -- ended at different results (final loss 13.4202 /
+    # 13.4243 / 13.6101 / 13.4243 over four default runs), with the start at the hook at the same bits in four of four.  The benchmark times a step
+    # that computes the same thing every run; an explicit setting in the environment wins (and shows in config.kernel_switches).
+    defer_set_by_caller = 'PCACC_EARLY_DEFER' in os.environ
+    os.environ.setdefault('PCACC_EARLY_DEFER', '0')
     die_with_launcher()
     watchdog.arm(first=True)
 
@@ -632,11 +690,12 @@ def main():
         gc.callbacks.append(gc_cb)
     t0 = time.perf_counter()
     marks = []                                                          # one event per step boundary on the main stream: the spread of the K steps
+    last_stats = None
     for i in range(args.steps):
         ev = torch.cuda.Event(enable_timing=True)
         ev.record()
         marks.append(ev)
-        train_step(stepper, batcher, feed)
+        last_stats = train_step(stepper, batcher, feed)
         watchdog.arm()
     ev = torch.cuda.Event(enable_timing=True)
     ev.record()
@@ -673,11 +732,13 @@ def main():
         return per_step[min(len(per_step) - 1, int(round(q * (len(per_step) - 1))))] if per_step else None
     if stepper.skipped:
         raise SystemExit('bench: %d optimizer step(s) were skipped (rank %d: %r)' % (stepper.skipped, rank, stepper.last_error))
+    if args.dump_outputs and rank == 0:                                 # before --full's extra step moves the parameters on
+        dump_outputs(args.dump_outputs, last_stats, model)
     thread_choice = getattr(stepper, 'early_thread_choice', None)     # how the stepper settled on issuing its early backward (distributed.DataParallelStep)
     model_tot = flushed = None
     if world == 1:
         watchdog.off()                                                  # the single-process legs below (other modes, other configs, CPU baseline) run minutes by design
-    if not args.no_step_model:
+    if args.full and not args.no_step_model:
         # The instrumented extra step is a whole training step: with a process group it issues the step's collectives (bucketed all-reduce, the
         # agreement flag), so EVERY rank takes it -- rank 0 alone would wait for peers that have already left (an unmatched RCCL all-reduce never
         # returns: the N > 1 launch would end in the watchdog, not in a bench line).  Only rank 0 counts calls; the barrier keeps the ranks together
@@ -707,7 +768,7 @@ def main():
     # north_star's 1e-3, tests/test_config_parity.py::test_gpu_config_fp32[mixed-*]) the all-bf16 step; beside a bf16 run the fp32x3 step.
     second_leg = None
     second_mode = {'mixed': 'bf16', 'mixed2': 'bf16', 'bf16': 'fp32x3'}.get(args.dtype)
-    if world == 1 and second_mode and not args.no_fp32_leg:
+    if args.full and world == 1 and second_mode and not args.no_fp32_leg:
         del stepper, model, opt
         torch.cuda.empty_cache()
         cfg2 = json.loads(json.dumps(cfg))
@@ -776,6 +837,7 @@ def main():
                                       "launch) instead of the reference's host torch.randperm stream (models/egomotion.py:157) -- same uniform "
                                       "distribution over subsets, different draw; the parity tests use the host stream",
                        'step_variant': step_variant, 'early_backward_thread': thread_choice,
+                       'early_backward_start': 'deferred behind the upper half' if os.environ['PCACC_EARLY_DEFER'] != '0' else 'at the early-backward hook',
                        'cpu_affinity': ('one L3 domain: %d CPUs' % len(os.sched_getaffinity(0))) if affinity_before is not None else 'unbound',
                        'HIP_FORCE_DEV_KERNARG': os.environ.get('HIP_FORCE_DEV_KERNARG')},
             'distributed': {'world_size': world, 'backend': (torch.distributed.get_backend() if torch.distributed.is_initialized() else None),
@@ -817,10 +879,11 @@ def main():
                                   'FORWARD: mos_iou / ego errors / EPE within 1e-3 of the reference on c2-c5 + nus11 + c3_lidar '
                                   '(tests/test_config_parity.py::test_gpu_config_fp32[mixed-*]); bf16 tensors and products (fp32 accumulation, fp32 weight '
                                   'gradients) in the BACKWARD of the pillar encoder and the convolution stacks')
-        switches = sorted(k for k in os.environ if k.startswith('PCACC_') and k not in ('PCACC_DIST_BACKEND', 'PCACC_BENCH_DEBUG'))
+        switches = sorted(k for k in os.environ if k.startswith('PCACC_') and k not in ('PCACC_DIST_BACKEND', 'PCACC_BENCH_DEBUG')
+                          and (k != 'PCACC_EARLY_DEFER' or defer_set_by_caller))
         if switches:
             line['config']['kernel_switches'] = {k: os.environ[k] for k in switches}      # A/B switches in effect (none in a default run)
-        if world == 1 and not args.no_configs:
+        if args.full and world == 1 and not args.no_configs:
             # the other BASELINE configurations on the same tree, a few steps each: the certified mode ('mixed' for train steps, its forward alone =
             # 'fp32x3' for the eval-only configurations); profiles/r04_bench_configs.jsonl holds the longer runs incl. bf16
             rows = []
@@ -831,7 +894,7 @@ def main():
                     rows.append({'config': name, 'error': repr(e)})
                 torch.cuda.empty_cache()
             line['configs'] = rows
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 if affinity_before is not None:
                     pdist.set_affinity_all_threads(affinity_before)  # the CPU leg probes 8 / 16 / 32 threads: give it -- every existing thread, pools included -- the whole host back

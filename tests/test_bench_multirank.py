@@ -95,7 +95,7 @@ def _launch(nproc, extra, env_extra, limit=170, hang_dump='45'):
 
 
 def test_two_gloo_ranks_share_the_gpu():
-    d = _launch(2, ['--steps', '3', '--warmup', '2', '--batch', '2', '--no-cpu-baseline', '--no-fp32-leg'], {'PCACC_DIST_BACKEND': 'gloo'})
+    d = _launch(2, ['--steps', '3', '--warmup', '2', '--batch', '2', '--full', '--no-cpu-baseline', '--no-fp32-leg'], {'PCACC_DIST_BACKEND': 'gloo'})
     assert d['n_gpus'] == 2 and d['steps'] == 3 and d['scaling'] == 'weak' and d['config']['parallelism'] == 'dp2'
     assert d['value'] > 0 and 'roofline' in d
     # the instrumented extra step behind `roofline_step` is a training step with collectives: both ranks take it (rank 0 alone would sit in an all-reduce
@@ -114,7 +114,7 @@ def test_one_rccl_rank_runs_the_production_step():
     """backend nccl (= RCCL) at world size 1 under the driver's launcher: the communicator is created, every gradient bucket goes through
     ncclAllReduce (AVG) on the process group's stream, the agreement MIN-reduce runs, and -- one rank per device -- the step is the staged
     two-stream step of N = 1.  The collectives of one rank move no data over xGMI; what this pins is that the production code path executes."""
-    d = _launch(1, ['--steps', '4', '--warmup', '7', '--batch', '2', '--no-cpu-baseline', '--no-fp32-leg', '--no-configs'],
+    d = _launch(1, ['--steps', '4', '--warmup', '7', '--batch', '2', '--full', '--no-cpu-baseline', '--no-fp32-leg', '--no-configs'],
                 {'PCACC_FORCE_PROCESS_GROUP': '1'})
     assert d['distributed']['backend'] == 'nccl' and d['distributed']['world_size'] == 1 and d['n_gpus'] == 1
     assert d['distributed']['collectives_per_step'] >= 2, d['distributed']                      # gradient buckets + the agreement reduce
@@ -143,6 +143,33 @@ def test_single_rank_line_keeps_the_contract():
     r = d['roofline']
     assert r['bound'] == 'hbm' and r['peak'] == 8000.0 and r['unit'] == 'GB/s' and 0.05 < r['frac'] < 1.0 and abs(r['frac'] - r['achieved'] / r['peak']) < 1e-9
     assert d['config']['step_variant'].startswith('staged') and 'cpu_affinity' in d['config'] and 'early_backward_thread' in d['config']
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` without `--full`: none of the extra legs (instrumented step, other mode, other
+    configurations, CPU baseline) runs, and DIR holds the last timed step's loss terms, parameters and gradient sample as float32 / float64 arrays
+    within 64 MB."""
+    import numpy as np
+    out_dir = str(tmp_path / 'outputs')
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '2', '--batch', '2', '--dump-outputs', out_dir]
+    rc, out, err = run_tree(cmd, dict(os.environ, PCACC_HANG_DUMP='60'), 240)
+    assert rc == 0, 'rc %r\n%s' % (rc, err[-4000:])
+    lines = [l for l in out.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, out[-2000:]
+    d = json.loads(lines[0])
+    assert d['steps'] == 3 and d['warmup'] == 2 and d['ms_per_step'] > 0 and d['dtype'] == 'mixed'
+    for k in ('roofline_step', 'bf16', 'matched_accuracy', 'configs', 'cpu_baseline'):
+        assert k not in d, k
+    assert d['roofline']['cold_cache'] is None
+    files = sorted(os.listdir(out_dir))
+    assert 'stats.loss.npy' in files and 'grad_sample.npy' in files and sum(f.startswith('param.') for f in files) > 100, files
+    total = 0
+    for f in files:
+        a = np.load(os.path.join(out_dir, f))
+        assert a.dtype in (np.float32, np.float64), (f, a.dtype)
+        assert np.isfinite(a).all(), f
+        total += os.path.getsize(os.path.join(out_dir, f))
+    assert total <= 64 * 2 ** 20, total
 
 
 def test_bench_starts_its_own_ranks():

@@ -224,3 +224,37 @@ def test_bench_self_launch_decides_without_touching_a_gpu(monkeypatch):
     monkeypatch.setenv('TORCHELASTIC_RUN_ID', 'x')
     assert bench.self_launch(['--gpus=8']) is None
     assert bench._descendants(os.getpid()) == [] or all(isinstance(p, int) for p in bench._descendants(os.getpid()))
+
+
+def test_bench_dump_outputs_writes_what_the_step_returned(tmp_path):
+    """bench.dump_outputs (`--dump-outputs DIR`): every loss term and metric of the step's result dictionary (nested dictionaries flattened, Python
+    numbers included, lists and tuples by index; any other type raises), every parameter and a seeded gradient sample, as float32 / float64 .npy files; two calls write the same sample."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_under_test', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Linear(7, 5), torch.nn.Linear(5, 3, bias=False))
+    loss = net(torch.randn(4, 7)).square().sum()
+    loss.backward()
+    stats = {'loss': loss, 'rot_error': 0.25, 'metric': {'union': 3, 'iou': torch.tensor(0.5, dtype=torch.float64)}, 'pair': (1.5, torch.ones(2))}
+    got = {}
+    for run in ('a', 'b'):
+        d = str(tmp_path / run)
+        n = bench.dump_outputs(d, stats, net)
+        got[run] = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+        assert n == sum(a.nbytes for a in got[run].values())
+    a = got['a']
+    assert sorted(a) == sorted(['stats.loss', 'stats.rot_error', 'stats.metric.union', 'stats.metric.iou', 'stats.pair.0', 'stats.pair.1', 'param.0.weight',
+                                'param.0.bias', 'param.1.weight', 'grad_sample', 'grad_sample_index'])
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a['stats.loss'] == np.float32(loss.item()) and a['stats.rot_error'] == 0.25 and a['stats.metric.iou'].dtype == np.float64
+    assert np.array_equal(a['param.0.weight'], net[0].weight.detach().numpy())
+    flat = torch.cat([p.grad.reshape(-1) for p in net.parameters()]).numpy()
+    assert a['grad_sample'].size == flat.size and np.array_equal(a['grad_sample'], flat[a['grad_sample_index'].astype(np.int64)])
+    assert all(np.array_equal(a[k], got['b'][k]) for k in a)
+    import pytest
+    with pytest.raises(TypeError):                                   # a result of a type the dump cannot hold is an error, not a silent gap
+        bench.dump_outputs(str(tmp_path / 'c'), {'name': 'skipped'}, net)
