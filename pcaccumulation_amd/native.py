@@ -7,6 +7,7 @@ never reached from this module.
 """
 import ctypes
 import os
+import re
 
 import torch
 
@@ -23,58 +24,49 @@ class NativeError(RuntimeError):
     pass
 
 
+_CTYPES = {'int': ctypes.c_int, 'int32_t': ctypes.c_int, 'int64_t': ctypes.c_int64, 'uint64_t': ctypes.c_uint64, 'size_t': ctypes.c_size_t,
+           'float': ctypes.c_float, 'double': ctypes.c_double}
+
+
+def _prototypes():
+    """{entry point: argtypes} of every `int pcacc_x(...);` include/pcacc.h declares.  Every pointer is a c_void_p: it takes None, an address, byref(...)
+    and a ctypes array, which is all this module passes."""
+    text = re.sub(r'/\*.*?\*/', '', open(os.path.join(_HERE, os.pardir, 'include', 'pcacc.h')).read(), flags=re.S)
+    protos = {}
+    for name, params in re.findall(r'\bint\s+(pcacc_\w+)\s*\(([^)]*)\)\s*;', text):
+        argtypes = []
+        for p in (params.split(',') if params.strip() != 'void' else ()):
+            ctype = ctypes.c_void_p if '*' in p else _CTYPES.get(' '.join(p.replace('const', ' ').split()[:-1]))
+            if ctype is None:
+                raise NativeError('include/pcacc.h: %s has a parameter of a type this binding does not know: %r' % (name, p.strip()))
+            argtypes.append(ctype)
+        protos[name] = argtypes
+    return protos
+
+
+_PROTOTYPES = _prototypes()
+EXPORTS = list(_PROTOTYPES)             # every `int` entry point include/pcacc.h declares, in its order (tests check the .so exports exactly these + pcacc_target)
+
+
 def lib():
-    """Load libpcacc_hip.so (after torch, so that it binds to the HIP runtime torch already loaded)."""
+    """Load libpcacc_hip.so (after torch, so that it binds to the HIP runtime torch already loaded) and give every entry point the signature
+    include/pcacc.h declares: from here on ctypes converts plain Python values at each call and refuses a missing argument or a wrong kind."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise NativeError('libpcacc_hip.so is not built (%s): run `python -c "import __graft_entry__ as g; '
                               'g.build()"` or `make -C pcaccumulation_amd/csrc`. There is no CPU fallback.' % LIB_PATH)
         _lib = ctypes.CDLL(LIB_PATH)
-        for name in EXPORTS:
+        for name, argtypes in _PROTOTYPES.items():
             try:
-                getattr(_lib, name).restype = ctypes.c_int
+                fn = getattr(_lib, name)
             except AttributeError:
                 if not os.environ.get('PCACC_LIB'):               # an experiment build of an earlier round (A/B runs) may lack entry points added since
                     raise
-        _lib.pcacc_target.restype = ctypes.c_char_p
+                continue
+            fn.restype, fn.argtypes = ctypes.c_int, argtypes
+        _lib.pcacc_target.restype, _lib.pcacc_target.argtypes = ctypes.c_char_p, []
     return _lib
-
-
-# every symbol include/pcacc.h declares (tests check the .so exports exactly these)
-EXPORTS = [
-    'pcacc_reload_switches', 'pcacc_cat2_rows', 'pcacc_collate_voxelize_workspace_bytes', 'pcacc_collate_voxelize', 'pcacc_rows_linear_split_dual', 'pcacc_rows_linear_few_dual', 'pcacc_pfn_block_split_forward_dual', 'pcacc_pool_skip_relu_backward_strided_y32', 'pcacc_conv3x3_split_dual', 'pcacc_conv3x3_split_cat', 'pcacc_upconv2x2_split_dual', 'pcacc_voxelize_workspace_bytes', 'pcacc_voxelize', 'pcacc_cell_index',
-    'pcacc_frame_pillars_workspace_bytes', 'pcacc_frame_pillars', 'pcacc_compact_mask_workspace_bytes', 'pcacc_compact_mask',
-    'pcacc_csr_workspace_bytes', 'pcacc_csr_build', 'pcacc_segment_mean3_maxlabel',
-    'pcacc_segment_workspace_bytes', 'pcacc_segment_max', 'pcacc_segment_max_backward', 'pcacc_segment_sum', 'pcacc_scatter_sum_small_workspace_bytes', 'pcacc_scatter_sum_small',
-    'pcacc_pfn_features', 'pcacc_pfn_features_ordered', 'pcacc_rows_linear', 'pcacc_rows_wgrad', 'pcacc_pillar_scatter', 'pcacc_gather_rows',
-    'pcacc_bilinear_gather', 'pcacc_bilinear_gather_backward', 'pcacc_bev_warp', 'pcacc_bev_warp_dual', 'pcacc_rigid_transform',
-    'pcacc_sinkhorn_kabsch_workspace_bytes', 'pcacc_sinkhorn_kabsch', 'pcacc_chamfer_workspace_bytes', 'pcacc_chamfer_forward', 'pcacc_chamfer_backward',
-    'pcacc_cluster_workspace_bytes', 'pcacc_cluster', 'pcacc_conv3x3_prepare_weights', 'pcacc_conv3x3_bf16',
-    'pcacc_rows_linear_bf16', 'pcacc_rows_linear_mixed', 'pcacc_rows_wgrad_mixed',
-    'pcacc_segment_max_t', 'pcacc_segment_max_dual', 'pcacc_segment_max_canvas', 'pcacc_segment_max_canvas_backward', 'pcacc_segment_max_backward_t', 'pcacc_segment_max_backward_acc', 'pcacc_segment_sum_t', 'pcacc_rows_wgrad_bf16_workspace_bytes', 'pcacc_rows_wgrad_bf16', 'pcacc_sample_subsets', 'pcacc_conv3x3_wgrad_workspace_bytes', 'pcacc_conv3x3_wgrad_bf16', 'pcacc_upload_words', 'pcacc_bilinear_base_cells', 'pcacc_bilinear_sorted_workspace_bytes', 'pcacc_bilinear_gather_backward_sorted', 'pcacc_prep_points',
-    'pcacc_kabsch_cov_forward', 'pcacc_kabsch_cov_backward', 'pcacc_kabsch_rt_forward', 'pcacc_kabsch_rt_backward', 'pcacc_ego_affinity_forward', 'pcacc_ego_affinity_backward_workspace_bytes', 'pcacc_ego_affinity_backward', 'pcacc_ego_perm_forward', 'pcacc_ego_perm_backward',
-    'pcacc_sinkhorn_train_workspace_bytes', 'pcacc_sinkhorn_forward', 'pcacc_sinkhorn_backward',
-    'pcacc_seg_loss_workspace_bytes', 'pcacc_seg_loss_forward', 'pcacc_seg_loss_backward',
-    'pcacc_offset_loss_workspace_bytes', 'pcacc_offset_loss_forward', 'pcacc_offset_loss_backward',
-    'pcacc_frames_max', 'pcacc_frames_max_backward', 'pcacc_rows_linear_cat_bf16', 'pcacc_rows_wgrad_cat_bf16',
-    'pcacc_pillar_scatter_timed', 'pcacc_pillar_scatter_t', 'pcacc_timer_create', 'pcacc_timer_elapsed_us', 'pcacc_timer_destroy',
-    'pcacc_svd3', 'pcacc_svd3_backward', 'pcacc_conv3x3_deep_supported', 'pcacc_conv3x3_deep_bf16', 'pcacc_conv3x3_prepare_weights_pair',
-    'pcacc_conv3x3_masked_bf16',
-    'pcacc_conv3x3_wgrad_deep_supported', 'pcacc_conv3x3_wgrad_deep_workspace_bytes', 'pcacc_conv3x3_wgrad_deep_bf16', 'pcacc_bn_rows_workspace_bytes', 'pcacc_bn_rows_forward', 'pcacc_bn_rows_backward',
-    'pcacc_tube_rows', 'pcacc_tube_code', 'pcacc_tube_code_backward', 'pcacc_tube_pose_forward', 'pcacc_tube_gap_forward', 'pcacc_tube_finish',
-    'pcacc_tube_gap_backward', 'pcacc_tube_pose_backward', 'pcacc_rows_wgrad_few_supported', 'pcacc_rows_wgrad_few_workspace_bytes', 'pcacc_rows_wgrad_few',
-    'pcacc_maxpool2x2_bf16', 'pcacc_pool_skip_relu_backward_bf16',
-    'pcacc_pfn_block_forward', 'pcacc_pfn_block_backward_workspace_bytes', 'pcacc_pfn_block_backward', 'pcacc_conv3x3_split_outmask', 'pcacc_conv3x3_outmask_supported', 'pcacc_conv3x3_outmask_bf16', 'pcacc_maxpool2x2_f32', 'pcacc_pool_skip_relu_backward_f32', 'pcacc_pool_skip_relu_backward_strided_bf16', 'pcacc_pool_skip_relu_backward_strided_f32', 'pcacc_bn_relu_rows_forward', 'pcacc_bn_relu_rows_backward', 'pcacc_bn_rows_backward_m', 'pcacc_bn_rows_forward_dual', 'pcacc_pfn_block_split_forward', 'pcacc_pfn_block_split_dgrad', 'pcacc_inv4x4',
-    'pcacc_conv3x3_split_prepare_weights', 'pcacc_conv3x3_split_supported', 'pcacc_conv3x3_split', 'pcacc_conv3x3_wgrad_split_workspace_bytes',
-    'pcacc_conv3x3_wgrad_split', 'pcacc_absmax256',
-    'pcacc_rows_linear_split', 'pcacc_rows_linear_cat_split', 'pcacc_rows_wgrad_split_workspace_bytes', 'pcacc_rows_wgrad_split',
-    'pcacc_rows_wgrad_cat_split', 'pcacc_upconv2x2_split_prepare_weights', 'pcacc_prepare_weights_batch', 'pcacc_upconv2x2_bf16_supported', 'pcacc_upconv2x2_bf16_prepare_weights', 'pcacc_upconv2x2_bf16',
-    'pcacc_upconv2x2_bf16_wgrad_workspace_bytes', 'pcacc_upconv2x2_bf16_wgrad', 'pcacc_upconv2x2_split_supported', 'pcacc_upconv2x2_split',
-    'pcacc_upconv2x2_wgrad_split_workspace_bytes', 'pcacc_upconv2x2_wgrad_split',
-    'pcacc_head_conv3x3_supported', 'pcacc_head_conv3x3_forward', 'pcacc_head_conv3x3_dgrad', 'pcacc_head_conv3x3_wgrad',
-    'pcacc_head_conv3x3_wgrad_workspace_bytes',
-]
 
 
 def x3_experiment(word):
@@ -125,8 +117,12 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
-def _i64(v):
-    return ctypes.c_int64(int(v))
+def _workspace(query, device, *sizes):
+    """The workspace tensor a launch needs: as many bytes as its `query` (a pcacc_*_workspace_bytes entry point) answers for `sizes`.
+    The launch gets _dev(ws), ws.numel()."""
+    need = ctypes.c_size_t(0)
+    _check(query(*sizes, ctypes.byref(need)), query.__name__[len('pcacc_'):-len('_bytes')])
+    return _ws(need.value, device)
 
 
 def _dtype_code(t):
@@ -146,14 +142,11 @@ def voxelize(points, voxel_size, pc_range, grid, nt, max_voxels):
     coords = torch.empty((max_voxels, 4), dtype=torch.int32, device=dev)
     p2v = torch.empty((n,), dtype=torch.int32, device=dev)
     num = torch.empty((1,), dtype=torch.int32, device=dev)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_voxelize_workspace_bytes(_i64(n), nx, ny, nz, int(nt), ctypes.byref(need)), 'voxelize_workspace')
-    ws = _ws(need.value, dev)
+    ws = _workspace(lib().pcacc_voxelize_workspace_bytes, dev, n, nx, ny, nz, int(nt))
     vs = (ctypes.c_float * 3)(*[float(v) for v in voxel_size])
     rg = (ctypes.c_float * 6)(*[float(v) for v in pc_range])
-    _check(lib().pcacc_voxelize(_dev(points, torch.float32, 'points'), _i64(n), vs, rg, nx, ny, nz, int(nt),
-                                int(max_voxels), _dev(coords), _dev(p2v), _dev(num), _dev(ws),
-                                ctypes.c_size_t(ws.numel()), _stream()), 'voxelize')
+    _check(lib().pcacc_voxelize(_dev(points, torch.float32, 'points'), n, vs, rg, nx, ny, nz, int(nt), int(max_voxels), _dev(coords), _dev(p2v), _dev(num), _dev(ws),
+                                ws.numel(), _stream()), 'voxelize')
     return coords, p2v, num
 
 
@@ -191,15 +184,13 @@ def collate_voxelize(samples, voxel_size, pc_range, grid, nt):
     coords = torch.empty((n, 5), dtype=torch.float64, device=dev)
     p2v = torch.empty((n, 1), dtype=torch.int32, device=dev)
     num = torch.empty((B,), dtype=torch.int32, device=dev)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_collate_voxelize_workspace_bytes(_i64(n), B, nx, ny, nz, int(nt), ctypes.byref(need)), 'collate_voxelize_workspace')
-    ws = _ws(need.value, dev)
+    ws = _workspace(lib().pcacc_collate_voxelize_workspace_bytes, dev, n, B, nx, ny, nz, int(nt))
     vs = (ctypes.c_float * 3)(*[float(v) for v in voxel_size])
     rg = (ctypes.c_float * 6)(*[float(v) for v in pc_range])
     opt = lambda k: _dev(out[k]) if labels[k] is not None else None
     _check(lib().pcacc_collate_voxelize(pts, tim, labels['sd_labels'], labels['inst_labels'], labels['fb_labels'], counts, B, vs, rg, nx, ny, nz, int(nt),
                                         _dev(out['input_points']), _dev(out['time_indice']), opt('sd_labels'), opt('inst_labels'), opt('fb_labels'),
-                                        _dev(coords), _dev(p2v), _dev(num), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'collate_voxelize')
+                                        _dev(coords), _dev(p2v), _dev(num), _dev(ws), ws.numel(), _stream()), 'collate_voxelize')
     out.update(coords=coords, point_to_voxel_map=p2v, num_voxels=num, _keep=keep)
     return out
 
@@ -216,7 +207,7 @@ def cell_index(coords, nx, ny, nt, n_batch):
         raise NativeError('coordinates must be float64 (collate layout) or int32, got %s' % coords.dtype)
     cell = torch.empty((m,), dtype=torch.int32, device=dev)
     c2p = torch.empty((n_batch * nt * ny * nx,), dtype=torch.int32, device=dev)
-    _check(lib().pcacc_cell_index(_dev(coords, None, 'coordinates'), is_f64, _i64(m), int(nx), int(ny), int(nt),
+    _check(lib().pcacc_cell_index(_dev(coords, None, 'coordinates'), is_f64, m, int(nx), int(ny), int(nt),
                                   int(n_batch), _dev(cell), _dev(c2p), _stream()), 'cell_index')
     return cell, c2p
 
@@ -226,11 +217,8 @@ def frame_pillars(cell2pillar, cells_per_frame, m):
     n_cells = cell2pillar.numel()
     sorted_p = torch.zeros((m,), dtype=torch.int32, device=dev)      # entries beyond the occupied-cell count (duplicate cells) stay valid ids
     offs = torch.empty((n_cells // cells_per_frame + 1,), dtype=torch.int32, device=dev)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_frame_pillars_workspace_bytes(_i64(n_cells), ctypes.byref(need)), 'frame_pillars_workspace')
-    ws = _ws(need.value, dev)
-    _check(lib().pcacc_frame_pillars(_dev(cell2pillar, torch.int32), _i64(n_cells), _i64(cells_per_frame),
-                                     _dev(sorted_p), _dev(offs), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()),
+    ws = _workspace(lib().pcacc_frame_pillars_workspace_bytes, dev, n_cells)
+    _check(lib().pcacc_frame_pillars(_dev(cell2pillar, torch.int32), n_cells, cells_per_frame, _dev(sorted_p), _dev(offs), _dev(ws), ws.numel(), _stream()),
            'frame_pillars')
     return sorted_p, offs
 
@@ -251,11 +239,8 @@ def compact_mask(mask, size):
         mask = mask.clone(memory_format=torch.contiguous_format)
         if mask.data_ptr() % 16:
             raise NativeError('compact_mask: the allocator returned an unaligned block')
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_compact_mask_workspace_bytes(_i64(n), ctypes.byref(need)), 'compact_mask_workspace')
-    ws = _ws(need.value, dev)
-    _check(lib().pcacc_compact_mask(_dev(mask, None, 'mask'), _i64(n), _dev(out), _i64(size), None, _dev(ws), ctypes.c_size_t(ws.numel()), _stream()),
-           'compact_mask')
+    ws = _workspace(lib().pcacc_compact_mask_workspace_bytes, dev, n)
+    _check(lib().pcacc_compact_mask(_dev(mask, None, 'mask'), n, _dev(out), size, None, _dev(ws), ws.numel(), _stream()), 'compact_mask')
     return out
 
 
@@ -264,11 +249,8 @@ def csr_build(p2v, m):
     dev = p2v.device
     offs = torch.empty((m + 1,), dtype=torch.int32, device=dev)
     order = torch.empty((n,), dtype=torch.int32, device=dev)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_csr_workspace_bytes(_i64(n), _i64(m), ctypes.byref(need)), 'csr_workspace')
-    ws = _ws(need.value, dev)
-    _check(lib().pcacc_csr_build(_dev(p2v, torch.int32, 'p2v'), _i64(n), _i64(m), _dev(offs), _dev(order), _dev(ws),
-                                 ctypes.c_size_t(ws.numel()), _stream()), 'csr_build')
+    ws = _workspace(lib().pcacc_csr_workspace_bytes, dev, n, m)
+    _check(lib().pcacc_csr_build(_dev(p2v, torch.int32, 'p2v'), n, m, _dev(offs), _dev(order), _dev(ws), ws.numel(), _stream()), 'csr_build')
     return offs, order
 
 
@@ -278,15 +260,12 @@ def segment_mean3_maxlabel(points, labels, offs, order, m):
     lab_out = torch.empty((m,), dtype=torch.int64, device=dev) if labels is not None else None
     _check(lib().pcacc_segment_mean3_maxlabel(
         _dev(points, torch.float32, 'points'), _dev(labels, torch.int64, 'labels') if labels is not None else None,
-        _dev(offs, torch.int32), _dev(order, torch.int32), _i64(m), _dev(mean),
-        _dev(lab_out) if lab_out is not None else None, _stream()), 'segment_mean3_maxlabel')
+        _dev(offs, torch.int32), _dev(order, torch.int32), m, _dev(mean), _dev(lab_out) if lab_out is not None else None, _stream()), 'segment_mean3_maxlabel')
     return mean, lab_out
 
 
 def _segment_ws(n, m, c, dev):
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_segment_workspace_bytes(_i64(n), _i64(m), int(c), ctypes.byref(need)), 'segment_workspace')
-    return _ws(need.value, dev)
+    return _workspace(lib().pcacc_segment_workspace_bytes, dev, n, m, int(c))
 
 
 def _seg_two_level(n, m):
@@ -304,8 +283,7 @@ def segment_max(src, offs, order, m):
     arg = torch.empty((m, c), dtype=torch.int32, device=src.device)
     ws = _segment_ws(n, m, c, src.device)
     _check(lib().pcacc_segment_max_t(_dev(src, None, 'src'), _dtype_code(src), int(c), _dev(offs, torch.int32), _dev(order, torch.int32),
-                                     _i64(n), _i64(m), _dev(out), _dev(arg), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()),
-           'segment_max')
+                                     n, m, _dev(out), _dev(arg), _dev(ws), ws.numel(), _stream()), 'segment_max')
     return out, arg
 
 
@@ -318,8 +296,8 @@ def segment_max_dual(src, offs, order, m):
     out16 = torch.empty((m, c), dtype=torch.bfloat16, device=src.device)
     arg = torch.empty((m, c), dtype=torch.int32, device=src.device)
     ws = _segment_ws(n, m, c, src.device)
-    _check(lib().pcacc_segment_max_dual(_dev(src, torch.float32, 'src'), int(c), _dev(offs, torch.int32), _dev(order, torch.int32), _i64(n), _i64(m),
-                                        _dev(out), _dev(out16), _dev(arg), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'segment_max_dual')
+    _check(lib().pcacc_segment_max_dual(_dev(src, torch.float32, 'src'), int(c), _dev(offs, torch.int32), _dev(order, torch.int32), n, m,
+                                        _dev(out), _dev(out16), _dev(arg), _dev(ws), ws.numel(), _stream()), 'segment_max_dual')
     return out, out16, arg
 
 
@@ -331,8 +309,7 @@ def segment_max_backward(grad_out, arg, p2v, n, out_dtype=None):
     out_dtype = out_dtype or grad_out.dtype
     g = torch.empty((n, c), dtype=out_dtype, device=grad_out.device)
     _check(lib().pcacc_segment_max_backward_t(_dev(grad_out, None, 'grad_out'), _dtype_code(grad_out), _dev(arg, torch.int32),
-                                              _dev(p2v, torch.int32), _i64(n), int(c), _dev(g), _dtype_code(g), _stream()),
-           'segment_max_backward')
+                                              _dev(p2v, torch.int32), n, int(c), _dev(g), _dtype_code(g), _stream()), 'segment_max_backward')
     return g
 
 
@@ -343,7 +320,7 @@ def segment_max_backward_acc(grad_out, arg, p2v, grad_src, want_amax=False):
         grad_out = grad_out.float()
     amax = _zero256(grad_src.device) if want_amax else None
     _check(lib().pcacc_segment_max_backward_acc(_dev(grad_out, None, 'grad_out'), _dtype_code(grad_out), _dev(arg, torch.int32), _dev(p2v, torch.int32),
-                                                _i64(n), int(c), _dev(grad_src, None, 'grad_src'), _dtype_code(grad_src),
+                                                n, int(c), _dev(grad_src, None, 'grad_src'), _dtype_code(grad_src),
                                                 _dev(amax) if want_amax else None, _stream()), 'segment_max_backward_acc')
     return amax
 
@@ -361,8 +338,8 @@ def segment_max_canvas(src, offs, order, m, cell2pillar):
     if scatter_timer is not None and c >= 32:
         t = KernelTimer()
         scatter_timer.append((t, n_cells, c, m, 'fused', n))
-    _check(lib().pcacc_segment_max_canvas(_dev(src, torch.float32, 'src'), int(c), _dev(offs, torch.int32), _dev(order, torch.int32), _i64(n), _i64(m),
-                                          _dev(cell2pillar, torch.int32), _i64(n_cells), _dev(canvas32), _dev(canvas16), _dev(arg),
+    _check(lib().pcacc_segment_max_canvas(_dev(src, torch.float32, 'src'), int(c), _dev(offs, torch.int32), _dev(order, torch.int32), n, m,
+                                          _dev(cell2pillar, torch.int32), n_cells, _dev(canvas32), _dev(canvas16), _dev(arg),
                                           t.start if t else None, t.stop if t else None, _stream()), 'segment_max_canvas')
     return canvas32, canvas16, arg
 
@@ -373,7 +350,7 @@ def segment_max_canvas_backward(grad_canvas, arg, p2v, cell, n, out_dtype=None):
     out_dtype = out_dtype or grad_canvas.dtype
     out = torch.empty((n, c), dtype=out_dtype, device=grad_canvas.device)
     _check(lib().pcacc_segment_max_canvas_backward(_dev(grad_canvas, None, 'grad_canvas'), _dtype_code(grad_canvas), _dev(arg, torch.int32), _dev(p2v, torch.int32),
-                                                   _dev(cell, torch.int32), _i64(n), int(c), _dev(out), _dtype_code(out), _stream()), 'segment_max_canvas_backward')
+                                                   _dev(cell, torch.int32), n, int(c), _dev(out), _dtype_code(out), _stream()), 'segment_max_canvas_backward')
     return out
 
 
@@ -386,7 +363,7 @@ def segment_sum(src, offs, order, m):
     out = torch.empty((m, c), dtype=out_dtype, device=src.device)
     ws = _segment_ws(n, m, c, src.device)
     _check(lib().pcacc_segment_sum_t(_dev(src, None, 'src'), _dtype_code(src), int(c), _dev(offs, torch.int32), _dev(order, torch.int32),
-                                     _i64(n), _i64(m), _dev(out), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'segment_sum')
+                                     n, m, _dev(out), _dev(ws), ws.numel(), _stream()), 'segment_sum')
     return out
 
 
@@ -423,9 +400,8 @@ def pillar_scatter(feats, cell2pillar, out_dtype=torch.float32):
     if scatter_timer is not None and c >= 32:
         t = KernelTimer()
         scatter_timer.append((t, n_cells, c, feats.shape[0], out_dtype, feats.dtype))
-    _check(lib().pcacc_pillar_scatter_t(_dev(feats, None, 'feats'), _dtype_code(feats), _dev(cell2pillar, torch.int32), _i64(n_cells),
-                                        int(c), _dev(canvas), _dtype_code(canvas), t.start if t else None, t.stop if t else None,
-                                        _stream()), 'pillar_scatter')
+    _check(lib().pcacc_pillar_scatter_t(_dev(feats, None, 'feats'), _dtype_code(feats), _dev(cell2pillar, torch.int32), n_cells,
+                                        int(c), _dev(canvas), _dtype_code(canvas), t.start if t else None, t.stop if t else None, _stream()), 'pillar_scatter')
     return canvas
 
 
@@ -436,7 +412,7 @@ def cat2_rows(a, b):
     if a.dtype != b.dtype or tuple(a.shape[:-1]) != tuple(b.shape[:-1]) or not a.is_contiguous() or not b.is_contiguous():
         raise NativeError('cat2_rows: two contiguous tensors of one dtype and equal leading dimensions expected')
     out = torch.empty(tuple(a.shape[:-1]) + (ca + cb,), dtype=a.dtype, device=a.device)
-    _check(lib().pcacc_cat2_rows(_dev(a, None, 'a'), int(ca * a.element_size()), _dev(b, None, 'b'), int(cb * b.element_size()), _i64(rows), _dev(out),
+    _check(lib().pcacc_cat2_rows(_dev(a, None, 'a'), int(ca * a.element_size()), _dev(b, None, 'b'), int(cb * b.element_size()), rows, _dev(out),
                                  _stream()), 'cat2_rows')
     return out
 
@@ -445,8 +421,7 @@ def gather_rows(src, idx):
     """out[i] = src[idx[i]] for a 2-D src with row size a multiple of 4 bytes; idx i32 (-1 -> zeros)."""
     row_bytes = src.shape[1] * src.element_size()
     out = torch.empty((idx.shape[0], src.shape[1]), dtype=src.dtype, device=src.device)
-    _check(lib().pcacc_gather_rows(_dev(src, None, 'src'), int(row_bytes), _dev(idx, torch.int32, 'idx'),
-                                   _i64(idx.shape[0]), _dev(out), _stream()), 'gather_rows')
+    _check(lib().pcacc_gather_rows(_dev(src, None, 'src'), int(row_bytes), _dev(idx, torch.int32, 'idx'), idx.shape[0], _dev(out), _stream()), 'gather_rows')
     return out
 
 
@@ -456,8 +431,7 @@ def bilinear_gather(fmap, points, map_idx, x_scale, y_scale):
     k = points.shape[0]
     out = torch.empty((k, c), dtype=torch.float32, device=fmap.device)
     _check(lib().pcacc_bilinear_gather(_dev(fmap, None, 'fmap'), _dtype_code(fmap), n_maps, h, w, c,
-                                       _dev(points, torch.float32, 'points'), _dev(map_idx, torch.int32, 'map_idx'),
-                                       _i64(k), ctypes.c_float(x_scale), ctypes.c_float(y_scale), _dev(out), _stream()),
+                                       _dev(points, torch.float32, 'points'), _dev(map_idx, torch.int32, 'map_idx'), k, x_scale, y_scale, _dev(out), _stream()),
            'bilinear_gather')
     return out
 
@@ -465,10 +439,8 @@ def bilinear_gather(fmap, points, map_idx, x_scale, y_scale):
 def bilinear_gather_backward(grad_out, shape, points, map_idx, x_scale, y_scale):
     n_maps, h, w, c = shape
     g = torch.zeros(shape, dtype=torch.float32, device=grad_out.device)
-    _check(lib().pcacc_bilinear_gather_backward(_dev(grad_out, torch.float32, 'grad_out'), n_maps, h, w, c,
-                                                _dev(points, torch.float32), _dev(map_idx, torch.int32),
-                                                _i64(points.shape[0]), ctypes.c_float(x_scale), ctypes.c_float(y_scale),
-                                                _dev(g), _stream()), 'bilinear_gather_backward')
+    _check(lib().pcacc_bilinear_gather_backward(_dev(grad_out, torch.float32, 'grad_out'), n_maps, h, w, c, _dev(points, torch.float32), _dev(map_idx, torch.int32),
+                                                points.shape[0], x_scale, y_scale, _dev(g), _stream()), 'bilinear_gather_backward')
     return g
 
 
@@ -476,9 +448,8 @@ def bev_warp(bev, inv_pose, x_reso, y_reso, x_min, y_min):
     """bev [B,T,H,W,C] channels-last; inv_pose [B,T,4,4] f32 -> warped [B,T,H,W,C]."""
     b, t, h, w, c = bev.shape
     out = torch.empty_like(bev)
-    _check(lib().pcacc_bev_warp(_dev(bev, None, 'bev'), _dtype_code(bev), b, t, h, w, c,
-                                _dev(inv_pose, torch.float32, 'inv_pose'), ctypes.c_float(x_reso), ctypes.c_float(y_reso),
-                                ctypes.c_float(x_min), ctypes.c_float(y_min), _dev(out), _stream()), 'bev_warp')
+    _check(lib().pcacc_bev_warp(_dev(bev, None, 'bev'), _dtype_code(bev), b, t, h, w, c, _dev(inv_pose, torch.float32, 'inv_pose'), x_reso, y_reso,
+                                x_min, y_min, _dev(out), _stream()), 'bev_warp')
     return out
 
 
@@ -488,16 +459,15 @@ def bev_warp_dual(bev, inv_pose, x_reso, y_reso, x_min, y_min):
     b, nt, h, w, c = bev.shape
     out = torch.empty_like(bev)
     out16 = torch.empty(bev.shape, dtype=torch.bfloat16, device=bev.device)
-    _check(lib().pcacc_bev_warp_dual(_dev(bev, torch.float32, 'bev'), b, nt, h, w, c, _dev(inv_pose, torch.float32, 'inv_pose'), ctypes.c_float(x_reso),
-                                     ctypes.c_float(y_reso), ctypes.c_float(x_min), ctypes.c_float(y_min), _dev(out), _dev(out16), _stream()), 'bev_warp_dual')
+    _check(lib().pcacc_bev_warp_dual(_dev(bev, torch.float32, 'bev'), b, nt, h, w, c, _dev(inv_pose, torch.float32, 'inv_pose'), x_reso,
+                                     y_reso, x_min, y_min, _dev(out), _dev(out16), _stream()), 'bev_warp_dual')
     return out, out16
 
 
 def rigid_transform(points, frame_idx, tsfm):
     out = torch.empty_like(points)
     _check(lib().pcacc_rigid_transform(_dev(points, torch.float32, 'points'), _dev(frame_idx, torch.int32, 'frame_idx'),
-                                       _dev(tsfm, torch.float32, 'tsfm'), _i64(points.shape[0]), _dev(out), _stream()),
-           'rigid_transform')
+                                       _dev(tsfm, torch.float32, 'tsfm'), points.shape[0], _dev(out), _stream()), 'rigid_transform')
     return out
 
 
@@ -509,12 +479,9 @@ def chamfer_forward(xyz1, xyz2):
     d2 = torch.empty((b, m), dtype=torch.float32, device=dev)
     i1 = torch.empty((b, n), dtype=torch.int32, device=dev)
     i2 = torch.empty((b, m), dtype=torch.int32, device=dev)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_chamfer_workspace_bytes(b, n, m, ctypes.byref(need)), 'chamfer_workspace')
-    ws = _ws(need.value, dev)
+    ws = _workspace(lib().pcacc_chamfer_workspace_bytes, dev, b, n, m)
     _check(lib().pcacc_chamfer_forward(_dev(xyz1, torch.float32, 'xyz1'), _dev(xyz2, torch.float32, 'xyz2'), b, n, m,
-                                       _dev(d1), _dev(i1), _dev(d2), _dev(i2), _dev(ws), ctypes.c_size_t(ws.numel()),
-                                       _stream()), 'chamfer_forward')
+                                       _dev(d1), _dev(i1), _dev(d2), _dev(i2), _dev(ws), ws.numel(), _stream()), 'chamfer_forward')
     return d1, d2, i1, i2
 
 
@@ -559,15 +526,13 @@ def rows_linear(x, w, bias=None, residual=None, pre_relu=False, post_relu=False,
     if all_bf16 and k in (32, 64, 128) and n in (32, 64, 128):
         _check(lib().pcacc_rows_linear_bf16(_dev(x, torch.bfloat16, 'x'), opt(in_mask, 'in_mask'), _dev(w, torch.float32, 'w'),
                                             _dev(bias, torch.float32, 'bias') if bias is not None else None, opt(residual, 'residual'),
-                                            opt(out_mask, 'out_mask'), _dev(y), _i64(rows), int(k), int(n), flags, _stream()),
-               'rows_linear_bf16')
+                                            opt(out_mask, 'out_mask'), _dev(y), rows, int(k), int(n), flags, _stream()), 'rows_linear_bf16')
         return y
     dt = (_row_dtype_bit(x, 1, 'x') | _row_dtype_bit(in_mask, 2, 'in_mask') | _row_dtype_bit(residual, 4, 'residual')
           | _row_dtype_bit(out_mask, 8, 'out_mask') | _row_dtype_bit(y, 16, 'y'))
     _check(lib().pcacc_rows_linear_mixed(_dev(x, None, 'x'), opt(in_mask, 'in_mask'), _dev(w, torch.float32, 'w'),
                                          _dev(bias, torch.float32, 'bias') if bias is not None else None, opt(residual, 'residual'),
-                                         opt(out_mask, 'out_mask'), _dev(y), _i64(rows), int(k), int(n), flags, dt, _stream()),
-           'rows_linear')
+                                         opt(out_mask, 'out_mask'), _dev(y), rows, int(k), int(n), flags, dt, _stream()), 'rows_linear')
     return y
 
 
@@ -589,25 +554,18 @@ def rows_wgrad(dy, x, dy_mask=None, x_relu=False, split=False):
     out = torch.empty((n, k + 1), dtype=torch.float32, device=dy.device)
     flags = (1 if x_relu else 0) | (2 if split else 0)
     if all(t is None or t.dtype == torch.bfloat16 for t in (dy, dy_mask, x)) and k % 32 == 0 and n % 32 == 0:
-        need = ctypes.c_size_t(0)
-        _check(lib().pcacc_rows_wgrad_bf16_workspace_bytes(_i64(rows), int(k), int(n), ctypes.byref(need)), 'rows_wgrad_bf16_workspace')
-        ws = _ws(need.value, dy.device)
+        ws = _workspace(lib().pcacc_rows_wgrad_bf16_workspace_bytes, dy.device, rows, int(k), int(n))
         _check(lib().pcacc_rows_wgrad_bf16(_dev(dy, torch.bfloat16, 'dy'), _dev(dy_mask, torch.bfloat16, 'dy_mask') if dy_mask is not None else None,
-                                           _dev(x, torch.bfloat16, 'x'), flags, _i64(rows), int(k), int(n), _dev(out),
-                                           _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'rows_wgrad_bf16')
+                                           _dev(x, torch.bfloat16, 'x'), flags, rows, int(k), int(n), _dev(out), _dev(ws), ws.numel(), _stream()), 'rows_wgrad_bf16')
         return _split_aug(out, n, k, split, True)
     dt = _row_dtype_bit(dy, 1, 'dy') | _row_dtype_bit(dy_mask, 2, 'dy_mask') | _row_dtype_bit(x, 4, 'x')
     if lib().pcacc_rows_wgrad_few_supported(int(k), int(n)):
-        need = ctypes.c_size_t(0)
-        _check(lib().pcacc_rows_wgrad_few_workspace_bytes(_i64(rows), int(k), int(n), ctypes.byref(need)), 'rows_wgrad_few_workspace')
-        ws = _ws(need.value, dy.device)
+        ws = _workspace(lib().pcacc_rows_wgrad_few_workspace_bytes, dy.device, rows, int(k), int(n))
         _check(lib().pcacc_rows_wgrad_few(_dev(dy, None, 'dy'), _dev(dy_mask, None, 'dy_mask') if dy_mask is not None else None, _dev(x, None, 'x'),
-                                          flags, _i64(rows), int(k), int(n), _dev(out), dt, _dev(ws), ctypes.c_size_t(ws.numel()),
-                                          _stream()), 'rows_wgrad_few')
+                                          flags, rows, int(k), int(n), _dev(out), dt, _dev(ws), ws.numel(), _stream()), 'rows_wgrad_few')
         return _split_aug(out, n, k, split, rows > 0)
     _check(lib().pcacc_rows_wgrad_mixed(_dev(dy, None, 'dy'), _dev(dy_mask, None, 'dy_mask') if dy_mask is not None else None,
-                                        _dev(x, None, 'x'), 1 if x_relu else 0, _i64(rows), int(k), int(n), _dev(out), dt, _stream()),
-           'rows_wgrad')
+                                        _dev(x, None, 'x'), 1 if x_relu else 0, rows, int(k), int(n), _dev(out), dt, _stream()), 'rows_wgrad')
     return _split_aug(out, n, k, split, False)
 
 
@@ -629,16 +587,12 @@ def pfn_features(points, p2v, pillar_mean, coords, time_indice, vx, vy, x_offset
     if order is None:
         _check(lib().pcacc_pfn_features(_dev(points, torch.float32, 'points'), _dev(p2v, torch.int32, 'p2v'),
                                         _dev(pillar_mean, torch.float32, 'pillar_mean'), _dev(coords, None, 'coordinates'), is_f64,
-                                        tcol if n else None, _i64(2), _i64(n), ctypes.c_double(vx), ctypes.c_double(vy),
-                                        ctypes.c_double(x_offset), ctypes.c_double(y_offset), ctypes.c_float(scale),
-                                        ctypes.c_float(n_frames), _dev(out), _stream()), 'pfn_features')
+                                        tcol if n else None, 2, n, vx, vy, x_offset, y_offset, scale, n_frames, _dev(out), _stream()), 'pfn_features')
         return out
     _check(lib().pcacc_pfn_features_ordered(_dev(points, torch.float32, 'points'), _dev(p2v, torch.int32, 'p2v'),
                                             _dev(pillar_mean, torch.float32, 'pillar_mean'), _dev(coords, None, 'coordinates'), is_f64,
-                                            tcol if n else None, _i64(2), _i64(n), ctypes.c_double(vx), ctypes.c_double(vy),
-                                            ctypes.c_double(x_offset), ctypes.c_double(y_offset), ctypes.c_float(scale),
-                                            ctypes.c_float(n_frames), _dev(order, torch.int32, 'order') if order is not None else None, _dev(out), _stream()),
-           'pfn_features')
+                                            tcol if n else None, 2, n, vx, vy, x_offset, y_offset, scale,
+                                            n_frames, _dev(order, torch.int32, 'order') if order is not None else None, _dev(out), _stream()), 'pfn_features')
     return out
 
 
@@ -646,15 +600,9 @@ def scatter_sum_small(src, idx, m):
     """out[m,c] = sum of src rows per idx, for m*c <= 8192 (LDS-privatised, no CSR)."""
     n, c = src.shape
     out = torch.empty((m, c), dtype=torch.float32, device=src.device)
-    if os.environ.get('PCACC_R05_ABI'):                           # A/B against a round-5 library (PCACC_LIB): its entry point took no workspace
-        _check(lib().pcacc_scatter_sum_small(_dev(src, torch.float32, 'src'), _dev(idx, torch.int32, 'idx'), _i64(n), int(c), int(m), _dev(out), _stream()),
-               'scatter_sum_small')
-        return out
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_scatter_sum_small_workspace_bytes(_i64(n), int(c), int(m), ctypes.byref(need)), 'scatter_sum_small_workspace')
-    ws = _ws(need.value, src.device)
-    _check(lib().pcacc_scatter_sum_small(_dev(src, torch.float32, 'src'), _dev(idx, torch.int32, 'idx'), _i64(n), int(c), int(m),
-                                         _dev(out), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'scatter_sum_small')
+    ws = _workspace(lib().pcacc_scatter_sum_small_workspace_bytes, src.device, n, int(c), int(m))
+    _check(lib().pcacc_scatter_sum_small(_dev(src, torch.float32, 'src'), _dev(idx, torch.int32, 'idx'), n, int(c), int(m),
+                                         _dev(out), _dev(ws), ws.numel(), _stream()), 'scatter_sum_small')
     return out
 
 
@@ -664,14 +612,11 @@ def sinkhorn_kabsch(feats_s, feats_t, coor_s, coor_t, thr2, params, n_iters):
     dev = feats_s.device
     perm = torch.empty((P, k, k), dtype=torch.float32, device=dev)
     pose = torch.empty((P, 4, 4), dtype=torch.float32, device=dev)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_sinkhorn_kabsch_workspace_bytes(int(P), int(k), ctypes.byref(need)), 'sinkhorn_kabsch_workspace')
-    ws = _ws(need.value, dev)
+    ws = _workspace(lib().pcacc_sinkhorn_kabsch_workspace_bytes, dev, int(P), int(k))
     _check(lib().pcacc_sinkhorn_kabsch(_dev(feats_s, torch.float32, 'feats_s'), _dev(feats_t, torch.float32, 'feats_t'),
                                        _dev(coor_s, torch.float32, 'coor_s'), _dev(coor_t, torch.float32, 'coor_t'),
                                        _dev(thr2, torch.float32, 'thr2'), _dev(params, torch.float32, 'params'), int(P), int(k), int(c),
-                                       int(n_iters), _dev(perm), _dev(pose), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()),
-           'sinkhorn_kabsch')
+                                       int(n_iters), _dev(perm), _dev(pose), _dev(ws), ws.numel(), _stream()), 'sinkhorn_kabsch')
     return perm, pose
 
 
@@ -681,14 +626,10 @@ def cluster(points, offset, sel, batch, n_batches, voxel_size, eps, min_samples,
     labels = torch.empty((n,), dtype=torch.int64, device=points.device)
     if n == 0:
         return labels
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_cluster_workspace_bytes(_i64(n), ctypes.byref(need)), 'cluster_workspace')
-    ws = _ws(need.value, points.device)
-    _check(lib().pcacc_cluster(_dev(points, torch.float32, 'points'),
-                               _dev(offset, torch.float32, 'offset') if offset is not None else None,
-                               _dev(sel, torch.uint8, 'sel'), _dev(batch, torch.int32, 'batch'), _i64(n), int(n_batches),
-                               ctypes.c_float(voxel_size), ctypes.c_double(eps), int(min_samples), int(min_p_cluster),
-                               _dev(labels), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'cluster')
+    ws = _workspace(lib().pcacc_cluster_workspace_bytes, points.device, n)
+    _check(lib().pcacc_cluster(_dev(points, torch.float32, 'points'), _dev(offset, torch.float32, 'offset') if offset is not None else None,
+                               _dev(sel, torch.uint8, 'sel'), _dev(batch, torch.int32, 'batch'), n, int(n_batches),
+                               voxel_size, eps, int(min_samples), int(min_p_cluster), _dev(labels), _dev(ws), ws.numel(), _stream()), 'cluster')
     return labels
 
 
@@ -761,8 +702,7 @@ def sample_subsets(counts, k, seed):
     """counts [D] i32 on the device -> [D, k] i64: k distinct indices below counts[d] per row (see include/pcacc.h)."""
     d = counts.shape[0]
     out = torch.empty((d, k), dtype=torch.int64, device=counts.device)
-    _check(lib().pcacc_sample_subsets(_dev(counts, torch.int32, 'counts'), int(d), int(k), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)),
-                                      _dev(out), _stream()), 'sample_subsets')
+    _check(lib().pcacc_sample_subsets(_dev(counts, torch.int32, 'counts'), int(d), int(k), int(seed) & (2 ** 64 - 1), _dev(out), _stream()), 'sample_subsets')
     return out
 
 
@@ -776,13 +716,9 @@ def conv3x3_wgrad(dy_rows, x_rows, frames=1, dt=0):
     n_img, h, w, c_out = dy_rows.shape
     c_in = x_rows.shape[3]
     dw = torch.empty((c_out * 9 * c_in + c_out,), dtype=torch.float32, device=dy_rows.device)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_conv3x3_wgrad_workspace_bytes(int(n_img), int(h), int(w), int(c_in), int(c_out), ctypes.byref(need)),
-           'conv3x3_wgrad_workspace')
-    ws = _ws(need.value, dy_rows.device)
+    ws = _workspace(lib().pcacc_conv3x3_wgrad_workspace_bytes, dy_rows.device, int(n_img), int(h), int(w), int(c_in), int(c_out))
     _check(lib().pcacc_conv3x3_wgrad_bf16(_dev(dy_rows, torch.bfloat16, 'dy'), _dev(x_rows, torch.bfloat16, 'x'), _dev(dw), int(n_img),
-                                          int(frames), int(dt), int(h), int(w), int(c_in), int(c_out), _dev(ws),
-                                          ctypes.c_size_t(ws.numel()), _stream()), 'conv3x3_wgrad')
+                                          int(frames), int(dt), int(h), int(w), int(c_in), int(c_out), _dev(ws), ws.numel(), _stream()), 'conv3x3_wgrad')
     return dw[:c_out * 9 * c_in].view(c_out, 9, c_in), dw[c_out * 9 * c_in:]
 
 
@@ -796,14 +732,10 @@ def conv3x3_wgrad_deep(dy_rows, x_rows, mask=None):
     c_in = x_rows.shape[3]
     dw = torch.empty((c_out, 9, c_in), dtype=torch.float32, device=dy_rows.device)
     db = torch.empty((c_out,), dtype=torch.float32, device=dy_rows.device)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_conv3x3_wgrad_deep_workspace_bytes(int(n_img), int(h), int(w), int(c_in), int(c_out), ctypes.byref(need)),
-           'conv3x3_wgrad_deep_workspace')
-    ws = _ws(need.value, dy_rows.device)
+    ws = _workspace(lib().pcacc_conv3x3_wgrad_deep_workspace_bytes, dy_rows.device, int(n_img), int(h), int(w), int(c_in), int(c_out))
     _check(lib().pcacc_conv3x3_wgrad_deep_bf16(_dev(dy_rows, torch.bfloat16, 'dy'), _dev(mask, torch.bfloat16, 'mask') if mask is not None else None,
                                                _dev(x_rows, torch.bfloat16, 'x'), _dev(dw), _dev(db),
-                                               int(n_img), int(h), int(w), int(c_in), int(c_out), _dev(ws), ctypes.c_size_t(ws.numel()),
-                                               _stream()), 'conv3x3_wgrad_deep')
+                                               int(n_img), int(h), int(w), int(c_in), int(c_out), _dev(ws), ws.numel(), _stream()), 'conv3x3_wgrad_deep')
     return dw, db
 
 
@@ -815,7 +747,7 @@ def absmax256(t):
         raise NativeError('absmax256: float32 GPU tensor expected, got %s on %s' % (t.dtype, t.device))
     if not (t.is_contiguous() or torch.ops.aten.is_non_overlapping_and_dense(t)):
         t = t.contiguous()                                     # the kernel walks the storage: it must hold exactly the tensor's elements
-    _check(lib().pcacc_absmax256(ctypes.c_void_p(t.data_ptr()), _i64(t.numel()), _dev(out), _stream()), 'absmax256')
+    _check(lib().pcacc_absmax256(ctypes.c_void_p(t.data_ptr()), t.numel(), _dev(out), _stream()), 'absmax256')
     return out
 
 
@@ -906,14 +838,10 @@ def conv3x3_wgrad_split(dy_rows, x_rows, frames=1, dt=0, mask=None, dy_amax=None
     x_amax = absmax256(x_rows) if x_amax is None else x_amax
     dw = torch.empty((c_out, 9, c_in), dtype=torch.float32, device=dy_rows.device)
     db = torch.empty((c_out,), dtype=torch.float32, device=dy_rows.device)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_conv3x3_wgrad_split_workspace_bytes(int(n_img), int(h), int(w), int(c_in), int(c_out), ctypes.byref(need)),
-           'conv3x3_wgrad_split_workspace')
-    ws = _ws(need.value, dy_rows.device)
+    ws = _workspace(lib().pcacc_conv3x3_wgrad_split_workspace_bytes, dy_rows.device, int(n_img), int(h), int(w), int(c_in), int(c_out))
     _check(lib().pcacc_conv3x3_wgrad_split(dyp, _dev(dy_amax, torch.float32, 'dy_amax'), _dev(mask, torch.float32, 'mask') if mask is not None else None,
                                            xp, _dev(x_amax, torch.float32, 'x_amax'), _dev(dw), _dev(db), int(n_img), int(frames), int(dt),
-                                           int(h), int(w), int(c_in), int(c_out), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()),
-           'conv3x3_wgrad_split')
+                                           int(h), int(w), int(c_in), int(c_out), _dev(ws), ws.numel(), _stream()), 'conv3x3_wgrad_split')
     return dw, db
 
 
@@ -1028,12 +956,10 @@ def upconv2x2_bf16_wgrad(dy_rows, x_rows, want_bias=True, like=None):
         dw = torch.empty((c_in, c_up, 2, 2), dtype=torch.float32, device=x_rows.device)
     dws = (ctypes.c_int64 * 4)(*dw.stride())
     db = torch.empty((c_up,), dtype=torch.float32, device=x_rows.device) if want_bias else None
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_upconv2x2_bf16_wgrad_workspace_bytes(int(n), int(h), int(w), int(c_in), int(c_up), ctypes.byref(need)), 'upconv2x2_bf16_wgrad_workspace')
-    ws = _ws(need.value, x_rows.device)
+    ws = _workspace(lib().pcacc_upconv2x2_bf16_wgrad_workspace_bytes, x_rows.device, int(n), int(h), int(w), int(c_in), int(c_up))
     _check(lib().pcacc_upconv2x2_bf16_wgrad(ctypes.c_void_p(dy_rows.data_ptr()), int(dp), ctypes.c_void_p(x_rows.data_ptr()), int(xp), ctypes.c_void_p(dw.data_ptr()),
                                             dws, _dev(db) if db is not None else None, int(n), int(h), int(w), int(c_in), int(c_up), _dev(ws),
-                                            ctypes.c_size_t(ws.numel()), _stream()), 'upconv2x2_bf16_wgrad')
+                                            ws.numel(), _stream()), 'upconv2x2_bf16_wgrad')
     return dw, db
 
 
@@ -1085,12 +1011,10 @@ def upconv2x2_wgrad_split(dy_rows, dy_amax, x_rows, x_amax):
     c_up = dy_rows.shape[3]
     dw = torch.empty((4 * c_up, c_in), dtype=torch.float32, device=x_rows.device)
     db4 = torch.empty((4 * c_up,), dtype=torch.float32, device=x_rows.device)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_upconv2x2_wgrad_split_workspace_bytes(int(n), int(h), int(w), int(c_in), int(c_up), ctypes.byref(need)), 'upconv2x2_wgrad_workspace')
-    ws = _ws(need.value, x_rows.device)
+    ws = _workspace(lib().pcacc_upconv2x2_wgrad_split_workspace_bytes, x_rows.device, int(n), int(h), int(w), int(c_in), int(c_up))
     _check(lib().pcacc_upconv2x2_wgrad_split(_dev(dy_rows, torch.float32, 'dy'), _dev(dy_amax, torch.float32, 'dy_amax'), _dev(x_rows, torch.float32, 'x'),
                                              _dev(x_amax, torch.float32, 'x_amax'), _dev(dw), _dev(db4), int(n), int(h), int(w), int(c_in), int(c_up),
-                                             _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'upconv2x2_wgrad_split')
+                                             _dev(ws), ws.numel(), _stream()), 'upconv2x2_wgrad_split')
     return dw.view(2, 2, c_up, c_in).permute(3, 2, 0, 1), db4.view(4, c_up).sum(0)
 
 
@@ -1124,12 +1048,10 @@ def head_conv3x3_wgrad(dy_rows, x_rows, want_bias=True):
     c_in = x_rows.shape[3]
     dw = torch.empty((c_out, c_in, 3, 3), dtype=torch.float32, device=dy_rows.device)
     db = torch.empty((c_out,), dtype=torch.float32, device=dy_rows.device) if want_bias else None
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_head_conv3x3_wgrad_workspace_bytes(int(n), int(h), int(w), int(c_in), int(c_out), ctypes.byref(need)), 'head_conv3x3_wgrad_workspace')
-    ws = _ws(need.value, dy_rows.device)
+    ws = _workspace(lib().pcacc_head_conv3x3_wgrad_workspace_bytes, dy_rows.device, int(n), int(h), int(w), int(c_in), int(c_out))
     _check(lib().pcacc_head_conv3x3_wgrad(_dev(dy_rows, torch.float32, 'dy'), _dev(x_rows, None, 'x'), _dtype_code(x_rows), _dev(dw),
                                           _dev(db) if db is not None else None, int(n), int(h), int(w), int(c_in), int(c_out), _dev(ws),
-                                          ctypes.c_size_t(ws.numel()), _stream()), 'head_conv3x3_wgrad')
+                                          ws.numel(), _stream()), 'head_conv3x3_wgrad')
     return dw, db
 
 
@@ -1152,12 +1074,12 @@ def rows_linear_split(x, x_amax, w, bias=None, residual=None, pre_relu=False, po
         y16 = torch.empty((rows, n), dtype=torch.bfloat16, device=x.device)
         _check(lib().pcacc_rows_linear_split_dual(_dev(x, torch.float32, 'x'), _dev(x_amax, torch.float32, 'x_amax'), _opt(in_mask, torch.float32, 'in_mask'),
                                                   _dev(w, torch.float32, 'w'), _opt(bias, torch.float32, 'bias'), _opt(residual, torch.float32, 'residual'),
-                                                  _opt(out_mask, torch.float32, 'out_mask'), _dev(y), _dev(y16), _dev(y_amax), _i64(rows), int(k),
+                                                  _opt(out_mask, torch.float32, 'out_mask'), _dev(y), _dev(y16), _dev(y_amax), rows, int(k),
                                                   int(n), flags, _stream()), 'rows_linear_split_dual')
         return y, y_amax, y16
     _check(lib().pcacc_rows_linear_split(_dev(x, torch.float32, 'x'), _dev(x_amax, torch.float32, 'x_amax'), _opt(in_mask, torch.float32, 'in_mask'),
                                          _dev(w, torch.float32, 'w'), _opt(bias, torch.float32, 'bias'), _opt(residual, torch.float32, 'residual'),
-                                         _opt(out_mask, torch.float32, 'out_mask'), _dev(y), _opt(y_amax, torch.float32, 'y_amax'), _i64(rows), int(k),
+                                         _opt(out_mask, torch.float32, 'out_mask'), _dev(y), _opt(y_amax, torch.float32, 'y_amax'), rows, int(k),
                                          int(n), flags, _stream()), 'rows_linear_split')
     return (y, y_amax) if want_amax else y
 
@@ -1172,7 +1094,7 @@ def rows_linear_few_dual(x, w, bias=None, residual=None, pre_relu=False, post_re
     y_amax = _zero256(x.device)
     flags = (1 if pre_relu else 0) | (2 if post_relu else 0)
     _check(lib().pcacc_rows_linear_few_dual(_dev(x, torch.float32, 'x'), _dev(w, torch.float32, 'w'), _opt(bias, torch.float32, 'bias'),
-                                            _opt(residual, torch.float32, 'residual'), _dev(y), _dev(y16), _dev(y_amax), _i64(rows), int(k), int(n),
+                                            _opt(residual, torch.float32, 'residual'), _dev(y), _dev(y16), _dev(y_amax), rows, int(k), int(n),
                                             flags, _stream()), 'rows_linear_few_dual')
     return y, y_amax, y16
 
@@ -1182,12 +1104,10 @@ def rows_wgrad_split(dy, dy_amax, x, x_amax, dy_mask=None, x_relu=False, split=F
     rows, n = dy.shape
     k = x.shape[1]
     out = torch.empty((n, k + 1), dtype=torch.float32, device=dy.device)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_rows_wgrad_split_workspace_bytes(_i64(rows), int(k), int(n), ctypes.byref(need)), 'rows_wgrad_split_workspace')
-    ws = _ws(need.value, dy.device)
+    ws = _workspace(lib().pcacc_rows_wgrad_split_workspace_bytes, dy.device, rows, int(k), int(n))
     _check(lib().pcacc_rows_wgrad_split(_dev(dy, torch.float32, 'dy'), _dev(dy_amax, torch.float32, 'dy_amax'), _opt(dy_mask, torch.float32, 'dy_mask'),
                                         _dev(x, torch.float32, 'x'), _dev(x_amax, torch.float32, 'x_amax'), (1 if x_relu else 0) | (2 if split else 0),
-                                        _i64(rows), int(k), int(n), _dev(out), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'rows_wgrad_split')
+                                        rows, int(k), int(n), _dev(out), _dev(ws), ws.numel(), _stream()), 'rows_wgrad_split')
     return _split_aug(out, n, k, split, rows > 0)
 
 
@@ -1201,7 +1121,7 @@ def rows_linear_cat_split(xa, xa_amax, xb, xb_amax, b_index, w, bias=None, resid
     _check(lib().pcacc_rows_linear_cat_split(_dev(xa, torch.float32, 'xa'), _dev(xa_amax, torch.float32, 'xa_amax'), _dev(xb, torch.float32, 'xb'),
                                              _dev(xb_amax, torch.float32, 'xb_amax'), _opt(b_index, torch.int32, 'b_index'), int(ka), None,
                                              _dev(w, torch.float32, 'w'), _opt(bias, torch.float32, 'bias'), _opt(residual, torch.float32, 'residual'),
-                                             None, None, _dev(y), None, 0, _opt(y_amax, torch.float32, 'y_amax'), _i64(rows), int(k), int(n), flags,
+                                             None, None, _dev(y), None, 0, _opt(y_amax, torch.float32, 'y_amax'), rows, int(k), int(n), flags,
                                              _stream()), 'rows_linear_cat_split')
     return (y, y_amax) if want_amax else y
 
@@ -1218,8 +1138,7 @@ def rows_linear_cat_backward_split(gy, gy_amax, w_t, dy_mask, xa, xb, b_index, p
                                              _opt(b_index, torch.int32, 'b_index'), 0, _opt(dy_mask, torch.float32, 'dy_mask'),
                                              _dev(w_t, torch.float32, 'w_t'), None, None,
                                              _dev(xa, torch.float32, 'xa') if pre_relu else None, _dev(xb, torch.float32, 'xb') if pre_relu else None,
-                                             _dev(ga), _dev(gb), int(ka), _dev(g_amax), _i64(rows), int(n), int(ka + kb), 0, _stream()),
-           'rows_linear_cat_backward_split')
+                                             _dev(ga), _dev(gb), int(ka), _dev(g_amax), rows, int(n), int(ka + kb), 0, _stream()), 'rows_linear_cat_backward_split')
     return ga, gb, g_amax
 
 
@@ -1229,14 +1148,12 @@ def rows_wgrad_cat_split(dy, dy_amax, xa, xa_amax, xb, xb_amax, b_index, dy_mask
     ka = xa.shape[1]
     k = ka + xb.shape[1]
     out = torch.empty((n, k + 1), dtype=torch.float32, device=dy.device)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_rows_wgrad_split_workspace_bytes(_i64(rows), int(k), int(n), ctypes.byref(need)), 'rows_wgrad_split_workspace')
-    ws = _ws(need.value, dy.device)
+    ws = _workspace(lib().pcacc_rows_wgrad_split_workspace_bytes, dy.device, rows, int(k), int(n))
     _check(lib().pcacc_rows_wgrad_cat_split(_dev(dy, torch.float32, 'dy'), _dev(dy_amax, torch.float32, 'dy_amax'), _opt(dy_mask, torch.float32, 'dy_mask'),
                                             _dev(xa, torch.float32, 'xa'), _dev(xa_amax, torch.float32, 'xa_amax'), _dev(xb, torch.float32, 'xb'),
                                             _dev(xb_amax, torch.float32, 'xb_amax'), _opt(b_index, torch.int32, 'b_index'), int(ka),
-                                            (1 if x_relu else 0) | (2 if split else 0), _i64(rows), int(k), int(n), _dev(out), _dev(ws),
-                                            ctypes.c_size_t(ws.numel()), _stream()), 'rows_wgrad_cat_split')
+                                            (1 if x_relu else 0) | (2 if split else 0), rows, int(k), int(n), _dev(out), _dev(ws),
+                                            ws.numel(), _stream()), 'rows_wgrad_cat_split')
     return _split_aug(out, n, k, split, rows > 0)
 
 
@@ -1252,7 +1169,7 @@ def upload_small(values, dtype, device):
         return out
     if nbytes % 4:
         raise NativeError('upload_small: byte size must be a multiple of 4')
-    _check(lib().pcacc_upload_words(ctypes.c_void_p(host.data_ptr()), _i64(nbytes // 4), _dev(out), _stream()), 'upload_words')
+    _check(lib().pcacc_upload_words(ctypes.c_void_p(host.data_ptr()), nbytes // 4, _dev(out), _stream()), 'upload_words')
     return out
 
 
@@ -1266,17 +1183,13 @@ def bilinear_gather_backward_sorted(grad_out, shape, points, map_idx, x_scale, y
     if k == 0:
         return out.zero_()
     cells = torch.empty((k,), dtype=torch.int32, device=dev)
-    _check(lib().pcacc_bilinear_base_cells(_dev(points, torch.float32, 'points'), _dev(map_idx, torch.int32, 'map_idx'), _i64(k),
-                                           int(n_maps), int(h), int(w), ctypes.c_float(x_scale), ctypes.c_float(y_scale),
-                                           _dev(cells), _stream()), 'bilinear_base_cells')
+    _check(lib().pcacc_bilinear_base_cells(_dev(points, torch.float32, 'points'), _dev(map_idx, torch.int32, 'map_idx'), k,
+                                           int(n_maps), int(h), int(w), x_scale, y_scale, _dev(cells), _stream()), 'bilinear_base_cells')
     offs, order = csr_build(cells, n_maps * h * w + 1)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_bilinear_sorted_workspace_bytes(_i64(k), int(c), _dtype_code(grad_out), ctypes.byref(need)), 'bilinear_sorted_workspace')
-    ws = _ws(need.value, dev)
+    ws = _workspace(lib().pcacc_bilinear_sorted_workspace_bytes, dev, k, int(c), _dtype_code(grad_out))
     _check(lib().pcacc_bilinear_gather_backward_sorted(_dev(grad_out, None, 'grad_out'), _dtype_code(grad_out), int(n_maps), int(h),
                                                        int(w), int(c), _dev(points, torch.float32, 'points'), _dev(offs, torch.int32),
-                                                       _dev(order, torch.int32), _i64(k), ctypes.c_float(x_scale), ctypes.c_float(y_scale),
-                                                       _dev(out), _dtype_code(out), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()),
+                                                       _dev(order, torch.int32), k, x_scale, y_scale, _dev(out), _dtype_code(out), _dev(ws), ws.numel(), _stream()),
            'bilinear_gather_backward_sorted')
     return out
 
@@ -1287,17 +1200,13 @@ def prep_points(points, tsfm12, noise, noise_scale, scale, crop_xy, z_min, z_max
     out = torch.empty_like(points)
     keep = torch.empty((m,), dtype=torch.uint8, device=points.device)
     _check(lib().pcacc_prep_points(_dev(points, torch.float64, 'points'), _dev(tsfm12, torch.float64, 'tsfm12') if tsfm12 is not None else None,
-                                   _dev(noise, torch.float64, 'noise') if noise is not None else None, ctypes.c_double(noise_scale),
-                                   ctypes.c_double(scale), ctypes.c_double(crop_xy), ctypes.c_double(z_min), ctypes.c_double(z_max),
-                                   1 if remove_ground else 0, ctypes.c_double(ground_z), _i64(m), _dev(out), _dev(keep), _stream()),
-           'prep_points')
+                                   _dev(noise, torch.float64, 'noise') if noise is not None else None, noise_scale, scale, crop_xy, z_min, z_max,
+                                   1 if remove_ground else 0, ground_z, m, _dev(out), _dev(keep), _stream()), 'prep_points')
     return out, keep
 
 
 def _sinkhorn_ws(P, k, dev):
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_sinkhorn_train_workspace_bytes(int(P), int(k), ctypes.byref(need)), 'sinkhorn_train_workspace')
-    return _ws(need.value, dev)
+    return _workspace(lib().pcacc_sinkhorn_train_workspace_bytes, dev, int(P), int(k))
 
 
 def sinkhorn_forward(log_alpha, n_iters):
@@ -1309,7 +1218,7 @@ def sinkhorn_forward(log_alpha, n_iters):
     lc = torch.empty((n_iters, P, k), dtype=torch.float32, device=dev)
     ws = _sinkhorn_ws(P, k, dev)
     _check(lib().pcacc_sinkhorn_forward(_dev(log_alpha, torch.float32, 'log_alpha'), int(P), int(k), int(n_iters), _dev(out), _dev(lr),
-                                        _dev(lc), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'sinkhorn_forward')
+                                        _dev(lc), _dev(ws), ws.numel(), _stream()), 'sinkhorn_forward')
     return out, lr, lc
 
 
@@ -1320,7 +1229,7 @@ def sinkhorn_backward(grad_log_perm, log_alpha, lse_rows, lse_cols):
     ws = _sinkhorn_ws(P, k, log_alpha.device)
     _check(lib().pcacc_sinkhorn_backward(_dev(grad_log_perm, torch.float32, 'grad'), _dev(log_alpha, torch.float32, 'log_alpha'),
                                          _dev(lse_rows, torch.float32), _dev(lse_cols, torch.float32), int(P), int(k), int(n_iters),
-                                         _dev(g), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'sinkhorn_backward')
+                                         _dev(g), _dev(ws), ws.numel(), _stream()), 'sinkhorn_backward')
     return g
 
 
@@ -1338,20 +1247,18 @@ def seg_loss_forward(logits, plane, labels, rows, n):
     metric = torch.empty((4, 2), dtype=torch.float64, device=dev)
     lov = torch.empty((2, n), dtype=torch.float32, device=dev)
     saved = torch.zeros((8,), dtype=torch.float32, device=dev)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_seg_loss_workspace_bytes(_i64(n), ctypes.byref(need)), 'seg_loss_workspace')
-    ws = _ws(need.value, dev)
-    _check(lib().pcacc_seg_loss_forward(_dev(logits, None, 'logits'), _dtype_code(logits), _i64(plane), _dev(labels, torch.int64, 'labels'),
-                                        _opt(rows, torch.int64, 'rows'), _i64(n), _dev(loss), _dev(metric), _dev(lov), _dev(saved), _dev(ws),
-                                        ctypes.c_size_t(ws.numel()), _stream()), 'seg_loss_forward')
+    ws = _workspace(lib().pcacc_seg_loss_workspace_bytes, dev, n)
+    _check(lib().pcacc_seg_loss_forward(_dev(logits, None, 'logits'), _dtype_code(logits), plane, _dev(labels, torch.int64, 'labels'),
+                                        _opt(rows, torch.int64, 'rows'), n, _dev(loss), _dev(metric), _dev(lov), _dev(saved), _dev(ws),
+                                        ws.numel(), _stream()), 'seg_loss_forward')
     return loss, metric, lov, saved
 
 
 def seg_loss_backward(logits, plane, labels, rows, n, lovasz_grad, saved, grad_bce, grad_lovasz):
     """Gradient of grad_bce * cross entropy + grad_lovasz * Lovasz w.r.t. the whole logit tensor (0 outside the rows)."""
     grad = torch.empty_like(logits)
-    _check(lib().pcacc_seg_loss_backward(_dev(logits, None, 'logits'), _dtype_code(logits), _i64(plane), _dev(labels, torch.int64, 'labels'),
-                                         _opt(rows, torch.int64, 'rows'), _i64(n), _i64(logits.numel() // 2), _dev(lovasz_grad, torch.float32),
+    _check(lib().pcacc_seg_loss_backward(_dev(logits, None, 'logits'), _dtype_code(logits), plane, _dev(labels, torch.int64, 'labels'),
+                                         _opt(rows, torch.int64, 'rows'), n, logits.numel() // 2, _dev(lovasz_grad, torch.float32),
                                          _dev(saved, torch.float32), _opt(grad_bce, torch.float32, 'grad_bce'),
                                          _opt(grad_lovasz, torch.float32, 'grad_lovasz'), _dev(grad), _stream()), 'seg_loss_backward')
     return grad
@@ -1364,15 +1271,13 @@ def offset_loss_forward(points, time_indice, inst_labels, label_base, ego_motion
     m = rows.shape[0] if rows is not None else n
     out = torch.empty((3,), dtype=torch.float32, device=dev)
     gt = torch.empty((m, 2), dtype=torch.float32, device=dev)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_offset_loss_workspace_bytes(_i64(m), _i64(k), ctypes.byref(need)), 'offset_loss_workspace')
-    ws = _ws(need.value, dev)
+    ws = _workspace(lib().pcacc_offset_loss_workspace_bytes, dev, m, k)
     _check(lib().pcacc_offset_loss_forward(_dev(points, torch.float32, 'points'), _dev(time_indice, torch.int64, 'time_indice'),
                                            _dev(inst_labels, torch.int64, 'inst_labels'), _dev(label_base, torch.int64, 'label_base'),
                                            _dev(ego_motion, torch.float32, 'ego_motion'), _dev(inst_motion, torch.float32, 'inst_motion'),
-                                           int(n_frames), _i64(n), _i64(k), _dev(transformed_points, torch.float32, 'transformed_points'),
-                                           _dev(offset_est, torch.float32, 'offset_est'), _opt(rows, torch.int64, 'rows'), _i64(m), _dev(out),
-                                           _dev(gt), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'offset_loss_forward')
+                                           int(n_frames), n, k, _dev(transformed_points, torch.float32, 'transformed_points'),
+                                           _dev(offset_est, torch.float32, 'offset_est'), _opt(rows, torch.int64, 'rows'), m, _dev(out),
+                                           _dev(gt), _dev(ws), ws.numel(), _stream()), 'offset_loss_forward')
     return out, gt
 
 
@@ -1380,7 +1285,7 @@ def offset_loss_backward(offset_gt, offset_est, rows, grad_norm, grad_dir):
     grad = torch.empty_like(offset_est)
     m = offset_gt.shape[0]
     _check(lib().pcacc_offset_loss_backward(_dev(offset_gt, torch.float32), _dev(offset_est, torch.float32, 'offset_est'),
-                                            _opt(rows, torch.int64, 'rows'), _i64(m), _i64(offset_est.shape[0]),
+                                            _opt(rows, torch.int64, 'rows'), m, offset_est.shape[0],
                                             _opt(grad_norm, torch.float32, 'grad_norm'), _opt(grad_dir, torch.float32, 'grad_dir'), _dev(grad),
                                             _stream()), 'offset_loss_backward')
     return grad
@@ -1392,7 +1297,7 @@ def frames_max(x):
     plane = x[0, 0].numel()
     out = torch.empty((S,) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)
     arg = torch.empty((S,) + tuple(x.shape[2:]), dtype=torch.uint8, device=x.device)
-    _check(lib().pcacc_frames_max(_dev(x, None, 'x'), _dtype_code(x), _i64(S), int(T), _i64(plane), _dev(out), _dev(arg), _stream()), 'frames_max')
+    _check(lib().pcacc_frames_max(_dev(x, None, 'x'), _dtype_code(x), S, int(T), plane, _dev(out), _dev(arg), _stream()), 'frames_max')
     return out, arg
 
 
@@ -1400,8 +1305,8 @@ def frames_max_backward(grad_out, arg, frames):
     S = grad_out.shape[0]
     plane = grad_out[0].numel()
     g = torch.empty((S, frames) + tuple(grad_out.shape[1:]), dtype=grad_out.dtype, device=grad_out.device)
-    _check(lib().pcacc_frames_max_backward(_dev(grad_out, None, 'grad_out'), _dev(arg, torch.uint8), _dtype_code(grad_out), _i64(S), int(frames),
-                                           _i64(plane), _dev(g), _stream()), 'frames_max_backward')
+    _check(lib().pcacc_frames_max_backward(_dev(grad_out, None, 'grad_out'), _dev(arg, torch.uint8), _dtype_code(grad_out), S, int(frames),
+                                           plane, _dev(g), _stream()), 'frames_max_backward')
     return g
 
 
@@ -1418,7 +1323,7 @@ def rows_linear_cat(xa, xb, b_index, w, bias=None, residual=None, pre_relu=False
     flags = (1 if pre_relu else 0) | (2 if post_relu else 0)
     _check(lib().pcacc_rows_linear_cat_bf16(_dev(xa, torch.bfloat16, 'xa'), _dev(xb, torch.bfloat16, 'xb'), _opt(b_index, torch.int32, 'b_index'),
                                             int(ka), None, _dev(w, torch.float32, 'w'), _opt(bias, torch.float32, 'bias'),
-                                            _opt(residual, torch.bfloat16, 'residual'), None, None, _dev(y), None, 0, _i64(rows), int(k), int(n),
+                                            _opt(residual, torch.bfloat16, 'residual'), None, None, _dev(y), None, 0, rows, int(k), int(n),
                                             flags, _stream()), 'rows_linear_cat')
     return y
 
@@ -1433,7 +1338,7 @@ def rows_linear_cat_backward(gy, w_t, dy_mask, xa, xb, b_index, pre_relu):
     _check(lib().pcacc_rows_linear_cat_bf16(_dev(gy, torch.bfloat16, 'gy'), None, _opt(b_index, torch.int32, 'b_index'), 0,
                                             _opt(dy_mask, torch.bfloat16, 'dy_mask'), _dev(w_t, torch.float32, 'w_t'), None, None,
                                             _dev(xa, torch.bfloat16, 'xa') if pre_relu else None, _dev(xb, torch.bfloat16, 'xb') if pre_relu else None,
-                                            _dev(ga), _dev(gb), int(ka), _i64(rows), int(n), int(ka + kb), 0, _stream()), 'rows_linear_cat_backward')
+                                            _dev(ga), _dev(gb), int(ka), rows, int(n), int(ka + kb), 0, _stream()), 'rows_linear_cat_backward')
     return ga, gb
 
 
@@ -1443,13 +1348,11 @@ def rows_wgrad_cat(dy, xa, xb, b_index, dy_mask=None, x_relu=False, split=False)
     ka = xa.shape[1]
     k = ka + xb.shape[1]
     out = torch.empty((n, k + 1), dtype=torch.float32, device=dy.device)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_rows_wgrad_bf16_workspace_bytes(_i64(rows), int(k), int(n), ctypes.byref(need)), 'rows_wgrad_bf16_workspace')
-    ws = _ws(need.value, dy.device)
+    ws = _workspace(lib().pcacc_rows_wgrad_bf16_workspace_bytes, dy.device, rows, int(k), int(n))
     _check(lib().pcacc_rows_wgrad_cat_bf16(_dev(dy, torch.bfloat16, 'dy'), _opt(dy_mask, torch.bfloat16, 'dy_mask'), _dev(xa, torch.bfloat16, 'xa'),
                                            _dev(xb, torch.bfloat16, 'xb'), _opt(b_index, torch.int32, 'b_index'), int(ka),
                                            (1 if x_relu else 0) | (2 if split else 0),
-                                           _i64(rows), int(k), int(n), _dev(out), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'rows_wgrad_cat')
+                                           rows, int(k), int(n), _dev(out), _dev(ws), ws.numel(), _stream()), 'rows_wgrad_cat')
     return _split_aug(out, n, k, split, rows > 0)
 
 
@@ -1458,15 +1361,14 @@ def svd3(a):
     n = a.shape[0]
     u, v = torch.empty_like(a), torch.empty_like(a)
     s = torch.empty((n, 3), dtype=torch.float32, device=a.device)
-    _check(lib().pcacc_svd3(_dev(a, torch.float32, 'a'), _i64(n), _dev(u), _dev(s), _dev(v), _stream()), 'svd3')
+    _check(lib().pcacc_svd3(_dev(a, torch.float32, 'a'), n, _dev(u), _dev(s), _dev(v), _stream()), 'svd3')
     return u, s, v
 
 
 def svd3_backward(u, s, v, gu, gs, gv):
     ga = torch.empty_like(u)
     _check(lib().pcacc_svd3_backward(_dev(u, torch.float32), _dev(s, torch.float32), _dev(v, torch.float32), _opt(gu, torch.float32, 'grad_u'),
-                                     _opt(gs, torch.float32, 'grad_s'), _opt(gv, torch.float32, 'grad_v'), _i64(u.shape[0]), _dev(ga), _stream()),
-           'svd3_backward')
+                                     _opt(gs, torch.float32, 'grad_s'), _opt(gv, torch.float32, 'grad_v'), u.shape[0], _dev(ga), _stream()), 'svd3_backward')
     return ga
 
 
@@ -1477,9 +1379,7 @@ def bn_rows_supported(x):
 
 
 def _bn_ws(rows, c, dev):
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_bn_rows_workspace_bytes(_i64(rows), int(c), ctypes.byref(need)), 'bn_rows_workspace')
-    return _ws(need.value, dev)
+    return _workspace(lib().pcacc_bn_rows_workspace_bytes, dev, rows, int(c))
 
 
 def bn_rows_forward(x, gamma, beta, eps, momentum, running_mean, running_var, relu=False):
@@ -1491,10 +1391,10 @@ def bn_rows_forward(x, gamma, beta, eps, momentum, running_mean, running_var, re
     invstd = torch.empty((c,), dtype=torch.float32, device=x.device)
     ws = _bn_ws(rows, c, x.device)
     fn = lib().pcacc_bn_relu_rows_forward if relu else lib().pcacc_bn_rows_forward
-    _check(fn(_dev(x, None, 'x'), _dtype_code(x), _i64(rows), int(c), _opt(gamma, torch.float32, 'gamma'),
-                                       _opt(beta, torch.float32, 'beta'), ctypes.c_float(eps), ctypes.c_float(momentum),
+    _check(fn(_dev(x, None, 'x'), _dtype_code(x), rows, int(c), _opt(gamma, torch.float32, 'gamma'),
+                                       _opt(beta, torch.float32, 'beta'), eps, momentum,
                                        _opt(running_mean, torch.float32, 'running_mean'), _opt(running_var, torch.float32, 'running_var'),
-                                       _dev(y), _dev(mean), _dev(invstd), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'bn_rows_forward')
+                                       _dev(y), _dev(mean), _dev(invstd), _dev(ws), ws.numel(), _stream()), 'bn_rows_forward')
     return y, mean, invstd
 
 
@@ -1508,10 +1408,10 @@ def bn_rows_forward_dual(x, gamma, beta, eps, momentum, running_mean, running_va
     mean = torch.empty((c,), dtype=torch.float32, device=x.device)
     invstd = torch.empty((c,), dtype=torch.float32, device=x.device)
     ws = _bn_ws(rows, c, x.device)
-    _check(lib().pcacc_bn_rows_forward_dual(_dev(x, torch.float32, 'x'), _i64(rows), int(c), _opt(gamma, torch.float32, 'gamma'), _opt(beta, torch.float32, 'beta'),
-                                            ctypes.c_float(eps), ctypes.c_float(momentum), _opt(running_mean, torch.float32, 'running_mean'),
+    _check(lib().pcacc_bn_rows_forward_dual(_dev(x, torch.float32, 'x'), rows, int(c), _opt(gamma, torch.float32, 'gamma'), _opt(beta, torch.float32, 'beta'),
+                                            eps, momentum, _opt(running_mean, torch.float32, 'running_mean'),
                                             _opt(running_var, torch.float32, 'running_var'), 1 if relu else 0, _dev(y), _dev(y16), _dev(am), _dev(mean),
-                                            _dev(invstd), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'bn_rows_forward_dual')
+                                            _dev(invstd), _dev(ws), ws.numel(), _stream()), 'bn_rows_forward_dual')
     return y, y16, am, mean, invstd
 
 
@@ -1527,20 +1427,20 @@ def bn_rows_backward(grad_y, x, gamma, save_mean, save_invstd, relu_beta=None, r
         raise NativeError('bn_rows_backward: grad_y must have the type of x')
     if want_amax:
         am = _zero256(x.device)
-        _check(lib().pcacc_bn_rows_backward_m(_dev(grad_y, None, 'grad_y'), _dev(x, None, 'x'), _dtype_code(x), _i64(rows), int(c),
+        _check(lib().pcacc_bn_rows_backward_m(_dev(grad_y, None, 'grad_y'), _dev(x, None, 'x'), _dtype_code(x), rows, int(c),
                                               _opt(gamma, torch.float32, 'gamma'), _opt(relu_beta, torch.float32, 'beta') if relu else None, 1 if relu else 0,
                                               _dev(save_mean, torch.float32), _dev(save_invstd, torch.float32), _dev(gx), _dev(am), _dev(gg), _dev(gb),
-                                              _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'bn_rows_backward_m')
+                                              _dev(ws), ws.numel(), _stream()), 'bn_rows_backward_m')
         return gx, gg, gb, am
     if relu:
-        _check(lib().pcacc_bn_relu_rows_backward(_dev(grad_y, None, 'grad_y'), _dev(x, None, 'x'), _dtype_code(x), _i64(rows), int(c),
+        _check(lib().pcacc_bn_relu_rows_backward(_dev(grad_y, None, 'grad_y'), _dev(x, None, 'x'), _dtype_code(x), rows, int(c),
                                                  _opt(gamma, torch.float32, 'gamma'), _opt(relu_beta, torch.float32, 'beta'),
                                                  _dev(save_mean, torch.float32), _dev(save_invstd, torch.float32), _dev(gx), _dev(gg), _dev(gb),
-                                                 _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'bn_relu_rows_backward')
+                                                 _dev(ws), ws.numel(), _stream()), 'bn_relu_rows_backward')
         return gx, gg, gb
-    _check(lib().pcacc_bn_rows_backward(_dev(grad_y, None, 'grad_y'), _dev(x, None, 'x'), _dtype_code(x), _i64(rows), int(c),
+    _check(lib().pcacc_bn_rows_backward(_dev(grad_y, None, 'grad_y'), _dev(x, None, 'x'), _dtype_code(x), rows, int(c),
                                         _opt(gamma, torch.float32, 'gamma'), _dev(save_mean, torch.float32), _dev(save_invstd, torch.float32),
-                                        _dev(gx), _dev(gg), _dev(gb), _dev(ws), ctypes.c_size_t(ws.numel()), _stream()), 'bn_rows_backward')
+                                        _dev(gx), _dev(gg), _dev(gb), _dev(ws), ws.numel(), _stream()), 'bn_rows_backward')
     return gx, gg, gb
 
 
@@ -1550,7 +1450,7 @@ def tube_rows(xyz, slot, slot_centre, n_frames):
     n = xyz.shape[0]
     rows = torch.empty((n, 4), dtype=torch.float32, device=xyz.device)
     _check(lib().pcacc_tube_rows(_dev(xyz, torch.float32, 'xyz'), _dev(slot, torch.int32, 'slot'), _dev(slot_centre, torch.float32, 'slot_centre'),
-                                 _i64(n), int(n_frames), _dev(rows), _stream()), 'tube_rows')
+                                 n, int(n_frames), _dev(rows), _stream()), 'tube_rows')
     return rows
 
 
@@ -1558,7 +1458,7 @@ def tube_code(geo, motion, frame, n_frames):
     n_inst, c = geo.shape
     code = torch.empty((n_inst * n_frames, 4 * c), dtype=torch.float32, device=geo.device)
     _check(lib().pcacc_tube_code(_dev(geo, torch.float32, 'geo'), _dev(motion, torch.float32, 'motion'), _dev(frame, torch.float32, 'frame'),
-                                 _i64(n_inst), int(n_frames), int(c), _dev(code), _stream()), 'tube_code')
+                                 n_inst, int(n_frames), int(c), _dev(code), _stream()), 'tube_code')
     return code
 
 
@@ -1567,7 +1467,7 @@ def tube_code_backward(grad_code, n_inst, n_frames, c):
     g_geo = torch.empty((n_inst, c), dtype=torch.float32, device=dev)
     g_motion = torch.empty((n_inst, c), dtype=torch.float32, device=dev)
     g_frame = torch.empty((n_inst * n_frames, c), dtype=torch.float32, device=dev)
-    _check(lib().pcacc_tube_code_backward(_dev(grad_code, torch.float32, 'grad_code'), _i64(n_inst), int(n_frames), int(c), _dev(g_geo),
+    _check(lib().pcacc_tube_code_backward(_dev(grad_code, torch.float32, 'grad_code'), n_inst, int(n_frames), int(c), _dev(g_geo),
                                           _dev(g_motion), _dev(g_frame), _stream()), 'tube_code_backward')
     return g_geo, g_motion, g_frame
 
@@ -1590,7 +1490,7 @@ def tube_gap_forward(rows, slot, pose_c, gt_c):
     n = rows.shape[0]
     pp = torch.empty((n, 4), dtype=torch.float32, device=rows.device)
     _check(lib().pcacc_tube_gap_forward(_dev(rows, torch.float32, 'rows'), _dev(slot, torch.int32, 'slot'), _dev(pose_c, torch.float32, 'pose_c'),
-                                        _dev(gt_c, torch.float32, 'gt_c'), _i64(n), _dev(pp), _stream()), 'tube_gap_forward')
+                                        _dev(gt_c, torch.float32, 'gt_c'), n, _dev(pp), _stream()), 'tube_gap_forward')
     return pp
 
 
@@ -1608,7 +1508,7 @@ def tube_gap_backward(rows, slot, pose_c, gt_c, weights, count, wsum, grad_l1, g
     _check(lib().pcacc_tube_gap_backward(_dev(rows, torch.float32, 'rows'), _dev(slot, torch.int32, 'slot'), _dev(pose_c, torch.float32, 'pose_c'),
                                          _dev(gt_c, torch.float32, 'gt_c'), _dev(weights, torch.float32, 'weights'),
                                          _dev(count, torch.float32, 'count'), _dev(wsum, torch.float32, 'wsum'),
-                                         _opt(grad_l1, torch.float32, 'grad_l1'), _opt(grad_l2, torch.float32, 'grad_l2'), _i64(n), _dev(g16),
+                                         _opt(grad_l1, torch.float32, 'grad_l1'), _opt(grad_l2, torch.float32, 'grad_l2'), n, _dev(g16),
                                          _stream()), 'tube_gap_backward')
     return g16
 
@@ -1630,9 +1530,9 @@ def maxpool2x2(x_rows):
     n, h, w, c = x_rows.shape
     out = torch.empty((n, h // 2, w // 2, c), dtype=x_rows.dtype, device=x_rows.device)
     if x_rows.dtype == torch.float32:
-        _check(lib().pcacc_maxpool2x2_f32(_dev(x_rows, torch.float32, 'x'), _i64(n), int(h), int(w), int(c), _dev(out), _stream()), 'maxpool2x2')
+        _check(lib().pcacc_maxpool2x2_f32(_dev(x_rows, torch.float32, 'x'), n, int(h), int(w), int(c), _dev(out), _stream()), 'maxpool2x2')
     else:
-        _check(lib().pcacc_maxpool2x2_bf16(_dev(x_rows, torch.bfloat16, 'x'), _i64(n), int(h), int(w), int(c), _dev(out), _stream()), 'maxpool2x2')
+        _check(lib().pcacc_maxpool2x2_bf16(_dev(x_rows, torch.bfloat16, 'x'), n, int(h), int(w), int(c), _dev(out), _stream()), 'maxpool2x2')
     return out
 
 
@@ -1662,8 +1562,7 @@ def pool_skip_relu_backward(y_rows, grad_pooled, grad_skip, want_amax=False):
                 grad_skip, pitch = grad_skip.contiguous(), c
             gs_ptr = ctypes.c_void_p(grad_skip.data_ptr())
         _check(lib().pcacc_pool_skip_relu_backward_strided_y32(_dev(y_rows, torch.float32, 'y'), _opt(grad_pooled, torch.bfloat16, 'grad_pooled'), gs_ptr,
-                                                               _i64(pitch), _i64(n), int(h), int(w), int(c), _dev(out), _stream()),
-               'pool_skip_relu_backward')
+                                                               pitch, n, int(h), int(w), int(c), _dev(out), _stream()), 'pool_skip_relu_backward')
         return out
     out = torch.empty_like(y_rows)
     f32 = y_rows.dtype == torch.float32
@@ -1679,12 +1578,11 @@ def pool_skip_relu_backward(y_rows, grad_pooled, grad_skip, want_amax=False):
     if f32:
         amax = _zero256(y_rows.device) if want_amax else None
         _check(lib().pcacc_pool_skip_relu_backward_strided_f32(_dev(y_rows, torch.float32, 'y'), _opt(grad_pooled, torch.float32, 'grad_pooled'), gs_ptr,
-                                                               _i64(pitch), _i64(n), int(h), int(w), int(c), _dev(out),
+                                                               pitch, n, int(h), int(w), int(c), _dev(out),
                                                                _dev(amax) if want_amax else None, _stream()), 'pool_skip_relu_backward')
         return (out, amax) if want_amax else out
     _check(lib().pcacc_pool_skip_relu_backward_strided_bf16(_dev(y_rows, torch.bfloat16, 'y'), _opt(grad_pooled, torch.bfloat16, 'grad_pooled'), gs_ptr,
-                                                            _i64(pitch), _i64(n), int(h), int(w), int(c), _dev(out), _stream()),
-           'pool_skip_relu_backward')
+                                                            pitch, n, int(h), int(w), int(c), _dev(out), _stream()), 'pool_skip_relu_backward')
     return out
 
 
@@ -1700,8 +1598,7 @@ def pfn_block_forward(xa, pooled, p2v, w0, b0, ws, w1, b1):
     hr = torch.empty((rows, 32), dtype=torch.bfloat16, device=xa.device)
     _check(lib().pcacc_pfn_block_forward(_dev(xa, torch.bfloat16, 'xa'), _opt(pooled, torch.bfloat16, 'pooled'), _opt(p2v, torch.int32, 'p2v'),
                                          _dev(w0, torch.float32, 'w0'), _opt(b0, torch.float32, 'b0'), _dev(ws, torch.float32, 'ws'),
-                                         _dev(w1, torch.float32, 'w1'), _opt(b1, torch.float32, 'b1'), _dev(out), _dev(hr), _i64(rows),
-                                         _stream()), 'pfn_block_forward')
+                                         _dev(w1, torch.float32, 'w1'), _opt(b1, torch.float32, 'b1'), _dev(out), _dev(hr), rows, _stream()), 'pfn_block_forward')
     return out, hr
 
 
@@ -1713,14 +1610,12 @@ def pfn_block_backward(xa, pooled, p2v, hr, grad_out, w0, ws, w1):
     gxa = torch.empty((rows, 32 if two else 64), dtype=torch.bfloat16, device=dev)
     gxb = torch.empty((rows, 32), dtype=torch.bfloat16, device=dev) if two else None
     gp = torch.empty((5184,), dtype=torch.float32, device=dev)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_pfn_block_backward_workspace_bytes(_i64(rows), ctypes.byref(need)), 'pfn_block_backward_workspace')
-    ws_buf = _ws(need.value, dev)
+    ws_buf = _workspace(lib().pcacc_pfn_block_backward_workspace_bytes, dev, rows)
     _check(lib().pcacc_pfn_block_backward(_dev(xa, torch.bfloat16, 'xa'), _opt(pooled, torch.bfloat16, 'pooled'), _opt(p2v, torch.int32, 'p2v'),
                                           _dev(hr, torch.bfloat16, 'relu_h'), _dev(grad_out, torch.bfloat16, 'grad_out'),
                                           _dev(w0, torch.float32, 'w0'), _dev(ws, torch.float32, 'ws'), _dev(w1, torch.float32, 'w1'),
-                                          _dev(gxa), _opt(gxb, torch.bfloat16, 'grad_xb'), _dev(gp), _i64(rows), _dev(ws_buf),
-                                          ctypes.c_size_t(ws_buf.numel()), _stream()), 'pfn_block_backward')
+                                          _dev(gxa), _opt(gxb, torch.bfloat16, 'grad_xb'), _dev(gp), rows, _dev(ws_buf),
+                                          ws_buf.numel(), _stream()), 'pfn_block_backward')
     return gxa, gxb, gp
 
 
@@ -1737,7 +1632,7 @@ def pfn_block_split_forward(xa, xa_amax, pooled, pooled_amax, p2v, w0, b0, ws, w
                                                _opt(pooled_amax, torch.float32, 'pooled_amax'), _opt(p2v, torch.int32, 'p2v'),
                                                _dev(w0, torch.float32, 'w0'), _opt(b0, torch.float32, 'b0'), _dev(ws, torch.float32, 'ws'),
                                                _dev(w1, torch.float32, 'w1'), _opt(b1, torch.float32, 'b1'), _dev(out), _dev(hr), _dev(xmask),
-                                               _dev(hmask), _dev(out_amax), _dev(hr_amax), _i64(rows), _stream()), 'pfn_block_split_forward')
+                                               _dev(hmask), _dev(out_amax), _dev(hr_amax), rows, _stream()), 'pfn_block_split_forward')
     return out, hr, xmask, hmask, out_amax, hr_amax
 
 
@@ -1752,7 +1647,7 @@ def pfn_block_split_forward_dual(xa, xa_amax, pooled, pooled_amax, p2v, w0, b0, 
                                                     _opt(pooled_amax, torch.float32, 'pooled_amax'), _opt(p2v, torch.int32, 'p2v'),
                                                     _dev(w0, torch.float32, 'w0'), _opt(b0, torch.float32, 'b0'), _dev(ws, torch.float32, 'ws'),
                                                     _dev(w1, torch.float32, 'w1'), _opt(b1, torch.float32, 'b1'), _dev(out), _dev(out16), _dev(hr16),
-                                                    _dev(out_amax), _i64(rows), _stream()), 'pfn_block_split_forward_dual')
+                                                    _dev(out_amax), rows, _stream()), 'pfn_block_split_forward_dual')
     return out, out_amax, out16, hr16
 
 
@@ -1767,8 +1662,7 @@ def pfn_block_split_dgrad(grad_out, grad_out_amax, xmask, hmask, w0, ws, w1, two
     _check(lib().pcacc_pfn_block_split_dgrad(_dev(grad_out, torch.float32, 'grad_out'), _dev(grad_out_amax, torch.float32, 'grad_out_amax'),
                                              _dev(xmask, torch.int64, 'xmask'), _dev(hmask, torch.int32, 'hmask'), _dev(w0, torch.float32, 'w0'),
                                              _dev(ws, torch.float32, 'ws'), _dev(w1, torch.float32, 'w1'), _dev(gxa),
-                                             _opt(gxb, torch.float32, 'grad_xb'), _dev(dh), _dev(gx_amax), _dev(dh_amax), _i64(rows), _stream()),
-           'pfn_block_split_dgrad')
+                                             _opt(gxb, torch.float32, 'grad_xb'), _dev(dh), _dev(gx_amax), _dev(dh_amax), rows, _stream()), 'pfn_block_split_dgrad')
     return gxa, gxb, dh, gx_amax, dh_amax
 
 
@@ -1786,12 +1680,10 @@ def ego_affinity_backward(grad_aff, aff, params):
     """-> (grad_dot [P,k,k], grad_params [2])."""
     gd = torch.empty_like(aff)
     gp = torch.empty((2,), dtype=torch.float32, device=aff.device)
-    need = ctypes.c_size_t(0)
-    _check(lib().pcacc_ego_affinity_backward_workspace_bytes(ctypes.byref(need)), 'ego_affinity_backward_workspace')
-    ws = _ws(need.value, aff.device)
+    ws = _workspace(lib().pcacc_ego_affinity_backward_workspace_bytes, aff.device)
     _check(lib().pcacc_ego_affinity_backward(_dev(grad_aff, torch.float32, 'grad_affinity'), _dev(aff, torch.float32, 'affinity'),
-                                             _dev(params, torch.float32, 'params'), _i64(aff.numel()), _dev(gd), _dev(gp), _dev(ws),
-                                             ctypes.c_size_t(ws.numel()), _stream()), 'ego_affinity_backward')
+                                             _dev(params, torch.float32, 'params'), aff.numel(), _dev(gd), _dev(gp), _dev(ws),
+                                             ws.numel(), _stream()), 'ego_affinity_backward')
     return gd, gp
 
 
@@ -1866,5 +1758,5 @@ def inv4x4(m):
     """[..., 4, 4] f32 -> inverses, one launch (include/pcacc.h: pcacc_inv4x4)."""
     x = m.contiguous().float()
     out = torch.empty_like(x)
-    _check(lib().pcacc_inv4x4(_dev(x, torch.float32, 'm'), _i64(x.numel() // 16), _dev(out), _stream()), 'inv4x4')
+    _check(lib().pcacc_inv4x4(_dev(x, torch.float32, 'm'), x.numel() // 16, _dev(out), _stream()), 'inv4x4')
     return out
