@@ -438,6 +438,42 @@ int pcacc_cluster(const float *points, const float *offset, const uint8_t *sel, 
                   int64_t *labels, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C2. Instance-segmentation evaluation of the test loop -- toolbox/cluster_eval.py:71-152 (ClusterEvaluation.forward:
+ * instances and their classes :79-95, coverage :98-124, precision / recall :127-152) for every sample of a batch in one
+ * call, as libs/loss.py:261-270 (evaluate_cluster) runs it sample by sample from libs/tester.py:93.  Replaces the double
+ * loop over (estimated, ground-truth) instance pairs -- two masks of length n and two host syncs per pair -- with one pass
+ * over the points and one over the non-empty pairs.  Integer atomics only: deterministic, and every number is the
+ * reference's, bit for bit.
+ *   inst_est, inst_gt [n] i64   instance ids, any value; 0 = background; compared per sample only
+ *   mos [n]                     ground-truth moving label, zero / non-zero, of type mos_dtype (PCACC_MOS_*):
+ *                               input_dict['sd_labels'][:, 0] as it is (i64), its .float(), or a bool tensor
+ *   batch [n] i32               sample of every point, 0 <= batch < n_batches
+ *   inst_capacity               rows per table (all samples together); pair_capacity: non-empty (est, gt) pairs
+ *   out                         16 i32 header words, then inst_capacity rows of estimated and inst_capacity rows of
+ *                               ground-truth instances; out_bytes >= 64 + 2 * inst_capacity * 32
+ *     header  [0] status: 0, or a sum of 1 = more instances than inst_capacity, 2 = more pairs than pair_capacity (call
+ *             again with more: nothing is truncated silently), 4 = a sample has more than 2^24 points (the class of an
+ *             instance is round() of an fp32 mean of 0/1 values, cluster_eval.py:85,94; below 2^24 points that is the
+ *             integer rule used here, above it the reference's own sum is no longer exact), 8 = a batch index out of range;
+ *             [1] estimated rows, [2] ground-truth rows, [3] non-empty pairs.  With status != 0 the rows are void.
+ *     row     { i64 id; u32 count; u32 moving; i32 sample; i32 class; f32 best_iou; i32 pad } in order of first sight --
+ *             the reference visits them by ascending id inside a sample (torch.unique), the host sorts.
+ *             class = 1 iff 2 * moving > count (Python's round(): a tie goes to 0).  best_iou = max over the instances
+ *             of the other table, same sample and class, of fp32(inter) / fp32(count_est + count_gt - inter), one IEEE
+ *             division as torch divides two int64 sums; 0.0 when none overlaps; -1.0 for an ESTIMATED instance whose
+ *             class has no ground-truth instance in its sample (cluster_eval.py:135).
+ * A status that only the device knows cannot be the return value (no synchronisation here): the return value covers the
+ * arguments, including n > n_batches * 2^24, where some sample is too large whatever `batch` holds.
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_MOS_I64 0
+#define PCACC_MOS_F32 1
+#define PCACC_MOS_U8 2
+int pcacc_cluster_eval_workspace_bytes(int64_t n, int32_t n_batches, int32_t inst_capacity, int32_t pair_capacity, size_t *bytes /*host*/);
+int pcacc_cluster_eval(const int64_t *inst_est, const int64_t *inst_gt, const void *mos, int32_t mos_dtype, const int32_t *batch, int64_t n,
+                       int32_t n_batches, int32_t inst_capacity, int32_t pair_capacity, void *out, size_t out_bytes,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

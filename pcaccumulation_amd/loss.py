@@ -3,8 +3,8 @@ compute_iou), libs/lovasz_softmax.py (Lovasz-Softmax, Berman et al. 2018, MIT) a
 
 Needed so that BASELINE.json's "fwd+bwd" metric runs end to end.  The terms that read the path's large tensors -- the two
 segmentation losses (cross entropy + Lovasz + IoU counters) and the offset loss -- are fused HIP passes (SURVEY.md 8f rank 3,
-csrc/loss.hip, ops.seg_loss / ops.offset_loss); the rest is a handful of scalar operations.  The cluster-evaluation hook (test
-mode only) is not carried over.
+csrc/loss.hip, ops.seg_loss / ops.offset_loss); the rest is a handful of scalar operations.  The cluster-evaluation hook of the test
+loop (evaluate_cluster, cluster_eval_offset) lives in cluster_eval.py and is created on first use.
 """
 import numpy as np
 import torch
@@ -106,9 +106,30 @@ class FuseLoss(nn.Module):
         self.ignore_index = -1
         self.softmax = nn.Softmax(dim=1)
         self._w_cache = {}
+        self._config = config
         for k, v in config.items():
             if k.startswith('w_') or k == 'obj_gamma':
                 setattr(self, k, v)
+
+    @property
+    def cluster_eval_offset(self):
+        """libs/loss.py:87.  Created when first asked for (the test loop only) and kept outside the module tree: constructing a FuseLoss opens
+        no file and registers nothing."""
+        ev = self.__dict__.get('_cluster_eval_offset')
+        if ev is None:
+            from .cluster_eval import ClusterEvaluation
+            ev = self.__dict__['_cluster_eval_offset'] = ClusterEvaluation(self._config)
+        return ev
+
+    def evaluate_cluster(self, predictions, input_dict):
+        """libs/loss.py:261-270: the instance evaluation of every sample of the batch -- one kernel call and one transfer instead of a call per
+        sample.  The moving labels go in as they are stored (no .float() copy)."""
+        time_indice = input_dict['time_indice']
+        n_batches = predictions.get('_n_batches')                     # MotionNet's test mode leaves it: no .max() read-back
+        if n_batches is None:
+            n_batches = int(time_indice[:, 0].max() + 1) if time_indice.size(0) else 1
+        self.cluster_eval_offset.forward_batch(predictions['inst_labels_est'], input_dict['inst_labels'][:, 0], input_dict['sd_labels'][:, 0],
+                                               time_indice[:, 0], n_batches)
 
     def get_ce_weights(self, gt_label, max_weights=50):
         """libs/loss.py:90-108, 'sqrt_inv_freq' mode (counts stay on the device: no .item())."""

@@ -633,6 +633,29 @@ def cluster(points, offset, sel, batch, n_batches, voxel_size, eps, min_samples,
     return labels
 
 
+CLUSTER_EVAL_HEADER_BYTES, CLUSTER_EVAL_ROW_BYTES = 64, 32
+_MOS_CODE = {torch.int64: 0, torch.float32: 1, torch.uint8: 2, torch.bool: 2}
+
+
+def cluster_eval(inst_est, inst_gt, mos, batch, n_batches, inst_capacity, pair_capacity):
+    """The instance tables of the test loop's clustering evaluation for a whole batch; see include/pcacc.h (C2).  inst_est, inst_gt [n] i64,
+    mos [n] i64 / f32 / bool / u8, batch [n] i32 -> one uint8 device tensor: 64 header bytes, inst_capacity estimated rows, inst_capacity
+    ground-truth rows of 32 bytes (pcaccumulation_amd/cluster_eval.py reads it with ONE transfer and calls again with more room when the
+    header says the tables were too small)."""
+    n = inst_est.shape[0]
+    if mos.dtype not in _MOS_CODE:
+        raise NativeError('cluster_eval: mos must be int64, float32, bool or uint8, got %s' % mos.dtype)
+    if inst_gt.shape[0] != n or mos.shape[0] != n or batch.shape[0] != n:
+        raise NativeError('cluster_eval: inst_est, inst_gt, mos and batch must have one entry per point')
+    dev = inst_est.device
+    out = torch.empty((CLUSTER_EVAL_HEADER_BYTES + 2 * int(inst_capacity) * CLUSTER_EVAL_ROW_BYTES,), dtype=torch.uint8, device=dev)
+    est, gt = _dev(inst_est, torch.int64, 'inst_est'), _dev(inst_gt, torch.int64, 'inst_gt')
+    ws = _workspace(lib().pcacc_cluster_eval_workspace_bytes, dev, n, int(n_batches), int(inst_capacity), int(pair_capacity))
+    _check(lib().pcacc_cluster_eval(est, gt, _dev(mos, None, 'mos'), _MOS_CODE[mos.dtype], _dev(batch, torch.int32, 'batch'), n, int(n_batches),
+                                    int(inst_capacity), int(pair_capacity), _dev(out), out.numel(), _dev(ws), ws.numel(), _stream()), 'cluster_eval')
+    return out
+
+
 def conv3x3_supported(c_in, c_out):
     return c_in >= 32 and c_out >= 32 and c_in % 32 == 0 and c_out % 32 == 0
 
