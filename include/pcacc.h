@@ -474,6 +474,51 @@ int pcacc_cluster_eval(const int64_t *inst_est, const int64_t *inst_gt, const vo
                        void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C3. Point-to-point ICP pose refinement, J independent jobs in one call -- models/egomotion.py:9-28 (refine_pose_with_icp),
+ * :360-384 (pose_refinement: every frame t >= 1 of a sample onto its anchor frame, model.ego_icp) and models/alignnet.py:54-112
+ * (run_icp / refine_pose_by_icp: every frame of an instance onto the instance's frame 0, model.tpointnet_icp).  Replaces one
+ * Open3D registration_icp(source, target, threshold, eye(4), TransformationEstimationPointToPoint(),
+ * ICPConvergenceCriteria(max_iteration)) call on the host per frame and per instance.
+ *   points [n,3] f32          all points; a segment s is the rows seg_offsets[s] .. seg_offsets[s+1]
+ *   seg_offsets [n_seg+1] i32 ascending, 0 <= offset <= n; n_seg <= 65535
+ *   jobs [n_jobs,2] i32       { source segment, target segment }; jobs may share a target (its index is built once per call)
+ *   init [n_jobs,4,4] f64     initial pose, applied to the source first (rows 0-2 are read, row 3 is taken as 0 0 0 1); NULL = identity
+ *   threshold                 maximum correspondence distance (> 0); also the edge of the grid cells
+ *   out_T [n_jobs,4,4] f64    T @ init, T the transformation registration_icp would return for the pre-transformed source: the
+ *                             refined pose both call sites form (`tsfm @ initial_pose`, egomotion.py:25)
+ *   out_fitness, out_rmse [n_jobs] f64   correspondences / source points, sqrt(sum d^2 / correspondences) (0 without any) of the last evaluation
+ *   out_iters [n_jobs] i32    updates applied (1 .. max_iter; 0 when max_iter = 0)
+ *   out_status [n_jobs] i32   a sum of PCACC_ICP_* below
+ * Algorithm (all float64, fp32 inputs promoted): correspondence of a source point = its nearest target point if within the
+ * threshold (equal distances: the LOWEST target index); then at most max_iter rounds of { update = least-squares rigid
+ * transform of the correspondences (Umeyama without scale: centroids, 3x3 covariance, SVD, reflection fix), identity without
+ * correspondences; T = update @ T; correspondences again; stop when |d fitness| < 1e-6 and |d rmse| < 1e-6 }.  The source is
+ * transformed by the composed pose each round (Open3D transforms it round by round: the same up to float64 rounding).
+ * Deterministic: no floating-point atomics, fixed-order sums; two calls give the same bits.  Convergence is decided per job on
+ * the device; the call never synchronises.
+ * Supported range: a point takes part only if its coordinates are finite and |coordinate| / threshold < 32767 (cells of edge
+ * `threshold`, 16 bits per axis); any other point -- as source after the current pose, or as target -- has no correspondence
+ * (it is never clamped into an edge cell and forms no address), and still counts in the denominator of the fitness.
+ * Empty source, empty target, no correspondence: identity update, fitness 0, rmse 0.  Fewer than three non-collinear
+ * correspondences (rank-deficient covariance) are outside the parity claim: the missing singular vectors are completed to a
+ * right-handed orthonormal basis (u0 x e_m for the axis m on which u0 is smallest, then u0 x u1), a zero covariance gives the
+ * identity rotation -- always a finite proper rotation, the same every run.  A singular value at or below 1e-10 * mean(t . q)
+ * (the rounding noise of the uncentred float64 sums the covariance is formed from) counts as zero.
+ * Tables that cannot be trusted (offsets not ascending or outside [0, n], a job naming a segment outside [0, n_seg)) address
+ * nothing: every job returns identity with PCACC_ICP_BAD_TABLE.
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_ICP_EMPTY_SOURCE 1
+#define PCACC_ICP_EMPTY_TARGET 2
+#define PCACC_ICP_NO_CORRESPONDENCE 4   /* the last evaluation found none */
+#define PCACC_ICP_RANK_DEFICIENT 8      /* some update completed a singular vector */
+#define PCACC_ICP_BAD_TABLE 16
+int pcacc_icp_point_to_point_workspace_bytes(int64_t n, int32_t n_seg, int32_t n_jobs, size_t *bytes /*host*/);
+int pcacc_icp_point_to_point(const float *points, int64_t n, const int32_t *seg_offsets, int32_t n_seg, const int32_t *jobs,
+                             int32_t n_jobs, const double *init, double threshold, int32_t max_iter, double *out_T,
+                             double *out_fitness, double *out_rmse, int32_t *out_iters, int32_t *out_status,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

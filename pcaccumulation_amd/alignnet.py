@@ -1,8 +1,8 @@
 """Instance-wise reconstruction wrapper: host mirror of models/alignnet.py (AlignNet, update_gt_inst_motion).
-Plain PyTorch-ROCm; the Open3D ICP refinements (`model.tpointnet_icp`) are off the hot path."""
+Plain PyTorch-ROCm; the ICP refinement (`model.tpointnet_icp`) is one batched native call (icp.py)."""
 import torch
 
-from . import native
+from . import icp, native
 from .ops import scatter
 from .tpointnet import TPointNet, BaseModel, reconstruct_sequence
 
@@ -38,8 +38,6 @@ class AlignNet(BaseModel):
         self.icp_threshold = config['tpointnet']['icp_threshold']
         self.mode = config['misc']['mode']
         self.refine_with_icp = config['model']['tpointnet_icp']
-        if self.refine_with_icp:
-            raise NotImplementedError('model.tpointnet_icp (Open3D ICP) is off the hot path (configs/default.yaml:117)')
 
     @staticmethod
     def padding_flags(inst_indice, time_indice, K, T, weights=None):
@@ -121,6 +119,7 @@ class AlignNet(BaseModel):
 
         results['tpointnet_loss_terms'] = dict()
         total = None
+        cloud_start = cloud                                                # the padded input points (alignnet.py:226), before any step moves them
         net_in['inst_motion_gt'] = remaining
         shared = self.alignment.shared_terms(net_in)                       # what the iterations have in common, once
         for it in range(self.n_iterations):
@@ -134,6 +133,12 @@ class AlignNet(BaseModel):
             # what is left of the GT motion after this step (remaining <- remaining @ step^-1) and the composed estimate
             # (total <- step @ total), alignnet.py:257-263: both come out of the slot kernel
             remaining, total = out['remaining'], out['total']
+
+        if self.refine_with_icp:
+            # alignnet.py:264-266: every frame of every instance onto the instance's frame 0, from the composed estimate, 50 rounds at most
+            results['_inst_icp_init'] = total                                   # the estimate the refinement started from
+            total, results['_icp_anchor_empty'], results['_inst_icp_status'] = icp.refine_instance_poses(cloud_start, frames, p_labels, total,
+                                                                                                            self.icp_threshold, 50)
 
         src = input_dict['transformed_points']
         moved_est = reconstruct_sequence(src, tcol[:, 1], labels, total, T)

@@ -14,7 +14,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import native, ops
+from . import icp, native, ops
 
 _EPS = 1e-20                       # toolbox/utils.py:13
 
@@ -130,9 +130,7 @@ class EgoMotionHead(nn.Module):
         self.dataset = config['data']['dataset']
         self.icp_threshold = pe['icp_threshold']
         self.icp_max_iter = pe['icp_max_iter']
-        self.refine_with_icp = config['model']['ego_icp']
-        if self.refine_with_icp:
-            raise NotImplementedError('model.ego_icp (Open3D ICP refinement) is off the hot path (configs/default.yaml:115)')
+        self.refine_with_icp = config['model']['ego_icp']                   # test-time ICP refinement of the sequence poses (icp.py)
         # 'reference': torch.randperm on the HOST generator, the reference's RNG stream (bit-reproducible against it);
         # 'device'   : the same uniform subset drawn with torch.randperm on the GPU generator (no 50 k-element host shuffle,
         #              1.8 ms each on the host, 32 of them per 4-sequence step).
@@ -413,14 +411,24 @@ class EgoMotionHead(nn.Module):
         means = ops.scatter(norms, pair, dim=0, dim_size=P, reduce="mean", plan=ops.ScatterPlan(pair, P))
         return means[:, 0].sum(), means[:, 1].sum(), P
 
-    def _finish(self, B, T, total_l1, total_l2, count, perm_matrix_list, chained_pose_est_list, chained_pose_gt_list, results):
-        """models/egomotion.py:448-469."""
+    def _finish(self, B, T, total_l1, total_l2, count, perm_matrix_list, chained_pose_est_list, chained_pose_gt_list, results, icp_inputs=None):
+        """models/egomotion.py:439-469.  icp_inputs (model.ego_icp): (raw input points [N,3], sample * T + frame [N], fb_est_per_point [N,1])."""
         chains = getattr(perm_matrix_list, 'chains', None)
         if chains is not None and chains[0].shape[0] == len(chained_pose_est_list):
             chained_pose_est, chained_pose_gt = chains
         else:
             chained_pose_est = torch.stack(chained_pose_est_list)
             chained_pose_gt = torch.stack(chained_pose_gt_list)
+        if self.refine_with_icp:
+            # models/egomotion.py:439-441: every frame's predicted-background points onto the anchor frame's, from the chained estimate; the
+            # refined poses (no gradient) replace it before the errors and ego_motion_est are formed, frame 0 becomes the identity.  All
+            # samples and frames in one call, nothing read back (the reference: one Open3D call and two transfers per frame)
+            if icp_inputs is None:
+                raise ValueError('model.ego_icp needs the raw points: forward_pillars(..., icp_inputs=(input_points, frame_idx, fb_est_per_point))')
+            raw_points, raw_frame, fb_per_point = icp_inputs
+            results['_ego_icp_init'] = chained_pose_est                         # the estimate the refinement started from
+            chained_pose_est, results['_ego_icp_status'] = icp.refine_ego_poses(raw_points, raw_frame, fb_per_point.reshape(raw_points.shape[0], -1)[:, 0] == 0,
+                                                                              chained_pose_est, B, T, self.icp_threshold, self.icp_max_iter)
         rot_est, rot_gt = chained_pose_est[:, :3, :3], chained_pose_gt[:, :3, :3]
         trans_est, trans_gt = chained_pose_est[:, :3, 3].unsqueeze(-1), chained_pose_gt[:, :3, 3].unsqueeze(-1)
         # 0-d tensors here; MotionNet.forward turns them into Python floats (the reference's .item(), egomotion.py:456)
@@ -435,7 +443,7 @@ class EgoMotionHead(nn.Module):
         results['ego_motion_est'] = chained_pose_est.view(B, T, 4, 4)
         results['ego_motion_gt'] = chained_pose_gt.view(B, T, 4, 4)
 
-    def forward_pillars(self, geo_rows, pillar_mean, pidx, ego_motion_gt, results, frame_offsets, bg_sorted_idx, bg_counts):
+    def forward_pillars(self, geo_rows, pillar_mean, pidx, ego_motion_gt, results, frame_offsets, bg_sorted_idx, bg_counts, icp_inputs=None):
         """Same computation as forward(), fed from pillar-level tensors instead of dense canvases, with no host sync:
           geo_rows [n_cells, C]  rows of the (un-normalised) ego feature map, normalised after the key-point gather;  pillar_mean [M,3]
           frame_offsets  host list [B*T+1]: slice of the cell-ordered pillar list (pidx.frame_pillars) per frame
@@ -472,7 +480,7 @@ class EgoMotionHead(nn.Module):
             sequences.append((points_list, getters, bg_list, ego_motion_gt[b]))
         flat = dict(sp=sp, cells=cells, geo_rows=geo_rows, pillar_mean=pillar_mean, bg_sorted_idx=bg_sorted_idx, bg_at=bg_at) if fast else None
         total_l1, total_l2, count = self._estimate_pairs(sequences, T, perm_l, rel_est, rel_gt, ch_est, ch_gt, normalise=True, flat=flat)
-        self._finish(B, T, total_l1, total_l2, count, perm_l, ch_est, ch_gt, results)
+        self._finish(B, T, total_l1, total_l2, count, perm_l, ch_est, ch_gt, results, icp_inputs)
 
     def forward(self, bev_feats, fb_est, occ_map, pts_mean_map, ego_motion_gt, input_points, fb_est_per_point, time_indice, results):
         """Reference signature (models/egomotion.py:387-469): dense [B,T,C,Ny,Nx] maps in, results dict filled."""
@@ -488,6 +496,7 @@ class EgoMotionHead(nn.Module):
                 bg_list.append((fb_est[b, t, 0].reshape(-1) == 0)[occ])
             sequences.append(self._sequence_from_masks(points_list, feats_list, bg_list, ego_motion_gt[b]))
         total_l1, total_l2, count = self._estimate_pairs(sequences, T, perm_l, rel_est, rel_gt, ch_est, ch_gt)
-        self._finish(B, T, total_l1, total_l2, count, perm_l, ch_est, ch_gt, results)
+        icp_inputs = (input_points, time_indice[:, 0].long() * T + time_indice[:, 1].long(), fb_est_per_point) if self.refine_with_icp else None
+        self._finish(B, T, total_l1, total_l2, count, perm_l, ch_est, ch_gt, results, icp_inputs)
         for k in ('ego_rot_error', 'ego_trans_error'):                       # reference signature returns floats
             results[k] = results[k].item()

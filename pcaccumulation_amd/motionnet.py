@@ -19,7 +19,7 @@ import weakref
 import torch
 import torch.nn as nn
 
-from . import native, ops
+from . import icp, native, ops
 from .alignnet import AlignNet
 from .cluster import Cluster
 from .egomotion import EgoMotionHead
@@ -308,8 +308,9 @@ class MotionNet(nn.Module):
 
         # 4. ego motion (fp32).  The per-cell L2 normalisation of motionnet.py:199 (no epsilon, trap 7) is applied to the
         #    gathered key-point rows inside the head instead of to the whole map.
+        icp_inputs = (input_points, frame_idx, fb_est_per_point) if self.ego_motion_head.refine_with_icp else None
         self.ego_motion_head.forward_pillars(geo_rows, pillar_mean, pidx, ego_motion_gt, results,
-                                             frame_offsets, bg_sorted_idx, bg_counts)
+                                             frame_offsets, bg_sorted_idx, bg_counts, icp_inputs=icp_inputs)
         # Everything below works on detached features and poses (motionnet.py:205-209): the graph of the pillar encoder, the
         # U-Net, the two heads and the ego head is complete here.  A training step may hook in (`after_ego`) to evaluate the loss terms
         # that live on it and back-propagate them now (FuseLoss.early_terms, distributed.DataParallelStep): the largest kernels of
@@ -417,10 +418,14 @@ class MotionNet(nn.Module):
     def _resolve_scalars(results):
         """Python floats for the scalar results the reference produces with .item() (egomotion.py:456, alignnet.py:280-281):
         one asynchronous device->host transfer for all of them, waited for when a value is first read (lazy.py)."""
-        keys = [k for k in ('ego_rot_error', 'ego_trans_error', 'inst_l2_error', 'dynamic_inst_l2_error')
+        keys = [k for k in ('ego_rot_error', 'ego_trans_error', 'inst_l2_error', 'dynamic_inst_l2_error', '_icp_anchor_empty')
                 if k in results and torch.is_tensor(dict.__getitem__(results, k))]
         if keys:
-            for k, v in zip(keys, lazy_scalars([dict.__getitem__(results, k) for k in keys])):
+            values = lazy_scalars([dict.__getitem__(results, k) for k in keys])
+            if keys[-1] == '_icp_anchor_empty':          # model.tpointnet_icp: the kernel's empty-anchor flag rides along; reading any scalar raises on it
+                for v in values:
+                    v.convert = icp.guarded(v.copy, len(keys) - 1, v.convert)
+            for k, v in zip(keys, values):
                 results[k] = v
 
     def _stpn_heads(self, stpn_map, points, batch_idx):

@@ -656,6 +656,32 @@ def cluster_eval(inst_est, inst_gt, mos, batch, n_batches, inst_capacity, pair_c
     return out
 
 
+ICP_EMPTY_SOURCE, ICP_EMPTY_TARGET, ICP_NO_CORRESPONDENCE, ICP_RANK_DEFICIENT, ICP_BAD_TABLE = 1, 2, 4, 8, 16
+
+
+def icp_point_to_point(points, seg_offsets, jobs, init, threshold, max_iter):
+    """Point-to-point ICP of J (source segment, target segment) jobs in one call; see include/pcacc.h (C3).  points [n,3] f32, seg_offsets [S+1] i32,
+    jobs [J,2] i32, init [J,4,4] f64 or None -> (T @ init [J,4,4] f64, fitness [J] f64, rmse [J] f64, iterations [J] i32, status [J] i32).  Nothing
+    is read back: the caller looks at `status` at its next transfer."""
+    n, n_seg, J = points.shape[0], seg_offsets.shape[0] - 1, jobs.shape[0]
+    dev = points.device
+    pose = torch.empty((J, 4, 4), dtype=torch.float64, device=dev)
+    fitness = torch.empty((J,), dtype=torch.float64, device=dev)
+    rmse = torch.empty((J,), dtype=torch.float64, device=dev)
+    iters = torch.empty((J,), dtype=torch.int32, device=dev)
+    status = torch.empty((J,), dtype=torch.int32, device=dev)
+    if init is not None and tuple(init.shape) != (J, 4, 4):
+        raise NativeError('icp_point_to_point: init must be [J,4,4], got %s' % (tuple(init.shape),))
+    if J == 0:
+        return pose, fitness, rmse, iters, status
+    ws = _workspace(lib().pcacc_icp_point_to_point_workspace_bytes, dev, n, int(n_seg), int(J))
+    _check(lib().pcacc_icp_point_to_point(_dev(points, torch.float32, 'points') if n else None, n, _dev(seg_offsets, torch.int32, 'seg_offsets'), int(n_seg),
+                                          _dev(jobs, torch.int32, 'jobs'), int(J), _dev(init, torch.float64, 'init') if init is not None else None,
+                                          float(threshold), int(max_iter), _dev(pose), _dev(fitness), _dev(rmse), _dev(iters), _dev(status),
+                                          _dev(ws), ws.numel(), _stream()), 'icp_point_to_point')
+    return pose, fitness, rmse, iters, status
+
+
 def conv3x3_supported(c_in, c_out):
     return c_in >= 32 and c_out >= 32 and c_in % 32 == 0 and c_out % 32 == 0
 
