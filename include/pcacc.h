@@ -519,6 +519,62 @@ int pcacc_icp_point_to_point(const float *points, int64_t n, const int32_t *seg_
                              void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C4. Accumulated scene cloud: a persistent voxel map that takes the points of one window per call and hands back one centroid per
+ * occupied voxel.  The reference has no such function (it shows per-window clouds with Open3D); this replaces the copy of every
+ * window's results['rec_est'] to the host and np.unique / Open3D voxel_down_sample there.
+ * Inputs of one add
+ *   points [n,3] f32          the window's points, 1 <= n <= 2^30
+ *   pose [4,4] f64            window-to-world, rows 0-2 are read; NULL = identity
+ *   moving [n] u8             predicted-moving flag (non-zero = moving); NULL = all 0
+ *   stamp                     one time stamp for the whole call
+ *   voxel_size                > 0, finite, the same for every call on a map
+ * Per point, all float64 with no FMA contraction, in this order and no other:
+ *   w_a = ((r_a0 * x + r_a1 * y) + r_a2 * z) + t_a;  i_a = floor(w_a / voxel_size) (one IEEE division);
+ *   q_a = llrint(w_a * 65536) (round to nearest even).
+ * A point is valid iff every w_a is finite, |w_a| < 32768 and -2^20 <= i_a < 2^20.  An invalid point is counted (`dropped`) and
+ * contributes nothing: it is never clamped and forms no address.
+ * Key of a voxel: (i_x + 2^20) << 42 | (i_y + 2^20) << 21 | (i_z + 2^20); ascending keys = lexicographic (x, y, z).
+ * The map: `capacity` rows, of which the first state[PCACC_ACCUM_NUM_VOXELS] are in use, ascending and duplicate-free in `keys`:
+ *   keys   [capacity] i64
+ *   acc    [5][capacity] i64      field-major: count, moving, sum q_x, sum q_y, sum q_z
+ *   stamps [2][capacity] i32      smallest and largest stamp of the calls that touched the voxel
+ *   state  [PCACC_ACCUM_STATE_WORDS] i64 device words, all 0 for an empty map (indices below)
+ * Everything is an integer and integer additions commute: the map depends on the SET of (point, flag, stamp) triples it was given,
+ * not on the order of points inside a call, of the calls, or on the run.
+ * pcacc_accum_add merges OUT OF PLACE: it reads in_* (in_capacity rows; may be NULL when in_capacity = 0) and writes the merged map
+ * to out_* (out_capacity rows, distinct buffers).  If the merged map has more than out_capacity voxels NOTHING is written to out_*,
+ * state[STATUS] = PCACC_ACCUM_TOO_SMALL and state[NEEDED] = the rows it takes; NUM_VOXELS and DROPPED stay, in_* are intact, and the
+ * caller repeats the call with larger out_* tables.  Otherwise state[STATUS] = 0, state[NUM_VOXELS] = rows of out_*, state[DROPPED]
+ * grows by this call's invalid points.  A state[NUM_VOXELS] outside [0, in_capacity] addresses nothing: PCACC_ACCUM_BAD_STATE.
+ * The status lives in a device word because only the device knows it (no synchronisation here); the return value covers the arguments.
+ * pcacc_accum_extract: the first m rows of a map, in key order, of which a row is kept iff count >= min_count and, when
+ * use_fraction != 0, float64(moving) / float64(count) <= max_moving_fraction.  Every output has room for m rows; *out_n = rows kept.
+ *   out_points [m,3] f32      float32((float64(sum q_a) / float64(count)) * 2^-16)
+ *   out_coords [m,3] i32      voxel indices (i_x, i_y, i_z)
+ *   out_count, out_moving [m] i64;  out_t_first, out_t_last [m] i32
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_ACCUM_STATE_WORDS 8
+#define PCACC_ACCUM_NUM_VOXELS 0       /* rows in use */
+#define PCACC_ACCUM_DROPPED 1          /* invalid points of all successful calls */
+#define PCACC_ACCUM_STATUS 2           /* of the last add: 0 or one of the two below */
+#define PCACC_ACCUM_NEEDED 3           /* rows the last add's merged map takes */
+#define PCACC_ACCUM_WINDOW_VOXELS 4    /* distinct voxels of the last add's points */
+#define PCACC_ACCUM_WINDOW_DROPPED 5   /* invalid points of the last add */
+#define PCACC_ACCUM_OK 0
+#define PCACC_ACCUM_TOO_SMALL 1
+#define PCACC_ACCUM_BAD_STATE 2
+int pcacc_accum_add_workspace_bytes(int64_t n, size_t *bytes /*host*/);
+int pcacc_accum_add(const float *points, int64_t n, const double *pose, const uint8_t *moving, int32_t stamp, double voxel_size,
+                    const int64_t *in_keys, const int64_t *in_acc, const int32_t *in_stamps, int64_t in_capacity,
+                    int64_t *out_keys, int64_t *out_acc, int32_t *out_stamps, int64_t out_capacity,
+                    int64_t *state, void *workspace, size_t workspace_bytes, void *stream);
+int pcacc_accum_extract_workspace_bytes(int64_t m, size_t *bytes /*host*/);
+int pcacc_accum_extract(const int64_t *keys, const int64_t *acc, const int32_t *stamps, int64_t capacity, int64_t m, int64_t min_count,
+                        int32_t use_fraction, double max_moving_fraction, float *out_points, int32_t *out_coords, int64_t *out_count,
+                        int64_t *out_moving, int32_t *out_t_first, int32_t *out_t_last, int64_t *out_n,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

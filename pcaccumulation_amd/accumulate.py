@@ -1,0 +1,192 @@
+"""Accumulated scene cloud: a voxel map on the device that grows window by window (include/pcacc.h C4).
+
+The test-mode forward returns results['rec_est']: the points of one T-frame window, motion-compensated into the window's anchor frame.
+AccumulatedCloud merges a scene's worth of such windows into ONE cloud -- one centroid per occupied voxel, with the number of points, how many of
+them were predicted moving, and the first / last time stamp -- without a copy of the points to the host.  All records are integers (fixed-point
+coordinate sums), so the map does not depend on the order of the points, on the order of the calls, or on the run.
+
+    m = AccumulatedCloud(voxel_size=0.1, device='cuda')
+    for k, (results, input_dict, pose) in enumerate(windows):
+        m.add_results(results, input_dict, pose=pose, stamp=k)
+    static = m.extract(min_count=2, max_moving_fraction=0.0)     # dict of device tensors
+
+There is no CPU path: a CPU tensor raises native.NativeError."""
+import numpy as np
+import torch
+
+from . import native
+
+_FIELDS = ('points', 'coords', 'count', 'moving', 't_first', 't_last')
+
+
+def _tables(capacity, device):
+    return (torch.empty((capacity,), dtype=torch.int64, device=device),
+            torch.empty((native.ACCUM_FIELDS, capacity), dtype=torch.int64, device=device),
+            torch.empty((2, capacity), dtype=torch.int32, device=device))
+
+
+class AccumulatedCloud(object):
+    def __init__(self, voxel_size, device='cuda', capacity=1 << 20):
+        voxel_size = float(voxel_size)
+        if not (voxel_size > 0.0 and np.isfinite(voxel_size)):
+            raise ValueError('voxel_size must be a positive finite number, got %r' % voxel_size)
+        if not 1 <= int(capacity) <= native.ACCUM_MAX_CAPACITY:
+            raise ValueError('capacity must lie in [1, 2^30], got %r' % capacity)
+        self.voxel_size = voxel_size
+        self.device = torch.device(device)
+        self.capacity = int(capacity)
+        self._cur = self._alt = self._state = None           # device memory is taken at the first add
+        self._n = 0
+        self._dropped = 0
+
+    # ---- state -------------------------------------------------------------------------------------------------------------------------
+    @property
+    def num_voxels(self):
+        return self._n
+
+    @property
+    def dropped(self):
+        """Points that were not accumulated: a non-finite coordinate, |coordinate| >= 32768 or a voxel index outside +-2^20."""
+        return self._dropped
+
+    def _ensure(self):
+        if self.device.type != 'cuda':
+            raise native.NativeError('AccumulatedCloud lives on the GPU (got device %s); the HIP path has no CPU fallback' % self.device)
+        if self._cur is None:
+            self._cur = _tables(self.capacity, self.device)
+            self._state = torch.zeros((native.ACCUM_STATE_WORDS,), dtype=torch.int64, device=self.device)
+
+    def clear(self):
+        self._n = self._dropped = 0
+        if self._state is not None:
+            self._state.zero_()
+
+    # ---- add ---------------------------------------------------------------------------------------------------------------------------
+    def _pose(self, pose):
+        if pose is None:
+            return None
+        if not torch.is_tensor(pose):
+            pose = torch.from_numpy(np.ascontiguousarray(pose, dtype=np.float64))
+        if tuple(pose.shape) != (4, 4):
+            raise ValueError('pose must be [4,4], got %s' % (tuple(pose.shape),))
+        return pose.to(device=self.device, dtype=torch.float64).contiguous()
+
+    def add(self, points, pose=None, moving=None, stamp=0):
+        """points [n,3] f32 (device), pose [4,4] window-to-world (tensor or array; None = identity), moving [n] bool / integer (non-zero = predicted
+        moving; None = none), stamp: one integer for the call.  Only the map's eight state words are read back."""
+        if not torch.is_tensor(points) or not points.is_cuda:
+            raise native.NativeError('add: points must be a tensor on the GPU; the HIP path has no CPU fallback')
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError('points must be [n,3], got %s' % (tuple(points.shape),))
+        n = points.shape[0]
+        if n > native.ACCUM_MAX_POINTS:
+            raise ValueError('at most 2^30 points per add, got %d' % n)
+        if moving is not None:
+            if not moving.is_cuda:
+                raise native.NativeError('add: moving must live on the GPU')
+            if tuple(moving.shape) != (n,):
+                raise ValueError('moving must be [n], got %s' % (tuple(moving.shape),))
+        if n == 0:
+            return self
+        self._ensure()
+        pts = points.detach().float().contiguous()
+        mv = (moving != 0).to(torch.uint8).contiguous() if moving is not None else None
+        pose = self._pose(pose)
+        out_cap = self.capacity
+        while True:
+            if self._alt is None or self._alt[0].shape[0] != out_cap:
+                self._alt = None                                   # release before taking the larger tables
+                self._alt = _tables(out_cap, self.device)
+            native.accum_add(pts, pose, mv, int(stamp), self.voxel_size, self._cur, self._alt, self._state)
+            state = self._state.tolist()                           # the one read-back of an add
+            status = state[native.ACCUM_STATUS]
+            if status == native.ACCUM_OK:
+                break
+            if status != native.ACCUM_TOO_SMALL:
+                raise native.NativeError('accum_add: the state words do not describe the map (status %d)' % status)
+            need = state[native.ACCUM_NEEDED]
+            if need > native.ACCUM_MAX_CAPACITY:
+                raise native.NativeError('accum_add: the map would take %d voxels, more than 2^30' % need)
+            while out_cap < need:                                  # growth by doubling; the map so far is untouched
+                out_cap = min(2 * out_cap, native.ACCUM_MAX_CAPACITY)
+        self._cur, self._alt = self._alt, self._cur
+        self.capacity = out_cap
+        self._n = state[native.ACCUM_NUM_VOXELS]
+        self._dropped = state[native.ACCUM_DROPPED]
+        return self
+
+    def add_results(self, results, input_dict, pose=None, stamp=0):
+        """A test / val-mode forward: results['rec_est'] with the predicted-moving flag as MotionNet hands it to Cluster
+        (results['mos_est'].argmax(1) == 1).  One sample per batch, or one pose per sample ([B,4,4])."""
+        points = results['rec_est']
+        moving = results['mos_est'].argmax(1) == 1
+        if pose is not None and not torch.is_tensor(pose):
+            pose = torch.from_numpy(np.ascontiguousarray(pose, dtype=np.float64))
+        batch = input_dict['time_indice'][:, 0]
+        if pose is not None and pose.dim() == 3:
+            for b in range(pose.shape[0]):
+                rows = torch.nonzero(batch == b).reshape(-1)
+                self.add(points.index_select(0, rows), pose[b], moving.index_select(0, rows), stamp)
+            return self
+        n_batches = results.get('_n_batches')
+        if n_batches is None:
+            n_batches = int(batch.max()) + 1 if batch.numel() else 1
+        if n_batches != 1:
+            raise ValueError('add_results: %d samples in the batch need one pose per sample, [B,4,4]' % n_batches)
+        return self.add(points, pose, moving, stamp)
+
+    # ---- extract -----------------------------------------------------------------------------------------------------------------------
+    def extract(self, min_count=1, max_moving_fraction=None):
+        """One row per voxel with count >= min_count and, when max_moving_fraction is given, moving / count <= max_moving_fraction, in
+        ascending (x, y, z) voxel order: points [V,3] f32 centroids, coords [V,3] i32, count, moving [V] i64, t_first, t_last [V] i32."""
+        self._ensure()
+        out = native.accum_extract(self._cur, self._n, min_count, max_moving_fraction)
+        kept = int(out[-1]) if self._n else 0
+        return {k: t[:kept] for k, t in zip(_FIELDS, out)}
+
+    # ---- persistence -------------------------------------------------------------------------------------------------------------------
+    def records(self):
+        """The integer records of the map as host arrays: keys [M] i64, acc [5,M] i64 (count, moving, sum q_x, sum q_y, sum q_z), stamps [2,M] i32."""
+        if self._cur is None or self._n == 0:
+            return (np.zeros((0,), np.int64), np.zeros((native.ACCUM_FIELDS, 0), np.int64), np.zeros((2, 0), np.int32))
+        keys, acc, stamps = self._cur
+        return keys[:self._n].cpu().numpy(), acc[:, :self._n].cpu().numpy(), stamps[:, :self._n].cpu().numpy()
+
+    def save(self, path):
+        keys, acc, stamps = self.records()
+        with open(path, 'wb') as f:
+            np.savez(f, keys=keys, acc=acc, stamps=stamps, voxel_size=np.float64(self.voxel_size), dropped=np.int64(self._dropped))
+
+    @classmethod
+    def load(cls, path, device='cuda'):
+        with np.load(path, allow_pickle=False) as z:
+            keys, acc, stamps = z['keys'], z['acc'], z['stamps']
+            voxel_size, dropped = float(z['voxel_size']), int(z['dropped'])
+        m = keys.shape[0]
+        if keys.dtype != np.int64 or acc.dtype != np.int64 or stamps.dtype != np.int32 or acc.shape != (native.ACCUM_FIELDS, m) or stamps.shape != (2, m):
+            raise ValueError('%s does not hold the records of an AccumulatedCloud' % path)
+        if m and (np.any(keys[1:] <= keys[:-1]) or keys[0] < 0):
+            raise ValueError('%s: the keys are not ascending' % path)
+        capacity = 64
+        while capacity < m:
+            capacity *= 2
+        self = cls(voxel_size, device, capacity)
+        self._ensure()
+        if m:
+            self._cur[0][:m] = torch.from_numpy(keys).to(self.device)
+            self._cur[1][:, :m] = torch.from_numpy(acc).to(self.device)
+            self._cur[2][:, :m] = torch.from_numpy(stamps).to(self.device)
+        host = [0] * native.ACCUM_STATE_WORDS
+        host[native.ACCUM_NUM_VOXELS], host[native.ACCUM_DROPPED] = m, dropped
+        self._state.copy_(torch.tensor(host, dtype=torch.int64))
+        self._n, self._dropped = m, dropped
+        return self
+
+
+def voxel_mean_downsample(points, voxel_size):
+    """One centroid per occupied voxel of `points` [n,3] (device), in ascending (x, y, z) voxel order: one add and one extract."""
+    n = points.shape[0] if torch.is_tensor(points) and points.dim() == 2 else 0
+    capacity = 64
+    while capacity < n:
+        capacity *= 2
+    return AccumulatedCloud(voxel_size, points.device if torch.is_tensor(points) else 'cuda', capacity).add(points).extract()['points']

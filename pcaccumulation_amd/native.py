@@ -682,6 +682,63 @@ def icp_point_to_point(points, seg_offsets, jobs, init, threshold, max_iter):
     return pose, fitness, rmse, iters, status
 
 
+ACCUM_STATE_WORDS, ACCUM_FIELDS = 8, 5
+ACCUM_NUM_VOXELS, ACCUM_DROPPED, ACCUM_STATUS, ACCUM_NEEDED, ACCUM_WINDOW_VOXELS, ACCUM_WINDOW_DROPPED = 0, 1, 2, 3, 4, 5
+ACCUM_OK, ACCUM_TOO_SMALL, ACCUM_BAD_STATE = 0, 1, 2
+ACCUM_MAX_POINTS = ACCUM_MAX_CAPACITY = 1 << 30
+
+
+def _accum_tables(tables, what):
+    """(keys [cap] i64, acc [5,cap] i64, stamps [2,cap] i32) -> their pointers and cap; see include/pcacc.h (C4)."""
+    keys, acc, stamps = tables
+    cap = keys.shape[0]
+    if tuple(acc.shape) != (ACCUM_FIELDS, cap) or tuple(stamps.shape) != (2, cap):
+        raise NativeError('%s: keys [cap], acc [%d,cap], stamps [2,cap] expected, got %s %s %s'
+                          % (what, ACCUM_FIELDS, tuple(keys.shape), tuple(acc.shape), tuple(stamps.shape)))
+    return _dev(keys, torch.int64, what + ' keys'), _dev(acc, torch.int64, what + ' acc'), _dev(stamps, torch.int32, what + ' stamps'), cap
+
+
+def accum_add(points, pose, moving, stamp, voxel_size, tables_in, tables_out, state):
+    """One window into a voxel map, out of place; see include/pcacc.h (C4).  points [n,3] f32 (n >= 1), pose [4,4] f64 or None, moving [n] u8 or None,
+    tables_in / tables_out = (keys, acc, stamps) of the map before and after, state [8] i64.  Nothing is read back: the caller looks at `state`."""
+    n = points.shape[0]
+    if points.dim() != 2 or points.shape[1] != 3 or n < 1:
+        raise NativeError('accum_add: points must be [n,3] with n >= 1, got %s' % (tuple(points.shape),))
+    pts = _dev(points, torch.float32, 'points')
+    if moving is not None and tuple(moving.shape) != (n,):
+        raise NativeError('accum_add: moving must be [n], got %s' % (tuple(moving.shape),))
+    if pose is not None and tuple(pose.shape) != (4, 4):
+        raise NativeError('accum_add: pose must be [4,4], got %s' % (tuple(pose.shape),))
+    if tuple(state.shape) != (ACCUM_STATE_WORDS,):
+        raise NativeError('accum_add: state must be [%d] int64' % ACCUM_STATE_WORDS)
+    ik, ia, is_, icap = _accum_tables(tables_in, 'accum_add input')
+    ok, oa, os_, ocap = _accum_tables(tables_out, 'accum_add output')
+    ws = _workspace(lib().pcacc_accum_add_workspace_bytes, points.device, n)
+    _check(lib().pcacc_accum_add(pts, n, _dev(pose, torch.float64, 'pose') if pose is not None else None,
+                                 _dev(moving, torch.uint8, 'moving') if moving is not None else None, int(stamp), float(voxel_size),
+                                 ik, ia, is_, icap, ok, oa, os_, ocap, _dev(state, torch.int64, 'state'), _dev(ws), ws.numel(), _stream()), 'accum_add')
+
+
+def accum_extract(tables, m, min_count, max_moving_fraction):
+    """The kept voxels of the first m rows of a map in key order; see include/pcacc.h (C4).  -> (points [m,3] f32, coords [m,3] i32, count [m] i64,
+    moving [m] i64, t_first [m] i32, t_last [m] i32, kept [1] i64): the caller reads `kept` and slices."""
+    keys, acc, stamps, cap = _accum_tables(tables, 'accum_extract')
+    dev = tables[0].device
+    m = int(m)
+    points = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    coords = torch.empty((m, 3), dtype=torch.int32, device=dev)
+    count = torch.empty((m,), dtype=torch.int64, device=dev)
+    moving = torch.empty((m,), dtype=torch.int64, device=dev)
+    t_first = torch.empty((m,), dtype=torch.int32, device=dev)
+    t_last = torch.empty((m,), dtype=torch.int32, device=dev)
+    kept = torch.empty((1,), dtype=torch.int64, device=dev)
+    ws = _workspace(lib().pcacc_accum_extract_workspace_bytes, dev, m)
+    _check(lib().pcacc_accum_extract(keys, acc, stamps, cap, m, int(min_count), 0 if max_moving_fraction is None else 1,
+                                     0.0 if max_moving_fraction is None else float(max_moving_fraction), _dev(points), _dev(coords), _dev(count),
+                                     _dev(moving), _dev(t_first), _dev(t_last), _dev(kept), _dev(ws), ws.numel(), _stream()), 'accum_extract')
+    return points, coords, count, moving, t_first, t_last, kept
+
+
 def conv3x3_supported(c_in, c_out):
     return c_in >= 32 and c_out >= 32 and c_in % 32 == 0 and c_out % 32 == 0
 
