@@ -9,6 +9,7 @@
 // reduction, 3x3 Jacobi SVD, reflection fix).  Used when no gradient is required (eval / val / test); training keeps the
 // batched torch formulation for autograd.
 #include "common.h"
+#include "svd3.h"
 
 #define EGO_TILE 64
 
@@ -177,56 +178,7 @@ __global__ __launch_bounds__(256) void ego_rows_finish_kernel(const float *__res
 }
 
 // ---- 4. weighted Kabsch (register_utils.py:268-313), one workgroup per pair -----------------------------------------------------
-__device__ void jacobi_svd3(const double a[3][3], double u[3][3], double s[3], double v[3][3])
-{
-    // one-sided Jacobi on the columns of A: A V = U diag(s)
-    double b[3][3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) { b[i][j] = a[i][j]; v[i][j] = (i == j); }
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        double off = 0.0;
-        for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                double alpha = 0, beta = 0, gamma = 0;
-                for (int i = 0; i < 3; ++i) { alpha += b[i][p] * b[i][p]; beta += b[i][q] * b[i][q]; gamma += b[i][p] * b[i][q]; }
-                off += gamma * gamma;
-                if (fabs(gamma) < 1e-300) continue;
-                const double zeta = (beta - alpha) / (2.0 * gamma);
-                const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
-                for (int i = 0; i < 3; ++i) {
-                    const double bp = b[i][p], bq = b[i][q];
-                    b[i][p] = c * bp - sn * bq; b[i][q] = sn * bp + c * bq;
-                    const double vp = v[i][p], vq = v[i][q];
-                    v[i][p] = c * vp - sn * vq; v[i][q] = sn * vp + c * vq;
-                }
-            }
-        if (off < 1e-40) break;
-    }
-    for (int j = 0; j < 3; ++j) {
-        double n = 0;
-        for (int i = 0; i < 3; ++i) n += b[i][j] * b[i][j];
-        s[j] = sqrt(n);
-    }
-    // order singular values descending (as LAPACK / torch.svd)
-    for (int x = 0; x < 2; ++x)
-        for (int y = x + 1; y < 3; ++y)
-            if (s[y] > s[x]) {
-                const double ts = s[x]; s[x] = s[y]; s[y] = ts;
-                for (int i = 0; i < 3; ++i) {
-                    const double tb = b[i][x]; b[i][x] = b[i][y]; b[i][y] = tb;
-                    const double tv = v[i][x]; v[i][x] = v[i][y]; v[i][y] = tv;
-                }
-            }
-    for (int j = 0; j < 3; ++j)
-        for (int i = 0; i < 3; ++i) u[i][j] = s[j] > 1e-300 ? b[i][j] / s[j] : (i == j);
-    if (s[2] <= 1e-300 * 1.0 || s[2] < 1e-12 * s[0]) {                 // rank-deficient: complete U with a cross product
-        u[0][2] = u[1][0] * u[2][1] - u[2][0] * u[1][1];
-        u[1][2] = u[2][0] * u[0][1] - u[0][0] * u[2][1];
-        u[2][2] = u[0][0] * u[1][1] - u[1][0] * u[0][1];
-    }
-}
-
+// the 3x3 SVD: jacobi_svd3 of svd3.h (orthonormal u, v for every finite input, rank-deficient and tiny ones included)
 __device__ __forceinline__ double block_sum256(double v, double *red)
 {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
