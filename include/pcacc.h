@@ -575,6 +575,50 @@ int pcacc_accum_extract(const int64_t *keys, const int64_t *acc, const int32_t *
                         void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C5. Per-voxel surface normals of the accumulated scene cloud: the covariance of the centroids around every kept voxel, its 3x3
+ * decomposition and an oriented normal.  Replaces the copy of up to 8 M centroids to the host and a KD-tree PCA there.  Adds no lookup,
+ * no nearest-neighbour query and no registration.
+ * Inputs
+ *   keys, acc, stamps, capacity, m                    the first m rows of a map, as for pcacc_accum_extract
+ *   min_count, use_fraction, max_moving_fraction      extract's filter
+ *   radius                    r in {1, 2, 3}, in voxels
+ *   min_neighbors             >= 3
+ *   viewpoints [S,3] f64      sensor position per stamp, or NULL with n_viewpoints = 0;  stamp_base: the stamp of its row 0
+ * Participating set: a row participates iff extract keeps it (count >= min_count, count > 0 and, when use_fraction != 0,
+ * float64(moving) / float64(count) <= max_moving_fraction).  Rows that do not participate are neither output rows nor neighbours.
+ * Output rows: the participating rows in key order -- row j of every output is row j of pcacc_accum_extract under the same filter.
+ * Every output has room for m rows; *out_n = rows written.
+ * Centroid of a row: c_a = (float64(sum q_a) / float64(count)) * 2^-16, the float64 value (not its float32 rounding).
+ * Neighbourhood of voxel i = (x, y, z): every participating voxel with |delta|_inf <= r, itself included, visited in ASCENDING KEY
+ * ORDER (dx = -r..r, inside it dy = -r..r, inside it z ascending).  An offset whose index leaves [-2^20, 2^20) on any axis is skipped
+ * BEFORE a key is formed: nothing out of range is clamped or turned into an address (a key whose y or z field overflowed would
+ * alias another voxel).  k = voxels visited (>= 1).
+ * Arithmetic, all float64 with no FMA contraction, in this order and no other (every sum starts at 0.0, terms in visiting order):
+ *   d = c_j - c_i;  S1_a += d_a (a = x, y, z);  S2_xx += d_x d_x, S2_xy += d_x d_y, S2_xz += d_x d_z, S2_yy += d_y d_y,
+ *   S2_yz += d_y d_z, S2_zz += d_z d_z;  then mu_a = S1_a / k;  C_ab = S2_ab / k - mu_a * mu_b (a <= b, mirrored);
+ *   jacobi_svd3(C) of csrc/svd3.h -> s descending and u;  normal = u[:,2].
+ *   out_eigenvalues [m,3] f32 = s;   out_neighbors [m] i32 = k;   out_flags [m] u8;   out_normals [m,3] f32
+ * Flags: PCACC_NORMAL_FEW_NEIGHBORS when k < min_neighbors; PCACC_NORMAL_DEGENERATE when s[1] <= 64 * 2^-52 * s[0] (SVD3_RANK_TOL:
+ * collinear, or a single point).  A row with either gets the normal (0, 0, 0) and no sign rule; eigenvalues and k are written for
+ * every row.
+ * Sign of a valid normal n: t = t_first - stamp_base.  With viewpoints and 0 <= t < S: e = viewpoint_t - c_i, n is negated iff
+ * (n_x e_x + n_y e_y) + n_z e_z < 0, and PCACC_NORMAL_VIEWPOINT is set (the normal was oriented by a viewpoint).  Otherwise n is
+ * negated iff the first non-zero of (n_z, n_y, n_x) is negative (-0.0 counts as zero).  Negation is 0.0 - n_a.
+ * A result depends on the set of integer records alone, visited in key order: two runs give the same bits, and so do two maps built
+ * from the same points in any order.  No floating-point atomics.
+ * Return value: PCACC_E_ARG for radius outside 1..3, min_neighbors < 3, m outside [0, capacity], n_viewpoints < 0 or a NULL table
+ * with n_viewpoints > 0; nothing is launched then.
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_NORMAL_FEW_NEIGHBORS 1
+#define PCACC_NORMAL_DEGENERATE 2
+#define PCACC_NORMAL_VIEWPOINT 4
+int pcacc_accum_normals_workspace_bytes(int64_t m, size_t *bytes /*host*/);
+int pcacc_accum_normals(const int64_t *keys, const int64_t *acc, const int32_t *stamps, int64_t capacity, int64_t m, int64_t min_count,
+                        int32_t use_fraction, double max_moving_fraction, int32_t radius, int32_t min_neighbors, const double *viewpoints,
+                        int64_t n_viewpoints, int64_t stamp_base, float *out_normals, float *out_eigenvalues, int32_t *out_neighbors,
+                        uint8_t *out_flags, int64_t *out_n, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

@@ -9,6 +9,8 @@ coordinate sums), so the map does not depend on the order of the points, on the 
     for k, (results, input_dict, pose) in enumerate(windows):
         m.add_results(results, input_dict, pose=pose, stamp=k)
     static = m.extract(min_count=2, max_moving_fraction=0.0)     # dict of device tensors
+    nrm = m.normals(radius=1, min_count=2, max_moving_fraction=0.0, viewpoints=sensor_positions)   # rows aligned with `static` (C5, section 9d)
+    m.save_ply('scene.ply', min_count=2, max_moving_fraction=0.0, viewpoints=sensor_positions)
 
 There is no CPU path: a CPU tensor raises native.NativeError."""
 import numpy as np
@@ -17,6 +19,9 @@ import torch
 from . import native
 
 _FIELDS = ('points', 'coords', 'count', 'moving', 't_first', 't_last')
+_NORMAL_FIELDS = ('normals', 'eigenvalues', 'neighbors', 'flags')
+_PLY_TYPES = {'float32': 'float', 'float64': 'double', 'int8': 'char', 'uint8': 'uchar', 'int16': 'short', 'uint16': 'ushort', 'int32': 'int',
+              'uint32': 'uint'}
 
 
 def _tables(capacity, device):
@@ -144,6 +149,40 @@ class AccumulatedCloud(object):
         kept = int(out[-1]) if self._n else 0
         return {k: t[:kept] for k, t in zip(_FIELDS, out)}
 
+    # ---- normals -----------------------------------------------------------------------------------------------------------------------
+    def normals(self, radius=1, min_neighbors=5, min_count=1, max_moving_fraction=None, viewpoints=None, stamp_base=0):
+        """One oriented surface normal per voxel that extract(min_count, max_moving_fraction) keeps, row for row (include/pcacc.h C5): the covariance
+        of the float64 centroids of the kept voxels within `radius` voxels (Chebyshev, the voxel itself included), its smallest eigenvector.
+        -> normals [V,3] f32 (zero where invalid), eigenvalues [V,3] f32 descending, neighbors [V] i32, flags [V] u8 (1: fewer than min_neighbors,
+        2: collinear or a single point, 4: oriented towards a viewpoint), valid [V] bool (neither 1 nor 2).
+        viewpoints [S,3] (tensor or array): the sensor position of stamp stamp_base + s; a voxel whose first stamp has a row there gets the normal
+        that faces it, every other voxel the normal whose first non-zero of (n_z, n_y, n_x) is positive.  Only the kept count is read back."""
+        radius, min_neighbors = int(radius), int(min_neighbors)
+        if not 1 <= radius <= 3:
+            raise ValueError('radius must be 1, 2 or 3 voxels, got %r' % radius)
+        if min_neighbors < 3:
+            raise ValueError('min_neighbors must be at least 3, got %r' % min_neighbors)
+        if viewpoints is not None:
+            if not torch.is_tensor(viewpoints):
+                viewpoints = torch.from_numpy(np.ascontiguousarray(viewpoints, dtype=np.float64))
+            if viewpoints.dim() != 2 or viewpoints.shape[1] != 3:
+                raise ValueError('viewpoints must be [S,3], got %s' % (tuple(viewpoints.shape),))
+        self._ensure()
+        if viewpoints is not None:
+            viewpoints = viewpoints.to(device=self.device, dtype=torch.float64).contiguous()
+        out = native.accum_normals(self._cur, self._n, min_count, max_moving_fraction, radius, min_neighbors, viewpoints, int(stamp_base))
+        kept = int(out[-1]) if self._n else 0
+        res = {k: t[:kept] for k, t in zip(_NORMAL_FIELDS, out)}
+        res['valid'] = (res['flags'] & (native.NORMAL_FEW_NEIGHBORS | native.NORMAL_DEGENERATE)) == 0
+        return res
+
+    def save_ply(self, path, normals=True, min_count=1, max_moving_fraction=None, **normal_args):
+        """extract(min_count, max_moving_fraction) as a binary PLY: x y z, with normals=True nx ny nz of normals(**normal_args) under the same filter
+        (rows without a valid normal are kept, with a zero normal), then count, moving, t_first, t_last."""
+        cloud = self.extract(min_count, max_moving_fraction)
+        nrm = self.normals(min_count=min_count, max_moving_fraction=max_moving_fraction, **normal_args)['normals'] if normals else None
+        write_ply(path, cloud['points'], nrm, [(k, cloud[k]) for k in ('count', 'moving', 't_first', 't_last')])
+
     # ---- persistence -------------------------------------------------------------------------------------------------------------------
     def records(self):
         """The integer records of the map as host arrays: keys [M] i64, acc [5,M] i64 (count, moving, sum q_x, sum q_y, sum q_z), stamps [2,M] i32."""
@@ -181,6 +220,47 @@ class AccumulatedCloud(object):
         self._state.copy_(torch.tensor(host, dtype=torch.int64))
         self._n, self._dropped = m, dropped
         return self
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+
+def write_ply(path, points, normals=None, fields=None):
+    """A binary little-endian PLY of V vertices from host or device arrays: x y z (float), nx ny nz (float) when normals [V,3] is given, then one
+    scalar property per entry of fields -- a dict or a list of (name, [V] array) -- in its order and in the array's own type (64-bit integers, which
+    PLY does not have, as int; values outside int32 raise ValueError)."""
+    pts = np.ascontiguousarray(_host(points), dtype=np.float32)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError('points must be [V,3], got %s' % (pts.shape,))
+    v = pts.shape[0]
+    cols = [(n, pts[:, a]) for a, n in enumerate(('x', 'y', 'z'))]
+    if normals is not None:
+        nrm = np.ascontiguousarray(_host(normals), dtype=np.float32)
+        if nrm.shape != (v, 3):
+            raise ValueError('normals must be [%d,3], got %s' % (v, nrm.shape))
+        cols += [(n, nrm[:, a]) for a, n in enumerate(('nx', 'ny', 'nz'))]
+    for name, col in (fields.items() if isinstance(fields, dict) else (fields or ())):
+        col = _host(col)
+        if col.dtype == np.bool_:
+            col = col.astype(np.uint8)
+        if col.dtype in (np.int64, np.uint64):
+            if v and (col.max() > np.iinfo(np.int32).max or col.min() < np.iinfo(np.int32).min):
+                raise ValueError('write_ply: %s does not fit the 32-bit integer of a PLY property' % name)
+            col = col.astype(np.int32)
+        if col.shape != (v,) or col.dtype.name not in _PLY_TYPES:
+            raise ValueError('write_ply: %s must be a [%d] column of a PLY scalar type, got %s %s' % (name, v, col.shape, col.dtype))
+        if not str(name).isidentifier() or name in [c[0] for c in cols]:
+            raise ValueError('write_ply: %r is no new property name' % (name,))
+        cols.append((str(name), col))
+    rows = np.empty((v,), dtype=[(n, c.dtype.newbyteorder('<')) for n, c in cols])
+    for n, c in cols:
+        rows[n] = c
+    header = ['ply', 'format binary_little_endian 1.0', 'element vertex %d' % v]
+    header += ['property %s %s' % (_PLY_TYPES[c.dtype.name], n) for n, c in cols]
+    with open(path, 'wb') as f:
+        f.write(('\n'.join(header + ['end_header']) + '\n').encode('ascii'))
+        f.write(rows.tobytes())
 
 
 def voxel_mean_downsample(points, voxel_size):

@@ -739,6 +739,34 @@ def accum_extract(tables, m, min_count, max_moving_fraction):
     return points, coords, count, moving, t_first, t_last, kept
 
 
+NORMAL_FEW_NEIGHBORS, NORMAL_DEGENERATE, NORMAL_VIEWPOINT = 1, 2, 4
+
+
+def accum_normals(tables, m, min_count, max_moving_fraction, radius, min_neighbors, viewpoints, stamp_base):
+    """Per-voxel normals of the kept voxels of the first m rows of a map, rows as accum_extract's under the same filter; see include/pcacc.h (C5).
+    viewpoints [S,3] f64 or None.  -> (normals [m,3] f32, eigenvalues [m,3] f32, neighbors [m] i32, flags [m] u8, kept [1] i64): the caller reads
+    `kept` and slices."""
+    keys, acc, stamps, cap = _accum_tables(tables, 'accum_normals')
+    dev = tables[0].device
+    m = int(m)
+    n_view = 0
+    if viewpoints is not None:
+        if viewpoints.dim() != 2 or viewpoints.shape[1] != 3:
+            raise NativeError('accum_normals: viewpoints must be [S,3], got %s' % (tuple(viewpoints.shape),))
+        n_view = viewpoints.shape[0]
+    normals = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    eigenvalues = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    neighbors = torch.empty((m,), dtype=torch.int32, device=dev)
+    flags = torch.empty((m,), dtype=torch.uint8, device=dev)
+    kept = torch.empty((1,), dtype=torch.int64, device=dev)
+    ws = _workspace(lib().pcacc_accum_normals_workspace_bytes, dev, m)
+    _check(lib().pcacc_accum_normals(keys, acc, stamps, cap, m, int(min_count), 0 if max_moving_fraction is None else 1,
+                                     0.0 if max_moving_fraction is None else float(max_moving_fraction), int(radius), int(min_neighbors),
+                                     _dev(viewpoints, torch.float64, 'viewpoints') if n_view else None, n_view, int(stamp_base), _dev(normals),
+                                     _dev(eigenvalues), _dev(neighbors), _dev(flags), _dev(kept), _dev(ws), ws.numel(), _stream()), 'accum_normals')
+    return normals, eigenvalues, neighbors, flags, kept
+
+
 def conv3x3_supported(c_in, c_out):
     return c_in >= 32 and c_out >= 32 and c_in % 32 == 0 and c_out % 32 == 0
 

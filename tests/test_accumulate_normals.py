@@ -1,0 +1,493 @@
+"""Per-voxel normals of the accumulated scene cloud (include/pcacc.h C5): AccumulatedCloud.normals / save_ply / write_ply.
+
+CPU leg: csrc/accum_normals.h -- the code the kernel runs -- built with g++ (-ffp-contract=off, every table index assert-checked) against the numpy
+restatement tests/accumulate_normals_reference.py (a dict of coordinates, float64 covariance, np.linalg.eigh): neighbour counts and validity flags
+equal, eigenvalues and normals inside the bounds below; the index bound with decoy voxels where an overflowed key would land; degenerate shapes;
+the PLY writer; header, binding and argument checks.
+GPU leg: the kernel against the host build BIT FOR BIT at r = 1, 2, 3 on every scene of the CPU leg and on a sheet of more than 65 536 voxels;
+orientation by viewpoints; order independence; row alignment with extract."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import accumulate_normals_reference as nref
+import accumulate_reference as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEV = 'cuda:0'
+OUT = ('normals', 'eigenvalues', 'neighbors', 'flags')
+EDGE = 1 << 20
+
+
+# ---- scenes ----------------------------------------------------------------------------------------------------------------------------
+def _plane():
+    rs = np.random.RandomState(7)
+    xy = rs.uniform(-1.65, 1.65, (20000, 2))
+    z = 0.37 * xy[:, 0] - 0.21 * xy[:, 1] + rs.normal(0, 0.01, 20000)
+    return np.concatenate([xy, z[:, None]], 1).astype(np.float32)
+
+
+def _sphere():
+    rs = np.random.RandomState(7)
+    d = rs.normal(0, 1, (40000, 3))
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    return (np.array([0.3, -0.2, 0.1]) + d * (1.5 + rs.normal(0, 0.005, 40000))[:, None]).astype(np.float32)
+
+
+SPHERE_CENTRE = np.array([0.3, -0.2, 0.1])
+
+
+def _two_sheets():
+    rs = np.random.RandomState(7)
+    xy = rs.uniform(-1, 1, (16000, 2))
+    z = np.where(rs.uniform(0, 1, 16000) < 0.5, 0.02, 0.32) + rs.normal(0, 0.005, 16000)
+    return np.concatenate([xy, z[:, None]], 1).astype(np.float32)
+
+
+def _centres(idx, vs):
+    return ((np.asarray(idx, np.float64) + 0.5) * vs).astype(np.float32)
+
+
+def _bound_voxels():
+    """Voxel indices at both ends of every axis (3 x 3 x 3 clusters that touch -2^20 and 2^20 - 1) and DECOYS exactly where a key with an overflowed
+    or borrowed y / z field would land: for (x, 2^20-1, z) the key of offset dy = +1 would be that of (x+1, -2^20, z); for (x, -2^20, z) and dy = -1
+    that of (x-1, 2^20-1, z); the same for z into y."""
+    vox = []
+    for axis in range(3):
+        for lo in (-EDGE, EDGE - 3):
+            for a in range(3):
+                for b in (-1, 0, 1):
+                    for c in (-1, 0, 1):
+                        v = [b, c]
+                        v.insert(axis, lo + a)
+                        vox.append(v)
+    cluster = np.array(vox, np.int64)
+    decoys = []
+    for x, y, z in cluster.tolist():
+        if y == EDGE - 1:
+            decoys.append((x + 1, -EDGE, z))
+        if y == -EDGE:
+            decoys.append((x - 1, EDGE - 1, z))
+        if z == EDGE - 1:
+            decoys.append((x, y + 1, -EDGE))
+        if z == -EDGE:
+            decoys.append((x, y - 1, EDGE - 1))
+    decoys = np.array([d for d in decoys if all(-EDGE <= c < EDGE for c in d)], np.int64)
+    return cluster, decoys
+
+
+def _scene(name):
+    """-> (voxel_size, [(points, moving or None, stamp)])."""
+    if name == 'plane':
+        return 0.1, [(_plane(), None, 0)]
+    if name == 'sphere':
+        return 0.1, [(_sphere(), None, 0)]
+    if name == 'two_sheets':
+        return 0.1, [(_two_sheets(), None, 0)]
+    if name == 'bound':
+        cluster, decoys = _bound_voxels()
+        return 0.01, [(_centres(np.concatenate([cluster, decoys]), 0.01), None, 0)]
+    if name == 'single':
+        return 0.1, [(np.array([[0.43, -1.21, 0.07]], np.float32), None, 0)]
+    if name == 'row9':
+        return 0.1, [(_centres([(k, 4, -2) for k in range(-4, 5)], 0.1), None, 0)]
+    if name == 'block27':
+        return 0.1, [(_centres([(x, y, z) for x in range(3) for y in range(3) for z in range(3)], 0.1), None, 0)]
+    if name == 'flagged':                                                        # several points per voxel, some predicted moving, two stamps
+        pts = _plane()
+        mv = np.random.RandomState(8).uniform(0, 1, pts.shape[0]) < 0.08
+        return 0.1, [(pts[:12000], mv[:12000], 3), (pts[12000:], mv[12000:], 1)]
+    assert name == 'wavy'                                                        # 26 m x 26 m at 0.1 m: four points in every column, > 65 536 voxels
+    g = np.arange(520) * 0.05 + 0.025 - 13.0
+    x, y = np.meshgrid(g, g, indexing='ij')
+    z = 0.4 * np.sin(0.9 * x) * np.cos(0.7 * y) + 0.013
+    pts = np.stack([x, y, z], -1).reshape(-1, 3)
+    return 0.1, [(np.concatenate([pts, [[40.0, 40.0, 40.0]]]).astype(np.float32), None, 0)]
+
+
+CPU_SCENES = ('plane', 'sphere', 'two_sheets', 'bound', 'single', 'row9', 'block27', 'flagged')
+FILTERS = {'flagged': dict(min_count=2, max_moving_fraction=0.0)}
+_maps = {}
+
+
+def _ref_map(name):
+    """The restatement's map of a scene, built once and shared (never modified)."""
+    if name not in _maps:
+        vs, adds = _scene(name)
+        r = ref.ReferenceMap(vs)
+        for pts, mv, stamp in adds:
+            r.add(pts, None, mv, stamp)
+        _maps[name] = r
+    return _maps[name]
+
+
+# ---- the host build ----------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope='module')
+def host_exe(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp('accn') / 'accum_normals_host_driver')
+    cxx = shutil.which('g++') or shutil.which('c++')
+    assert cxx, 'the host-build test needs a C++ compiler'
+    subprocess.check_call([cxx, '-O2', '-g', '-std=c++17', '-ffp-contract=off', '-DACC_HOST_CHECK', '-Wall', '-Werror',
+                           '-I', os.path.join(ROOT, 'pcaccumulation_amd', 'csrc'), os.path.join(ROOT, 'tests', 'accum_normals_host_driver.cpp'), '-o', exe])
+    return exe
+
+
+_host_cache = {}
+
+
+def _host(exe, tmp_path, name, radius, min_neighbors=5, min_count=1, max_moving_fraction=None, viewpoints=None, stamp_base=0, records=None, spare=3):
+    """The g++ build of accum_normals.h on the records of a scene (every assert of the driver aborts it) -> dict with the float64 results and, as
+    'normals32' / 'eigenvalues32', their float32 roundings: what the kernel must write."""
+    key = (name, radius, min_neighbors, min_count, max_moving_fraction, stamp_base, None if viewpoints is None else np.asarray(viewpoints).tobytes())
+    if records is None and key in _host_cache:
+        return _host_cache[key]
+    keys, acc, stamps = _ref_map(name).records() if records is None else records
+    m = keys.shape[0]
+    vp = np.zeros((0, 3)) if viewpoints is None else np.ascontiguousarray(viewpoints, np.float64).reshape(-1, 3)
+    tag = '%s_r%d_%d' % (name, radius, len(_host_cache))
+    path, out = str(tmp_path / (tag + '.bin')), str(tmp_path / (tag + '.out'))
+    with open(path, 'wb') as f:
+        f.write(np.array([m, max(m + spare, 1), min_count, 0 if max_moving_fraction is None else 1, radius, min_neighbors, vp.shape[0], stamp_base],
+                         np.int64).tobytes())
+        f.write(np.array([0.0 if max_moving_fraction is None else max_moving_fraction], np.float64).tobytes())
+        f.write(np.ascontiguousarray(keys, np.int64).tobytes() + np.ascontiguousarray(acc, np.int64).tobytes() + np.ascontiguousarray(stamps, np.int32).tobytes())
+        f.write(vp.tobytes())
+    subprocess.check_call([exe, path, out])
+    raw = open(out, 'rb').read()
+    v = int(np.frombuffer(raw, np.int64, 1)[0])
+    off, res = 8, {}
+    for k, dt, cols in (('normals', np.float64, 3), ('eigenvalues', np.float64, 3), ('neighbors', np.int32, 1), ('flags', np.uint8, 1),
+                        ('normals32', np.float32, 3), ('eigenvalues32', np.float32, 3)):
+        a = np.frombuffer(raw, dt, v * cols, off)
+        off += a.nbytes
+        res[k] = a.reshape(v, 3) if cols == 3 else a
+    assert off == len(raw)
+    if records is None:
+        _host_cache[key] = res
+    return res
+
+
+def _fallback_sign_ok(n):
+    first = np.where(n[:, 2] != 0, n[:, 2], np.where(n[:, 1] != 0, n[:, 1], n[:, 0]))
+    return first > 0
+
+
+def _check_against_restatement(got, want, normals_too=True):
+    """Integers equal; eigenvalues |got - want| <= 1e-12 want[0] + 1e-9 want; float64 normals after sign alignment within 1e-10 per component on the
+    valid rows whose relative gap is >= 1e-3.  -> (valid rows, valid rows below the gap rule)."""
+    assert np.array_equal(got['neighbors'], want['neighbors'])
+    assert np.array_equal(got['flags'] & 3, want['flags'] & 3)
+    bound = 1e-12 * want['eigenvalues'][:, :1] + 1e-9 * want['eigenvalues']
+    err = np.abs(got['eigenvalues'] - want['eigenvalues'])
+    assert np.all(err <= bound), (np.flatnonzero((err > bound).any(1))[:8], err.max())
+    valid = (want['flags'] & 3) == 0
+    assert np.all(got['normals'][~valid] == 0.0)
+    n = got['normals'][valid]
+    assert np.all(np.abs(np.linalg.norm(n, axis=1) - 1.0) < 1e-12)
+    assert np.all(_fallback_sign_ok(n))                                          # no viewpoints here: first non-zero of (n_z, n_y, n_x) positive
+    clear = valid & (want['gap'] >= 1e-3)
+    if normals_too and clear.any():
+        sign = np.sign((got['normals'][clear] * want['normals'][clear]).sum(1))[:, None]
+        diff = np.abs(got['normals'][clear] * sign - want['normals'][clear])
+        assert diff.max() <= 1e-10, diff.max()
+    return int(valid.sum()), int((valid & ~clear).sum())
+
+
+# ---- CPU -------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', ['plane', 'sphere', 'two_sheets'])
+def test_host_build_against_the_restatement(host_exe, tmp_path, name):
+    """(a) The surfaces.  No valid row may fall below the gap rule and at least 99 % of the rows are valid: the normal bound speaks about (nearly) every
+    row of these scenes, not about a remainder."""
+    r = _ref_map(name)
+    assert r.num_voxels > 700
+    for radius in (1, 2, 3):
+        got = _host(host_exe, tmp_path, name, radius)
+        want = nref.normals(r, radius, 5)
+        n_valid, n_unclear = _check_against_restatement(got, want)
+        assert n_unclear == 0, (radius, n_unclear, want['gap'][(want['flags'] & 3) == 0].min())
+        assert n_valid >= 0.99 * r.num_voxels, (radius, n_valid, r.num_voxels)
+        if name == 'plane':                                                      # and the normal IS the plane's, up to the noise of the centroids
+            truth = np.array([-0.37, 0.21, 1.0]) / np.linalg.norm([-0.37, 0.21, 1.0])
+            valid = (got['flags'] & 3) == 0
+            assert np.median(np.abs(got['normals'][valid] @ truth)) > 0.99
+
+
+def test_host_build_at_the_index_bound_ignores_decoys(host_exe, tmp_path):
+    """(b) Voxel size 0.01 puts +-2^20 inside |w| < 32768.  Offsets that leave the grid are skipped before a key is formed: the driver's asserts stay
+    silent and a decoy sitting where the overflowed key would land is never counted."""
+    r = _ref_map('bound')
+    cluster, decoys = _bound_voxels()
+    keys = r.records()[0]
+    coords = np.stack([(keys >> 42) & 0x1fffff, (keys >> 21) & 0x1fffff, keys & 0x1fffff], 1) - ref.BIAS
+    have = set(map(tuple, coords.tolist()))
+    assert have == set(map(tuple, cluster.tolist())) | set(map(tuple, decoys.tolist()))      # every intended voxel exists, and no other
+    assert len(decoys) >= 36 and coords.min() == -EDGE and coords.max() == EDGE - 1
+    for axis in range(3):
+        assert coords[:, axis].min() == -EDGE and coords[:, axis].max() == EDGE - 1
+    for radius in (1, 2, 3):
+        got = _host(host_exe, tmp_path, 'bound', radius)
+        want = nref.normals(r, radius, 5)
+        assert np.array_equal(got['neighbors'], want['neighbors']), radius
+        assert np.array_equal(got['flags'] & 1, want['flags'] & 1), radius
+        # the aliasing this guards against would show here: what a decoy adds to a corner voxel's count
+        where = {tuple(c): j for j, c in enumerate(coords.tolist())}
+        j = where[(0, EDGE - 1, 0)]
+        honest = sum(1 for c in have if max(abs(c[0]), abs(c[1] - (EDGE - 1)), abs(c[2])) <= radius)
+        assert got['neighbors'][j] == honest and (1, -EDGE, 0) in have
+
+
+def test_host_build_on_degenerate_shapes(host_exe, tmp_path):
+    """(c) One voxel; nine in a row (rank 1); a full 3 x 3 x 3 block of voxel centres (exact eigenvalue ties); a filter that removes neighbours."""
+    for radius in (1, 2, 3):
+        got = _host(host_exe, tmp_path, 'single', radius)
+        assert got['neighbors'].tolist() == [1] and got['flags'].tolist() == [3]
+        assert np.all(got['normals'] == 0.0) and np.all(got['eigenvalues'] == 0.0)
+        got = _host(host_exe, tmp_path, 'row9', radius)
+        want = nref.normals(_ref_map('row9'), radius, 5)
+        assert np.array_equal(got['neighbors'], want['neighbors']) and got['neighbors'].max() == min(9, 2 * radius + 1)
+        assert np.all(got['flags'] & 2) and np.all(got['normals'] == 0.0)
+        assert np.array_equal(got['flags'], want['flags'])
+        got = _host(host_exe, tmp_path, 'block27', radius)
+        want = nref.normals(_ref_map('block27'), radius, 5)
+        _check_against_restatement(got, want, normals_too=False)
+        assert got['neighbors'][13] == 27 and got['flags'][13] == 0
+        centre = got['normals'][13]
+        assert np.all(np.isfinite(centre)) and abs(np.linalg.norm(centre) - 1.0) < 1e-12
+    r = _ref_map('flagged')
+    f = FILTERS['flagged']
+    kept = r.extract(**f)['count'].shape[0]
+    assert 0.2 * r.num_voxels < kept < 0.9 * r.num_voxels                        # the filter does remove neighbours
+    for radius in (1, 2):
+        got = _host(host_exe, tmp_path, 'flagged', radius, **f)
+        want = nref.normals(r, radius, 5, **f)
+        assert got['neighbors'].shape[0] == kept                                 # rows align with extract
+        _check_against_restatement(got, want)
+        unfiltered = _host(host_exe, tmp_path, 'flagged', radius)
+        assert unfiltered['neighbors'].shape[0] == r.num_voxels and unfiltered['neighbors'].sum() > got['neighbors'].sum()
+
+
+def _read_ply(path):
+    raw = open(path, 'rb').read()
+    end = raw.index(b'end_header\n') + len(b'end_header\n')
+    lines = raw[:end].decode('ascii').split('\n')
+    assert lines[0] == 'ply' and lines[1] == 'format binary_little_endian 1.0' and lines[2].startswith('element vertex ')
+    v = int(lines[2].split()[2])
+    types = {'float': '<f4', 'double': '<f8', 'char': 'i1', 'uchar': 'u1', 'short': '<i2', 'ushort': '<u2', 'int': '<i4', 'uint': '<u4'}
+    props = [l.split() for l in lines[3:] if l.startswith('property ')]
+    assert len(props) == len(lines) - 5                                          # nothing else between the element line and end_header
+    dtype = np.dtype([(name, types[t]) for _, t, name in props])
+    assert len(raw) - end == v * dtype.itemsize
+    return np.frombuffer(raw, dtype, v, end)
+
+
+def test_write_ply(tmp_path):
+    """(d) The header parsed back, the payload equal to the arrays: with and without normals and extra fields, V = 0 and V = 5."""
+    from pcaccumulation_amd.accumulate import write_ply
+    rs = np.random.RandomState(3)
+    for v in (0, 5):
+        pts, nrm = rs.normal(0, 1, (v, 3)).astype(np.float32), rs.normal(0, 1, (v, 3)).astype(np.float32)
+        count, t_first, w = rs.randint(1, 1000, v).astype(np.int64), rs.randint(-5, 5, v).astype(np.int32), rs.normal(0, 1, v)
+        flags = rs.randint(0, 8, v).astype(np.uint8)
+        path = str(tmp_path / ('a%d.ply' % v))
+        write_ply(path, pts)
+        got = _read_ply(path)
+        assert got.dtype.names == ('x', 'y', 'z') and got.shape == (v,)
+        assert np.stack([got['x'], got['y'], got['z']], 1).tobytes() == pts.tobytes()
+        write_ply(path, torch.from_numpy(pts), torch.from_numpy(nrm))
+        got = _read_ply(path)
+        assert got.dtype.names == ('x', 'y', 'z', 'nx', 'ny', 'nz')
+        assert np.stack([got[k] for k in got.dtype.names], 1).tobytes() == np.concatenate([pts, nrm], 1).tobytes()
+        write_ply(path, pts, nrm, [('count', count), ('t_first', torch.from_numpy(t_first)), ('weight', w), ('flags', flags)])
+        got = _read_ply(path)
+        assert got.dtype.names == ('x', 'y', 'z', 'nx', 'ny', 'nz', 'count', 't_first', 'weight', 'flags')
+        assert [got.dtype[k].str for k in ('count', 't_first', 'weight', 'flags')] == ['<i4', '<i4', '<f8', '|u1']
+        assert np.array_equal(got['count'], count) and got['t_first'].tobytes() == t_first.tobytes() and got['weight'].tobytes() == w.tobytes()
+        assert got['flags'].tobytes() == flags.tobytes() and got['nz'].tobytes() == nrm[:, 2].tobytes()
+        write_ply(path, pts, None, {'flags': flags})
+        assert _read_ply(path).dtype.names == ('x', 'y', 'z', 'flags')
+    with pytest.raises(ValueError):
+        write_ply(str(tmp_path / 'bad.ply'), np.zeros((5, 2), np.float32))
+    with pytest.raises(ValueError):
+        write_ply(str(tmp_path / 'bad.ply'), np.zeros((5, 3), np.float32), np.zeros((4, 3), np.float32))
+    with pytest.raises(ValueError):
+        write_ply(str(tmp_path / 'bad.ply'), np.zeros((5, 3), np.float32), None, {'count': np.full(5, 1 << 40, np.int64)})
+
+
+def test_header_binding_and_argument_checks():
+    """(e)"""
+    from pcaccumulation_amd import native
+    from pcaccumulation_amd.accumulate import AccumulatedCloud
+    header = open(os.path.join(ROOT, 'include', 'pcacc.h')).read()
+    for name in ('pcacc_accum_normals_workspace_bytes', 'pcacc_accum_normals'):
+        assert ('int %s(' % name) in header
+        assert name in native.EXPORTS
+    assert ' C5. ' in header
+    assert os.path.exists(os.path.join(ROOT, 'pcaccumulation_amd', 'csrc', 'accum_normals.h'))
+    assert callable(native.accum_normals)
+    cpu_tables = (torch.zeros(4, dtype=torch.int64), torch.zeros(5, 4, dtype=torch.int64), torch.zeros(2, 4, dtype=torch.int32))
+    with pytest.raises(native.NativeError):
+        native.accum_normals(cpu_tables, 0, 1, None, 1, 5, None, 0)
+    with pytest.raises(native.NativeError):
+        AccumulatedCloud(voxel_size=0.1, device='cpu', capacity=64).normals()
+    with pytest.raises(native.NativeError):
+        AccumulatedCloud(voxel_size=0.1, device='cpu', capacity=64).save_ply(os.devnull)
+    m = AccumulatedCloud(voxel_size=0.1, device='cuda', capacity=64)             # takes no device memory before the first add
+    for bad in (dict(radius=0), dict(radius=4), dict(min_neighbors=2), dict(viewpoints=np.zeros((4, 2))), dict(viewpoints=torch.zeros(3)),
+                dict(viewpoints=np.zeros((2, 3, 1)))):
+        with pytest.raises(ValueError):
+            m.normals(**bad)
+
+
+# ---- GPU -------------------------------------------------------------------------------------------------------------------------------
+def _device_map(name, capacity=64):
+    from pcaccumulation_amd.accumulate import AccumulatedCloud
+    vs, adds = _scene(name)
+    m = AccumulatedCloud(vs, DEV, capacity)
+    for pts, mv, stamp in adds:
+        m.add(torch.from_numpy(pts).to(DEV), None, None if mv is None else torch.from_numpy(mv).to(DEV), stamp)
+    return m
+
+
+def _assert_kernel_bits(got, host, what):
+    """The kernel's four outputs against the float32 rounding of the host build, byte for byte."""
+    for k, hk in (('normals', 'normals32'), ('eigenvalues', 'eigenvalues32'), ('neighbors', 'neighbors'), ('flags', 'flags')):
+        a, b = np.ascontiguousarray(got[k].cpu().numpy()), np.ascontiguousarray(host[hk])
+        assert a.dtype == b.dtype and a.shape == b.shape, (what, k, a.dtype, a.shape, b.shape)
+        if a.tobytes() != b.tobytes():
+            rows = np.flatnonzero((a != b).reshape(a.shape[0], -1).any(1))
+            raise AssertionError((what, k, rows.size, rows[:8].tolist()))
+    assert np.array_equal(got['valid'].cpu().numpy(), (host['flags'] & 3) == 0), what
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', CPU_SCENES)
+def test_kernel_equals_the_host_build_bits_gpu(host_exe, tmp_path, name):
+    """(f) Same code, same float64 operations, no FMA contraction on either side: equal bytes, at r = 1, 2, 3."""
+    m = _device_map(name)
+    for x, y in zip(m.records(), _ref_map(name).records()):
+        assert x.tobytes() == y.tobytes()
+    filters = [dict()] + ([FILTERS[name]] if name in FILTERS else [])
+    for f in filters:
+        for radius in (1, 2, 3):
+            got = m.normals(radius=radius, min_neighbors=5, **f)
+            assert sorted(got) == sorted(OUT + ('valid',))
+            _assert_kernel_bits(got, _host(host_exe, tmp_path, name, radius, **f), (name, radius, f))
+    if name == 'plane':
+        assert m.num_voxels % 64 != 0
+
+
+@pytest.mark.gpu
+def test_kernel_on_more_than_65536_voxels_gpu(host_exe, tmp_path):
+    """(f) More than 256 workgroups of 256 rows, M no multiple of 64."""
+    m = _device_map('wavy', capacity=1 << 17)
+    assert m.num_voxels > 65536 + 256 and m.num_voxels % 64 != 0
+    got = m.normals(radius=1)
+    host = _host(host_exe, tmp_path, 'wavy', 1, records=m.records())
+    _assert_kernel_bits(got, host, 'wavy')
+    assert got["valid"].sum().item() >= 0.99 * m.num_voxels                      # all but corners of the rim and the one far voxel
+    assert got['neighbors'][-1].item() == 1 and got['flags'][-1].item() == 3      # (40, 40, 40): alone
+
+
+@pytest.mark.gpu
+def test_empty_map_and_a_filter_that_keeps_nothing_gpu():
+    from pcaccumulation_amd.accumulate import AccumulatedCloud
+    m = AccumulatedCloud(0.1, DEV, 64)
+    m.add(torch.zeros((0, 3), device=DEV))
+    for got in (m.normals(), _device_map('plane').normals(min_count=10 ** 6)):
+        assert [tuple(got[k].shape) for k in OUT + ('valid',)] == [(0, 3), (0, 3), (0,), (0,), (0,)]
+        assert got['normals'].dtype == torch.float32 and got['neighbors'].dtype == torch.int32 and got['flags'].dtype == torch.uint8
+
+
+@pytest.mark.gpu
+def test_orientation_by_viewpoints_gpu(host_exe, tmp_path):
+    """(g) The restatement's normals are within 0.997 of radial on this sphere and the second viewpoint lies 0.37 from the centre of a sphere of
+    radius 1.5 (at most 15 degrees off the radius): no sign is marginal."""
+    from pcaccumulation_amd.accumulate import AccumulatedCloud
+    pts = _sphere()
+    want = nref.normals(_ref_map('sphere'), 1, 5)
+    ok = (want['flags'] & 3) == 0
+    radial = SPHERE_CENTRE - want['centroids']
+    radial /= np.linalg.norm(radial, axis=1)[:, None]
+    assert np.abs((want['normals'] * radial).sum(1))[ok].min() > 0.997
+    # one call, the viewpoint at the centre
+    m = _device_map('sphere')
+    got = m.normals(viewpoints=SPHERE_CENTRE[None])
+    _assert_kernel_bits(got, _host(host_exe, tmp_path, 'sphere', 1, viewpoints=SPHERE_CENTRE[None]), 'centre')
+    n, flags, valid = got['normals'].cpu().numpy().astype(np.float64), got['flags'].cpu().numpy(), got['valid'].cpu().numpy()
+    assert valid.sum() == ok.sum() > 3000
+    assert np.all(flags[valid] & 4) and not np.any(flags[~valid] & 4)
+    assert np.all((n * (SPHERE_CENTRE - want['centroids'])).sum(1)[valid] > 0)
+    # three calls: stamps 10 and 11 with a viewpoint each, stamp 15 outside the table
+    vp = np.stack([SPHERE_CENTRE, SPHERE_CENTRE + np.array([0.3, 0.2, -0.1])])
+    parts = (pts[:, 2] < -0.4, (pts[:, 2] >= -0.4) & (pts[:, 2] < 0.6), pts[:, 2] >= 0.6)
+    m3, r3 = AccumulatedCloud(0.1, DEV, 64), ref.ReferenceMap(0.1)
+    for part, stamp in zip(parts, (10, 11, 15)):
+        m3.add(torch.from_numpy(pts[part]).to(DEV), stamp=stamp)
+        r3.add(pts[part], stamp=stamp)
+    got = m3.normals(viewpoints=torch.from_numpy(vp).to(DEV), stamp_base=10)
+    _assert_kernel_bits(got, _host(host_exe, tmp_path, 'sphere3', 1, viewpoints=vp, stamp_base=10, records=r3.records()), 'three calls')
+    t_first = m3.extract()['t_first'].cpu().numpy()
+    cent = nref.normals(r3, 1, 5)['centroids']
+    n, flags, valid = got['normals'].cpu().numpy().astype(np.float64), got['flags'].cpu().numpy(), got['valid'].cpu().numpy()
+    for s in (0, 1):
+        rows = valid & (t_first == 10 + s)
+        assert rows.sum() > 300 and np.all(flags[rows] & 4)
+        assert np.all((n[rows] * (vp[s] - cent[rows])).sum(1) > 0)
+    rows = valid & (t_first == 15)
+    assert rows.sum() > 300 and not np.any(flags[rows] & 4)
+    assert np.all(_fallback_sign_ok(n[rows]))
+    assert (n[rows] * (SPHERE_CENTRE - cent[rows])).sum(1).max() < 0             # the cap above the centre: z up is outward there
+    # a table that begins after every stamp names no row: the fallback everywhere
+    none = m3.normals(viewpoints=vp, stamp_base=100)
+    plain = m3.normals()
+    assert all(torch.equal(none[k], plain[k]) for k in OUT)
+
+
+@pytest.mark.gpu
+def test_order_independence_gpu(tmp_path):
+    """(h) A result depends on the set of integer records alone."""
+    from pcaccumulation_amd.accumulate import AccumulatedCloud
+    pts = _plane()
+    base = _device_map('plane')
+    want = base.normals(radius=2)
+    again = base.normals(radius=2)
+    assert all(torch.equal(again[k], want[k]) for k in OUT + ('valid',))
+    perm = np.random.RandomState(9).permutation(pts.shape[0])
+    shuffled = AccumulatedCloud(0.1, DEV, 64)
+    for part in np.array_split(perm, 3)[::-1]:
+        shuffled.add(torch.from_numpy(pts[part]).to(DEV))
+    base.save(str(tmp_path / 'plane.npz'))
+    loaded = AccumulatedCloud.load(str(tmp_path / 'plane.npz'), DEV)
+    for name, m in (('shuffled', shuffled), ('loaded', loaded)):
+        got = m.normals(radius=2)
+        for k in OUT + ('valid',):
+            assert torch.equal(got[k], want[k]), (name, k)
+    assert want['valid'].sum().item() > 1500
+
+
+@pytest.mark.gpu
+def test_rows_align_with_extract_and_save_ply_gpu(tmp_path):
+    """(i)"""
+    m = _device_map('flagged')
+    for f in (dict(), dict(min_count=2, max_moving_fraction=0.0), dict(min_count=4), dict(max_moving_fraction=0.1)):
+        cloud, nrm = m.extract(**f), m.normals(**f)
+        assert 0 < nrm['neighbors'].shape[0] == cloud['count'].shape[0] <= m.num_voxels, f
+        assert all(nrm[k].shape[0] == cloud['count'].shape[0] for k in OUT + ('valid',))
+    f = dict(min_count=2, max_moving_fraction=0.0)
+    cloud, nrm = m.extract(**f), m.normals(radius=1, min_neighbors=6, **f)
+    path = str(tmp_path / 'scene.ply')
+    m.save_ply(path, radius=1, min_neighbors=6, **f)
+    got = _read_ply(path)
+    assert got.dtype.names == ('x', 'y', 'z', 'nx', 'ny', 'nz', 'count', 'moving', 't_first', 't_last')
+    assert np.stack([got['x'], got['y'], got['z']], 1).tobytes() == cloud['points'].cpu().numpy().tobytes()
+    assert np.stack([got['nx'], got['ny'], got['nz']], 1).tobytes() == nrm['normals'].cpu().numpy().tobytes()
+    for k in ('count', 'moving', 't_first', 't_last'):
+        assert np.array_equal(got[k], cloud[k].cpu().numpy()), k
+    invalid = ~nrm['valid'].cpu().numpy()
+    assert invalid.any() and np.all(got['nx'][invalid] == 0) and np.all(got['nz'][invalid] == 0)      # kept, with a zero normal
+    m.save_ply(path, normals=False, **f)
+    assert _read_ply(path).dtype.names == ('x', 'y', 'z', 'count', 'moving', 't_first', 't_last')

@@ -1,0 +1,154 @@
+"""Time the per-voxel normals of the accumulated scene cloud (include/pcacc.h C5, AccumulatedCloud.normals) on the 40-window drifting scene of
+tools/bench_accumulate.py (8 M voxels at 0.1 m) and, beside it on the same machine, what a user does without it: the copy of the map's records to
+the host and a vectorised numpy PCA there (np.searchsorted on the copied keys for every offset of the neighbourhood, float64 sums, np.linalg.eigh).
+  GPU legs   r = 1 and r = 2, without a filter and under extract's min_count=2, max_moving_fraction=0.0; device events around the call (kernels and
+             the read-back of the kept count included), one warm-up call, median of 5.
+  host leg   on the sub-map of the first --baseline-rows rows (a slab in x: the keys ascend in x) -- the full map takes minutes per radius on the
+             host -- with the GPU timed on the same sub-map; neighbour counts are compared for equality, normals up to sign.
+Results go to --out.  Nothing is gated on them.
+Usage: python tools/bench_accumulate_normals.py [--windows 40] [--baseline-rows 1000000] [--no-baseline] [--out profiles/accum_normals_bench.txt]"""
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+
+BIAS = 1 << 20
+FILTERS = (('no filter', dict()), ('min_count=2, max_moving_fraction=0.0', dict(min_count=2, max_moving_fraction=0.0)))
+
+
+def gpu_time(torch, fn, repeats=5):
+    fn()                                                                         # warm-up: code objects, allocator
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1))
+    return float(np.median(times)), times, out
+
+
+def host_normals(keys, acc, radius, min_neighbors, min_count=1, max_moving_fraction=None):
+    """The contract in vectorised numpy on host records: one np.searchsorted per offset, in key order.  -> neighbors, flags & 3, normals (unsigned)."""
+    keep = (acc[0] >= min_count) & (acc[0] > 0)
+    if max_moving_fraction is not None:
+        keep &= acc[1].astype(np.float64) / np.maximum(acc[0], 1).astype(np.float64) <= max_moving_fraction
+    k = keys[keep]
+    cent = (acc[2:5, keep].T.astype(np.float64) / acc[0, keep].astype(np.float64)[:, None]) * 2.0 ** -16
+    v = k.shape[0]
+    c = [((k >> s) & 0x1fffff) - BIAS for s in (42, 21, 0)]
+    n = np.zeros(v, np.int32)
+    s1, s2 = np.zeros((v, 3)), np.zeros((v, 6))
+    rng = range(-radius, radius + 1)
+    for dx in rng:
+        for dy in rng:
+            for dz in rng:
+                q = [c[0] + dx, c[1] + dy, c[2] + dz]
+                ok = np.ones(v, bool)
+                for a in q:
+                    ok &= (a >= -BIAS) & (a < BIAS)
+                qk = np.where(ok, ((q[0] + BIAS) << 42) | ((q[1] + BIAS) << 21) | (q[2] + BIAS), 0)
+                p = np.minimum(np.searchsorted(k, qk), max(v - 1, 0))
+                hit = ok & (k[p] == qk)
+                d = np.where(hit[:, None], cent[p] - cent, 0.0)
+                n += hit
+                s1 += d
+                s2 += np.stack([d[:, 0] * d[:, 0], d[:, 0] * d[:, 1], d[:, 0] * d[:, 2], d[:, 1] * d[:, 1], d[:, 1] * d[:, 2], d[:, 2] * d[:, 2]], 1)
+    mu = s1 / n[:, None]
+    cov = np.empty((v, 3, 3))
+    for j, (a, b) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+        cov[:, a, b] = cov[:, b, a] = s2[:, j] / n - mu[:, a] * mu[:, b]
+    w, vec = np.linalg.eigh(cov)
+    w = np.maximum(w, 0.0)
+    flags = (n < min_neighbors).astype(np.uint8) | ((w[:, 1] <= 64 * 2.0 ** -52 * w[:, 2]).astype(np.uint8) << 1)
+    with np.errstate(all='ignore'):
+        gap = np.where(w[:, 2] > 0, (w[:, 1] - w[:, 0]) / w[:, 2], 0.0)
+    return n, flags, vec[:, :, 0], gap
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--windows', type=int, default=40)
+    ap.add_argument('--frames', type=int, default=5)
+    ap.add_argument('--pts-per-frame', type=int, default=160000)
+    ap.add_argument('--voxel', type=float, default=0.1)
+    ap.add_argument('--baseline-rows', type=int, default=1000000)
+    ap.add_argument('--no-baseline', action='store_true')
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'accum_normals_bench.txt'))
+    a = ap.parse_args()
+    import torch
+    from bench_accumulate import drift
+    from pcaccumulation_amd.accumulate import AccumulatedCloud
+    from pcaccumulation_amd.config import default_config
+    from pcaccumulation_amd.synthetic import make_sequence
+    dev = torch.device('cuda:0')
+    cfg = default_config('waymo', 'test', n_sweeps=a.frames)
+    lines = ['tools/bench_accumulate_normals.py --windows %d --frames %d --pts-per-frame %d --voxel %g --baseline-rows %d   (%s; GPU: device events '
+             'around each call, median of 5 after one warm-up; host: perf_counter)'
+             % (a.windows, a.frames, a.pts_per_frame, a.voxel, a.baseline_rows, torch.cuda.get_device_name(0))]
+    def emit():
+        print(lines[-1], flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:                                              # rewritten line by line: a run that is cut short leaves what it measured
+            f.write('\n'.join(lines) + '\n')
+
+    rng = np.random.RandomState(0)
+    m = AccumulatedCloud(a.voxel, dev, 1 << 20)
+    for k in range(a.windows):
+        s = make_sequence(500 + k, a.frames, a.pts_per_frame, cfg, mode='lidar_scan')
+        pts = np.ascontiguousarray(s['input_points'][:, :3], np.float32)
+        m.add(torch.from_numpy(pts).to(dev), drift(k), torch.from_numpy(rng.rand(pts.shape[0]) < 0.1).to(dev), k)
+    viewpoints = torch.from_numpy(np.stack([drift(k)[:3, 3] for k in range(a.windows)])).to(dev)
+    lines.append('map: %d windows -> %d voxels (capacity %d)' % (a.windows, m.num_voxels, m.capacity))
+    emit()
+
+    def report(cloud, what):
+        for fname, f in FILTERS:
+            for radius in (1, 2):
+                med, times, out = gpu_time(torch, lambda: cloud.normals(radius=radius, viewpoints=viewpoints, **f))
+                lines.append('GPU %s, %s, r = %d: %d rows, %d valid, mean k %.1f; median %.2f ms (%s)'
+                             % (what, fname, radius, out['flags'].shape[0], int(out['valid'].sum()), float(out['neighbors'].float().mean()),
+                                med, ' '.join('%.2f' % t for t in times)))
+                emit()
+
+    report(m, 'full map')
+    if not a.no_baseline and m.num_voxels:
+        rows = min(a.baseline_rows, m.num_voxels)
+        keys, acc, stamps = m.records()
+        with tempfile.TemporaryDirectory() as tmp:                               # the sub-map as a map of its own, through the public save format
+            path = os.path.join(tmp, 'sub.npz')
+            np.savez(path, keys=keys[:rows], acc=np.ascontiguousarray(acc[:, :rows]), stamps=np.ascontiguousarray(stamps[:, :rows]),
+                     voxel_size=np.float64(a.voxel), dropped=np.int64(0))
+            sub = AccumulatedCloud.load(path, dev)
+        del keys, acc, stamps
+        report(sub, 'sub-map of the first %d rows' % rows)
+        for fname, f in FILTERS:
+            for radius in (1, 2):
+                got = sub.normals(radius=radius, **f)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                hk, ha, _ = sub.records()                                        # the copy a user makes today, then the PCA in numpy
+                n, flags, nrm, gap = host_normals(hk, ha, radius, 5, **f)
+                t_host = time.perf_counter() - t0
+                g_n, g_flags = got['neighbors'].cpu().numpy(), got['flags'].cpu().numpy()
+                clear = (flags == 0) & (gap >= 1e-3)
+                g_nrm = got['normals'].cpu().numpy().astype(np.float64)[clear]
+                diff = np.abs(np.abs((g_nrm * nrm[clear]).sum(1)) - 1.0).max() if clear.any() else 0.0
+                lines.append('host sub-map, %s, r = %d: copy + numpy (searchsorted per offset, eigh) %.1f s for %d rows; neighbours equal: %s; '
+                             'flags equal: %s; largest |1 - |n_gpu . n_host|| on the %d valid rows with gap >= 1e-3: %.2g'
+                             % (fname, radius, t_host, n.shape[0], bool(np.array_equal(n, g_n)), bool(np.array_equal(flags, g_flags & 3)),
+                                int(clear.sum()), diff))
+                emit()
+
+
+if __name__ == '__main__':
+    main()
