@@ -619,6 +619,55 @@ int pcacc_accum_normals(const int64_t *keys, const int64_t *acc, const int32_t *
                         uint8_t *out_flags, int64_t *out_n, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C6. Scan-to-map registration against the accumulated scene cloud: point-to-plane ICP of one scan onto the kept voxels of a map, with the
+ * normals of C5.  It returns the scan-to-world pose to hand to pcacc_accum_add.  Replaces the copy of the scan and of up to 8 M centroids to
+ * the host and a KD-tree ICP there.  Adds no lookup and no nearest-neighbour query, and does not modify the map.
+ * Inputs
+ *   points [n,3] f32, 0 <= n <= 2^24;  moving [n] u8 or NULL (non-zero = predicted moving: the point takes part in nothing)
+ *   init_pose [4,4] f64       rows 0-2 are read, row 3 is taken as 0 0 0 1; NULL = identity
+ *   voxel_size                of the map;  max_distance in (0, voxel_size];  max_iter in [0, 10000]
+ *   keys, acc, capacity, m; min_count, use_fraction, max_moving_fraction     the map and extract's filter, as for pcacc_accum_normals
+ *   normals [n_rows,3] f32, flags [n_rows] u8     out_normals / out_flags of pcacc_accum_normals on this map under this filter;
+ *                             n_rows = the rows it wrote (its *out_n), which the caller knows
+ * Per point, all float64 with no FMA contraction, in the order csrc/accum_register.h writes down and no other:
+ *   w = pose . p with C4's transform; valid iff C4's rule holds (every w_a finite, |w_a| < 32768, floor(w_a / voxel_size) in [-2^20, 2^20)).
+ *   An invalid point has no correspondence: it is never clamped and forms no key.  It still counts in the fitness denominator.
+ *   Candidates: every map row the filter keeps whose normal has neither PCACC_NORMAL_FEW_NEIGHBORS nor PCACC_NORMAL_DEGENERATE, in the
+ *   3 x 3 x 3 voxels around the point's voxel, visited in ascending key order; offsets that leave [-2^20, 2^20) are skipped before a key
+ *   is formed.  Correspondence: the candidate with the smallest d2 = |w - c_j|^2 (c_j the float64 centroid of C5; strict <: ties go to the
+ *   lowest key), accepted iff d2 <= max_distance^2.  The contract IS this 27-voxel search; nothing is claimed about a global nearest
+ *   neighbour.  With n_j the float32 normal widened to double: r = n . (w - c), J = (w x n, n); the 21 upper entries of J J^T, the 6 of
+ *   J r, r^2 and 1 are summed over the scan in a fixed order (slots of 256 consecutive points: a tree at strides 32..1 inside each group
+ *   of 64, the 4 group sums left to right, the slots in ascending order) -- no floating-point atomics.
+ * Per round: A = sum J J^T scaled to unit diagonal, Cholesky in float64; a diagonal entry that is not > 0 or a pivot <= 1e-10 (a plane,
+ * an edge, too few points leave a direction unconstrained) sets PCACC_REGISTER_DEGENERATE and ends the job with the pose so far;
+ * otherwise A x = -b for x = (omega, t), R_d = the rotation of the unit quaternion (1, omega / 2) / |.|, pose <- [R_d | t] pose.
+ * fitness = correspondences / eligible points (eligible = not flagged moving), rmse = sqrt(sum r^2 / correspondences).  Stop when
+ * |d fitness| < 1e-6 and |d rmse| < 1e-6 against the previous round, or after max_iter updates (PCACC_REGISTER_MAX_ITER).  The stop is
+ * decided on the device: 2 (max_iter + 1) launches are queued and the call never synchronises.
+ * Outputs (device): out_pose [4,4] f64 scan-to-world; out_fitness, out_rmse f64; out_iterations (updates applied), out_status (a sum of
+ * the bits below), out_correspondences (of the last evaluation) i32.  Every status bit except PCACC_REGISTER_MAX_ITER leaves fitness and
+ * rmse at 0 and the pose at the last good value: the pose so far for DEGENERATE, the pose of the last evaluation that had
+ * correspondences otherwise -- init_pose when nothing ever matched.
+ * normals / flags that do not have the rows the filter keeps (n_rows differs from the kept count): PCACC_REGISTER_BAD_TABLE, init_pose,
+ * no round runs.  Every table index is range-checked against m, n_rows and capacity: a table that does not fit addresses nothing.
+ * Return value: PCACC_E_ARG for n outside [0, 2^24], m outside [0, capacity], n_rows outside [0, m], max_distance outside
+ * (0, voxel_size], max_iter outside [0, 10000] or a NULL table of non-zero size; nothing is launched then.
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_REGISTER_NO_ELIGIBLE 1        /* every point is flagged moving, or n = 0 */
+#define PCACC_REGISTER_NO_CANDIDATE 2       /* no kept map row has a valid normal */
+#define PCACC_REGISTER_NO_CORRESPONDENCE 4
+#define PCACC_REGISTER_DEGENERATE 8
+#define PCACC_REGISTER_MAX_ITER 16
+#define PCACC_REGISTER_BAD_TABLE 32
+int pcacc_accum_register_workspace_bytes(int64_t n, int64_t m, size_t *bytes /*host*/);
+int pcacc_accum_register(const float *points, int64_t n, const uint8_t *moving, const double *init_pose, double voxel_size,
+                         double max_distance, int32_t max_iter, const int64_t *keys, const int64_t *acc, int64_t capacity, int64_t m,
+                         int64_t min_count, int32_t use_fraction, double max_moving_fraction, const float *normals, const uint8_t *flags,
+                         int64_t n_rows, double *out_pose, double *out_fitness, double *out_rmse, int32_t *out_iterations,
+                         int32_t *out_status, int32_t *out_correspondences, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

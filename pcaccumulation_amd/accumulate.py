@@ -7,6 +7,8 @@ coordinate sums), so the map does not depend on the order of the points, on the 
 
     m = AccumulatedCloud(voxel_size=0.1, device='cuda')
     for k, (results, input_dict, pose) in enumerate(windows):
+        if k:                                                    # refine the (drifting) pose against the map so far: C6, section 9e
+            pose = m.register_results(results, input_dict, init_pose=pose, min_count=2, max_moving_fraction=0.0)['pose']
         m.add_results(results, input_dict, pose=pose, stamp=k)
     static = m.extract(min_count=2, max_moving_fraction=0.0)     # dict of device tensors
     nrm = m.normals(radius=1, min_count=2, max_moving_fraction=0.0, viewpoints=sensor_positions)   # rows aligned with `static` (C5, section 9d)
@@ -20,6 +22,7 @@ from . import native
 
 _FIELDS = ('points', 'coords', 'count', 'moving', 't_first', 't_last')
 _NORMAL_FIELDS = ('normals', 'eigenvalues', 'neighbors', 'flags')
+_REGISTER_FIELDS = ('pose', 'fitness', 'rmse', 'iterations', 'status', 'correspondences')
 _PLY_TYPES = {'float32': 'float', 'float64': 'double', 'int8': 'char', 'uint8': 'uchar', 'int16': 'short', 'uint16': 'ushort', 'int32': 'int',
               'uint32': 'uint'}
 
@@ -175,6 +178,55 @@ class AccumulatedCloud(object):
         res = {k: t[:kept] for k, t in zip(_NORMAL_FIELDS, out)}
         res['valid'] = (res['flags'] & (native.NORMAL_FEW_NEIGHBORS | native.NORMAL_DEGENERATE)) == 0
         return res
+
+    # ---- register ----------------------------------------------------------------------------------------------------------------------
+    def register(self, points, init_pose=None, moving=None, max_distance=None, max_iter=30, min_count=1, max_moving_fraction=None, radius=1,
+                 min_neighbors=5, viewpoints=None, stamp_base=0):
+        """Point-to-plane ICP of a scan onto the map (include/pcacc.h C6): the scan-to-world pose to hand to add().  The map is not modified.
+        points [n,3] f32 (device), init_pose [4,4] (tensor or array; None = identity), moving [n] (non-zero = predicted moving: the point takes part
+        in nothing), max_distance in (0, voxel_size] (None = voxel_size): a point matches the nearest kept centroid with a valid normal among the
+        3 x 3 x 3 voxels around it, if within max_distance.  min_count, max_moving_fraction, radius, min_neighbors, viewpoints, stamp_base mean what
+        they mean in normals().
+        -> dict of device tensors: pose [4,4] f64, fitness, rmse (f64 scalars), iterations, status, correspondences (i32 scalars); status is a sum
+        of native.REGISTER_* bits (0 = converged).  Every bit except REGISTER_MAX_ITER leaves fitness and rmse at 0 and the pose at the last good
+        value (init_pose when nothing ever matched).
+        Every call computes the normals anew, because the rows move with every add: the cost of one normals() call (profiles/accum_normals_bench.txt:
+        2.78 ms at 8.0 M voxels and r = 1 without a filter, 1.07 ms with min_count=2, max_moving_fraction=0.0) comes on top of the rounds (profiles/accum_register_bench.txt: about
+        2 ms per round at 800 k points against 2 - 8 M voxels).  Only the kept count that normals() reads is read back."""
+        if not torch.is_tensor(points) or not points.is_cuda:
+            raise native.NativeError('register: points must be a tensor on the GPU; the HIP path has no CPU fallback')
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError('points must be [n,3], got %s' % (tuple(points.shape),))
+        n = points.shape[0]
+        if n > native.REGISTER_MAX_POINTS:
+            raise ValueError('at most 2^24 points per register, got %d' % n)
+        if moving is not None:
+            if not moving.is_cuda:
+                raise native.NativeError('register: moving must live on the GPU')
+            if tuple(moving.shape) != (n,):
+                raise ValueError('moving must be [n], got %s' % (tuple(moving.shape),))
+        max_distance = self.voxel_size if max_distance is None else float(max_distance)
+        if not 0.0 < max_distance <= self.voxel_size:
+            raise ValueError('max_distance must lie in (0, voxel_size = %r], got %r' % (self.voxel_size, max_distance))
+        if not 0 <= int(max_iter) <= native.REGISTER_MAX_ITERATIONS:
+            raise ValueError('max_iter must lie in [0, %d], got %r' % (native.REGISTER_MAX_ITERATIONS, max_iter))
+        init = self._pose(init_pose)
+        nrm = self.normals(radius, min_neighbors, min_count, max_moving_fraction, viewpoints, stamp_base)
+        pts = points.detach().float().contiguous()
+        mv = (moving != 0).to(torch.uint8).contiguous() if moving is not None else None
+        out = native.accum_register(pts, mv, init, self.voxel_size, max_distance, int(max_iter), self._cur, self._n, min_count,
+                                    max_moving_fraction, nrm['normals'], nrm['flags'])
+        return dict(zip(_REGISTER_FIELDS, out))
+
+    def register_results(self, results, input_dict, init_pose=None, **kw):
+        """register() of a test / val-mode forward: results['rec_est'], with results['mos_est'].argmax(1) == 1 as `moving`.  One sample per batch."""
+        batch = input_dict['time_indice'][:, 0]
+        n_batches = results.get('_n_batches')
+        if n_batches is None:
+            n_batches = int(batch.max()) + 1 if batch.numel() else 1
+        if n_batches != 1:
+            raise ValueError('register_results: one sample per batch, got %d' % n_batches)
+        return self.register(results['rec_est'], init_pose, results['mos_est'].argmax(1) == 1, **kw)
 
     def save_ply(self, path, normals=True, min_count=1, max_moving_fraction=None, **normal_args):
         """extract(min_count, max_moving_fraction) as a binary PLY: x y z, with normals=True nx ny nz of normals(**normal_args) under the same filter

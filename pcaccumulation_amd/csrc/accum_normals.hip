@@ -3,12 +3,13 @@
 // The map of accum.hip is a sorted, duplicate-free key list whose low bits are z: the neighbourhood of a voxel is (2r+1)^2 binary searches, each
 // followed by a walk over at most 2r+1 consecutive rows.  No hash table, no floating-point atomics, no LDS beyond the scan's, no inline assembly.
 //   pass 1   keep flags (extract's predicate) -> scan.h -> dst[m]: output row of every map row, -1 = does not participate; rows[kept]: its inverse.
-//            dst serves as the neighbour test AND the output row: a neighbour costs one gather, not a re-evaluation of the predicate.
+//            (accn_rows_launch of accum_rows.h: accum_register.hip calls the same launch sequence.)  dst serves as the neighbour test AND the output row: a neighbour costs one gather, not a re-evaluation of the predicate.
 //   pass 2   one lane per participating row, consecutive lanes on consecutive rows (their searches land next to each other); the whole result of a
 //            voxel is accum_normal_voxel of accum_normals.h -- the code the host build runs with every index assert-checked; outputs written once.
 // Everything a result depends on is the set of integer records, visited in key order: two runs give the same bits.
 #include "scan.h"
 #include "accum_normals.h"
+#include "accum_rows.h"
 
 #define ACCN_BLOCK 256
 #define ACCN_MAX_CAPACITY ((int64_t)1 << 30)        // as accum.hip: int scans and int row numbers
@@ -55,22 +56,37 @@ static __global__ __launch_bounds__(ACCN_BLOCK) void accn_normals_kernel(const u
     }
 }
 
-static size_t accn_ws(int64_t m, int **dst, int **kpos, int **rows, int **chunk, char *base)
+size_t accn_rows_carve(int64_t m, AccnRows *t, char *base)
 {
     size_t off = 0;
     auto take = [&](size_t bytes) { char *p = base + off; off += pcacc_align(bytes); return p; };
-    *dst = (int *)take((size_t)m * 4);
-    *kpos = (int *)take((size_t)(m + 1) * 4);
-    *rows = (int *)take((size_t)m * 4);
-    *chunk = (int *)take((size_t)pcacc_chunks(m) * 4);
+    t->dst = (int *)take((size_t)m * 4);
+    t->kpos = (int *)take((size_t)(m + 1) * 4);
+    t->rows = (int *)take((size_t)m * 4);
+    t->chunk = (int *)take((size_t)pcacc_chunks(m) * 4);
     return off;
+}
+
+int accn_rows_launch(const int64_t *acc, int64_t capacity, int64_t m, int64_t min_count, int use_fraction, double max_moving_fraction, const AccnRows &t,
+                     int64_t *out_n, hipStream_t st)
+{
+    const int grid = pcacc_grid(m, ACCN_BLOCK);
+    const int nc = pcacc_chunks(m);
+    hipLaunchKernelGGL(accn_keep_kernel, dim3(grid), dim3(ACCN_BLOCK), 0, st, acc, capacity, m, min_count, use_fraction, max_moving_fraction, t.dst);
+    hipLaunchKernelGGL(chunk_sums_i32, dim3(nc), dim3(256), 0, st, (const int *)t.dst, m, t.chunk);
+    hipLaunchKernelGGL(scan_chunk_sums, dim3(1), dim3(1024), 0, st, t.chunk, nc, (int *)nullptr, -1);
+    hipLaunchKernelGGL(chunk_scan_i32, dim3(nc), dim3(256), 0, st, (const int *)t.dst, m, (const int *)t.chunk, t.kpos, 1, (int *)nullptr);     // kpos[m] = kept
+    PCACC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(accn_dst_kernel, dim3(grid), dim3(ACCN_BLOCK), 0, st, t.dst, (const int *)t.kpos, m, t.rows, out_n);
+    PCACC_CHECK_LAUNCH();
+    return PCACC_OK;
 }
 
 extern "C" int pcacc_accum_normals_workspace_bytes(int64_t m, size_t *bytes)
 {
     if (!bytes || m < 0 || m > ACCN_MAX_CAPACITY) return PCACC_E_ARG;
-    int *a, *b, *c, *d;
-    *bytes = accn_ws(m > 0 ? m : 1, &a, &b, &c, &d, nullptr);
+    AccnRows t;
+    *bytes = accn_rows_carve(m > 0 ? m : 1, &t, nullptr);
     return PCACC_OK;
 }
 
@@ -85,16 +101,10 @@ extern "C" int pcacc_accum_normals(const int64_t *keys, const int64_t *acc, cons
     hipStream_t st = pcacc_stream(stream);
     if (m == 0) return hipMemsetAsync(out_n, 0, sizeof(int64_t), st) == hipSuccess ? PCACC_OK : PCACC_E_LAUNCH;
     if (!keys || !acc || !stamps || !out_normals || !out_eigenvalues || !out_neighbors || !out_flags || !workspace) return PCACC_E_ARG;
-    int *dst, *kpos, *rows, *chunk;
-    if (workspace_bytes < accn_ws(m, &dst, &kpos, &rows, &chunk, (char *)workspace)) return PCACC_E_WORKSPACE;
-    const int grid = pcacc_grid(m, ACCN_BLOCK);
-    const int nc = pcacc_chunks(m);
-    hipLaunchKernelGGL(accn_keep_kernel, dim3(grid), dim3(ACCN_BLOCK), 0, st, acc, capacity, m, min_count, (int)use_fraction, max_moving_fraction, dst);
-    hipLaunchKernelGGL(chunk_sums_i32, dim3(nc), dim3(256), 0, st, (const int *)dst, m, chunk);
-    hipLaunchKernelGGL(scan_chunk_sums, dim3(1), dim3(1024), 0, st, chunk, nc, (int *)nullptr, -1);
-    hipLaunchKernelGGL(chunk_scan_i32, dim3(nc), dim3(256), 0, st, (const int *)dst, m, (const int *)chunk, kpos, 1, (int *)nullptr);     // kpos[m] = kept
-    PCACC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(accn_dst_kernel, dim3(grid), dim3(ACCN_BLOCK), 0, st, dst, (const int *)kpos, m, rows, out_n);
+    AccnRows t;
+    if (workspace_bytes < accn_rows_carve(m, &t, (char *)workspace)) return PCACC_E_WORKSPACE;
+    if (accn_rows_launch(acc, capacity, m, min_count, (int)use_fraction, max_moving_fraction, t, out_n, st) != PCACC_OK) return PCACC_E_LAUNCH;
+    const int *dst = t.dst, *rows = t.rows, *kpos = t.kpos;
     // a lane carries ~100 VGPRs of float64 state and serial searches: many small workgroups spread over the CUs, not a short grid-stride loop
     hipLaunchKernelGGL(accn_normals_kernel, dim3(pcacc_grid(m, ACCN_BLOCK, 1 << 22)), dim3(ACCN_BLOCK), 0, st, (const unsigned long long *)keys, acc, stamps,
                        capacity, m, (const int *)dst, (const int *)rows, (const int *)(kpos + m), (int)radius, (int)min_neighbors,

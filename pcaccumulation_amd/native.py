@@ -767,6 +767,42 @@ def accum_normals(tables, m, min_count, max_moving_fraction, radius, min_neighbo
     return normals, eigenvalues, neighbors, flags, kept
 
 
+REGISTER_NO_ELIGIBLE, REGISTER_NO_CANDIDATE, REGISTER_NO_CORRESPONDENCE, REGISTER_DEGENERATE, REGISTER_MAX_ITER, REGISTER_BAD_TABLE = 1, 2, 4, 8, 16, 32
+REGISTER_MAX_POINTS, REGISTER_MAX_ITERATIONS = 1 << 24, 10000
+
+
+def accum_register(points, moving, init_pose, voxel_size, max_distance, max_iter, tables, m, min_count, max_moving_fraction, normals, flags):
+    """Point-to-plane registration of a scan onto the first m rows of a map; see include/pcacc.h (C6).  points [n,3] f32, moving [n] u8 or None,
+    init_pose [4,4] f64 or None, normals [V,3] f32 / flags [V] u8 = accum_normals' rows on this map under the same filter (sliced to its kept count).
+    -> (pose [4,4] f64, fitness [] f64, rmse [] f64, iterations [] i32, status [] i32, correspondences [] i32) on the device; nothing is read back."""
+    keys, acc, _, cap = _accum_tables(tables, 'accum_register')
+    dev = tables[0].device
+    n, m = points.shape[0], int(m)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise NativeError('accum_register: points must be [n,3], got %s' % (tuple(points.shape),))
+    if moving is not None and tuple(moving.shape) != (n,):
+        raise NativeError('accum_register: moving must be [n], got %s' % (tuple(moving.shape),))
+    if init_pose is not None and tuple(init_pose.shape) != (4, 4):
+        raise NativeError('accum_register: init_pose must be [4,4], got %s' % (tuple(init_pose.shape),))
+    v = normals.shape[0]
+    if tuple(normals.shape) != (v, 3) or tuple(flags.shape) != (v,):
+        raise NativeError('accum_register: normals [V,3] and flags [V] expected, got %s %s' % (tuple(normals.shape), tuple(flags.shape)))
+    pts = _dev(points, torch.float32, 'points')
+    mv = _dev(moving, torch.uint8, 'moving') if moving is not None else None
+    init = _dev(init_pose, torch.float64, 'init_pose') if init_pose is not None else None
+    nrm, flg = _dev(normals, torch.float32, 'normals'), _dev(flags, torch.uint8, 'flags')
+    pose = torch.empty((4, 4), dtype=torch.float64, device=dev)
+    stats = torch.empty((2,), dtype=torch.float64, device=dev)
+    words = torch.empty((3,), dtype=torch.int32, device=dev)
+    ws = _workspace(lib().pcacc_accum_register_workspace_bytes, dev, n, m)
+    _check(lib().pcacc_accum_register(pts if n else None, n, mv if n else None, init, float(voxel_size), float(max_distance), int(max_iter), keys, acc, cap, m,
+                                      int(min_count), 0 if max_moving_fraction is None else 1,
+                                      0.0 if max_moving_fraction is None else float(max_moving_fraction), nrm if v else None, flg if v else None, v,
+                                      _dev(pose), _dev(stats[0:1]), _dev(stats[1:2]), _dev(words[0:1]), _dev(words[1:2]), _dev(words[2:3]),
+                                      _dev(ws), ws.numel(), _stream()), 'accum_register')
+    return pose, stats[0], stats[1], words[0], words[1], words[2]
+
+
 def conv3x3_supported(c_in, c_out):
     return c_in >= 32 and c_out >= 32 and c_in % 32 == 0 and c_out % 32 == 0
 
