@@ -491,7 +491,7 @@ int pcacc_cluster_eval(const int64_t *inst_est, const int64_t *inst_gt, const vo
  *   out_status [n_jobs] i32   a sum of PCACC_ICP_* below
  * Algorithm (all float64, fp32 inputs promoted): correspondence of a source point = its nearest target point if within the
  * threshold (equal distances: the LOWEST target index); then at most max_iter rounds of { update = least-squares rigid
- * transform of the correspondences (Umeyama without scale: centroids, 3x3 covariance, SVD, reflection fix), identity without
+ * transform of the correspondences (Umeyama without scale: centroids, 3x3 covariance, the SVD of csrc/svd3.h, reflection fix), identity without
  * correspondences; T = update @ T; correspondences again; stop when |d fitness| < 1e-6 and |d rmse| < 1e-6 }.  The source is
  * transformed by the composed pose each round (Open3D transforms it round by round: the same up to float64 rounding).
  * Deterministic: no floating-point atomics, fixed-order sums; two calls give the same bits.  Convergence is decided per job on
@@ -500,10 +500,11 @@ int pcacc_cluster_eval(const int64_t *inst_est, const int64_t *inst_gt, const vo
  * `threshold`, 16 bits per axis); any other point -- as source after the current pose, or as target -- has no correspondence
  * (it is never clamped into an edge cell and forms no address), and still counts in the denominator of the fitness.
  * Empty source, empty target, no correspondence: identity update, fitness 0, rmse 0.  Fewer than three non-collinear
- * correspondences (rank-deficient covariance) are outside the parity claim: the missing singular vectors are completed to a
- * right-handed orthonormal basis (u0 x e_m for the axis m on which u0 is smallest, then u0 x u1), a zero covariance gives the
+ * correspondences (rank-deficient covariance) are outside the parity claim: csrc/svd3.h completes the missing singular vectors
+ * to a right-handed orthonormal basis (u0 x e_m for the axis m on which u0 is smallest, then u0 x u1), a zero covariance gives the
  * identity rotation -- always a finite proper rotation, the same every run.  A singular value at or below 1e-10 * mean(t . q)
- * (the rounding noise of the uncentred float64 sums the covariance is formed from) counts as zero.
+ * (the rounding noise of the uncentred float64 sums the covariance is formed from) counts as zero (jacobi_svd3_floor).
+ * The whole round is header code (csrc/icp_round.h) that a g++ build compiles as well: the kernels give that build's bits.
  * Tables that cannot be trusted (offsets not ascending or outside [0, n], a job naming a segment outside [0, n_seg)) address
  * nothing: every job returns identity with PCACC_ICP_BAD_TABLE.
  * ---------------------------------------------------------------------------------------------- */

@@ -35,22 +35,22 @@ struct AccnResult {
 };
 
 // i itself when it lies in [0, n), else -1 (nothing is addressed); the host build asserts.
-ACC_HD int64_t accn_index(int64_t i, int64_t n)
+PCACC_HD int64_t accn_index(int64_t i, int64_t n)
 {
-    ACC_BOUND(i, n);
+    PCACC_BOUND(i, n);
     return (i >= 0 && i < n) ? i : -1;
 }
 
-ACC_HD bool accn_in_range(int64_t idx) { return idx >= -(int64_t)ACC_IDX_BIAS && idx < (int64_t)ACC_IDX_BIAS; }
+PCACC_HD bool accn_in_range(int64_t idx) { return idx >= -(int64_t)ACC_IDX_BIAS && idx < (int64_t)ACC_IDX_BIAS; }
 
-ACC_HD double accn_centroid(int64_t sum_q, int64_t count)
+PCACC_HD double accn_centroid(int64_t sum_q, int64_t count)
 {
-    ACC_NO_CONTRACT
+    PCACC_NO_CONTRACT
     return ((double)sum_q / (double)count) * (1.0 / ACC_FIXED_ONE);
 }
 
 // The z run of column (cx, cy) around cz: rows [*first, *first + n) of keys[0..m), n <= 2r+1 returned.  0 when the column lies outside the grid.
-ACC_HD int accn_column(const unsigned long long *keys, int64_t m, int64_t cx, int64_t cy, int64_t cz, int r, int64_t *first)
+PCACC_HD int accn_column(const unsigned long long *keys, int64_t m, int64_t cx, int64_t cy, int64_t cz, int r, int64_t *first)
 {
     *first = 0;
     if (!accn_in_range(cx) || !accn_in_range(cy)) return 0;
@@ -71,10 +71,10 @@ ACC_HD int accn_column(const unsigned long long *keys, int64_t m, int64_t cx, in
 
 // The whole result of map row i (a participating row: dst[i] >= 0).  dst[m]: output row of every map row, -1 = does not participate.
 // false (and *out untouched, nothing addressed) when i is no row of the map.
-ACC_HD bool accum_normal_voxel(const unsigned long long *keys, const int64_t *acc, const int32_t *stamps, int64_t capacity, int64_t m, const int *dst,
-                               int64_t i, int radius, int min_neighbors, const double *viewpoints, int64_t n_viewpoints, int64_t stamp_base, AccnResult *out)
+PCACC_HD bool accum_normal_voxel(const unsigned long long *keys, const int64_t *acc, const int32_t *stamps, int64_t capacity, int64_t m, const int *dst,
+                                 int64_t i, int radius, int min_neighbors, const double *viewpoints, int64_t n_viewpoints, int64_t stamp_base, AccnResult *out)
 {
-    ACC_NO_CONTRACT
+    PCACC_NO_CONTRACT
     if (accn_index(i, m) < 0 || m > capacity) return false;
     int32_t c[3];
     accum_unkey(keys[i], c);

@@ -24,7 +24,7 @@
 // diagonal A_aa that is not > 0 or a pivot <= 1e-10 (C3's zero threshold) means a direction nothing constrains (a plane, an edge, too few points):
 // DEGENERATE.  Otherwise L y = -bs, L^T z = y, x_a = z_a / d_a, x = (omega, t).
 // Update: h = omega / 2; s = sqrt(1 + ((h_x h_x + h_y h_y) + h_z h_z)); q = (1, h) / s (w, x, y, z); R_d = the rotation of the unit quaternion q (no sin /
-// cos; a proper rotation to rounding); T <- [R_d | t] T with N_rc = ((R_r0 T_0c + R_r1 T_1c) + R_r2 T_2c) (+ t_r for c = 3).
+// cos; a proper rotation to rounding); T <- [R_d | t] T by hd.h's pcacc_pose_compose: N_rc = ((R_r0 T_0c + R_r1 T_1c) + R_r2 T_2c) (+ t_r for c = 3).
 // Round k = 0 .. max_iter (accr_round): sums -> correspondences nc, fitness = nc / eligible, rmse = sqrt(sum r^2 / nc); stop when k > 0 and
 // |d fitness| < 1e-6 and |d rmse| < 1e-6, or when k = max_iter (status MAX_ITER unless it converged at that very round); else solve and update.
 #pragma once
@@ -34,7 +34,6 @@
 #define ACCR_SLOT 256
 #define ACCR_GROUP 64
 #define ACCR_PIVOT_TOL 1e-10
-#define ACCR_STOP_TOL 1e-6
 
 #define ACCR_NO_ELIGIBLE 1            // every point is flagged moving, or the scan is empty
 #define ACCR_NO_CANDIDATE 2           // no map row under the filter has a valid normal
@@ -52,13 +51,13 @@ struct AccrState {
 };
 
 // World coordinates and voxel of point p under T; false = invalid, w and idx then hold nothing.
-ACC_HD bool accr_world(const double *T, const float *p, double voxel_size, double w[3], int64_t idx[3])
+PCACC_HD bool accr_world(const double *T, const float *p, double voxel_size, double w[3], int64_t idx[3])
 {
-    ACC_NO_CONTRACT
+    PCACC_NO_CONTRACT
     const double x = p[0], y = p[1], z = p[2];
     for (int a = 0; a < 3; ++a) {
         const double v = ((T[4 * a] * x + T[4 * a + 1] * y) + T[4 * a + 2] * z) + T[4 * a + 3];
-        if (!accum_finite(v) || !(__builtin_fabs(v) < ACC_COORD_LIMIT)) return false;
+        if (!pcacc_finite(v) || !(__builtin_fabs(v) < ACC_COORD_LIMIT)) return false;
         const double c = __builtin_floor(v / voxel_size);
         if (!(c >= -(double)ACC_IDX_BIAS && c < (double)ACC_IDX_BIAS)) return false;
         w[a] = v;
@@ -68,7 +67,7 @@ ACC_HD bool accr_world(const double *T, const float *p, double voxel_size, doubl
 }
 
 // Output row of map row p when it is a candidate, else -1: dst[p] in [0, n_rows) and neither flag 1 nor flag 2 on it.
-ACC_HD int64_t accr_candidate(const int *dst, const uint8_t *flags, int64_t n_rows, int64_t p)
+PCACC_HD int64_t accr_candidate(const int *dst, const uint8_t *flags, int64_t n_rows, int64_t p)
 {
     const int64_t j = dst[p];
     if (j < 0) return -1;
@@ -77,10 +76,10 @@ ACC_HD int64_t accr_candidate(const int *dst, const uint8_t *flags, int64_t n_ro
 }
 
 // The correspondence of world point w in voxel idx: its map row (and *out_row = the row of the normal tables, c = its centroid, *out_d2), or -1.
-ACC_HD int64_t accr_match(const unsigned long long *keys, const int64_t *acc, int64_t capacity, int64_t m, const int *dst, const uint8_t *flags,
-                          int64_t n_rows, const double w[3], const int64_t idx[3], double max_d2, int64_t *out_row, double c[3], double *out_d2)
+PCACC_HD int64_t accr_match(const unsigned long long *keys, const int64_t *acc, int64_t capacity, int64_t m, const int *dst, const uint8_t *flags,
+                            int64_t n_rows, const double w[3], const int64_t idx[3], double max_d2, int64_t *out_row, double c[3], double *out_d2)
 {
-    ACC_NO_CONTRACT
+    PCACC_NO_CONTRACT
     int64_t best = -1, best_row = -1;
     double best_d2 = 0.0;
     if (m > capacity) return -1;
@@ -111,9 +110,9 @@ ACC_HD int64_t accr_match(const unsigned long long *keys, const int64_t *acc, in
 }
 
 // The 29 terms of a correspondence (world point w, centroid c, float32 normal n32 of the matched row).
-ACC_HD void accr_terms(const double w[3], const double c[3], const float *n32, double t[ACCR_TERMS])
+PCACC_HD void accr_terms(const double w[3], const double c[3], const float *n32, double t[ACCR_TERMS])
 {
-    ACC_NO_CONTRACT
+    PCACC_NO_CONTRACT
     const double nx = n32[0], ny = n32[1], nz = n32[2];
     const double ex = w[0] - c[0], ey = w[1] - c[1], ez = w[2] - c[2];
     const double r = (nx * ex + ny * ey) + nz * ez;
@@ -131,9 +130,9 @@ ACC_HD void accr_terms(const double w[3], const double c[3], const float *n32, d
 }
 
 // The 29 terms of scan point i (all +0.0 without a correspondence); *out_map_row = the matched map row or -1.
-ACC_HD void accr_point(const unsigned long long *keys, const int64_t *acc, int64_t capacity, int64_t m, const int *dst, const float *normals,
-                       const uint8_t *flags, int64_t n_rows, const double *T, const float *points, const uint8_t *moving, int64_t n, int64_t i,
-                       double voxel_size, double max_d2, double t[ACCR_TERMS], int64_t *out_map_row)
+PCACC_HD void accr_point(const unsigned long long *keys, const int64_t *acc, int64_t capacity, int64_t m, const int *dst, const float *normals,
+                         const uint8_t *flags, int64_t n_rows, const double *T, const float *points, const uint8_t *moving, int64_t n, int64_t i,
+                         double voxel_size, double max_d2, double t[ACCR_TERMS], int64_t *out_map_row)
 {
     for (int k = 0; k < ACCR_TERMS; ++k) t[k] = 0.0;
     *out_map_row = -1;
@@ -149,9 +148,9 @@ ACC_HD void accr_point(const unsigned long long *keys, const int64_t *acc, int64
 }
 
 // The sum of one term over a slot: v[ACCR_SLOT] is used as scratch.
-ACC_HD double accr_slot_sum(double *v)
+PCACC_HD double accr_slot_sum(double *v)
 {
-    ACC_NO_CONTRACT
+    PCACC_NO_CONTRACT
     for (int g = 0; g < ACCR_SLOT / ACCR_GROUP; ++g)
         for (int s = ACCR_GROUP / 2; s > 0; s >>= 1)
             for (int l = 0; l < s; ++l) v[g * ACCR_GROUP + l] = v[g * ACCR_GROUP + l] + v[g * ACCR_GROUP + l + s];
@@ -161,15 +160,15 @@ ACC_HD double accr_slot_sum(double *v)
 }
 
 // x = (omega, t) of the summed terms; false = DEGENERATE (x then holds nothing).
-ACC_HD bool accr_solve(const double s[ACCR_TERMS], double x[6])
+PCACC_HD bool accr_solve(const double s[ACCR_TERMS], double x[6])
 {
-    ACC_NO_CONTRACT
+    PCACC_NO_CONTRACT
     double A[6][6], L[6][6], d[6], y[6];
     int k = 0;
     for (int a = 0; a < 6; ++a)
         for (int b = a; b < 6; ++b) { A[a][b] = s[k]; A[b][a] = s[k]; ++k; }
     for (int a = 0; a < 6; ++a) {
-        if (!(A[a][a] > 0.0) || !accum_finite(A[a][a])) return false;
+        if (!(A[a][a] > 0.0) || !pcacc_finite(A[a][a])) return false;
         d[a] = __builtin_sqrt(A[a][a]);
     }
     for (int a = 0; a < 6; ++a)
@@ -197,36 +196,29 @@ ACC_HD bool accr_solve(const double s[ACCR_TERMS], double x[6])
     }
     for (int a = 0; a < 6; ++a) {
         x[a] = x[a] / d[a];
-        if (!accum_finite(x[a])) return false;
+        if (!pcacc_finite(x[a])) return false;
     }
     return true;
 }
 
 // T <- [R_d | t] T for x = (omega, t); rows 0-2 of T.
-ACC_HD void accr_compose(const double x[6], double *T)
+PCACC_HD void accr_compose(const double x[6], double *T)
 {
-    ACC_NO_CONTRACT
+    PCACC_NO_CONTRACT
     const double hx = x[0] / 2.0, hy = x[1] / 2.0, hz = x[2] / 2.0;
     const double s = __builtin_sqrt(1.0 + ((hx * hx + hy * hy) + hz * hz));
     const double qw = 1.0 / s, qx = hx / s, qy = hy / s, qz = hz / s;
-    double R[3][3], N[12];
-    R[0][0] = 1.0 - 2.0 * (qy * qy + qz * qz); R[0][1] = 2.0 * (qx * qy - qw * qz); R[0][2] = 2.0 * (qx * qz + qw * qy);
-    R[1][0] = 2.0 * (qx * qy + qw * qz); R[1][1] = 1.0 - 2.0 * (qx * qx + qz * qz); R[1][2] = 2.0 * (qy * qz - qw * qx);
-    R[2][0] = 2.0 * (qx * qz - qw * qy); R[2][1] = 2.0 * (qy * qz + qw * qx); R[2][2] = 1.0 - 2.0 * (qx * qx + qy * qy);
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 4; ++c) {
-            const double v = (R[r][0] * T[c] + R[r][1] * T[4 + c]) + R[r][2] * T[8 + c];
-            N[4 * r + c] = c == 3 ? v + x[3 + r] : v;
-        }
-    for (int k = 0; k < 12; ++k) T[k] = N[k];
+    double R[9];
+    R[0] = 1.0 - 2.0 * (qy * qy + qz * qz); R[1] = 2.0 * (qx * qy - qw * qz); R[2] = 2.0 * (qx * qz + qw * qy);
+    R[3] = 2.0 * (qx * qy + qw * qz); R[4] = 1.0 - 2.0 * (qx * qx + qz * qz); R[5] = 2.0 * (qy * qz - qw * qx);
+    R[6] = 2.0 * (qx * qz - qw * qy); R[7] = 2.0 * (qy * qz + qw * qx); R[8] = 1.0 - 2.0 * (qx * qx + qy * qy);
+    pcacc_pose_compose(R, x + 3, T);
 }
 
 // A fresh job: the pose is rows 0-2 of init (NULL = identity), row 3 is 0 0 0 1.
-ACC_HD void accr_init(AccrState *st, const double *init, int64_t eligible, int64_t candidates)
+PCACC_HD void accr_init(AccrState *st, const double *init, int64_t eligible, int64_t candidates)
 {
-    for (int k = 0; k < 12; ++k) st->T[k] = init ? init[k] : ((k % 5 == 0) ? 1.0 : 0.0);
-    st->T[12] = st->T[13] = st->T[14] = 0.0;
-    st->T[15] = 1.0;
+    pcacc_pose_seed(st->T, init);
     for (int k = 0; k < 16; ++k) st->T_good[k] = st->T[k];
     st->fit = st->rmse = 0.0;
     st->eligible = eligible;
@@ -239,7 +231,7 @@ struct AccrOut {                      // written once, by the round that finishe
     int32_t *iterations, *status, *correspondences;
 };
 
-ACC_HD void accr_finish(AccrState *st, const AccrOut *o, const double *pose, double fit, double rmse, int iters, int status, double nc)
+PCACC_HD void accr_finish(AccrState *st, const AccrOut *o, const double *pose, double fit, double rmse, int iters, int status, double nc)
 {
     for (int k = 0; k < 16; ++k) o->pose[k] = pose[k];
     *o->fitness = fit;
@@ -253,9 +245,9 @@ ACC_HD void accr_finish(AccrState *st, const AccrOut *o, const double *pose, dou
 }
 
 // Round `round` of a job that is not done, from the summed terms of the evaluation under st->T.
-ACC_HD void accr_round(AccrState *st, const double s[ACCR_TERMS], int round, int max_iter, const AccrOut *o)
+PCACC_HD void accr_round(AccrState *st, const double s[ACCR_TERMS], int round, int max_iter, const AccrOut *o)
 {
-    ACC_NO_CONTRACT
+    PCACC_NO_CONTRACT
     if (st->status & ACCR_BAD_TABLE) { accr_finish(st, o, st->T_good, 0.0, 0.0, 0, ACCR_BAD_TABLE, 0.0); return; }
     if (st->eligible <= 0 || st->candidates <= 0) {
         accr_finish(st, o, st->T_good, 0.0, 0.0, st->iters,
@@ -267,7 +259,7 @@ ACC_HD void accr_round(AccrState *st, const double s[ACCR_TERMS], int round, int
     const double fit = nc / (double)st->eligible;
     const double rmse = __builtin_sqrt(s[27] / nc);
     for (int k = 0; k < 16; ++k) st->T_good[k] = st->T[k];
-    const bool converged = round > 0 && __builtin_fabs(fit - st->fit) < ACCR_STOP_TOL && __builtin_fabs(rmse - st->rmse) < ACCR_STOP_TOL;
+    const bool converged = round > 0 && pcacc_icp_stop(fit, st->fit, rmse, st->rmse);
     if (converged || round >= max_iter) {
         accr_finish(st, o, st->T, fit, rmse, round, st->status | (converged ? 0 : ACCR_MAX_ITER), nc);
         return;

@@ -7,27 +7,22 @@
 //   icp_insert   every finite, in-range point of a target segment claims the hash slot of its (segment, cell) key with one 64-bit CAS and
 //                counts itself there; icp_fill (behind a scan of the counts: scan.h) writes the point lists.  The index is built ONCE per call:
 //                the target of a job is fixed over all rounds, and the T - 1 jobs of a sample share one target segment.
-//   icp_corr     round r, workgroup (job, slice): the slice's source points under the job's current pose, nearest target through the 27-cell
-//                walk of icp_grid.h, 17 float64 sums (count, sum q, sum t, sum t q^T, sum d^2) reduced in a fixed order into the slot of (job, slice).
-//   icp_update   round r, one wave per job: the slots added in slice order, fitness / rmse, the convergence test against the previous round,
-//                then the least-squares rigid update (Umeyama without scale, 3x3 one-sided Jacobi SVD) composed onto the pose.
-// All arithmetic on coordinates is float64.  No floating-point atomics, no order that depends on scheduling: the order of the entries in a cell's
-// list does (integer atomics), but the walk picks by (distance^2, index), so two runs give the same bits.  Convergence is per job on the device;
-// a finished job's later rounds return at once; the host never waits inside the loop (2 * (max_iter + 1) launches, queued back to back).
+//   icp_corr     round r, workgroup (job, slice): every lane runs icp_lane_sums of icp_round.h -- the slice's source points under the job's current
+//                pose, nearest target through the 27-cell walk of icp_grid.h, 17 float64 sums (count, sum q, sum t, sum t q^T, sum d^2) -- and the
+//                workgroup reduces them in icp_tree_sum's order in LDS into the slot of (job, slice).
+//   icp_update   round r, one wave per job: the slots added in slice order, then icp_round of icp_round.h on one lane: fitness / rmse, the
+//                convergence test against the previous round, the least-squares rigid update (Umeyama without scale on svd3.h's SVD) composed
+//                onto the pose.
+// Every value a result depends on is computed by icp_grid.h / icp_round.h, the code the host build runs with every index assert-checked; this file
+// holds the index build, the LDS tree and the launches.  All arithmetic on coordinates is float64.  No floating-point atomics, no order that depends
+// on scheduling: the order of the entries in a cell's list does (integer atomics), but the walk picks by (distance^2, index), so two runs give the
+// same bits, and they are the host build's.  Convergence is per job on the device; a finished job's later rounds return at once; the host never
+// waits inside the loop (2 * (max_iter + 1) launches, queued back to back).
 #include "common.h"
-#include "icp_grid.h"
+#include "icp_round.h"
 #include "scan.h"
 
-#define ICP_BLOCK 256
-#define ICP_SUMS 17
-#define ICP_MAX_SLICES 64
 #define ICP_BAD_TABLE 1            // ctrl[0]
-
-struct IcpState {                  // per job, in the workspace
-    double T[16];                  // accumulated update @ initial pose
-    double fit, rmse;              // of the previous round
-    int32_t done, iters, status, pad;
-};
 
 struct IcpWs {
     unsigned long long *keys;      // [slots]      | zero-filled per call
@@ -58,13 +53,7 @@ static size_t icp_carve(IcpWs *w, char *base, int64_t n, int32_t n_seg, int32_t 
     uint32_t slots = 64;
     while ((int64_t)slots < 2 * n) slots <<= 1;
     w->slots = slots;
-    // slices of a job's source: enough workgroups to fill the device when there are few jobs, never more than 256-point pieces of the whole array
-    int slices = n_jobs > 0 ? 2048 / n_jobs : 1;
-    const int64_t pieces = (n + ICP_BLOCK - 1) / ICP_BLOCK;
-    if (slices > ICP_MAX_SLICES) slices = ICP_MAX_SLICES;
-    if (slices > pieces) slices = (int)pieces;
-    if (slices < 1) slices = 1;
-    w->slices = slices;
+    w->slices = icp_slices(n, n_jobs);
     w->keys = (unsigned long long *)take((size_t)slots * 8);
     w->cnt = (int32_t *)take((size_t)slots * 4);
     w->tflag = (int32_t *)take((size_t)n_seg * 4);
@@ -74,7 +63,7 @@ static size_t icp_carve(IcpWs *w, char *base, int64_t n, int32_t n_seg, int32_t 
     w->pslot = (int32_t *)take((size_t)(n > 0 ? n : 1) * 4);
     w->list = (int32_t *)take((size_t)(n > 0 ? n : 1) * 4);
     w->sums = (int32_t *)take(((size_t)pcacc_chunks(slots) + 1) * 4);
-    w->partial = (double *)take((size_t)(n_jobs > 0 ? n_jobs : 1) * slices * ICP_SUMS * 8);
+    w->partial = (double *)take((size_t)(n_jobs > 0 ? n_jobs : 1) * w->slices * ICP_SUMS * 8);
     w->state = (IcpState *)take((size_t)(n_jobs > 0 ? n_jobs : 1) * sizeof(IcpState));
     return off;
 }
@@ -102,9 +91,7 @@ __global__ __launch_bounds__(ICP_BLOCK) void icp_setup(const int32_t *__restrict
         IcpState &s = w.state[i];
         if (src < 0 || src >= n_seg || tgt < 0 || tgt >= n_seg) atomicOr(&w.ctrl[0], ICP_BAD_TABLE);
         else w.tflag[tgt] = 1;
-        for (int k = 0; k < 12; ++k) s.T[k] = init ? init[16 * (int64_t)i + k] : ((k % 5 == 0) ? 1.0 : 0.0);
-        s.T[12] = s.T[13] = s.T[14] = 0.0;
-        s.T[15] = 1.0;
+        pcacc_pose_seed(s.T, init ? init + 16 * (int64_t)i : nullptr);
         s.fit = s.rmse = 0.0;
         s.done = s.iters = s.status = s.pad = 0;
     }
@@ -153,123 +140,21 @@ __global__ __launch_bounds__(ICP_BLOCK) void icp_corr(const float *__restrict__ 
     const int j = blockIdx.x, slice = blockIdx.y;
     if (w.ctrl[0] != 0 || w.state[j].done) return;                          // uniform over the workgroup
     const int src = jobs[2 * j], tgt = jobs[2 * j + 1];
-    const int64_t lo = offsets[src], hi = offsets[src + 1];
-    const int64_t per = (hi - lo + w.slices - 1) / w.slices;
-    const int64_t a = lo + slice * per, b = a + per < hi ? a + per : hi;
+    int64_t a, b;
+    icp_slice_bounds(offsets[src], offsets[src + 1], w.slices, slice, &a, &b);
     IcpGrid g;
     g.keys = w.keys; g.start = w.start; g.list = w.list; g.points = points; g.mask = w.slots - 1; g.n = n; g.n_list = n; g.h = h;
-    double T[12];
+    double T[12], acc[ICP_SUMS];
     for (int k = 0; k < 12; ++k) T[k] = w.state[j].T[k];
-    double acc[ICP_SUMS];
-    for (int k = 0; k < ICP_SUMS; ++k) acc[k] = 0.0;
-    for (int64_t i = a + threadIdx.x; i < b; i += ICP_BLOCK) {
-        double q[3], d2;
-        icp_apply(T, points + 3 * i, q);
-        const int64_t m = icp_nearest(g, tgt, q, thr2, &d2);
-        if (m < 0) continue;
-        const double t[3] = {(double)points[3 * m], (double)points[3 * m + 1], (double)points[3 * m + 2]};
-        acc[0] += 1.0;
-        for (int c = 0; c < 3; ++c) {
-            acc[1 + c] += q[c];
-            acc[4 + c] += t[c];
-            for (int d = 0; d < 3; ++d) acc[7 + 3 * c + d] += t[c] * q[d];
-        }
-        acc[16] += d2;
-    }
+    icp_lane_sums(g, tgt, T, thr2, a, b, threadIdx.x, acc);
     for (int k = 0; k < ICP_SUMS; ++k) red[k][threadIdx.x] = acc[k];
     __syncthreads();
-    for (int s = ICP_BLOCK / 2; s > 0; s >>= 1) {                           // fixed tree: the same order every run
+    for (int s = ICP_BLOCK / 2; s > 0; s >>= 1) {                           // icp_tree_sum's order
         if ((int)threadIdx.x < s)
-            for (int k = 0; k < ICP_SUMS; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
+            for (int k = 0; k < ICP_SUMS; ++k) red[k][threadIdx.x] = red[k][threadIdx.x] + red[k][threadIdx.x + s];
         __syncthreads();
     }
     if (threadIdx.x < ICP_SUMS) w.partial[((int64_t)j * w.slices + slice) * ICP_SUMS + threadIdx.x] = red[threadIdx.x][0];
-}
-
-// A = U diag(sigma) V^T of a 3x3 by one-sided Jacobi rotations of the columns; the rotation U S V^T with S = diag(1, 1, +-1), the -1 on the
-// smallest singular value when det(U) det(V) < 0 (Umeyama's reflection fix).  Columns of U whose singular value vanishes against the largest
-// (fewer than three non-collinear correspondences) are completed to a right-handed orthonormal basis: always a finite proper rotation, and the
-// same one every run; A = 0 gives the identity.  `noise` is the rounding noise of the covariance (it is formed from uncentred float64 sums:
-// sum t q^T / k - mean t mean q^T): a singular value at or below it counts as zero, so that a covariance that is zero in exact arithmetic -- every
-// source point matched to ONE target point -- gives the identity and not a rotation read out of rounding errors.  Returns true when a column
-// had to be completed.
-__device__ bool icp_rotation(const double cov[9], double noise, double R[9])
-{
-#pragma clang fp contract(off)
-    double A[3][3], V[3][3];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) { A[r][c] = cov[3 * r + c]; V[r][c] = r == c ? 1.0 : 0.0; }
-    for (int sweep = 0; sweep < 40; ++sweep) {
-        bool rotated = false;
-        for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                double alpha = 0.0, beta = 0.0, gamma = 0.0;
-                for (int k = 0; k < 3; ++k) { alpha += A[k][p] * A[k][p]; beta += A[k][q] * A[k][q]; gamma += A[k][p] * A[k][q]; }
-                if (gamma == 0.0 || fabs(gamma) <= 1e-17 * sqrt(alpha * beta)) continue;
-                rotated = true;
-                const double zeta = (beta - alpha) / (2.0 * gamma);
-                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-                for (int k = 0; k < 3; ++k) {
-                    const double ap = A[k][p], aq = A[k][q], vp = V[k][p], vq = V[k][q];
-                    A[k][p] = c * ap - s * aq; A[k][q] = s * ap + c * aq;
-                    V[k][p] = c * vp - s * vq; V[k][q] = s * vp + c * vq;
-                }
-            }
-        if (!rotated) break;
-    }
-    double sig[3];
-    for (int c = 0; c < 3; ++c) sig[c] = sqrt(A[0][c] * A[0][c] + A[1][c] * A[1][c] + A[2][c] * A[2][c]);
-    int i0 = 0, i1 = 1, i2 = 2, tmp;                                          // sigma descending, ties by column index
-    if (sig[i1] > sig[i0]) { tmp = i0; i0 = i1; i1 = tmp; }
-    if (sig[i2] > sig[i1]) { tmp = i1; i1 = i2; i2 = tmp; }
-    if (sig[i1] > sig[i0]) { tmp = i0; i0 = i1; i1 = tmp; }
-    for (int k = 0; k < 9; ++k) R[k] = (k % 4 == 0) ? 1.0 : 0.0;
-    if (!(sig[i0] > noise) || !icp_finite(sig[i0])) return true;
-    double tol = 64.0 * 2.220446049250313e-16 * sig[i0];
-    if (tol < noise) tol = noise;
-    double U[3][3];
-    bool completed = false;
-    for (int k = 0; k < 3; ++k) U[k][i0] = A[k][i0] / sig[i0];
-    if (sig[i1] > tol) {
-        for (int k = 0; k < 3; ++k) U[k][i1] = A[k][i1] / sig[i1];
-    } else {                                                                  // any unit vector orthogonal to u0: u0 x e_m, m the axis u0 leans on least
-        completed = true;
-        int m = 0;
-        if (fabs(U[1][i0]) < fabs(U[m][i0])) m = 1;
-        if (fabs(U[2][i0]) < fabs(U[m][i0])) m = 2;
-        double e[3] = {0.0, 0.0, 0.0};
-        e[m] = 1.0;
-        double v[3] = {U[1][i0] * e[2] - U[2][i0] * e[1], U[2][i0] * e[0] - U[0][i0] * e[2], U[0][i0] * e[1] - U[1][i0] * e[0]};
-        const double nv = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-        for (int k = 0; k < 3; ++k) U[k][i1] = v[k] / nv;
-    }
-    if (sig[i2] > tol) {
-        for (int k = 0; k < 3; ++k) U[k][i2] = A[k][i2] / sig[i2];
-    } else {
-        completed = true;
-        U[0][i2] = U[1][i0] * U[2][i1] - U[2][i0] * U[1][i1];
-        U[1][i2] = U[2][i0] * U[0][i1] - U[0][i0] * U[2][i1];
-        U[2][i2] = U[0][i0] * U[1][i1] - U[1][i0] * U[0][i1];
-    }
-    auto det3 = [](const double M[3][3]) {
-        return M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
-               M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-    };
-    double S[3] = {1.0, 1.0, 1.0};
-    if (det3(U) * det3(V) < 0.0) S[i2] = -1.0;
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) {
-            double v = 0.0;
-            for (int k = 0; k < 3; ++k) v += U[r][k] * S[k] * V[c][k];
-            R[3 * r + c] = v;
-        }
-    for (int k = 0; k < 9; ++k)
-        if (!icp_finite(R[k])) {
-            for (int m = 0; m < 9; ++m) R[m] = (m % 4 == 0) ? 1.0 : 0.0;
-            return true;
-        }
-    return completed;
 }
 
 __global__ __launch_bounds__(64) void icp_update(const int32_t *__restrict__ offsets, const int32_t *__restrict__ jobs, int round, int max_iter,
@@ -282,7 +167,7 @@ __global__ __launch_bounds__(64) void icp_update(const int32_t *__restrict__ off
     IcpState &st = w.state[j];
     if (w.ctrl[0] != 0) {                                                   // a table that cannot be trusted: identity, and the status says so
         if (threadIdx.x == 0 && round == 0) {
-            for (int k = 0; k < 16; ++k) out_T[16 * (int64_t)j + k] = (k % 5 == 0) ? 1.0 : 0.0;
+            pcacc_pose_seed(out_T + 16 * (int64_t)j, nullptr);
             out_fit[j] = out_rmse[j] = 0.0;
             out_iters[j] = 0;
             out_status[j] = PCACC_ICP_BAD_TABLE;
@@ -298,43 +183,8 @@ __global__ __launch_bounds__(64) void icp_update(const int32_t *__restrict__ off
     __syncthreads();
     if (threadIdx.x != 0) return;
     const int src = jobs[2 * j], tgt = jobs[2 * j + 1];
-    const int64_t n_src = (int64_t)offsets[src + 1] - offsets[src], n_tgt = (int64_t)offsets[tgt + 1] - offsets[tgt];
-    const double nc = sums[0];
-    const double fit = n_src > 0 ? nc / (double)n_src : 0.0;
-    const double rmse = nc > 0.0 ? sqrt(sums[16] / nc) : 0.0;
-    int status = st.status | (n_src == 0 ? PCACC_ICP_EMPTY_SOURCE : 0) | (n_tgt == 0 ? PCACC_ICP_EMPTY_TARGET : 0);
-    const bool converged = round > 0 && fabs(fit - st.fit) < 1e-6 && fabs(rmse - st.rmse) < 1e-6;
-    if (converged || round >= max_iter) {
-        if (!(nc > 0.0)) status |= PCACC_ICP_NO_CORRESPONDENCE;
-        for (int k = 0; k < 16; ++k) out_T[16 * (int64_t)j + k] = st.T[k];
-        out_fit[j] = fit;
-        out_rmse[j] = rmse;
-        out_iters[j] = round;
-        out_status[j] = status;
-        st.status = status;
-        st.done = 1;
-        return;
-    }
-    if (nc > 0.0) {                                                         // no correspondences: the update is the identity
-        double ms[3], mt[3], cov[9], R[9], t[3];
-        for (int c = 0; c < 3; ++c) { ms[c] = sums[1 + c] / nc; mt[c] = sums[4 + c] / nc; }
-        for (int c = 0; c < 3; ++c)
-            for (int d = 0; d < 3; ++d) cov[3 * c + d] = sums[7 + 3 * c + d] / nc - mt[c] * ms[d];
-        // 1e-10 of the mean of t . q: far above the rounding of the sums (2^-53 times at most the number of terms), far below the covariance of
-        // any cloud that has an extent (a singular value of 1e-10 of the squared distance from the origin is a thickness of micrometres)
-        const double noise = 1e-10 * (fabs(sums[7]) + fabs(sums[11]) + fabs(sums[15])) / nc;
-        if (icp_rotation(cov, noise, R)) status |= PCACC_ICP_RANK_DEFICIENT;
-        for (int c = 0; c < 3; ++c) t[c] = mt[c] - (R[3 * c] * ms[0] + R[3 * c + 1] * ms[1] + R[3 * c + 2] * ms[2]);
-        double N[12];
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 4; ++c)
-                N[4 * r + c] = R[3 * r] * st.T[c] + R[3 * r + 1] * st.T[4 + c] + R[3 * r + 2] * st.T[8 + c] + (c == 3 ? t[r] : 0.0);
-        for (int k = 0; k < 12; ++k) st.T[k] = N[k];
-    }
-    st.fit = fit;
-    st.rmse = rmse;
-    st.iters = round + 1;
-    st.status = status;
+    const IcpOut o = {out_T + 16 * (int64_t)j, out_fit + j, out_rmse + j, out_iters + j, out_status + j};
+    icp_round(&st, sums, (int64_t)offsets[src + 1] - offsets[src], (int64_t)offsets[tgt + 1] - offsets[tgt], round, max_iter, &o);
 }
 
 extern "C" int pcacc_icp_point_to_point(const float *points, int64_t n, const int32_t *seg_offsets, int32_t n_seg, const int32_t *jobs,

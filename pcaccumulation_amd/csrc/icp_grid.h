@@ -11,26 +11,7 @@
 // list[start[s] .. start[s + 1]) (target point indices, in no particular order: the walk orders candidates by (distance^2, index) itself,
 // so equal distances resolve to the lowest target index whatever the order of insertion was).
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define ICP_HD __host__ __device__ __forceinline__
-#else
-#define ICP_HD static inline
-#endif
-#if defined(ICP_HOST_CHECK)
-#include <assert.h>
-#define ICP_BOUND(i, n) assert((int64_t)(i) >= 0 && (int64_t)(i) < (int64_t)(n))
-#else
-#define ICP_BOUND(i, n) ((void)0)
-#endif
-
-// no FMA contraction in the distance and the transform: the kernels, the g++ build and a numpy restatement then round alike
-#if defined(__clang__)
-#define ICP_NO_CONTRACT _Pragma("clang fp contract(off)")
-#else
-#define ICP_NO_CONTRACT
-#endif
+#include "hd.h"
 
 #define ICP_CELL_MIN (-32768)
 #define ICP_CELL_MAX 32767
@@ -46,38 +27,36 @@ struct IcpGrid {
     double h;                         // cell edge
 };
 
-ICP_HD bool icp_finite(double v) { return v - v == 0.0; }             // false for NaN and +-Inf
-
 // Cell index of v, valid only when the function returns true: v is finite and floor(v / h) lies in [lo, hi].
-ICP_HD bool icp_cell(double v, double h, int lo, int hi, int *cell)
+PCACC_HD bool icp_cell(double v, double h, int lo, int hi, int *cell)
 {
-    if (!icp_finite(v)) return false;
+    if (!pcacc_finite(v)) return false;
     const double c = __builtin_floor(v / h);
     if (!(c >= (double)lo && c <= (double)hi)) return false;           // also false when v / h overflowed
     *cell = (int)c;
     return true;
 }
 
-ICP_HD bool icp_target_cell(const double p[3], double h, int c[3])
+PCACC_HD bool icp_target_cell(const double p[3], double h, int c[3])
 {
     return icp_cell(p[0], h, ICP_CELL_MIN, ICP_CELL_MAX, &c[0]) && icp_cell(p[1], h, ICP_CELL_MIN, ICP_CELL_MAX, &c[1]) &&
            icp_cell(p[2], h, ICP_CELL_MIN, ICP_CELL_MAX, &c[2]);
 }
 
-ICP_HD bool icp_query_cell(const double p[3], double h, int c[3])
+PCACC_HD bool icp_query_cell(const double p[3], double h, int c[3])
 {
     return icp_cell(p[0], h, ICP_CELL_MIN + 1, ICP_CELL_MAX - 1, &c[0]) && icp_cell(p[1], h, ICP_CELL_MIN + 1, ICP_CELL_MAX - 1, &c[1]) &&
            icp_cell(p[2], h, ICP_CELL_MIN + 1, ICP_CELL_MAX - 1, &c[2]);
 }
 
 // seg in [0, ICP_MAX_SEGMENTS), cell indices in [ICP_CELL_MIN, ICP_CELL_MAX]
-ICP_HD unsigned long long icp_key(int seg, int ix, int iy, int iz)
+PCACC_HD unsigned long long icp_key(int seg, int ix, int iy, int iz)
 {
     return ((unsigned long long)(seg + 1) << 48) | ((unsigned long long)(ix - ICP_CELL_MIN) << 32) |
            ((unsigned long long)(iy - ICP_CELL_MIN) << 16) | (unsigned long long)(iz - ICP_CELL_MIN);
 }
 
-ICP_HD uint32_t icp_hash(unsigned long long x, uint32_t mask)         // the 64-bit finaliser of MurmurHash3
+PCACC_HD uint32_t icp_hash(unsigned long long x, uint32_t mask)         // the 64-bit finaliser of MurmurHash3
 {
     x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
     x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
@@ -86,25 +65,25 @@ ICP_HD uint32_t icp_hash(unsigned long long x, uint32_t mask)         // the 64-
 }
 
 // The segment that holds point i -- the last s with offsets[s] <= i, which skips empty segments -- or -1.  offsets [n_seg + 1] ascending.
-ICP_HD int icp_segment_of(const int32_t *offsets, int n_seg, int64_t i)
+PCACC_HD int icp_segment_of(const int32_t *offsets, int n_seg, int64_t i)
 {
-    ICP_BOUND(n_seg, n_seg + 1);
+    PCACC_BOUND(n_seg, n_seg + 1);
     if (i < offsets[0] || i >= offsets[n_seg]) return -1;
     int lo = 0, hi = n_seg;                                   // offsets[lo] <= i < offsets[hi]
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
-        ICP_BOUND(mid, n_seg + 1);
+        PCACC_BOUND(mid, n_seg + 1);
         if (offsets[mid] <= i) lo = mid; else hi = mid;
     }
     return lo;
 }
 
 // Slot of `key`, or -1 when the table does not hold it.  Read-only; at most mask + 1 probes.
-ICP_HD int64_t icp_find(const unsigned long long *keys, uint32_t mask, unsigned long long key)
+PCACC_HD int64_t icp_find(const unsigned long long *keys, uint32_t mask, unsigned long long key)
 {
     uint32_t s = icp_hash(key, mask);
     for (uint32_t probes = 0; probes <= mask; ++probes, s = (s + 1) & mask) {
-        ICP_BOUND(s, (int64_t)mask + 1);
+        PCACC_BOUND(s, (int64_t)mask + 1);
         const unsigned long long k = keys[s];
         if (k == key) return s;
         if (k == 0) return -1;
@@ -114,9 +93,9 @@ ICP_HD int64_t icp_find(const unsigned long long *keys, uint32_t mask, unsigned 
 
 // Nearest point of segment `seg` to q among the 27 cells around q: index into g.points or -1; *d2_out its squared distance.
 // A candidate counts iff d2 <= thr2; of equal d2 the lowest index wins.  float64 throughout, the fp32 coordinates promoted.
-ICP_HD int64_t icp_nearest(const IcpGrid &g, int seg, const double q[3], double thr2, double *d2_out)
+PCACC_HD int64_t icp_nearest(const IcpGrid &g, int seg, const double q[3], double thr2, double *d2_out)
 {
-    ICP_NO_CONTRACT
+    PCACC_NO_CONTRACT
     int c[3];
     if (!icp_query_cell(q, g.h, c)) return -1;
     int64_t best = -1;
@@ -126,12 +105,12 @@ ICP_HD int64_t icp_nearest(const IcpGrid &g, int seg, const double q[3], double 
             for (int dz = -1; dz <= 1; ++dz) {
                 const int64_t s = icp_find(g.keys, g.mask, icp_key(seg, c[0] + dx, c[1] + dy, c[2] + dz));
                 if (s < 0) continue;
-                ICP_BOUND(s + 1, (int64_t)g.mask + 2);
+                PCACC_BOUND(s + 1, (int64_t)g.mask + 2);
                 const int32_t lo = g.start[s], hi = g.start[s + 1];
                 for (int32_t e = lo; e < hi; ++e) {
-                    ICP_BOUND(e, g.n_list);
+                    PCACC_BOUND(e, g.n_list);
                     const int64_t i = g.list[e];
-                    ICP_BOUND(i, g.n);
+                    PCACC_BOUND(i, g.n);
                     const double ex = (double)g.points[3 * i] - q[0], ey = (double)g.points[3 * i + 1] - q[1],
                                  ez = (double)g.points[3 * i + 2] - q[2];
                     const double d2 = ex * ex + ey * ey + ez * ez;
@@ -144,9 +123,9 @@ ICP_HD int64_t icp_nearest(const IcpGrid &g, int seg, const double q[3], double 
 }
 
 // R p + t of a row-major 4x4 (the last row is taken as 0 0 0 1), float64.
-ICP_HD void icp_apply(const double *T, const float *p, double q[3])
+PCACC_HD void icp_apply(const double *T, const float *p, double q[3])
 {
-    ICP_NO_CONTRACT
+    PCACC_NO_CONTRACT
     const double x = p[0], y = p[1], z = p[2];
     q[0] = T[0] * x + T[1] * y + T[2] * z + T[3];
     q[1] = T[4] * x + T[5] * y + T[6] * z + T[7];

@@ -13,27 +13,21 @@
 //     u_1 = the unit vector along u_0 x e_m (m the axis u_0 leans on least) and u_2 = u_0 x u_1; u = I at rank 0 (v = I there: nothing rotated).
 // So u and v are orthonormal for every finite input, and v diag(1, 1, det(v u^T)) u^T is a proper rotation.  Where LAPACK's answer is a function
 // of the matrix -- (s_1 + sign(det a) s_2) / s_0 away from 0 -- that rotation is LAPACK's; below, it is one valid choice inside the null space,
-// the same one every run.  NaN goes in, NaN comes out.
+// the same one every run.  NaN goes in, NaN comes out.  The one 3x3 SVD of the library: the covariances of C5's normals (accum_normals.h) and
+// of C3's ICP update (icp_round.h, through jacobi_svd3_floor) go through it as well.
 #pragma once
 #include <math.h>
 
-#if defined(__HIPCC__)
-#define SVD3_HD __host__ __device__ inline
-#else
-#define SVD3_HD static inline
-#endif
-#if defined(__clang__)
-#define SVD3_NO_CONTRACT _Pragma("clang fp contract(off)")
-#else
-#define SVD3_NO_CONTRACT
-#endif
+#include "hd.h"
 
 #define SVD3_PAIR_EPS 8.881784197001252e-16            // 4 * 2^-52: rounding leaves |cos| of two orthogonal columns at ~3 * 2^-53
 #define SVD3_RANK_TOL 1.4210854715202004e-14           // 64 * 2^-52
 
-SVD3_HD void jacobi_svd3(const double a[3][3], double u[3][3], double s[3], double v[3][3])
+// `zero_floor`: an absolute value at or below which a singular value counts as zero as well (0 = none) -- for a caller whose matrix carries rounding noise
+// of a known size that is NOT relative to s[0] (icp_round.h: a covariance formed from uncentred sums).  Returns the rank, 0 .. 3.
+PCACC_HD_PLAIN int jacobi_svd3_floor(const double a[3][3], double zero_floor, double u[3][3], double s[3], double v[3][3])
 {
-    SVD3_NO_CONTRACT
+    PCACC_NO_CONTRACT
     double b[3][3];
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) { b[i][j] = a[i][j]; v[i][j] = (i == j); }
@@ -72,12 +66,13 @@ SVD3_HD void jacobi_svd3(const double a[3][3], double u[3][3], double s[3], doub
                     const double tv = v[i][x]; v[i][x] = v[i][y]; v[i][y] = tv;
                 }
             }
-    if (s[0] == 0.0) {                                                                       // rank 0
+    if (s[0] <= zero_floor) {                                                                     // rank 0 (s[0] == 0 without a floor; NaN goes on)
         for (int i = 0; i < 3; ++i)
             for (int j = 0; j < 3; ++j) u[i][j] = (i == j);
-        return;
+        return 0;
     }
-    const double tol = SVD3_RANK_TOL * s[0];
+    double tol = SVD3_RANK_TOL * s[0];
+    if (tol < zero_floor) tol = zero_floor;
     for (int i = 0; i < 3; ++i) u[i][0] = b[i][0] / s[0];
     if (s[1] > tol) {
         for (int i = 0; i < 3; ++i) u[i][1] = b[i][1] / s[1];
@@ -97,4 +92,7 @@ SVD3_HD void jacobi_svd3(const double a[3][3], double u[3][3], double s[3], doub
         u[1][2] = u[2][0] * u[0][1] - u[0][0] * u[2][1];
         u[2][2] = u[0][0] * u[1][1] - u[1][0] * u[0][1];
     }
+    return 1 + (s[1] > tol) + (s[2] > tol);
 }
+
+PCACC_HD_PLAIN void jacobi_svd3(const double a[3][3], double u[3][3], double s[3], double v[3][3]) { (void)jacobi_svd3_floor(a, 0.0, u, s, v); }

@@ -1,6 +1,6 @@
 // Host build of pcaccumulation_amd/csrc/accum_grid.h (tests/test_accumulate.py): the per-point arithmetic and the index arithmetic of the window
 // reduction, the search and the merge -- the functions the kernels of accum.hip call -- run stage by stage on the CPU with every table index
-// assert-checked (-DACC_HOST_CHECK), before anything runs on a GPU.
+// assert-checked (-DPCACC_HOST_CHECK), before anything runs on a GPU.
 //   in : i64 n_adds, i64 capacity, i64 min_count, i64 use_fraction, f64 max_moving_fraction, f64 voxel_size, then per add
 //        i64 n, i64 stamp, i64 has_pose, f64 pose[16], f32 points[3n], u8 moving[n]
 //   out: per add and point 5 i64 (valid, key, q_x, q_y, q_z); then i64 M, dropped, growths; keys[M]; acc[5][M]; stamps[2][M] as i64;
@@ -114,10 +114,10 @@ int main(int argc, char **argv)
         // K7
         for (int64_t p = 0; p < cur.m; ++p) {
             const int64_t j = accum_lower_bound(wkey.data(), runs, cur.keys[p]);
-            ACC_BOUND(j, n + 1);
+            PCACC_BOUND(j, n + 1);
             const int64_t d = accum_merge_dst(p, mrank[j], total);
             assert(d >= 0);
-            ACC_BOUND(d, alt.cap);
+            PCACC_BOUND(d, alt.cap);
             const bool hit = j < runs && wkey[j] == cur.keys[p];
             assert(alt.acc[accum_field(0, d, alt.cap)] == 0);                    // no destination is written twice
             alt.keys[d] = cur.keys[p];
@@ -131,7 +131,7 @@ int main(int argc, char **argv)
             if (!miss[j]) continue;
             const int64_t d = accum_merge_dst(pos[j], mrank[j], total);
             assert(d >= 0);
-            ACC_BOUND(d, alt.cap);
+            PCACC_BOUND(d, alt.cap);
             assert(alt.acc[accum_field(0, d, alt.cap)] == 0);
             alt.keys[d] = wkey[j];
             for (int fl = 0; fl < ACC_FIELDS; ++fl) alt.acc[accum_field(fl, d, alt.cap)] = wacc[accum_field(fl, j, n)];

@@ -1,6 +1,6 @@
 // Host build of pcaccumulation_amd/csrc/accum_normals.h (tests/test_accumulate_normals.py): the offset / range test, the neighbour row search and the
 // whole result of a voxel -- the function the kernel of accum_normals.hip calls -- run on the CPU with every table index assert-checked
-// (-DACC_HOST_CHECK), before anything runs on a GPU.  Pass 1 (keep flags, scan, dst / rows tables) is restated here with the same helpers.
+// (-DPCACC_HOST_CHECK), before anything runs on a GPU.  Pass 1 (keep flags, scan, dst / rows tables) is restated here with the same helpers.
 //   in : i64 m, capacity, min_count, use_fraction, radius, min_neighbors, n_viewpoints, stamp_base; f64 max_moving_fraction;
 //        i64 keys[m]; i64 acc[5][m]; i32 stamps[2][m]; f64 viewpoints[n_viewpoints][3]
 //   out: i64 V; f64 normals[V][3]; f64 eigenvalues[V][3]; i32 neighbors[V]; u8 flags[V]; f32 normals[V][3]; f32 eigenvalues[V][3]
@@ -62,7 +62,7 @@ int main(int argc, char **argv)
         const int64_t d = dst[i] ? accum_merge_dst(kpos[i], 0, kept) : -1;
         assert(!dst[i] || d >= 0);
         dst[i] = (int)d;
-        if (d >= 0) { ACC_BOUND(d, m); assert(rows[d] == -1); rows[d] = (int)i; }
+        if (d >= 0) { PCACC_BOUND(d, m); assert(rows[d] == -1); rows[d] = (int)i; }
     }
     // pass 2
     std::vector<double> n64(3 * kept), e64(3 * kept);

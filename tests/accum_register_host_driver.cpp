@@ -1,6 +1,6 @@
 // Host build of pcaccumulation_amd/csrc/accum_register.h (tests/test_accumulate_register.py): the whole registration -- row table, normals (C5's
 // accum_normal_voxel), then every round: accr_point per scan point, accr_slot_sum per slot and term, the slots in order, accr_round -- run on the CPU
-// with every table index assert-checked (-DACC_HOST_CHECK), before anything runs on a GPU.  The tables sit at a capacity above m with poison behind
+// with every table index assert-checked (-DPCACC_HOST_CHECK), before anything runs on a GPU.  The tables sit at a capacity above m with poison behind
 // row m.  The loop stops where the device's stops: the rounds after `done` would return at once.
 //   in : i64 m, capacity, min_count, use_fraction, radius, min_neighbors, n_viewpoints, stamp_base, n, has_moving, max_iter, has_init;
 //        f64 max_moving_fraction, voxel_size, max_distance; i64 keys[m]; i64 acc[5][m]; i32 stamps[2][m]; f64 viewpoints[n_viewpoints][3];
@@ -69,7 +69,7 @@ int main(int argc, char **argv)
         const int64_t d = dst[i] ? accum_merge_dst(kpos[i], 0, kept) : -1;
         assert(!dst[i] || d >= 0);
         dst[i] = (int)d;
-        if (d >= 0) { ACC_BOUND(d, m); assert(rows[d] == -1); rows[d] = (int)i; }
+        if (d >= 0) { PCACC_BOUND(d, m); assert(rows[d] == -1); rows[d] = (int)i; }
     }
     std::vector<float> n32(3 * kept);
     std::vector<uint8_t> fl(kept);

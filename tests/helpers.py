@@ -1,5 +1,7 @@
 """Shared builders for the parity tests (inputs are regenerated from seeds, never read from /root/reference)."""
 import os
+import shutil
+import subprocess
 
 import numpy as np
 
@@ -7,6 +9,20 @@ import oracle
 from pcaccumulation_amd.config import default_config
 from pcaccumulation_amd.dataloader import collate_fn
 from pcaccumulation_amd.synthetic import make_sequence, attach_voxels
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def build_host_driver(tmp_path, name):
+    """g++ build of tests/<name>.cpp on the headers of pcaccumulation_amd/csrc -- the code the kernels run -- without FMA contraction and with every
+    table index assert-checked (csrc/hd.h: PCACC_BOUND); returns the executable in tmp_path."""
+    exe = os.path.join(str(tmp_path), name)
+    cxx = shutil.which('g++') or shutil.which('c++')
+    assert cxx, 'the host-build test needs a C++ compiler'
+    subprocess.check_call([cxx, '-O2', '-g', '-std=c++17', '-ffp-contract=off', '-DPCACC_HOST_CHECK', '-Wall', '-Werror',
+                           '-I', os.path.join(ROOT, 'pcaccumulation_amd', 'csrc'), os.path.join(ROOT, 'tests', name + '.cpp'), '-o', exe])
+    return exe
 
 
 def oracle_voxeliser(cfg):

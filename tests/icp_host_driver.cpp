@@ -1,18 +1,22 @@
-// Host build of the ICP target index (pcaccumulation_amd/csrc/icp_grid.h): the cell / key arithmetic, the hash probe and the 27-cell walk the
-// kernels of icp.hip run, compiled with g++ and ICP_HOST_CHECK so that EVERY table index is assert-checked.  tests/test_icp.py builds it, feeds
-// it a scene (far-away, NaN and Inf points included) and compares the correspondences with brute force -- before anything runs on a GPU.
-//   usage: icp_host_driver <scene.bin> <out.bin>
+// Host build of the ICP refinement (pcaccumulation_amd/csrc/icp_grid.h, icp_round.h): the cell / key arithmetic, the hash probe, the 27-cell walk, the
+// slice sums in the kernels' order and the whole round logic the kernels of icp.hip run, compiled with g++ and PCACC_HOST_CHECK so that EVERY table
+// index is assert-checked.  tests/test_icp.py builds it, feeds it a scene (far-away, NaN and Inf points included), compares the correspondences with
+// brute force and the loop's results with the numpy restatement -- before anything runs on a GPU; the GPU test then holds the kernels to this build
+// bit for bit.
+//   usage: icp_host_driver <scene.bin> <out.bin> [<max_iter> <loop.bin>]
 //   scene: int64 n, n_seg, n_jobs; double threshold; float points[n][3]; int32 offsets[n_seg + 1]; int32 jobs[n_jobs][2]; double init[n_jobs][16]
-//   out:   per job, per source point (segment order): int64 index of its correspondence in `points`, or -1
-#ifndef ICP_HOST_CHECK
-#define ICP_HOST_CHECK
+//   out:   per job, per source point (segment order): int64 index of its correspondence in `points` under the initial pose, or -1
+//   loop:  per job: double pose[16], fitness, rmse; int32 iterations, status -- the loop stops where the device's stops: the rounds after `done`
+//          would return at once
+#ifndef PCACC_HOST_CHECK
+#define PCACC_HOST_CHECK
 #endif
 #include <stdio.h>
 #include <stdlib.h>
 
 #include <vector>
 
-#include "icp_grid.h"
+#include "icp_round.h"
 
 template <class T>
 static void read_n(FILE *f, T *p, size_t count)
@@ -22,7 +26,7 @@ static void read_n(FILE *f, T *p, size_t count)
 
 int main(int argc, char **argv)
 {
-    if (argc != 3) return 2;
+    if (argc != 3 && argc != 5) return 2;
     FILE *f = fopen(argv[1], "rb");
     if (!f) return 2;
     int64_t head[3];
@@ -56,7 +60,7 @@ int main(int argc, char **argv)
     for (int64_t i = 0; i < n; ++i) {
         const int seg = icp_segment_of(offsets.data(), (int)n_seg, i);
         if (seg < 0) continue;
-        ICP_BOUND(seg, n_seg);
+        PCACC_BOUND(seg, n_seg);
         if (!tflag[seg]) continue;
         const double p[3] = {points[3 * i], points[3 * i + 1], points[3 * i + 2]};
         int c[3];
@@ -67,7 +71,7 @@ int main(int argc, char **argv)
         uint32_t s = icp_hash(key, mask);
         uint32_t probes = 0;
         for (; probes <= mask; ++probes, s = (s + 1) & mask) {
-            ICP_BOUND(s, slots);
+            PCACC_BOUND(s, slots);
             if (keys[s] == 0) keys[s] = key;
             if (keys[s] == key) break;
         }
@@ -82,8 +86,8 @@ int main(int argc, char **argv)
         const int32_t s = pslot[i];
         if (s < 0) continue;
         const int64_t e = (int64_t)start[s] + cursor[s]++;
-        ICP_BOUND(e, start[s + 1]);
-        ICP_BOUND(e, n);
+        PCACC_BOUND(e, start[s + 1]);
+        PCACC_BOUND(e, n);
         list[e] = (int32_t)i;
     }
 
@@ -95,7 +99,7 @@ int main(int argc, char **argv)
     for (int64_t j = 0; j < n_jobs; ++j) {
         const int src = jobs[2 * j], tgt = jobs[2 * j + 1];
         for (int64_t i = offsets[src]; i < offsets[src + 1]; ++i) {
-            ICP_BOUND(i, n);
+            PCACC_BOUND(i, n);
             double q[3], d2 = 0.0;
             icp_apply(&init[16 * j], &points[3 * i], q);
             const int64_t m = icp_nearest(g, tgt, q, thr * thr, &d2);
@@ -105,6 +109,41 @@ int main(int argc, char **argv)
             }
             fwrite(&m, sizeof(m), 1, o);
         }
+    }
+    fclose(o);
+    if (argc != 5) return 0;
+
+    const int max_iter = atoi(argv[3]);
+    const int slices = icp_slices(n, (int32_t)n_jobs);
+    o = fopen(argv[4], "wb");
+    if (!o) return 2;
+    for (int64_t j = 0; j < n_jobs; ++j) {
+        const int src = jobs[2 * j], tgt = jobs[2 * j + 1];
+        IcpState st;
+        pcacc_pose_seed(st.T, &init[16 * j]);
+        st.fit = st.rmse = 0.0;
+        st.done = st.iters = st.status = st.pad = 0;
+        double pose[16], fit = 0.0, rmse = 0.0;
+        int32_t iters = -1, status = -1;
+        const IcpOut out = {pose, &fit, &rmse, &iters, &status};
+        for (int round = 0; round <= max_iter && !st.done; ++round) {
+            double sums[ICP_SUMS], part[ICP_SUMS];
+            for (int k = 0; k < ICP_SUMS; ++k) sums[k] = 0.0;
+            for (int s = 0; s < slices; ++s) {                        // icp_update: the slots in slice order
+                int64_t a, b;
+                icp_slice_bounds(offsets[src], offsets[src + 1], slices, s, &a, &b);
+                assert(a >= offsets[src] && b <= offsets[src + 1]);
+                icp_slice_sums(g, tgt, st.T, thr * thr, a, b, part);
+                for (int k = 0; k < ICP_SUMS; ++k) sums[k] = sums[k] + part[k];
+            }
+            icp_round(&st, sums, (int64_t)offsets[src + 1] - offsets[src], (int64_t)offsets[tgt + 1] - offsets[tgt], round, max_iter, &out);
+        }
+        assert(st.done && iters >= 0 && iters <= max_iter);
+        fwrite(pose, sizeof(double), 16, o);
+        fwrite(&fit, sizeof(fit), 1, o);
+        fwrite(&rmse, sizeof(rmse), 1, o);
+        fwrite(&iters, sizeof(iters), 1, o);
+        fwrite(&status, sizeof(status), 1, o);
     }
     fclose(o);
     return 0;

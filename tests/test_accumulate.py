@@ -7,7 +7,6 @@ g++ and run stage by stage with every table index assert-checked; the header, th
 GPU leg: one add at the sizes where a stage can go wrong, merges at both ends of the map, growth, invalid input, order independence, the extract
 filters, save / load, and the model tie-in on the model_tiny_test inputs."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,6 +14,7 @@ import pytest
 import torch
 
 import accumulate_reference as ref
+from helpers import build_host_driver
 from pcaccumulation_amd.config import default_config
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -96,15 +96,6 @@ def test_restatement_unique_formulation_equals_a_per_point_loop():
     assert max(r[0] for r in a.rec.values()) > 1                                 # some voxel did sum several points
 
 
-def _host_driver(tmp_path):
-    exe = str(tmp_path / 'accum_host_driver')
-    cxx = shutil.which('g++') or shutil.which('c++')
-    assert cxx, 'the host-build test needs a C++ compiler'
-    subprocess.check_call([cxx, '-O2', '-g', '-std=c++17', '-ffp-contract=off', '-DACC_HOST_CHECK', '-Wall', '-Werror',
-                           '-I', os.path.join(ROOT, 'pcaccumulation_amd', 'csrc'), os.path.join(ROOT, 'tests', 'accum_host_driver.cpp'), '-o', exe])
-    return exe
-
-
 def _run_host_driver(exe, tmp_path, tag, voxel_size, adds, capacity=64, min_count=1, max_moving_fraction=None):
     """adds: [(points, pose or None, moving or None, stamp)] -> the driver's map against the restatement; every assert of the driver aborts it."""
     path, out = str(tmp_path / (tag + '.bin')), str(tmp_path / (tag + '.out'))
@@ -171,7 +162,7 @@ def _edge_points(voxel_size):
 def test_host_build_of_accum_grid_matches_the_restatement(tmp_path):
     """Order of work: key, validity, fixed point and the reduction / search / merge index helpers of csrc/accum_grid.h -- the code the kernels run --
     compiled with g++, every table index assert-checked, against the restatement, before any GPU test."""
-    exe = _host_driver(tmp_path)
+    exe = build_host_driver(tmp_path, 'accum_host_driver')
     for vs in (0.1, 0.01):                                                       # at 0.01 the index bound (+-10485.76) lies inside |w| < 32768
         e = _edge_points(vs)
         r, _ = _run_host_driver(exe, tmp_path, 'edge_%g' % vs, vs, [(e, None, None, 0), (e[::-1], None, _flags(2, e.shape[0]), 1)])

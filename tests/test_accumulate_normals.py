@@ -7,7 +7,6 @@ the PLY writer; header, binding and argument checks.
 GPU leg: the kernel against the host build BIT FOR BIT at r = 1, 2, 3 on every scene of the CPU leg and on a sheet of more than 65 536 voxels;
 orientation by viewpoints; order independence; row alignment with extract."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -16,6 +15,7 @@ import torch
 
 import accumulate_normals_reference as nref
 import accumulate_reference as ref
+from helpers import build_host_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = 'cuda:0'
@@ -128,12 +128,7 @@ def _ref_map(name):
 # ---- the host build ----------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope='module')
 def host_exe(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp('accn') / 'accum_normals_host_driver')
-    cxx = shutil.which('g++') or shutil.which('c++')
-    assert cxx, 'the host-build test needs a C++ compiler'
-    subprocess.check_call([cxx, '-O2', '-g', '-std=c++17', '-ffp-contract=off', '-DACC_HOST_CHECK', '-Wall', '-Werror',
-                           '-I', os.path.join(ROOT, 'pcaccumulation_amd', 'csrc'), os.path.join(ROOT, 'tests', 'accum_normals_host_driver.cpp'), '-o', exe])
-    return exe
+    return build_host_driver(tmp_path_factory.mktemp('accn'), 'accum_normals_host_driver')
 
 
 _host_cache = {}

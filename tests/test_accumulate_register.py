@@ -6,7 +6,6 @@ np.linalg.solve): correspondence rows, counts, status and iterations equal; pose
 GPU leg: the kernels against the host build BIT FOR BIT at max_iter = 1 and at convergence on every scene of the CPU leg; reproducibility; the map
 untouched; drifted windows registered before their add; argument errors; the model tie-in."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,6 +14,7 @@ import torch
 
 import accumulate_reference as ref
 import accumulate_register_reference as rref
+from helpers import build_host_driver
 from pcaccumulation_amd.config import default_config
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -213,12 +213,7 @@ def _args(case, max_iter):
 # ---- the host build ----------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope='module')
 def host_exe(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp('accr') / 'accum_register_host_driver')
-    cxx = shutil.which('g++') or shutil.which('c++')
-    assert cxx, 'the host-build test needs a C++ compiler'
-    subprocess.check_call([cxx, '-O2', '-g', '-std=c++17', '-ffp-contract=off', '-DACC_HOST_CHECK', '-Wall', '-Werror',
-                           '-I', os.path.join(ROOT, 'pcaccumulation_amd', 'csrc'), os.path.join(ROOT, 'tests', 'accum_register_host_driver.cpp'), '-o', exe])
-    return exe
+    return build_host_driver(tmp_path_factory.mktemp('accr'), 'accum_register_host_driver')
 
 
 def _run_host(exe, tmp_path, records, voxel_size, points, a, spare=3):
@@ -396,7 +391,7 @@ def test_header_binding_and_argument_checks():
     for word, bit in (('NO_ELIGIBLE', 1), ('NO_CANDIDATE', 2), ('NO_CORRESPONDENCE', 4), ('DEGENERATE', 8), ('MAX_ITER', 16), ('BAD_TABLE', 32)):
         assert ('PCACC_REGISTER_%s %d' % (word, bit)) in header and getattr(native, 'REGISTER_' + word) == bit == getattr(rref, word)
     text = open(os.path.join(ROOT, 'pcaccumulation_amd', 'csrc', 'accum_register.h')).read()
-    assert '#include <hip' not in text and 'ACC_NO_CONTRACT' in text and 'ACC_HD' in text
+    assert '#include <hip' not in text and 'PCACC_NO_CONTRACT' in text and 'PCACC_HD' in text
     assert callable(native.accum_register)
     with pytest.raises(native.NativeError):
         AccumulatedCloud(voxel_size=0.1, device='cuda', capacity=64).register(torch.zeros(4, 3))

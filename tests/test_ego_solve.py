@@ -11,8 +11,6 @@ GPU leg: (a) ops.svd3 + ops.kabsch_rt on the same families, fp32 outputs; (b) th
 (c) the fused kernel through native.sinkhorn_kabsch at k in {3, 7, 65, 257}, healthy and degenerate pairs mixed in one batch, the expected pose
 computed from the kernel's own returned perm so that only the Kabsch stage is measured."""
 import functools
-import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -20,8 +18,8 @@ import pytest
 import torch
 
 import kabsch_reference as ref
+from helpers import build_host_driver
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 POW2 = (-60, -40, -30, -20, 0, 20, 40, 60)
 DEC = (1e-18, 1e-12, 1e-10, 1e-9, 1e-6, 1.0, 1e6, 1e12, 1e18)
 # families whose every matrix must lie inside the parity claim (asserted from the restatement); the others hold members that are property-only
@@ -180,11 +178,7 @@ def check_scale_invariance(u, s, v, rot):
 @pytest.fixture(scope='module')
 def host_svd3(tmp_path_factory):
     d = tmp_path_factory.mktemp('svd3_host')
-    exe = str(d / 'svd3_host_driver')
-    cxx = shutil.which('g++') or shutil.which('c++')
-    assert cxx, 'the host-build test needs a C++ compiler'
-    subprocess.check_call([cxx, '-O2', '-g', '-std=c++17', '-ffp-contract=off',
-                           '-I', os.path.join(ROOT, 'pcaccumulation_amd', 'csrc'), os.path.join(ROOT, 'tests', 'svd3_host_driver.cpp'), '-o', exe])
+    exe = build_host_driver(d, 'svd3_host_driver')
 
     def run(a):
         a = np.ascontiguousarray(a, np.float64).reshape(-1, 9)

@@ -3,6 +3,10 @@
 The reference is tests/icp_reference.py, a float64 numpy restatement of Open3D's documented registration_icp (Open3D has no ROCm build; the
 last test of the CPU block compares the restatement with Open3D itself where that is installed).
 
+Order of work.  CPU: csrc/icp_grid.h, icp_round.h and svd3.h -- the code the kernels run -- built with g++ (-ffp-contract=off, every table index
+assert-checked): the walk against brute force, then the whole loop against the restatement.  GPU: the kernels against that host build BIT FOR BIT
+after one update and at convergence, and against the restatement inside the parity bound below.
+
 Parity bound.  Largest deviation of the kernel from the restatement over the kernel-level scenes of this file (41 jobs), measured on an
 MI355X (profiles/icp_parity.txt): pose entries 4.0e-15, translation 3.7e-15 m, angle between the rotations 4.2e-6 degrees (acos next to 1
 resolves no better: acos(1 - 2^-53) is 8.5e-7 degrees).  Each bound is ten times its measured maximum, floored at 1e-9, and below the
@@ -11,7 +15,6 @@ compared for equality, iteration counts may differ by one.  Covariances of rank 
 outside the claim: there the restatement's own answer is LAPACK's arbitrary completion of a null space (tests/icp_reference.py: rank2_ratio).
 """
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -19,6 +22,7 @@ import pytest
 import torch
 
 import icp_reference as ref
+from helpers import build_host_driver
 from pcaccumulation_amd.config import default_config
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -147,30 +151,31 @@ def test_restatement_recovers_known_motion():
         assert np.array_equal(out['T'], np.eye(4)) and out['fitness'] == 0.0 and out['rmse'] == 0.0
 
 
-def _host_driver(tmp_path):
-    exe = str(tmp_path / 'icp_host_driver')
-    cxx = shutil.which('g++') or shutil.which('c++')
-    assert cxx, 'the host-build test needs a C++ compiler'
-    subprocess.check_call([cxx, '-O1', '-g', '-std=c++17', '-ffp-contract=off', '-DICP_HOST_CHECK', '-Wall', '-Werror',
-                           '-I', os.path.join(ROOT, 'pcaccumulation_amd', 'csrc'), os.path.join(ROOT, 'tests', 'icp_host_driver.cpp'), '-o', exe])
-    return exe
+LOOP_RECORD = np.dtype([('pose', np.float64, (4, 4)), ('fitness', np.float64), ('rmse', np.float64), ('iterations', np.int32), ('status', np.int32)])
 
 
-def _run_host_driver(exe, tmp_path, sc, tag):
+def _run_host_driver(exe, tmp_path, sc, tag, max_iter=None):
+    """The driver's correspondences under the initial poses; with max_iter, the results of its whole loop instead (one LOOP_RECORD per job)."""
     path, out = str(tmp_path / (tag + '.bin')), str(tmp_path / (tag + '.out'))
     with open(path, 'wb') as f:
         f.write(np.array([sc['points'].shape[0], sc['offsets'].shape[0] - 1, sc['jobs'].shape[0]], np.int64).tobytes())
         f.write(np.array([sc['threshold']], np.float64).tobytes())
         for a, dt in ((sc['points'], np.float32), (sc['offsets'], np.int32), (sc['jobs'], np.int32), (sc['init'], np.float64)):
             f.write(np.ascontiguousarray(a, dt).tobytes())
-    subprocess.check_call([exe, path, out])                                     # an assert of the driver aborts it: non-zero exit
-    return np.fromfile(out, np.int64)
+    if max_iter is None:
+        subprocess.check_call([exe, path, out])                                 # an assert of the driver aborts it: non-zero exit
+        return np.fromfile(out, np.int64)
+    loop = str(tmp_path / ('%s.loop%d' % (tag, max_iter)))
+    subprocess.check_call([exe, path, out, str(max_iter), loop])
+    got = np.fromfile(loop, LOOP_RECORD)
+    assert got.shape[0] == sc['jobs'].shape[0]
+    return got
 
 
 def test_host_build_of_the_grid_walk_matches_brute_force(tmp_path):
     """Order of work: the cell / key arithmetic and the 27-cell walk of csrc/icp_grid.h -- the code the kernels run -- compiled with g++, every
     table index assert-checked, on the GPU tests' scenes including the far-away, NaN and Inf points; correspondences = brute force."""
-    exe = _host_driver(tmp_path)
+    exe = build_host_driver(tmp_path, 'icp_host_driver')
     poisoned, _ = _poisoned(_scene('ragged'))
     edge = _edge_scene()
     for tag, sc in (('single', _scene('single')), ('ragged', _scene('ragged')), ('tie', _scene('tie')), ('poisoned', poisoned), ('edge', edge)):
@@ -204,6 +209,88 @@ def _edge_scene():
     src = (tgt.astype(np.float64) + [0.1, 0, 0]).astype(np.float32)
     sc = _pack([src, tgt, src[:, [1, 0, 2]], tgt[:, [1, 0, 2]], src[:, [1, 2, 0]], tgt[:, [1, 2, 0]]], [(0, 1), (2, 3), (4, 5)])
     return dict(sc, threshold=h, max_iter=5)
+
+
+def _partition_scene():
+    """The smallest scene at which the partition of a source into slices can go wrong: 1603 points and 4 jobs give 7 slices, so job 0 (700 source
+    points on 900 targets) is cut into 7 slices of 100 -- every slice ends inside a wave and most lanes of the tree hold 0.0; beside it sources of
+    0, 1 and 2 points (fewer points than slices)."""
+    rng = np.random.RandomState(11)
+    tgt = rng.uniform(-4, 4, (900, 3)).astype(np.float32)
+    srcs = [_moved_subset(rng, tgt, n, 1.5, 0.04, outliers=n // 10) for n in (700, 0, 1, 2)]
+    return dict(_pack([tgt] + srcs, [(1 + j, 0) for j in range(4)], [ref.rigid(rng, 0.3, 0.01) for _ in range(4)]), threshold=0.2, max_iter=50)
+
+
+def _reference_in_range(source, target, threshold, init, max_iter):
+    """The restatement under the supported range (include/pcacc.h C3): in every evaluation a source point whose cell leaves [-32767, 32766] or a target
+    point whose cell leaves [-32768, 32767] has no correspondence -- brute force alone would pair a source beyond the range with a target beyond it."""
+    plain = ref.nearest
+
+    def nearest(src, tgt, thr):
+        with np.errstate(invalid='ignore', over='ignore'):
+            cs, ct = np.floor(src / thr), np.floor(tgt / thr)
+            src = np.where(((cs >= -32767) & (cs <= 32766)).all(1)[:, None], src, np.nan)
+            tgt = np.where(((ct >= -32768) & (ct <= 32767)).all(1)[:, None], tgt, np.nan)
+        return plain(src, tgt, thr)
+    ref.nearest = nearest
+    try:
+        return ref.icp(source, target, threshold, init, max_iter)
+    finally:
+        ref.nearest = plain
+
+
+def _loop_scenes():
+    """(tag, scene) of everything the whole loop is run on, on the host and on the GPU."""
+    if 'loop' not in _CACHE:
+        _CACHE['loop'] = (('single', _scene('single')), ('ragged', _scene('ragged')), ('tie', _scene('tie')), ('poisoned', _poisoned(_scene('ragged'))[0]),
+                          ('edge', _edge_scene()), ('partition', _partition_scene()))
+    return _CACHE['loop']
+
+
+def test_host_build_of_the_loop_matches_the_restatement(tmp_path):
+    """csrc/icp_round.h on csrc/svd3.h -- the slice sums in the kernels' order, the statistics, the stop rule, the status bits, the update and the
+    composition the kernels run -- compiled with g++, every index assert-checked, run to the end on every scene: each job against the restatement
+    with the bounds the GPU tests apply to the kernel (_assert_job); a job whose covariance is of rank <= 1 in the restatement is outside the claim
+    and is held to 'finite proper rotation, status says rank-deficient' for the pose, and to the restatement's fitness, rmse and iterations.  The poisoned scene is held to the clean one as the GPU test holds it."""
+    from pcaccumulation_amd import native
+    exe = build_host_driver(tmp_path, 'icp_host_driver')
+    results = {}
+    for tag, sc in _loop_scenes():
+        got = _run_host_driver(exe, tmp_path, sc, tag, sc['max_iter'])
+        as_gpu = results[tag] = (got['pose'], got['fitness'], got['rmse'], got['iterations'], got['status'])
+        n_src = np.diff(sc['offsets'])[sc['jobs'][:, 0]]
+        n_tgt = np.diff(sc['offsets'])[sc['jobs'][:, 1]]
+        assert np.array_equal((got['status'] & native.ICP_EMPTY_SOURCE) != 0, n_src == 0), tag
+        assert np.array_equal((got['status'] & native.ICP_EMPTY_TARGET) != 0, n_tgt == 0), tag
+        assert (got['status'] & native.ICP_BAD_TABLE == 0).all(), tag
+        if tag == 'poisoned':
+            continue
+        claimed = deficient = 0
+        for j, (s, t) in enumerate(sc['jobs']):
+            seg = lambda k: sc['points'][sc['offsets'][k]:sc['offsets'][k + 1]]
+            want = _reference(tag)[j] if tag in ('single', 'ragged', 'tie') else _reference_in_range(seg(s), seg(t), sc['threshold'], sc['init'][j], sc['max_iter'])
+            _assert_proper_rotation(got['pose'][j])
+            matched = want['correspondences'][want['correspondences'] >= 0]
+            if want['rank_ratio'] < 1e-6 and np.unique(matched).size >= 2:
+                # outside the parity claim for the pose: a null space completed two ways.  (Every source on ONE target is a covariance of zero in exact
+                # arithmetic: the identity rotation here -- the noise floor -- and in LAPACK, and the job is compared like any other; the tie scene
+                # rests on it.)  The sources of these jobs are collinear -- two points, or the edge scene's rows along an axis -- and the two completions
+                # differ by a rotation about their line, which leaves them where they are: fitness, rmse and the stop are the restatement's.
+                assert got['status'][j] & native.ICP_RANK_DEFICIENT, (tag, j)
+                assert got['fitness'][j] == want['fitness'] and abs(got['rmse'][j] - want['rmse']) <= POSE_BOUND, (tag, j, got['fitness'][j], got['rmse'][j])
+                assert abs(int(got['iterations'][j]) - want['iterations']) <= 1, (tag, j)
+                deficient += 1
+                continue
+            _assert_job(tag, j, as_gpu, want)
+            claimed += 1
+            if want['fitness'] == 0.0:                                          # nothing to match: the pose stays the initial pose
+                assert got['status'][j] & native.ICP_NO_CORRESPONDENCE and got['rmse'][j] == 0.0
+                np.testing.assert_array_equal(got['pose'][j][:3], sc['init'][j][:3])
+        assert deficient == {'partition': 1, 'edge': 3}.get(tag, 0) and claimed + deficient == sc['jobs'].shape[0], (tag, deficient)
+    # index 0 of each target segment wins: job 0 moves the source to x = -0.1, job 1 to x = +0.1 (one correspondence: t = mt - ms exactly)
+    np.testing.assert_allclose(results['tie'][0][0][:3, 3], [np.float32(-0.1), 0, 0], atol=1e-15)
+    np.testing.assert_allclose(results['tie'][0][1][:3, 3], [np.float32(0.1), 0, 0], atol=1e-15)
+    _assert_poisoned_equals_clean(_scene('ragged'), dict(_loop_scenes())['poisoned'], results['ragged'], results['poisoned'])
 
 
 def test_heads_construct_with_icp_flags():
@@ -346,12 +433,8 @@ def test_icp_tie_goes_to_lowest_index_gpu():
         np.testing.assert_allclose(pose[j], want['pose'], atol=POSE_BOUND)
 
 
-@pytest.mark.gpu
-def test_icp_far_and_non_finite_points_gpu():
-    sc = _scene('ragged')
-    poisoned, _ = _poisoned(sc)
-    clean = _run_gpu(sc)
-    got = _run_gpu(poisoned)
+def _assert_poisoned_equals_clean(sc, poisoned, clean, got):
+    """clean, got: (pose, fitness, rmse, iterations, status) of the scene and of the scene with far / NaN / Inf points mixed in."""
     n_clean = np.diff(sc['offsets'])[sc['jobs'][:, 0]]
     n_all = np.diff(poisoned['offsets'])[poisoned['jobs'][:, 0]]
     worst = 0.0
@@ -370,11 +453,37 @@ def test_icp_far_and_non_finite_points_gpu():
 
 
 @pytest.mark.gpu
+def test_icp_far_and_non_finite_points_gpu():
+    sc = _scene('ragged')
+    poisoned, _ = _poisoned(sc)
+    _assert_poisoned_equals_clean(sc, poisoned, _run_gpu(sc), _run_gpu(poisoned))
+
+
+@pytest.mark.gpu
 def test_icp_run_to_run_bits_gpu():
     sc = _scene('ragged')
     a, b = _run_gpu(sc), _run_gpu(sc)
     for x, y in zip(a, b):
         assert x.tobytes() == y.tobytes()
+
+
+@pytest.mark.gpu
+def test_icp_equals_the_host_build_bits_gpu(tmp_path):
+    """pcacc_icp_point_to_point against the g++ build of the same headers (icp_grid.h, icp_round.h, svd3.h): pose, fitness, rmse, iterations and
+    status BIT FOR BIT, after one update (max_iter = 1) and at convergence, on every scene of the CPU leg -- the partition scene included.  The same
+    operations in the same order on IEEE doubles: there is no tolerance to choose."""
+    exe = build_host_driver(tmp_path, 'icp_host_driver')
+    for tag, sc in _loop_scenes():
+        for max_iter in (1, sc['max_iter']):
+            host = _run_host_driver(exe, tmp_path, sc, tag, max_iter)
+            got = _run_gpu(dict(sc, max_iter=max_iter))
+            for name, g in zip(('pose', 'fitness', 'rmse', 'iterations', 'status'), got):
+                h = np.ascontiguousarray(host[name])
+                assert g.dtype == h.dtype and g.shape == h.shape, (tag, max_iter, name)
+                differ = np.flatnonzero((g.reshape(g.shape[0], -1).view(np.uint8) != h.reshape(h.shape[0], -1).view(np.uint8)).any(1))
+                assert differ.size == 0, (tag, max_iter, name, differ[:10], g[differ[:2]], h[differ[:2]])
+            if max_iter > 1 and tag in ('single', 'ragged', 'partition'):
+                assert (got[3] > 1).any() and (got[3] < max_iter).any()          # the loop did iterate, and the stop rule did end it
 
 
 @pytest.mark.gpu
