@@ -3,7 +3,7 @@
 from /root/reference, CPU, this container only -- see ref_harness.py for the stand-ins of absent
 third-party modules).  The fixtures are data: seeds / inputs and the reference's outputs.
 
-    python tests/golden/make_golden.py [ops] [model] [chamfer]
+    python tests/golden/make_golden.py [ops] [model] [chamfer] [aniso]
 
 Inputs that are large are regenerated from a seed by pcaccumulation_amd.synthetic (numpy legacy
 RandomState, byte-stable); only small tensors, samples and digests are stored.
@@ -210,3 +210,6 @@ if __name__ == '__main__':
     if 'model' in what:
         from make_golden_model import gen_model
         gen_model(save, sha)
+    if 'aniso' in what:
+        from make_golden_aniso import gen_aniso
+        gen_aniso(save)

@@ -47,17 +47,18 @@ def _epe(out, inp, n_frames):
     return err[t > 0]
 
 
-def _run(cfg, seeds, n_frames, ppf, mode, fwd_seed, train, tweaks=None, points='uniform'):
+def _run(cfg, seeds, n_frames, ppf, mode, fwd_seed, train, tweaks=None, points='uniform', gen_cfg=None, tweak_fn=None):
+    """gen_cfg: the config the sequences are drawn for when it is not the one they are voxelised on; tweak_fn: replaces _tweak_biases."""
     from models.motionnet import MotionNet
     from libs.loss import FuseLoss
     cfg = dict(cfg)
     cfg['misc'] = dict(cfg['misc'], mode=mode)
     vox = rh.voxeliser(cfg)
-    inp = rh.collate([attach_voxels(make_sequence(s, n_frames, ppf, cfg, mode=points), vox) for s in seeds])
+    inp = rh.collate([attach_voxels(make_sequence(s, n_frames, ppf, gen_cfg or cfg, mode=points), vox) for s in seeds])
     model = MotionNet(cfg)
     fill_state_dict_(model)
     if tweaks is None:
-        tweaks = _tweak_biases(model, inp, fwd_seed)
+        tweaks = (tweak_fn or _tweak_biases)(model, inp, fwd_seed)
     else:
         with torch.no_grad():
             sd = model.state_dict()

@@ -69,6 +69,36 @@ def _tiny_val(dev, golden, compute_dtype='fp32'):
     return g, out, stats, inp
 
 
+def _tiny_val_aniso(dev, golden):
+    """_tiny_val on the non-square grid with non-square cells (helpers.aniso_cfg; tests/golden/make_golden_aniso.py)."""
+    from helpers import aniso_batch
+    g = golden('model_tiny_val_aniso')
+    cfg, inp = aniso_batch([int(s) for s in g['seeds']], int(g['n_frames']), int(g['pts_per_frame']))
+    model = MotionNet(cfg)
+    fill_state_dict_(model)
+    with torch.no_grad():
+        sd = model.state_dict()
+        for k, v in zip(g['tweak_keys'], g['tweak_vals']):
+            sd[str(k)] += torch.from_numpy(v)
+    model = model.to(dev).eval()
+    if dev.type == 'cuda':
+        model.channels_last_()
+    inp = _to(inp, dev)
+    loss_fn = FuseLoss(cfg['loss'])
+    torch.manual_seed(int(g['fwd_seed']))
+    with torch.no_grad():
+        out = model(inp)
+        stats = loss_fn(out, inp)
+    return g, out, stats, inp
+
+
+def _no_flips(g, out):
+    """The fixture's smallest |fg - bg| logit gap at an occupied pillar (fb_margin) is at least 4 x the tolerance on fb_seg_est: a result within
+    tolerance cannot flip a point, so the comparisons behind `if flips == 0` in _assert_tiny_val_fp32 always run."""
+    assert float(g['fb_margin']) >= 2e-3
+    assert int((out['fb_est_per_points'].cpu().numpy() != g['fb_est_per_points']).sum()) == 0
+
+
 def _assert_tiny_val_fp32(g, out, stats, inp, atol):
     c = lambda t: t.detach().float().cpu().numpy()
     assert np.array_equal(c(out['fb_seg_gt']), g['fb_seg_gt'])
@@ -154,6 +184,14 @@ def test_host_logic_tiny_val(double, golden):
     np.testing.assert_allclose(epe.numpy(), g['epe'], rtol=1e-3, atol=1e-3)
 
 
+def test_host_logic_tiny_val_aniso(double, golden):
+    g, out, stats, inp = _tiny_val_aniso(double, golden)
+    assert tuple(out['fb_seg_est'].shape) == (2, 3, 2, 96, 64)
+    _no_flips(g, out)
+    _assert_tiny_val_fp32(g, out, stats, inp, atol=1e-4)
+    _check_metrics(g, out, stats, inp, 3, dict(ego=1e-3, iou=1e-3, epe=1e-3))
+
+
 def test_host_logic_tiny_train_backward(double, golden):
     g, model, out, stats, inp = _tiny_train(double, golden)
     _assert_tiny_train(g, model, out, stats, rtol=1e-3)
@@ -163,6 +201,14 @@ def test_host_logic_tiny_train_backward(double, golden):
 @pytest.mark.gpu
 def test_gpu_tiny_val_fp32(golden):
     g, out, stats, inp = _tiny_val(torch.device('cuda:0'), golden)
+    _assert_tiny_val_fp32(g, out, stats, inp, atol=5e-4)
+    _check_metrics(g, out, stats, inp, 3, dict(ego=1e-3, iou=1e-3, epe=1e-3))
+
+
+@pytest.mark.gpu
+def test_gpu_tiny_val_aniso_fp32(golden):
+    g, out, stats, inp = _tiny_val_aniso(torch.device('cuda:0'), golden)
+    _no_flips(g, out)
     _assert_tiny_val_fp32(g, out, stats, inp, atol=5e-4)
     _check_metrics(g, out, stats, inp, 3, dict(ego=1e-3, iou=1e-3, epe=1e-3))
 
