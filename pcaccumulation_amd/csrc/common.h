@@ -64,6 +64,10 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f)
 // two fp32 -> two packed bf16 (round to nearest even) in one instruction: v_cvt_pk_bf16_f32 on gfx950
 typedef __bf16 pcacc_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float pcacc_f32x2 __attribute__((ext_vector_type(2)));
+// MFMA operands: a bf16 A / B fragment, the 32x32 fp32 accumulator, one 8-byte half of a fragment (ds_read_b64_tr_b16)
+typedef __bf16 pcacc_bf16x8 __attribute__((ext_vector_type(8)));
+typedef float pcacc_f32x16 __attribute__((ext_vector_type(16)));
+typedef short pcacc_s16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint32_t pcacc_pack_bf16x2(float lo, float hi)
 {
     const pcacc_f32x2 f = {lo, hi};
@@ -86,6 +90,18 @@ __device__ __forceinline__ void pcacc_st4(void *p, bool bf16, int64_t i4, float4
     else reinterpret_cast<uint2 *>(p)[i4] = make_uint2(pcacc_pack_bf16x2(v.x, v.y), pcacc_pack_bf16x2(v.z, v.w));
 }
 
+// max(x, 0) on two packed bf16: clear the halves whose sign bit is set
+__device__ __forceinline__ uint32_t pcacc_relu2(uint32_t v)
+{
+    const uint32_t neg = (v >> 15) & 0x00010001u;
+    return v & ~(neg * 0xffffu);
+}
+
+// Three masks on packed bf16 pairs.  All drop a half of v where the same half of the mask is zero or negative; they differ where it is NaN,
+// and each has users that rely on its rule -- do not merge them:
+//     pcacc_relu_mask2   +NaN keeps, -NaN drops   (integer compare of the bits)
+//     mm_mask2           any NaN drops            (mask > 0)
+//     conv_mask2         any NaN keeps            (not mask <= 0: aten::threshold_backward)
 // ReLU backward on the fly: eight packed bf16 gradients, zeroed where the forward output y (same positions) is not > 0 -- what
 // aten::threshold_backward(grad, y, 0) computes, fused into the staging of the kernels that consume the gradient.
 __device__ __forceinline__ uint32_t pcacc_relu_mask2(uint32_t g, uint32_t y)
@@ -93,6 +109,23 @@ __device__ __forceinline__ uint32_t pcacc_relu_mask2(uint32_t g, uint32_t y)
     const uint32_t lo = ((int32_t)(y << 16) > 0) ? 0x0000ffffu : 0u;
     const uint32_t hi = ((int32_t)(y & 0xffff0000u) > 0) ? 0xffff0000u : 0u;
     return g & (lo | hi);
+}
+// keep the halves of v whose mask half is > 0
+__device__ __forceinline__ uint32_t mm_mask2(uint32_t v, uint32_t m)
+{
+    const uint32_t lo = m & 0xffffu, hi = m >> 16;                        // > 0: sign clear, not zero, not NaN
+    const uint32_t lo_ok = (lo != 0 && lo <= 0x7f80u) ? 0x0000ffffu : 0u;
+    const uint32_t hi_ok = (hi != 0 && hi <= 0x7f80u) ? 0xffff0000u : 0u;
+    return v & (lo_ok | hi_ok);
+}
+// aten::threshold_backward(v, m, 0) on packed bf16 pairs: a half of v is dropped where the same half of m is <= 0 (zeros of either sign,
+// negative numbers, -inf); NaN compares false and keeps it, as the library does
+__device__ __forceinline__ uint32_t conv_mask2(uint32_t v, uint32_t m)
+{
+    auto drop = [](uint32_t h) { const uint32_t mag = h & 0x7fffu; return mag == 0u || ((h & 0x8000u) && mag <= 0x7f80u); };
+    const uint32_t lo = drop(m & 0xffffu) ? 0u : 0xffffu;
+    const uint32_t hi = drop(m >> 16) ? 0u : 0xffff0000u;
+    return v & (lo | hi);
 }
 __device__ __forceinline__ uint4 pcacc_relu_mask8(uint4 g, uint4 y)
 {

@@ -13,8 +13,6 @@
 // 8 elements so that the 16-byte fragment reads of 16 consecutive pixels / channels hit 64 distinct banks.
 #include "common.h"
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
 #define CV_TH 8
 #define CV_TW 32
 #define CV_PW (CV_TW + 2)
@@ -92,7 +90,7 @@ extern "C" int pcacc_conv3x3_prepare_weights_pair(const float *w, int32_t c_out,
 // issue its stores one pass later (loads and stores share the vmcnt counter: a wait for the prefetched patch would
 // otherwise also wait for stores issued just before it).  `bias` points at the wave's first channel (or is NULL).
 template <int R, int CT>
-__device__ __forceinline__ void conv_pack_tile(const f32x16_t (&acc)[R][CT], const float *__restrict__ bias, int relu, int lh,
+__device__ __forceinline__ void conv_pack_tile(const pcacc_f32x16 (&acc)[R][CT], const float *__restrict__ bias, int relu, int lh,
                                                uint2 (&pk)[R][CT][4])
 {
 #pragma unroll
@@ -116,16 +114,6 @@ __device__ __forceinline__ void conv_pack_tile(const f32x16_t (&acc)[R][CT], con
 }
 
 // `row0` = first of the wave's R rows inside the tile, `co` = its first output channel
-// aten::threshold_backward(v, m, 0) on packed bf16 pairs: a half of v is dropped where the same half of m is <= 0 (zeros of either sign,
-// negative numbers, -inf); NaN compares false and keeps it, as the library does
-__device__ __forceinline__ uint32_t conv_mask2(uint32_t v, uint32_t m)
-{
-    auto drop = [](uint32_t h) { const uint32_t mag = h & 0x7fffu; return mag == 0u || ((h & 0x8000u) && mag <= 0x7f80u); };
-    const uint32_t lo = drop(m & 0xffffu) ? 0u : 0xffffu;
-    const uint32_t hi = drop(m >> 16) ? 0u : 0xffff0000u;
-    return v & (lo | hi);
-}
-
 // omask (may be NULL): a map of the output's shape; results are stored as zero where it is <= 0 -- the data gradient of a layer whose input
 // was a ReLU output leaves already masked for that ReLU (the producer then needs no threshold pass of its own)
 // A lane holds 4 channels (8 bytes) of each of the four 8-channel groups of its pixel, lane + 32 the other 4: stored as they are, every
@@ -179,7 +167,7 @@ __device__ __forceinline__ void conv_store_packed(const uint2 (&pk)[R][CT][4], u
 }
 
 template <int CT>
-__device__ __forceinline__ void conv_store_tile(const f32x16_t (&acc)[2][CT], const float *__restrict__ bias, uint16_t *__restrict__ out,
+__device__ __forceinline__ void conv_store_tile(const pcacc_f32x16 (&acc)[2][CT], const float *__restrict__ bias, uint16_t *__restrict__ out,
                                                 int img, int y0, int x0, int h, int w, int c_out, int co0, int relu, int wave, int lp,
                                                 int lh, const uint16_t *__restrict__ omask = nullptr)
 {
@@ -214,7 +202,7 @@ __global__ __launch_bounds__(CV_THREADS) void conv3x3_mfma_kernel(const uint16_t
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lp = lane & 31, lh = lane >> 5;
 
-    f32x16_t acc[2][CT];
+    pcacc_f32x16 acc[2][CT];
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -272,11 +260,11 @@ __global__ __launch_bounds__(CV_THREADS) void conv3x3_mfma_kernel(const uint16_t
                 const uint16_t *wrow = wl + lp * PS + lh * 8;
 #pragma unroll
                 for (int kc = 0; kc < CS / 16; ++kc) {
-                    const bf16x8_t b0 = *reinterpret_cast<const bf16x8_t *>(prow0 + kc * 16);
-                    const bf16x8_t b1 = *reinterpret_cast<const bf16x8_t *>(prow1 + kc * 16);
+                    const pcacc_bf16x8 b0 = *reinterpret_cast<const pcacc_bf16x8 *>(prow0 + kc * 16);
+                    const pcacc_bf16x8 b1 = *reinterpret_cast<const pcacc_bf16x8 *>(prow1 + kc * 16);
 #pragma unroll
                     for (int ct = 0; ct < CT; ++ct) {
-                        const bf16x8_t a = *reinterpret_cast<const bf16x8_t *>(wrow + ct * 32 * PS + kc * 16);
+                        const pcacc_bf16x8 a = *reinterpret_cast<const pcacc_bf16x8 *>(wrow + ct * 32 * PS + kc * 16);
                         acc[0][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b0, acc[0][ct], 0, 0, 0);
                         acc[1][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b1, acc[1][ct], 0, 0, 0);
                     }
@@ -292,20 +280,20 @@ __global__ __launch_bounds__(CV_THREADS) void conv3x3_mfma_kernel(const uint16_t
 // two steps ahead of the MFMAs that consume them.  `pbase` = patch + (row0*CV_PW + lp)*PS + lh*8; `wbase` = the wave's
 // first weight row of tap 0 + lp*PS + lh*8; consecutive taps are TAP_ROWS rows apart.
 template <int R, int CT, int CS, int TAP_ROWS>
-__device__ __forceinline__ void conv_pass_mfma(f32x16_t (&acc)[R][CT], const uint16_t *pbase, const uint16_t *wbase)
+__device__ __forceinline__ void conv_pass_mfma(pcacc_f32x16 (&acc)[R][CT], const uint16_t *pbase, const uint16_t *wbase)
 {
     constexpr int PS = CS + 8;
     constexpr int KC = CS / 16;
     constexpr int STEPS = 9 * KC;
     constexpr int AHEAD = 2;
-    bf16x8_t fb[AHEAD + 1][R], fa[AHEAD + 1][CT];
+    pcacc_bf16x8 fb[AHEAD + 1][R], fa[AHEAD + 1][CT];
     auto load = [&](int slot, int s) {
         const int tap = s / KC, kc = s % KC;
         const uint16_t *p = pbase + ((tap / 3) * CV_PW + tap % 3) * PS + kc * 16;
 #pragma unroll
-        for (int m = 0; m < R; ++m) fb[slot][m] = *reinterpret_cast<const bf16x8_t *>(p + m * CV_PW * PS);
+        for (int m = 0; m < R; ++m) fb[slot][m] = *reinterpret_cast<const pcacc_bf16x8 *>(p + m * CV_PW * PS);
 #pragma unroll
-        for (int ct = 0; ct < CT; ++ct) fa[slot][ct] = *reinterpret_cast<const bf16x8_t *>(wbase + (tap * TAP_ROWS + ct * 32) * PS + kc * 16);
+        for (int ct = 0; ct < CT; ++ct) fa[slot][ct] = *reinterpret_cast<const pcacc_bf16x8 *>(wbase + (tap * TAP_ROWS + ct * 32) * PS + kc * 16);
     };
 #pragma unroll
     for (int s = 0; s < AHEAD && s < STEPS; ++s) load(s, s);
@@ -327,19 +315,19 @@ __device__ __forceinline__ void conv_pass_mfma(f32x16_t (&acc)[R][CT], const uin
 // layer's weights + patch take 77 KB instead of 96: two workgroups per CU.  `lrow` = the lane's patch row for tap (0,0) of the wave's
 // first pixel row; `wtap0` = the lane's weight row of tap 0; `wsw` = its swizzled element offset of channel chunk lh.
 template <int R>
-__device__ __forceinline__ void conv_pass_mfma_swz(f32x16_t (&acc)[R][1], const uint16_t *patch, int lrow, int lh, const uint16_t *wtap0, int wsw)
+__device__ __forceinline__ void conv_pass_mfma_swz(pcacc_f32x16 (&acc)[R][1], const uint16_t *patch, int lrow, int lh, const uint16_t *wtap0, int wsw)
 {
     constexpr int STEPS = 18;
     constexpr int AHEAD = 2;
-    bf16x8_t fb[AHEAD + 1][R], fa[AHEAD + 1];
+    pcacc_bf16x8 fb[AHEAD + 1][R], fa[AHEAD + 1];
     auto load = [&](int slot, int s) {
         const int tap = s / 2, kc = s % 2;
 #pragma unroll
         for (int m = 0; m < R; ++m) {
             const int v = lrow + (tap / 3 + m) * CV_PW + tap % 3;
-            fb[slot][m] = *reinterpret_cast<const bf16x8_t *>(patch + v * 32 + (((kc * 2 + lh) ^ ((v >> 2) & 3)) << 3));
+            fb[slot][m] = *reinterpret_cast<const pcacc_bf16x8 *>(patch + v * 32 + (((kc * 2 + lh) ^ ((v >> 2) & 3)) << 3));
         }
-        fa[slot] = *reinterpret_cast<const bf16x8_t *>(wtap0 + tap * 32 * 32 + (wsw ^ (kc * 16)));
+        fa[slot] = *reinterpret_cast<const pcacc_bf16x8 *>(wtap0 + tap * 32 * 32 + (wsw ^ (kc * 16)));
     };
 #pragma unroll
     for (int s = 0; s < AHEAD; ++s) load(s, s);
@@ -446,7 +434,7 @@ void conv3x3_resident_kernel(
         fetch(cur, f);
     }
 
-    f32x16_t acc[R][CTW];
+    pcacc_f32x16 acc[R][CTW];
     uint2 pend[R][CTW][4];                                     // finished tile waiting for its stores
     bool have_pend = false, fresh = true;
     while (k < n_mine) {
@@ -641,8 +629,7 @@ extern "C" int pcacc_conv3x3_masked_bf16(const uint16_t *in, const uint16_t *in_
 // and one wave's LDS latency hides behind another's MFMAs (r02: with every wave holding all 9 taps of a quarter of the pixels the
 // kernel ran one wave per SIMD -- 310 registers -- at 15 % matrix-pipe utilisation, and its accumulators had to be folded through
 // LDS at the end).  Workgroups are persistent; one workspace slot per workgroup, a second launch sums the slots.
-typedef short cv_s16x4 __attribute__((ext_vector_type(4)));
-union cv_frag { bf16x8_t v; cv_s16x4 h[2]; };
+union cv_frag { pcacc_bf16x8 v; pcacc_s16x4 h[2]; };
 
 template <int CO_T, int CI_T>
 __global__ __launch_bounds__(CV_THREADS) void conv3x3_wgrad_kernel(const uint16_t *__restrict__ dy, const uint16_t *__restrict__ x,
@@ -662,7 +649,7 @@ __global__ __launch_bounds__(CV_THREADS) void conv3x3_wgrad_kernel(const uint16_
     const int pair = wave % PAIRS, grp = wave / PAIRS;
     const int ct = pair / CI_T, it = pair % CI_T;
 
-    f32x16_t acc[NT];                                          // local tap j = tap grp + j * TG
+    pcacc_f32x16 acc[NT];                                          // local tap j = tap grp + j * TG
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -747,8 +734,8 @@ __global__ __launch_bounds__(CV_THREADS) void conv3x3_wgrad_kernel(const uint16_
             const int ry = s >> 1, xb = (s & 1) * 16;
             const uint16_t *pa = sdy + (ry * CV_TW + xb + tr_row) * YS + ct * 32 + tr_col;
             cv_frag af;
-            af.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((cv_s16x4 __attribute__((address_space(3))) *)pa);
-            af.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((cv_s16x4 __attribute__((address_space(3))) *)(pa + 4 * YS));
+            af.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)pa);
+            af.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pa + 4 * YS));
             if (it == 0 && grp == 0) {                         // bias gradient = column sums of dY: the fragment is at hand
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
@@ -761,8 +748,8 @@ __global__ __launch_bounds__(CV_THREADS) void conv3x3_wgrad_kernel(const uint16_
                 if (tap < 9) {
                     const uint16_t *pb = sx + ((ry + tap / 3) * CV_PW + xb + tap % 3 + tr_row) * XS + it * 32 + tr_col;
                     cv_frag bf;
-                    bf.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((cv_s16x4 __attribute__((address_space(3))) *)pb);
-                    bf.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((cv_s16x4 __attribute__((address_space(3))) *)(pb + 4 * XS));
+                    bf.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)pb);
+                    bf.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb + 4 * XS));
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af.v, bf.v, acc[j], 0, 0, 0);
                 }
             }

@@ -18,8 +18,6 @@
 #include <cstdio>
 #include <cstdlib>
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
 #define CD_THREADS 512
 #define CD_PCH 10                              // patch pieces (16 B) a thread carries per channel slice
@@ -64,7 +62,7 @@ __global__ __launch_bounds__(CD_THREADS) void conv3x3_strip_kernel(const uint16_
         poff[j] = ok ? (y * pw + x) * PS : 0;
         pyx[j] = ok ? ((y0 + y) << 16 | x) : -1;
     }
-    f32x16_t acc[MT][2];
+    pcacc_f32x16 acc[MT][2];
 #pragma unroll
     for (int j = 0; j < MT; ++j)
 #pragma unroll
@@ -171,12 +169,12 @@ __global__ __launch_bounds__(CD_THREADS) void conv3x3_strip_kernel(const uint16_
             const int toff = ((tap / 3) * pw + tap % 3) * PS + lh * 8;
             constexpr int KC = CS / 16;
             constexpr int FB = MT >= 3 ? 1 : 2;                // fragment sets: the 3-tile waves have no registers for a second one
-            bf16x8_t fa[FB][2], fb[FB][MT];
+            pcacc_bf16x8 fa[FB][2], fb[FB][MT];
             auto load = [&](int slot, int kc) {
 #pragma unroll
-                for (int n = 0; n < 2; ++n) fa[slot][n] = *reinterpret_cast<const bf16x8_t *>(wb + n * 32 * PS + kc * 16);
+                for (int n = 0; n < 2; ++n) fa[slot][n] = *reinterpret_cast<const pcacc_bf16x8 *>(wb + n * 32 * PS + kc * 16);
 #pragma unroll
-                for (int j = 0; j < MT; ++j) fb[slot][j] = *reinterpret_cast<const bf16x8_t *>(patch + poff[j] + toff + kc * 16);
+                for (int j = 0; j < MT; ++j) fb[slot][j] = *reinterpret_cast<const pcacc_bf16x8 *>(patch + poff[j] + toff + kc * 16);
             };
             if (FB == 2) load(0, 0);
 #pragma unroll
@@ -339,8 +337,7 @@ extern "C" int pcacc_conv3x3_deep_bf16(const uint16_t *in, const uint16_t *in_ma
 // accumulators per wave, so a dY fragment is read once per 4-5 MFMAs and no wave shares an output element with another.  Pixels of
 // a strip are consecutive in row-major order; a per-strip LDS table maps a pixel to the patch row of its top-left tap (no
 // divisions in the loop).  One partial slot per workgroup goes to the workspace, a second launch sums the slots.
-typedef short cd_s16x4 __attribute__((ext_vector_type(4)));
-union cd_frag { bf16x8_t v; cd_s16x4 h[2]; };
+union cd_frag { pcacc_bf16x8 v; pcacc_s16x4 h[2]; };
 #define CDW_MAXP 256                                       // pixels per strip
 #define CDW_PCH 11                                         // staged 16-byte pieces (dY rows + X patch) a thread carries
 
@@ -373,7 +370,7 @@ __global__ __launch_bounds__(CD_THREADS) void conv3x3_wgrad_strip_kernel(const u
     for (int q = threadIdx.x; q < py_rows; q += CD_THREADS) ptab[q] = q < n_px ? (uint16_t)((q / sw) * pw + q % sw) : 0;
 
     const int tap0 = grp * TG, n_tap = grp ? 9 - TG : TG;      // this wave's taps (wave-uniform)
-    f32x16_t acc[TG];
+    pcacc_f32x16 acc[TG];
 #pragma unroll
     for (int t = 0; t < TG; ++t)
 #pragma unroll
@@ -442,13 +439,13 @@ __global__ __launch_bounds__(CD_THREADS) void conv3x3_wgrad_strip_kernel(const u
         auto load_a = [&](int s, cd_frag &af, int &p0, int &p1) {
             const int r0 = s * 16 + tr_row;
             const uint16_t *pa = sdy + r0 * YS + ct * 32 + tr_col;
-            af.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((cd_s16x4 __attribute__((address_space(3))) *)pa);
-            af.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((cd_s16x4 __attribute__((address_space(3))) *)(pa + 4 * YS));
+            af.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)pa);
+            af.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pa + 4 * YS));
             p0 = ptab[r0]; p1 = ptab[r0 + 4];
         };
         auto load_b = [&](cd_frag &bf, const uint16_t *pb0, const uint16_t *pb1, int t) {
-            bf.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((cd_s16x4 __attribute__((address_space(3))) *)(pb0 + toff[t]));
-            bf.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((cd_s16x4 __attribute__((address_space(3))) *)(pb1 + toff[t]));
+            bf.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb0 + toff[t]));
+            bf.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb1 + toff[t]));
         };
         cd_frag af_n;
         int p0_n, p1_n;

@@ -1,18 +1,6 @@
 // 3x3 (and 3x3x3 over frames) convolution at fp32 accuracy on the 16-bit matrix cores ("fp32x3" compute mode): fp32 channels-last in
-// and out, every product formed from fp16 hi / lo halves of SCALED operands,
-//
-//     s x = x_hi + x_lo (+ 2^-22 s|x|),  t w = w_hi + w_lo:   (t w)(s x)  ~=  w_hi x_lo + w_lo x_hi + w_hi x_hi      (w_lo x_lo <= 2^-22 dropped)
-//
-// three v_mfma_f32_32x32x16_f16 per fragment pair, fp32 accumulation, result divided by s t.  fp16 carries 11 significant bits, so hi + lo
-// keep 22 (fp32 has 24): relative error ~3e-7 per product -- the first version of this file split into bf16 halves (8 + 8 bits, 4e-6
-// per product, 2e-5 after the U-Net) and left the c4 scene-flow EPE 1.04e-3 from the reference and the gradient norms of the
-// ill-conditioned loss terms up to 6 % off (profiles/r03_gradnorm_sensitivity.txt).  fp16's narrow exponent range is handled by
-// power-of-two scales: s per input TENSOR (from its absolute maximum, pcacc_absmax256: the scaled maximum lands in [2^13, 2^14)), t per
-// output-channel row of the weights (fixed when the weights are prepared).  Elements far below the tensor's maximum lose relative, not
-// absolute precision (their lo half becomes subnormal): errors stay below 2^-22 of the LARGEST operand, which is what a sum needs.
-// Rate: a third of the fp16 / bf16 matrix rate = 5x the fp32 MFMA rate (v_mfma_f32_32x32x2_f32 runs at 1/16).  This is the mode in
-// which the dense stacks (models/unet.py:11-20,45-113, models/stpn.py:13-43 -- fp32 convolutions in the reference) meet north_star's
-// 1e-3 on hand-written kernels; the fp32 mode used the library's fp32 convolutions for that (98.8 ms per step, 43 ms of it MIOpen).
+// and out, every product formed from fp16 hi / lo halves of scaled operands -- fp32x3.h has the arithmetic and its error bound.  The scales: s per
+// input tensor (pcacc_absmax256), t per output-channel row of the weights (fixed when the weights are prepared).
 //
 // One kernel family covers every layer (c_in, c_out multiples of 32; forward, and on mirrored / transposed weights the data
 // gradient):
@@ -29,13 +17,11 @@
 //     (2 NW + 2 MT) / (3 NW MT) = 0.67 at 2 x 2 -- the split turns the LDS-bound 32/64-channel layers of the bf16 kernels into
 //     matrix-pipe-bound ones.
 #include "common.h"
+#include "fp32x3.h"
 
 #include <cstdio>
 #include <cstdlib>
 
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
 // [r5] experiment (CSP_SHADOW_NT=1): the bf16 shadow of a forward result ('mixed' mode) is read by the BACKWARD pass, a whole forward later; stored
 // with the streaming policy it should not push the fp32 result out of the caches.  Measured the other way round: step 31.55 ms with streaming shadow
@@ -68,10 +54,9 @@ __device__ __forceinline__ void csp_store_shadow(uint16_t *p, uint32_t a, uint32
 #define CSP_THREADS 512
 #define CSP_PCH 6                              // 8-channel patch chunks (two float4) a thread carries per slice
 #define CSP_LDS_MAX (160 * 1024)
-#define CSP_AMAX_PARTS 256                     // partial maxima pcacc_absmax256 leaves for its consumers
 
 // ---- absolute maximum of a tensor: 256 partial maxima, every one always written (no initialisation, no second launch); the consumers
-// reduce the 256 values themselves (csp_scale_from_parts) ---------------------------------------------------------------------------------
+// reduce the 256 values themselves (x3_amax of fp32x3.h) ----------------------------------------------------------------------------------
 #define CSP_AMAX_THREADS 1024
 __global__ __launch_bounds__(CSP_AMAX_THREADS) void absmax256_kernel(const float *__restrict__ x, int64_t n, float *__restrict__ parts)
 {
@@ -115,52 +100,17 @@ __global__ __launch_bounds__(CSP_AMAX_THREADS) void absmax256_kernel(const float
 extern "C" int pcacc_absmax256(const float *x, int64_t n, float *parts, void *stream)
 {
     if (!x || !parts || n < 0 || (reinterpret_cast<uintptr_t>(x) & 15)) return PCACC_E_ARG;
-    hipLaunchKernelGGL(absmax256_kernel, dim3(CSP_AMAX_PARTS), dim3(CSP_AMAX_THREADS), 0, pcacc_stream(stream), x, n, parts);
+    hipLaunchKernelGGL(absmax256_kernel, dim3(X3_AMAX_PARTS), dim3(CSP_AMAX_THREADS), 0, pcacc_stream(stream), x, n, parts);
     PCACC_CHECK_LAUNCH();
     return 0;
 }
 
-// power-of-two scale that puts a tensor's absolute maximum into [2^13, 2^14) (fp16 overflows at 65504); 1 for an all-zero tensor.
-// A non-finite maximum gives scale 1: the non-finite element then reaches the output as inf / NaN, as it would in fp32 arithmetic.
-__device__ __forceinline__ float csp_scale_of(float amax)
-{
-    if (!(amax > 0.f) || !(amax < __builtin_inff())) return 1.f;
-    int k;
-    frexpf(amax, &k);                                         // amax = m 2^k, m in [0.5, 1)
-    return ldexpf(1.f, 14 - k);
-}
-
-// every lane reduces the 256 partial maxima (wave-uniform result, no LDS, no barrier)
-__device__ __forceinline__ float csp_scale_from_parts(const float *__restrict__ parts)
-{
-    const int lane = threadIdx.x & 63;
-    float m = fmaxf(fmaxf(parts[lane], parts[lane + 64]), fmaxf(parts[lane + 128], parts[lane + 192]));
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
-    return csp_scale_of(m);
-}
-
-__device__ __forceinline__ uint32_t csp_pack_f16x2(float a, float b)
-{
-    const pcacc_f32x2 f = {a, b};
-    const f16x2_t r = __builtin_convertvector(f, f16x2_t);    // round to nearest even
-    return *reinterpret_cast<const uint32_t *>(&r);
-}
-__device__ __forceinline__ pcacc_f32x2 csp_unpack_f16x2(uint32_t v)
-{
-    return __builtin_convertvector(*reinterpret_cast<const f16x2_t *>(&v), pcacc_f32x2);
-}
 #ifdef PCACC_X3_EXPERIMENT
-__device__ int csp_xword;                                    // common.h: precision-map experiment build
-extern "C" int pcacc_x3_experiment_conv(int word, void *stream)
-{
-    if (hipStreamSynchronize(pcacc_stream(stream)) != hipSuccess) return PCACC_E_LAUNCH;     // kernels already queued keep the word they were launched under
-    return hipMemcpyToSymbol(HIP_SYMBOL(csp_xword), &word, sizeof(int)) == hipSuccess ? PCACC_OK : PCACC_E_LAUNCH;
-}
+extern "C" int pcacc_x3_experiment_conv(int word, void *stream) { return x3_set_word(word, stream); }
 // a 16-byte piece of a prepared WEIGHT plane (plane 0 = hi, 1 = lo) as the experiment sees it
 __device__ __forceinline__ uint4 csp_x_weight(uint4 v, int plane)
 {
-    const int f = PCACC_X_W(csp_xword);
+    const int f = PCACC_X_W(x3_xword);
     if (plane == 1) return (f & 5) ? make_uint4(0u, 0u, 0u, 0u) : v;
     if (f & 4) {
         uint32_t *u = reinterpret_cast<uint32_t *>(&v);
@@ -176,31 +126,6 @@ __device__ __forceinline__ uint4 csp_x_weight(uint4 v, int plane)
     return v;
 }
 #endif
-__device__ __forceinline__ void csp_split2(float a, float b, uint32_t &hi, uint32_t &lo)
-{
-#ifdef PCACC_X3_EXPERIMENT
-    const bool drop = pcacc_x_apply(PCACC_X_ACT(csp_xword), a, b);
-#endif
-    hi = csp_pack_f16x2(a, b);
-    const pcacc_f32x2 back = csp_unpack_f16x2(hi);
-    lo = csp_pack_f16x2(a - back[0], b - back[1]);           // exact differences (Sterbenz); an inf hi gives NaN here, as it should
-#ifdef PCACC_X3_EXPERIMENT
-    if (drop) lo = 0u;
-#endif
-}
-// eight fp32, scaled by s -> eight fp16 hi + eight fp16 lo (round to nearest even both times)
-__device__ __forceinline__ void csp_split8(const float4 &a, const float4 &b, float s, uint4 &hi, uint4 &lo)
-{
-    csp_split2(a.x * s, a.y * s, hi.x, lo.x);
-    csp_split2(a.z * s, a.w * s, hi.y, lo.y);
-    csp_split2(b.x * s, b.y * s, hi.z, lo.z);
-    csp_split2(b.z * s, b.w * s, hi.w, lo.w);
-}
-
-__device__ __forceinline__ float4 csp_relu_mask4(float4 g, float4 y)
-{
-    return make_float4(y.x > 0.f ? g.x : 0.f, y.y > 0.f ? g.y : 0.f, y.z > 0.f ? g.z : 0.f, y.w > 0.f ? g.w : 0.f);
-}
 
 // ---- weight preparation: fp32 [O][I][KT][3][3] read through its strides -> fp16 [2 = hi, lo][KT*9][O'][I'] + fp32 [O'] ----------------
 // forward form (O' = O, I' = I) and data-gradient form (O' = I, I' = O, taps and frame taps mirrored) in one launch: one workgroup per
@@ -253,7 +178,7 @@ __device__ __forceinline__ void csp_prepare_row(const float *__restrict__ w, int
     __shared__ float sm[4];
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
     __syncthreads();
-    const float t = csp_scale_of(fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3])));
+    const float t = x3_scale_of(fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3])));
     if (threadIdx.x == 0) (transpose ? inv_bwd : inv_fwd)[row] = 1.f / t;
     uint16_t *dst = transpose ? out_bwd : out_fwd;
     auto put = [&](int e, float raw) {
@@ -306,10 +231,6 @@ extern "C" int pcacc_conv3x3_split_prepare_weights(const float *w, int32_t c_out
 // relu == CSP_OUTMASK: no bias, no ReLU -- `bias` carries an fp32 map of the output's shape and the result is stored as zero where that map is
 // <= 0 (aten::threshold_backward semantics: NaN keeps): the data gradient of conv -> ReLU -> conv masked for the first ReLU where it is stored
 #define CSP_OUTMASK 2
-__device__ __forceinline__ float4 csp_outmask4(float4 v, float4 m)
-{
-    return make_float4(m.x <= 0.f ? 0.f : v.x, m.y <= 0.f ? 0.f : v.y, m.z <= 0.f ? 0.f : v.z, m.w <= 0.f ? 0.f : v.w);
-}
 
 template <int CS, int NW, int NGW, int MT, int TAPS, bool MASKED>        // MASKED: in_mask != NULL, a compile-time fact (see conv3x3_split_res_kernel)
 __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_kernel(const float *__restrict__ in, const float *__restrict__ in_amax,
@@ -344,7 +265,7 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_kernel(const float 
     const int lp = lane & 31, lh = lane >> 5;
     const int mg = wave % MG, ngw = wave / MG;
     const int n_px = rows * bw;
-    const float sx = csp_scale_from_parts(in_amax);            // power-of-two scale of the input tensor
+    const float sx = x3_scale_of(x3_amax(in_amax, nullptr)); // power-of-two scale of the input tensor
 
     // frame taps that exist for this image (uniform): a missing frame contributes zeros
     const int t_frame = img % frames;
@@ -363,7 +284,7 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_kernel(const float 
         poff[j] = ok ? (y * pw + x) * PS : 0;
         pyx[j] = ok ? ((y0 + y) << 16 | (x0 + x)) : -1;
     }
-    f32x16_t acc[MT][NW];
+    x3_f32x16 acc[MT][NW];
 #pragma unroll
     for (int j = 0; j < MT; ++j)
 #pragma unroll
@@ -418,8 +339,8 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_kernel(const float 
         if constexpr (MASKED) {
 #pragma unroll
             for (int q = 0; q < CSP_PCH; ++q) {
-                preg[q][0] = csp_relu_mask4(preg[q][0], *reinterpret_cast<const float4 *>(in_mask + offs[q]));
-                preg[q][1] = csp_relu_mask4(preg[q][1], *reinterpret_cast<const float4 *>(in_mask + offs[q] + 4));
+                preg[q][0] = x3_mask4(preg[q][0], *reinterpret_cast<const float4 *>(in_mask + offs[q]));
+                preg[q][1] = x3_mask4(preg[q][1], *reinterpret_cast<const float4 *>(in_mask + offs[q] + 4));
             }
         }
         pok = okb;
@@ -432,7 +353,7 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_kernel(const float 
                 uint4 hi, lo;
                 const bool ok = (pok >> q) & 1;                  // outside the image: zeros (the load came from a clamped position)
                 const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-                csp_split8(ok ? preg[q][0] : z, ok ? preg[q][1] : z, sx, hi, lo);
+                x3_split8(ok ? preg[q][0] : z, ok ? preg[q][1] : z, sx, hi, lo);
                 uint16_t *dst = patch + (c / C8) * PS + (c % C8) * 8;
                 *reinterpret_cast<uint4 *>(dst) = hi;
                 *reinterpret_cast<uint4 *>(dst + plane) = lo;
@@ -488,17 +409,17 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_kernel(const float 
             const int toff = (TAPS == 1 ? pw + 1 : (tap / 3) * pw + tap % 3) * PS + lh * 8;     // one tap: the pixel itself
             constexpr int KC = CS / 16;
             constexpr int FB = (MT * NW >= 6 || MT >= 3) ? 1 : 2;   // fragment sets: the widest waves have no registers for a second one
-            f16x8_t ah[FB][NW], al[FB][NW], bh[FB][MT], bl[FB][MT];
+            x3_f16x8 ah[FB][NW], al[FB][NW], bh[FB][MT], bl[FB][MT];
             auto load = [&](int slot, int kc) {
 #pragma unroll
                 for (int n = 0; n < NW; ++n) {
-                    ah[slot][n] = *reinterpret_cast<const f16x8_t *>(wa + n * 32 * PS + kc * 16);
-                    al[slot][n] = *reinterpret_cast<const f16x8_t *>(wa + WPL + n * 32 * PS + kc * 16);
+                    ah[slot][n] = *reinterpret_cast<const x3_f16x8 *>(wa + n * 32 * PS + kc * 16);
+                    al[slot][n] = *reinterpret_cast<const x3_f16x8 *>(wa + WPL + n * 32 * PS + kc * 16);
                 }
 #pragma unroll
                 for (int j = 0; j < MT; ++j) {
-                    bh[slot][j] = *reinterpret_cast<const f16x8_t *>(patch + poff[j] + toff + kc * 16);
-                    bl[slot][j] = *reinterpret_cast<const f16x8_t *>(patch + plane + poff[j] + toff + kc * 16);
+                    bh[slot][j] = *reinterpret_cast<const x3_f16x8 *>(patch + poff[j] + toff + kc * 16);
+                    bl[slot][j] = *reinterpret_cast<const x3_f16x8 *>(patch + plane + poff[j] + toff + kc * 16);
                 }
             };
             if (FB == 2) load(0, 0);
@@ -561,7 +482,7 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_kernel(const float 
                 sc = make_float4(sc.x * inv_sx, sc.y * inv_sx, sc.z * inv_sx, sc.w * inv_sx);
                 float4 v = make_float4(acc[j][n][4 * g] * sc.x + bv.x, acc[j][n][4 * g + 1] * sc.y + bv.y, acc[j][n][4 * g + 2] * sc.z + bv.z,
                                        acc[j][n][4 * g + 3] * sc.w + bv.w);
-                if (relu == CSP_OUTMASK) v = csp_outmask4(v, *reinterpret_cast<const float4 *>(bias + ((dst + c) - out)));
+                if (relu == CSP_OUTMASK) v = x3_outmask4(v, *reinterpret_cast<const float4 *>(bias + ((dst + c) - out)));
                 else if (relu) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
                 *reinterpret_cast<float4 *>(dst + c) = v;
                 if (out16)                                     // 'mixed' mode: the bf16 shadow of the result (same element offsets), for the bf16 backward
@@ -573,7 +494,7 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_kernel(const float 
     if (out_amax) {                                            // uniform: one atomic per wave into one of 256 slots (zeroed by the caller)
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) omax = fmaxf(omax, __shfl_xor(omax, d, 64));
-        if (lane == 0) atomicMax(reinterpret_cast<unsigned *>(out_amax) + (blockIdx.x & (CSP_AMAX_PARTS - 1)), __float_as_uint(omax));
+        if (lane == 0) atomicMax(reinterpret_cast<unsigned *>(out_amax) + (blockIdx.x & (X3_AMAX_PARTS - 1)), __float_as_uint(omax));
     }
 }
 
@@ -646,7 +567,7 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
     const int n_px = rows * bw;
     const int nc = c_in / CS;
     const int tiles_img = tiles_y * tiles_x, n_tiles = n_img * tiles_img;
-    const float sx = csp_scale_from_parts(in_amax);
+    const float sx = x3_scale_of(x3_amax(in_amax, nullptr));
     const float inv_sx = 1.f / sx;
     if ((int)threadIdx.x < WROWS) {                            // published by the first pass's barriers
         sb[threadIdx.x] = wscale[blockIdx.x % co_groups * WROWS + threadIdx.x] * inv_sx;
@@ -705,8 +626,8 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
         if constexpr (MASKED) {                                // the masked data gradient of the fp32x3 backward (not on the mixed mode's path)
 #pragma unroll
             for (int q = 0; q < PCH; ++q) {
-                preg[q][0] = csp_relu_mask4(preg[q][0], *reinterpret_cast<const float4 *>(in_mask + offs[q]));
-                preg[q][1] = csp_relu_mask4(preg[q][1], *reinterpret_cast<const float4 *>(in_mask + offs[q] + 4));
+                preg[q][0] = x3_mask4(preg[q][0], *reinterpret_cast<const float4 *>(in_mask + offs[q]));
+                preg[q][1] = x3_mask4(preg[q][1], *reinterpret_cast<const float4 *>(in_mask + offs[q] + 4));
             }
         }
         pok = okb;
@@ -719,7 +640,7 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
                 uint4 hi, lo;
                 const bool ok = (pok >> q) & 1;                  // outside the image: zeros (the load came from a clamped position)
                 const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-                csp_split8(ok ? preg[q][0] : z, ok ? preg[q][1] : z, sx, hi, lo);
+                x3_split8(ok ? preg[q][0] : z, ok ? preg[q][1] : z, sx, hi, lo);
                 uint16_t *dst = patch + (c / C8) * PS + (c % C8) * 8;
                 *reinterpret_cast<uint4 *>(dst) = hi;
                 *reinterpret_cast<uint4 *>(dst + plane) = lo;
@@ -763,7 +684,7 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
     fetch_patch(cur, f, cs);
     fetch_w(f, cs);
     if (!RESTAGE) write_w();                                   // a one-slice layer (RESTAGE false): its nine tap tiles are staged once; the first pass's barriers publish them
-    f32x16_t acc[MT][NW];
+    x3_f32x16 acc[MT][NW];
     // a finished tile's values wait in registers and leave one pass later, right after the next patch loads are issued: the wait for those
     // loads at the top of a pass (vmcnt counts stores too) then finds the stores a whole MFMA phase old instead of just issued -- as
     // written before, load burst, MFMA phase and store burst took turns (57 + 53 + 71 us of a 181 us layer, measured by knocking each out)
@@ -849,20 +770,20 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
             pyx[j] = ok ? ((y0 + y) << 16 | (x0 + x)) : -1;
         }
         if (!(CSR_EXP & 1)) {
-            f16x8_t ah[AHEAD + 1][NW], al[AHEAD + 1][NW], bh[AHEAD + 1][MT], bl[AHEAD + 1][MT];
+            x3_f16x8 ah[AHEAD + 1][NW], al[AHEAD + 1][NW], bh[AHEAD + 1][MT], bl[AHEAD + 1][MT];
             const uint16_t *wa = wl + lp * PS + lh * 8;
             auto load = [&](int slt, int st) __attribute__((always_inline)) {
                 const int tap = st / KC, kc = st - tap * KC;
                 const int toff = ((tap / 3) * pw + tap % 3) * PS + lh * 8 + kc * 16;
 #pragma unroll
                 for (int n = 0; n < NW; ++n) {
-                    ah[slt][n] = *reinterpret_cast<const f16x8_t *>(wa + (tap * WROWS + n * 32) * PS + kc * 16);
-                    al[slt][n] = *reinterpret_cast<const f16x8_t *>(wa + WPL + (tap * WROWS + n * 32) * PS + kc * 16);
+                    ah[slt][n] = *reinterpret_cast<const x3_f16x8 *>(wa + (tap * WROWS + n * 32) * PS + kc * 16);
+                    al[slt][n] = *reinterpret_cast<const x3_f16x8 *>(wa + WPL + (tap * WROWS + n * 32) * PS + kc * 16);
                 }
 #pragma unroll
                 for (int j = 0; j < MT; ++j) {
-                    bh[slt][j] = *reinterpret_cast<const f16x8_t *>(patch + poff[j] + toff);
-                    bl[slt][j] = *reinterpret_cast<const f16x8_t *>(patch + plane + poff[j] + toff);
+                    bh[slt][j] = *reinterpret_cast<const x3_f16x8 *>(patch + poff[j] + toff);
+                    bl[slt][j] = *reinterpret_cast<const x3_f16x8 *>(patch + plane + poff[j] + toff);
                 }
             };
 #pragma unroll
@@ -914,7 +835,7 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
                         if (relu == CSP_OUTMASK) {             // ... unless that pixel's own result is masked away
                             const int yx = line_pyx(j, g, y0, x0);
                             ok = yx >= 0;
-                            if (ok) v = csp_outmask4(v, *reinterpret_cast<const float4 *>(bias + (((int64_t)img * h + (yx >> 16)) * w + (yx & 0xffff)) * c_out + co0 + n * 32 + 4 * (lp >> 2)));
+                            if (ok) v = x3_outmask4(v, *reinterpret_cast<const float4 *>(bias + (((int64_t)img * h + (yx >> 16)) * w + (yx & 0xffff)) * c_out + co0 + n * 32 + 4 * (lp >> 2)));
                         }
                         pend[j][n][g] = v;
                         if (ok) {
@@ -945,7 +866,7 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
                                                acc[j][n][4 * g + 3] * sc.w + bv.w);
                         if (relu == CSP_OUTMASK) {
                             if (pyx[j] >= 0)
-                                v = csp_outmask4(v, *reinterpret_cast<const float4 *>(bias + (((int64_t)img * h + (pyx[j] >> 16)) * w + (pyx[j] & 0xffff)) * c_out + co0 + c));
+                                v = x3_outmask4(v, *reinterpret_cast<const float4 *>(bias + (((int64_t)img * h + (pyx[j] >> 16)) * w + (pyx[j] & 0xffff)) * c_out + co0 + c));
                         } else if (relu) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
                         pend[j][n][g] = v;
                         if (pyx[j] >= 0) {
@@ -970,7 +891,7 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
     if (out_amax) {
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) omax = fmaxf(omax, __shfl_xor(omax, d, 64));
-        if (lane == 0) atomicMax(reinterpret_cast<unsigned *>(out_amax) + (blockIdx.x & (CSP_AMAX_PARTS - 1)), __float_as_uint(omax));
+        if (lane == 0) atomicMax(reinterpret_cast<unsigned *>(out_amax) + (blockIdx.x & (X3_AMAX_PARTS - 1)), __float_as_uint(omax));
     }
 }
 
@@ -1225,15 +1146,14 @@ extern "C" int pcacc_conv3x3_split_outmask(const float *in, const float *in_amax
 // scaled hi / lo planes while they are staged channels-last, the fragments ("8 consecutive pixels of one channel") come through the LDS
 // transpose read; 8 waves = (co tile, ci tile) pairs x tap groups; three MFMAs per fragment pair.  The ReLU backward of dY is applied
 // while staging (dy_mask = the layer's forward output).  One partial slot per workgroup, a second launch sums the slots.
-typedef short csp_s16x4 __attribute__((ext_vector_type(4)));
-union csp_frag { f16x8_t v; csp_s16x4 h[2]; };
+union csp_frag { x3_f16x8 v; pcacc_s16x4 h[2]; };
 #define CSW_PCH 6                                          // staged 8-channel chunks (dY rows + X patch) a thread carries
 
-__device__ __forceinline__ f16x8_t csp_tr_frag(const uint16_t *p, int stride4)
+__device__ __forceinline__ x3_f16x8 csp_tr_frag(const uint16_t *p, int stride4)
 {
     csp_frag f;
-    f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((csp_s16x4 __attribute__((address_space(3))) *)p);
-    f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((csp_s16x4 __attribute__((address_space(3))) *)(p + stride4));
+    f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)p);
+    f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(p + stride4));
     return f.v;
 }
 
@@ -1268,11 +1188,11 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_wgrad_split_kernel(const 
     const int n_blocks = gridDim.x / slots, lb = xcd ? pcacc_xcd_block(blockIdx.x, gridDim.x) : 0;
     const int block = xcd ? lb % n_blocks : blockIdx.x / slots, slot = xcd ? lb / n_blocks : blockIdx.x % slots;
     const int co0 = (block / ci_blocks) * CO, ci0 = (block % ci_blocks) * CI;
-    const float sy = csp_scale_from_parts(dy_amax), sxs = csp_scale_from_parts(x_amax);   // the reduce launch divides by sy * sxs
+    const float sy = x3_scale_of(x3_amax(dy_amax, nullptr)), sxs = x3_scale_of(x3_amax(x_amax, nullptr));   // the reduce launch divides by sy * sxs
 
     for (int q = threadIdx.x; q < py_rows; q += CSP_THREADS) ptab[q] = q < n_px ? (uint16_t)((q / bw) * pw + q % bw) : 0;
 
-    f32x16_t acc[NT];                                          // local tap j = tap grp + j * G
+    x3_f32x16 acc[NT];                                         // local tap j = tap grp + j * G
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -1314,8 +1234,8 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_wgrad_split_kernel(const 
             float4 a = *reinterpret_cast<const float4 *>(src), b = *reinterpret_cast<const float4 *>(src + 4);
             if (msrc && is_y) {
                 const float *m = msrc + pos * c_out + c8 * 8;
-                a = csp_relu_mask4(a, *reinterpret_cast<const float4 *>(m));
-                b = csp_relu_mask4(b, *reinterpret_cast<const float4 *>(m + 4));
+                a = x3_mask4(a, *reinterpret_cast<const float4 *>(m));
+                b = x3_mask4(b, *reinterpret_cast<const float4 *>(m + 4));
             }
             const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
             sreg[q][0] = ok ? a : z;
@@ -1329,7 +1249,7 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_wgrad_split_kernel(const 
             if (c >= n_chunks) continue;
             uint4 hi, lo;
             const bool is_y = c < y_chunks;
-            csp_split8(sreg[q][0], sreg[q][1], is_y ? sy : sxs, hi, lo);
+            x3_split8(sreg[q][0], sreg[q][1], is_y ? sy : sxs, hi, lo);
             const int e = is_y ? c : c - y_chunks;
             uint16_t *dst = is_y ? sdy + (e / YC8) * YS + (e % YC8) * 8 : sx + (e / XC8) * XS + (e % XC8) * 8;
             const int pl = is_y ? yplane : xplane;
@@ -1375,10 +1295,10 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_wgrad_split_kernel(const 
                 if (tap < TAPS) {
                     const int toff = (TAPS == 1 ? pw + 1 : (tap / 3) * pw + tap % 3) * XS;
                     csp_frag bh, bl;
-                    bh.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((csp_s16x4 __attribute__((address_space(3))) *)(pb0 + toff));
-                    bh.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((csp_s16x4 __attribute__((address_space(3))) *)(pb1 + toff));
-                    bl.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((csp_s16x4 __attribute__((address_space(3))) *)(pb0 + xplane + toff));
-                    bl.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((csp_s16x4 __attribute__((address_space(3))) *)(pb1 + xplane + toff));
+                    bh.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb0 + toff));
+                    bh.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb1 + toff));
+                    bl.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb0 + xplane + toff));
+                    bl.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb1 + xplane + toff));
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah.v, bl.v, acc[j], 0, 0, 0);
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al.v, bh.v, acc[j], 0, 0, 0);
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah.v, bh.v, acc[j], 0, 0, 0);
@@ -1411,7 +1331,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_split_reduce_kernel(const floa
                                                                       const float *__restrict__ x_amax, float *__restrict__ dw,
                                                                       float *__restrict__ db)
 {
-    const float inv_y = 1.f / csp_scale_from_parts(dy_amax), inv_yx = inv_y / csp_scale_from_parts(x_amax);
+    const float inv_y = 1.f / x3_scale_of(x3_amax(dy_amax, nullptr)), inv_yx = inv_y / x3_scale_of(x3_amax(x_amax, nullptr));
     const int slot_elems = cob * taps * cib + cob, ci_blocks = c_in / cib;
     const int64_t n_w = (int64_t)c_out * taps * c_in;
     const int64_t e = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
@@ -1571,7 +1491,7 @@ __device__ __forceinline__ void upconv_prepare_row(const float *__restrict__ w, 
     __shared__ float sm[4];
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
     __syncthreads();
-    const float t = csp_scale_of(fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3])));
+    const float t = x3_scale_of(fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3])));
     if (threadIdx.x == 0) (bwd ? inv_bwd : inv_fwd)[row] = 1.f / t;
     uint16_t *dst = (bwd ? out_bwd : out_fwd) + (int64_t)row * n;
     for (int e = threadIdx.x; e < n; e += 256) {

@@ -449,7 +449,6 @@ extern "C" int pcacc_rows_linear_mixed(const void *x, const void *in_mask, const
 // v_mfma_f32_32x32x2_f32 (A = dY^T: n x 2 rows, B = X: 2 rows x k) whose operands are two ds_read_b32 per MFMA.
 // Workgroup partials go to the zero-filled output with one fp32 atomic per element per workgroup.
 // ---------------------------------------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 // tiles per wave (template parameter WG_MAX_TILES): 1 when there are <= 4 output tiles (keeps the register footprint of the
 // common 32/64-wide layers small: 4 workgroups per CU overlap staging and MFMA), 2 for <= 8, 6 for the 128 x 129 case.
 
@@ -464,7 +463,7 @@ __global__ __launch_bounds__(256) void rows_wgrad_kernel(const void *__restrict_
     float *sdy = lds, *sx = lds + WG_ROWS * NS;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int half = lane >> 5, li = lane & 31;
-    f32x16 acc[WG_MAX_TILES];
+    pcacc_f32x16 acc[WG_MAX_TILES];
 #pragma unroll
     for (int t = 0; t < WG_MAX_TILES; ++t)
 #pragma unroll

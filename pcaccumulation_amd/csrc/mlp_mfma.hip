@@ -11,31 +11,13 @@
 // 8-byte channel quads and leaves through fully coalesced 16-byte stores, where residual / ReLU / output mask are applied.
 #include "common.h"
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
 #define MM_TILE 128
 #define MM_THREADS 256
 #define MM_PRE_RELU 1
 #define MM_POST_RELU 2
 
-// max(x, 0) on two packed bf16: clear the halves whose sign bit is set
-__device__ __forceinline__ uint32_t mm_relu2(uint32_t v)
-{
-    const uint32_t neg = (v >> 15) & 0x00010001u;
-    return v & ~(neg * 0xffffu);
-}
-
-// keep the halves of v whose mask half is > 0
-__device__ __forceinline__ uint32_t mm_mask2(uint32_t v, uint32_t m)
-{
-    const uint32_t lo = m & 0xffffu, hi = m >> 16;                        // > 0: sign clear, not zero, not NaN
-    const uint32_t lo_ok = (lo != 0 && lo <= 0x7f80u) ? 0x0000ffffu : 0u;
-    const uint32_t hi_ok = (hi != 0 && hi <= 0x7f80u) ? 0xffff0000u : 0u;
-    return v & (lo_ok | hi_ok);
-}
-
-__device__ __forceinline__ uint4 mm_relu8(uint4 v) { return make_uint4(mm_relu2(v.x), mm_relu2(v.y), mm_relu2(v.z), mm_relu2(v.w)); }
+__device__ __forceinline__ uint4 mm_relu8(uint4 v) { return make_uint4(pcacc_relu2(v.x), pcacc_relu2(v.y), pcacc_relu2(v.z), pcacc_relu2(v.w)); }
 __device__ __forceinline__ uint4 mm_mask8(uint4 v, uint4 m)
 {
     return make_uint4(mm_mask2(v.x, m.x), mm_mask2(v.y, m.y), mm_mask2(v.z, m.z), mm_mask2(v.w, m.w));
@@ -120,7 +102,7 @@ __global__ __launch_bounds__(MM_THREADS) void rows_linear_bf16_kernel(const uint
         __syncthreads();
         if (tile + gridDim.x < n_tiles) fetch(tile + gridDim.x);              // in flight during the MFMAs and the store phase
 
-        f32x16_t acc[CT];
+        pcacc_f32x16 acc[CT];
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
@@ -129,10 +111,10 @@ __global__ __launch_bounds__(MM_THREADS) void rows_linear_bf16_kernel(const uint
         const uint16_t *wrow = ws + lp * XS + lh * 8;
 #pragma unroll
         for (int kc = 0; kc < K / 16; ++kc) {
-            const bf16x8_t b = *reinterpret_cast<const bf16x8_t *>(xrow + kc * 16);
+            const pcacc_bf16x8 b = *reinterpret_cast<const pcacc_bf16x8 *>(xrow + kc * 16);
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
-                const bf16x8_t a = *reinterpret_cast<const bf16x8_t *>(wrow + ct * 32 * XS + kc * 16);
+                const pcacc_bf16x8 a = *reinterpret_cast<const pcacc_bf16x8 *>(wrow + ct * 32 * XS + kc * 16);
                 acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[ct], 0, 0, 0);
             }
         }
@@ -251,8 +233,7 @@ extern "C" int pcacc_rows_linear_cat_bf16(const uint16_t *xa, const uint16_t *xb
 // Rows per staged tile: 64 for the widest layers (128 features each side: 4 sixteen-byte pieces of dY and of X per thread), more for the
 // narrow ones so that every thread still has 4 + 4 pieces in flight and a barrier pair is paid per 128 / 256 rows instead of per 64
 // (the 32 -> 32 layers of the pillar encoder ran 49 tile iterations of 8 MFMAs each per workgroup: barrier-bound at 3.6 TB/s).
-typedef short wg_s16x4 __attribute__((ext_vector_type(4)));
-union wg_frag { bf16x8_t v; wg_s16x4 h[2]; uint16_t e[8]; };
+union wg_frag { pcacc_bf16x8 v; pcacc_s16x4 h[2]; uint16_t e[8]; };
 
 template <int MAX_TILES, int WG_R, int NW = 4>
 __global__ __launch_bounds__(NW * 64) void rows_wgrad_bf16_kernel(const uint16_t *__restrict__ dY, const uint16_t *__restrict__ dy_mask,
@@ -267,7 +248,7 @@ __global__ __launch_bounds__(NW * 64) void rows_wgrad_bf16_kernel(const uint16_t
     uint16_t *sdy = wlds, *sx = wlds + WG_R * NS;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lp = lane & 31, lh = lane >> 5;
-    f32x16_t acc[MAX_TILES];
+    pcacc_f32x16 acc[MAX_TILES];
 #pragma unroll
     for (int t = 0; t < MAX_TILES; ++t)
 #pragma unroll
@@ -365,11 +346,11 @@ __global__ __launch_bounds__(NW * 64) void rows_wgrad_bf16_kernel(const uint16_t
                 const uint16_t *pb = sx + tr_row * KS + (ones ? 0 : kt * 32) + tr_col;
                 for (int r0 = r_lo; r0 < r_hi; r0 += 16) {
                     wg_frag a, b;
-                    a.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wg_s16x4 __attribute__((address_space(3))) *)(pa + r0 * NS));
-                    a.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wg_s16x4 __attribute__((address_space(3))) *)(pa + (r0 + 4) * NS));
+                    a.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pa + r0 * NS));
+                    a.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pa + (r0 + 4) * NS));
                     if (!ones) {
-                        b.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wg_s16x4 __attribute__((address_space(3))) *)(pb + r0 * KS));
-                        b.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wg_s16x4 __attribute__((address_space(3))) *)(pb + (r0 + 4) * KS));
+                        b.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb + r0 * KS));
+                        b.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb + (r0 + 4) * KS));
                     } else {
 #pragma unroll
                         for (int j = 0; j < 8; ++j)

@@ -1,6 +1,6 @@
 // Per-point linear layers at fp32 accuracy on the 16-bit matrix cores ("fp32x3" compute mode): fp32 rows in and out, every product
 // formed from fp16 hi / lo halves of power-of-two scaled operands (three v_mfma_f32_32x32x16_f16 per fragment pair, fp32 accumulation;
-// see conv_split.hip for the arithmetic and its error bound).  Same contracts as the bf16 kernels of mlp_mfma.hip,
+// see fp32x3.h for the arithmetic and its error bound).  Same contracts as the bf16 kernels of mlp_mfma.hip,
 //     Y = [relu]( [relu|mask](X) @ W^T + b [+ residual] ) [masked],          dW_aug = dYeff^T @ [Xeff | 1],
 // on the pillar encoder (models/pillar_encoder.py:13-55,113-122), the STPN point heads (models/stpn.py:94-102) and the TubeNet
 // embeddings (models/tpointnet.py:176-196) -- nn.Linear in fp32 in the reference.  The fp32 mode ran these layers on the fp32 vector
@@ -10,76 +10,18 @@
 // Scales: the row tensors come with their absolute maxima (pcacc_absmax256, one scale per tensor; two-piece rows take the larger of the
 // two pieces' maxima); the weight matrix is scaled per output row inside the kernel (a workgroup stages the whole [N][K] matrix anyway).
 #include "common.h"
+#include "fp32x3.h"
 
-typedef _Float16 ms_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 ms_f16x2 __attribute__((ext_vector_type(2)));
-typedef float ms_f32x16 __attribute__((ext_vector_type(16)));
-typedef short ms_s16x4 __attribute__((ext_vector_type(4)));
-union ms_frag { ms_f16x8 v; ms_s16x4 h[2]; uint16_t e[8]; };
+union ms_frag { x3_f16x8 v; pcacc_s16x4 h[2]; uint16_t e[8]; };
 
 #define MS_TILE 128
 #define MS_THREADS 256
 #define MS_PRE_RELU 1
 #define MS_POST_RELU 2
 
-__device__ __forceinline__ float ms_scale_of(float amax)
-{
-    if (!(amax > 0.f) || !(amax < __builtin_inff())) return 1.f;
-    int k;
-    frexpf(amax, &k);
-    return ldexpf(1.f, 14 - k);
-}
-// largest of the 256 partial maxima of one tensor (and of a second one when given): wave-uniform, no LDS
-__device__ __forceinline__ float ms_amax(const float *__restrict__ parts, const float *__restrict__ parts2)
-{
-    const int lane = threadIdx.x & 63;
-    float m = fmaxf(fmaxf(parts[lane], parts[lane + 64]), fmaxf(parts[lane + 128], parts[lane + 192]));
-    if (parts2) m = fmaxf(m, fmaxf(fmaxf(parts2[lane], parts2[lane + 64]), fmaxf(parts2[lane + 128], parts2[lane + 192])));
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
-    return m;
-}
-__device__ __forceinline__ uint32_t ms_pack(float a, float b)
-{
-    const pcacc_f32x2 f = {a, b};
-    const ms_f16x2 r = __builtin_convertvector(f, ms_f16x2);
-    return *reinterpret_cast<const uint32_t *>(&r);
-}
 #ifdef PCACC_X3_EXPERIMENT
-__device__ int ms_xword;                                     // common.h: precision-map experiment build
-extern "C" int pcacc_x3_experiment_rows(int word, void *stream)
-{
-    if (hipStreamSynchronize(pcacc_stream(stream)) != hipSuccess) return PCACC_E_LAUNCH;     // kernels already queued keep the word they were launched under
-    return hipMemcpyToSymbol(HIP_SYMBOL(ms_xword), &word, sizeof(int)) == hipSuccess ? PCACC_OK : PCACC_E_LAUNCH;
-}
+extern "C" int pcacc_x3_experiment_rows(int word, void *stream) { return x3_set_word(word, stream); }
 #endif
-// WEIGHT: the operand is a weight (the experiment build treats activations and weights separately; no difference in the shipped library)
-template <bool WEIGHT = false>
-__device__ __forceinline__ void ms_split2(float a, float b, uint32_t &hi, uint32_t &lo)
-{
-#ifdef PCACC_X3_EXPERIMENT
-    const bool drop = pcacc_x_apply(WEIGHT ? PCACC_X_W(ms_xword) : PCACC_X_ACT(ms_xword), a, b);
-#endif
-    hi = ms_pack(a, b);
-    const pcacc_f32x2 back = __builtin_convertvector(*reinterpret_cast<const ms_f16x2 *>(&hi), pcacc_f32x2);
-    lo = ms_pack(a - back[0], b - back[1]);
-#ifdef PCACC_X3_EXPERIMENT
-    if (drop) lo = 0u;
-#endif
-}
-template <bool WEIGHT = false>
-__device__ __forceinline__ void ms_split8(const float4 &a, const float4 &b, float s, uint4 &hi, uint4 &lo)
-{
-    ms_split2<WEIGHT>(a.x * s, a.y * s, hi.x, lo.x);
-    ms_split2<WEIGHT>(a.z * s, a.w * s, hi.y, lo.y);
-    ms_split2<WEIGHT>(b.x * s, b.y * s, hi.z, lo.z);
-    ms_split2<WEIGHT>(b.z * s, b.w * s, hi.w, lo.w);
-}
-__device__ __forceinline__ float4 ms_relu4(float4 v) { return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)); }
-__device__ __forceinline__ float4 ms_mask4(float4 v, float4 m)
-{
-    return make_float4(m.x > 0.f ? v.x : 0.f, m.y > 0.f ? v.y : 0.f, m.z > 0.f ? v.z : 0.f, m.w > 0.f ? v.w : 0.f);
-}
 
 // A row made of two pieces ("virtual concatenation"): columns [0,ka) from a[row], columns [ka,K) from b[idx[row]] (idx == NULL: b[row]);
 // b == NULL: the plain contiguous [rows,K] layout of `a` (RowPieces of mlp_mfma.hip on fp32 rows).
@@ -137,18 +79,18 @@ __global__ __launch_bounds__(MS_THREADS) void rows_linear_split_kernel(const flo
     __syncthreads();
     for (int e = threadIdx.x; e < N * K / 2; e += MS_THREADS) {
         const int n = (2 * e) / K, k = (2 * e) % K;
-        const float t = ms_scale_of(__uint_as_float(wmax[n]));
+        const float t = x3_scale_of(__uint_as_float(wmax[n]));
         const float2 w2 = *reinterpret_cast<const float2 *>(W + (int64_t)n * K + k);
         uint32_t hi, lo;
-        ms_split2<true>(w2.x * t, w2.y * t, hi, lo);
+        x3_split2<true>(w2.x * t, w2.y * t, hi, lo);
         *reinterpret_cast<uint32_t *>(ws + n * XS + k) = hi;
         *reinterpret_cast<uint32_t *>(ws + WPLANE + n * XS + k) = lo;
     }
     if (threadIdx.x < N) {
         bias_l[threadIdx.x] = bias ? bias[threadIdx.x] : 0.f;
-        invt[threadIdx.x] = 1.f / ms_scale_of(__uint_as_float(wmax[threadIdx.x]));
+        invt[threadIdx.x] = 1.f / x3_scale_of(__uint_as_float(wmax[threadIdx.x]));
     }
-    const float sx = ms_scale_of(ms_amax(x_amax, x_amax2));
+    const float sx = x3_scale_of(x3_amax(x_amax, x_amax2));
     const float inv_sx = 1.f / sx;
 
     const int64_t n_tiles = (rows + MS_TILE - 1) / MS_TILE;
@@ -193,12 +135,12 @@ __global__ __launch_bounds__(MS_THREADS) void rows_linear_split_kernel(const flo
         const bool ok = (xok >> q) & 1;
         a = ok ? xreg[q][0] : z;
         b = ok ? xreg[q][1] : z;
-        if (flags & MS_PRE_RELU) { a = ms_relu4(a); b = ms_relu4(b); }
+        if (flags & MS_PRE_RELU) { a = x3_relu4(a); b = x3_relu4(b); }
         if (in_mask) {                                                        // uniform; the masked layers of the fp32x3 backward
             const int64_t e = xbase + (int64_t)(threadIdx.x + q * MS_THREADS) * 8;
             if (ok) {
-                a = ms_mask4(a, *reinterpret_cast<const float4 *>(in_mask + e));
-                b = ms_mask4(b, *reinterpret_cast<const float4 *>(in_mask + e + 4));
+                a = x3_mask4(a, *reinterpret_cast<const float4 *>(in_mask + e));
+                b = x3_mask4(b, *reinterpret_cast<const float4 *>(in_mask + e + 4));
             }
         }
     };
@@ -214,7 +156,7 @@ __global__ __launch_bounds__(MS_THREADS) void rows_linear_split_kernel(const flo
             uint4 hi, lo;
             float4 xa, xb;
             staged(q, xa, xb);
-            ms_split8(xa, xb, sx, hi, lo);
+            x3_split8(xa, xb, sx, hi, lo);
             uint16_t *dst = xs + (c / (K / 8)) * XS + (c % (K / 8)) * 8;
             *reinterpret_cast<uint4 *>(dst) = hi;
             *reinterpret_cast<uint4 *>(dst + XPLANE) = lo;
@@ -222,7 +164,7 @@ __global__ __launch_bounds__(MS_THREADS) void rows_linear_split_kernel(const flo
         __syncthreads();
         if (tile + gridDim.x < n_tiles) fetch(tile + gridDim.x);              // in flight during the MFMAs and the store phase
 
-        ms_f32x16 acc[CT];
+        x3_f32x16 acc[CT];
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
@@ -231,12 +173,12 @@ __global__ __launch_bounds__(MS_THREADS) void rows_linear_split_kernel(const flo
         const uint16_t *wrow = ws + lp * XS + lh * 8;
 #pragma unroll
         for (int kc = 0; kc < K / 16; ++kc) {
-            const ms_f16x8 bh = *reinterpret_cast<const ms_f16x8 *>(xrow + kc * 16);
-            const ms_f16x8 bl = *reinterpret_cast<const ms_f16x8 *>(xrow + XPLANE + kc * 16);
+            const x3_f16x8 bh = *reinterpret_cast<const x3_f16x8 *>(xrow + kc * 16);
+            const x3_f16x8 bl = *reinterpret_cast<const x3_f16x8 *>(xrow + XPLANE + kc * 16);
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
-                const ms_f16x8 ah = *reinterpret_cast<const ms_f16x8 *>(wrow + ct * 32 * XS + kc * 16);
-                const ms_f16x8 al = *reinterpret_cast<const ms_f16x8 *>(wrow + WPLANE + ct * 32 * XS + kc * 16);
+                const x3_f16x8 ah = *reinterpret_cast<const x3_f16x8 *>(wrow + ct * 32 * XS + kc * 16);
+                const x3_f16x8 al = *reinterpret_cast<const x3_f16x8 *>(wrow + WPLANE + ct * 32 * XS + kc * 16);
                 acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[ct], 0, 0, 0);
                 acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[ct], 0, 0, 0);
                 acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[ct], 0, 0, 0);
@@ -266,10 +208,10 @@ __global__ __launch_bounds__(MS_THREADS) void rows_linear_split_kernel(const flo
                 const float4 r = *reinterpret_cast<const float4 *>(residual + e);
                 v = make_float4(v.x + r.x, v.y + r.y, v.z + r.z, v.w + r.w);
             }
-            if (flags & MS_POST_RELU) v = ms_relu4(v);
+            if (flags & MS_POST_RELU) v = x3_relu4(v);
             const int64_t row = e / N;
             const int col = (int)(e % N);
-            if (out_mask) v = ms_mask4(v, *reinterpret_cast<const float4 *>(ms_piece(out_mask, ms2, N, row, col)));
+            if (out_mask) v = x3_mask4(v, *reinterpret_cast<const float4 *>(ms_piece(out_mask, ms2, N, row, col)));
             omax = fmaxf(fmaxf(omax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
             if (!(v.x == v.x && v.y == v.y && v.z == v.z && v.w == v.w)) omax = __builtin_inff();
             if (!Y2 || na < 0) {                                              // na < 0: Y2 is the bf16 SHADOW of Y ('mixed' mode), same offsets
@@ -314,7 +256,7 @@ __global__ __launch_bounds__(MS_THREADS, 2) void rows_linear_split_fm_kernel(con
     const int ct = wave % CT, rg = wave / CT;
 
     // this wave's weight rows n = ct * 32 + lp: row maximum -> power-of-two scale -> hi / lo fragments in registers
-    ms_f16x8 wh[KC], wl[KC];
+    x3_f16x8 wh[KC], wl[KC];
     {
         const float *wrow = W + (int64_t)(ct * 32 + lp) * K + lh * 8;
         float m = 0.f;
@@ -326,20 +268,20 @@ __global__ __launch_bounds__(MS_THREADS, 2) void rows_linear_split_fm_kernel(con
             if (!(a.x == a.x && a.y == a.y && a.z == a.z && a.w == a.w && b.x == b.x && b.y == b.y && b.z == b.z && b.w == b.w)) m = __builtin_inff();
         }
         m = fmaxf(m, __shfl_xor(m, 32, 64));                   // the row's other k-half
-        const float t = ms_scale_of(m);
+        const float t = x3_scale_of(m);
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc) {
             uint4 hi, lo;
-            ms_split8<true>(*reinterpret_cast<const float4 *>(wrow + kc * 16), *reinterpret_cast<const float4 *>(wrow + kc * 16 + 4), t, hi, lo);
-            wh[kc] = *reinterpret_cast<const ms_f16x8 *>(&hi);
-            wl[kc] = *reinterpret_cast<const ms_f16x8 *>(&lo);
+            x3_split8<true>(*reinterpret_cast<const float4 *>(wrow + kc * 16), *reinterpret_cast<const float4 *>(wrow + kc * 16 + 4), t, hi, lo);
+            wh[kc] = *reinterpret_cast<const x3_f16x8 *>(&hi);
+            wl[kc] = *reinterpret_cast<const x3_f16x8 *>(&lo);
         }
         if (rg == 0 && lh == 0) {
             invt[ct * 32 + lp] = 1.f / t;
             bias_l[ct * 32 + lp] = bias ? bias[ct * 32 + lp] : 0.f;
         }
     }
-    const float sx = ms_scale_of(ms_amax(x_amax, x_amax2));
+    const float sx = x3_scale_of(x3_amax(x_amax, x_amax2));
     const float inv_sx = 1.f / sx;
 
     const int64_t n_tiles = (rows + MS_TILE - 1) / MS_TILE;
@@ -384,12 +326,12 @@ __global__ __launch_bounds__(MS_THREADS, 2) void rows_linear_split_fm_kernel(con
         const bool ok = (xok >> q) & 1;
         a = ok ? xreg[q][0] : z;
         b = ok ? xreg[q][1] : z;
-        if (flags & MS_PRE_RELU) { a = ms_relu4(a); b = ms_relu4(b); }
+        if (flags & MS_PRE_RELU) { a = x3_relu4(a); b = x3_relu4(b); }
         if (in_mask) {                                                        // uniform; the masked layers of the fp32x3 backward
             const int64_t e = xbase + (int64_t)(threadIdx.x + q * MS_THREADS) * 8;
             if (ok) {
-                a = ms_mask4(a, *reinterpret_cast<const float4 *>(in_mask + e));
-                b = ms_mask4(b, *reinterpret_cast<const float4 *>(in_mask + e + 4));
+                a = x3_mask4(a, *reinterpret_cast<const float4 *>(in_mask + e));
+                b = x3_mask4(b, *reinterpret_cast<const float4 *>(in_mask + e + 4));
             }
         }
     };
@@ -405,7 +347,7 @@ __global__ __launch_bounds__(MS_THREADS, 2) void rows_linear_split_fm_kernel(con
             uint4 hi, lo;
             float4 xa, xb;
             staged(q, xa, xb);
-            ms_split8(xa, xb, sx, hi, lo);
+            x3_split8(xa, xb, sx, hi, lo);
             uint16_t *dst = xs + (c / (K / 8)) * XS + (c % (K / 8)) * 8;
             *reinterpret_cast<uint4 *>(dst) = hi;
             *reinterpret_cast<uint4 *>(dst + XPLANE) = lo;
@@ -413,7 +355,7 @@ __global__ __launch_bounds__(MS_THREADS, 2) void rows_linear_split_fm_kernel(con
         __syncthreads();
         if (tile + gridDim.x < n_tiles) fetch(tile + gridDim.x);              // in flight during the MFMAs and the store phase
 
-        ms_f32x16 acc[RT];
+        x3_f32x16 acc[RT];
 #pragma unroll
         for (int j = 0; j < RT; ++j)
 #pragma unroll
@@ -423,8 +365,8 @@ __global__ __launch_bounds__(MS_THREADS, 2) void rows_linear_split_fm_kernel(con
         for (int kc = 0; kc < KC; ++kc)
 #pragma unroll
             for (int j = 0; j < RT; ++j) {
-                const ms_f16x8 bh = *reinterpret_cast<const ms_f16x8 *>(xrow + j * 32 * XS + kc * 16);
-                const ms_f16x8 bl = *reinterpret_cast<const ms_f16x8 *>(xrow + XPLANE + j * 32 * XS + kc * 16);
+                const x3_f16x8 bh = *reinterpret_cast<const x3_f16x8 *>(xrow + j * 32 * XS + kc * 16);
+                const x3_f16x8 bl = *reinterpret_cast<const x3_f16x8 *>(xrow + XPLANE + j * 32 * XS + kc * 16);
                 acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[kc], bl, acc[j], 0, 0, 0);
                 acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[kc], bh, acc[j], 0, 0, 0);
                 acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[kc], bh, acc[j], 0, 0, 0);
@@ -454,10 +396,10 @@ __global__ __launch_bounds__(MS_THREADS, 2) void rows_linear_split_fm_kernel(con
                 const float4 r = *reinterpret_cast<const float4 *>(residual + e);
                 v = make_float4(v.x + r.x, v.y + r.y, v.z + r.z, v.w + r.w);
             }
-            if (flags & MS_POST_RELU) v = ms_relu4(v);
+            if (flags & MS_POST_RELU) v = x3_relu4(v);
             const int64_t row = e / N;
             const int col = (int)(e % N);
-            if (out_mask) v = ms_mask4(v, *reinterpret_cast<const float4 *>(ms_piece(out_mask, ms2, N, row, col)));
+            if (out_mask) v = x3_mask4(v, *reinterpret_cast<const float4 *>(ms_piece(out_mask, ms2, N, row, col)));
             omax = fmaxf(fmaxf(omax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
             if (!(v.x == v.x && v.y == v.y && v.z == v.z && v.w == v.w)) omax = __builtin_inff();
             if (!Y2 || na < 0) {                                              // na < 0: Y2 is the bf16 SHADOW of Y ('mixed' mode), same offsets
@@ -604,8 +546,8 @@ __global__ __launch_bounds__(NW * 64) void rows_wgrad_split_kernel(const float *
     uint16_t *sdy = wlds, *sx = wlds + 2 * yplane;             // [2][WG_R][NS], [2][WG_R][KS]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lp = lane & 31, lh = lane >> 5;
-    const float sy = ms_scale_of(ms_amax(dy_amax, nullptr)), sxs = ms_scale_of(ms_amax(x_amax, x_amax2));
-    ms_f32x16 acc[MAX_TILES];
+    const float sy = x3_scale_of(x3_amax(dy_amax, nullptr)), sxs = x3_scale_of(x3_amax(x_amax, x_amax2));
+    x3_f32x16 acc[MAX_TILES];
 #pragma unroll
     for (int t = 0; t < MAX_TILES; ++t)
 #pragma unroll
@@ -640,8 +582,8 @@ __global__ __launch_bounds__(NW * 64) void rows_wgrad_split_kernel(const float *
                 b = *reinterpret_cast<const float4 *>(src + 4);
                 if (dy_mask) {
                     const float *m = dy_mask + row0 * N + (int64_t)i * 8;
-                    a = ms_mask4(a, *reinterpret_cast<const float4 *>(m));
-                    b = ms_mask4(b, *reinterpret_cast<const float4 *>(m + 4));
+                    a = x3_mask4(a, *reinterpret_cast<const float4 *>(m));
+                    b = x3_mask4(b, *reinterpret_cast<const float4 *>(m + 4));
                 }
             }
             yreg[q][0] = a;
@@ -655,7 +597,7 @@ __global__ __launch_bounds__(NW * 64) void rows_wgrad_split_kernel(const float *
                                        : xs2.b + (int64_t)prow[q] * (K - xs2.ka) + (col - xs2.ka);
                 c = *reinterpret_cast<const float4 *>(src);
                 d = *reinterpret_cast<const float4 *>(src + 4);
-                if (x_relu) { c = ms_relu4(c); d = ms_relu4(d); }
+                if (x_relu) { c = x3_relu4(c); d = x3_relu4(d); }
             }
             xreg[q][0] = c;
             xreg[q][1] = d;
@@ -674,7 +616,7 @@ __global__ __launch_bounds__(NW * 64) void rows_wgrad_split_kernel(const float *
             if (i < ny) {
                 const int e = i * 8;
                 uint4 hi, lo;
-                ms_split8(yreg[q][0], yreg[q][1], sy, hi, lo);
+                x3_split8(yreg[q][0], yreg[q][1], sy, hi, lo);
                 uint2 *dst = reinterpret_cast<uint2 *>(sdy + (e / N) * NS + e % N);
                 dst[0] = make_uint2(hi.x, hi.y);
                 dst[1] = make_uint2(hi.z, hi.w);
@@ -685,7 +627,7 @@ __global__ __launch_bounds__(NW * 64) void rows_wgrad_split_kernel(const float *
             if (i < nx) {
                 const int e = i * 8;
                 uint4 hi, lo;
-                ms_split8(xreg[q][0], xreg[q][1], sxs, hi, lo);
+                x3_split8(xreg[q][0], xreg[q][1], sxs, hi, lo);
                 uint2 *dst = reinterpret_cast<uint2 *>(sx + (e / K) * KS + e % K);
                 dst[0] = make_uint2(hi.x, hi.y);
                 dst[1] = make_uint2(hi.z, hi.w);
@@ -712,15 +654,15 @@ __global__ __launch_bounds__(NW * 64) void rows_wgrad_split_kernel(const float *
                 const uint16_t *pb = sx + tr_row * KS + (ones ? 0 : kt * 32) + tr_col;
                 for (int r0 = r_lo; r0 < r_hi; r0 += 16) {
                     ms_frag ah, al, bh, bl;
-                    ah.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ms_s16x4 __attribute__((address_space(3))) *)(pa + r0 * NS));
-                    ah.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ms_s16x4 __attribute__((address_space(3))) *)(pa + (r0 + 4) * NS));
-                    al.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ms_s16x4 __attribute__((address_space(3))) *)(pa + yplane + r0 * NS));
-                    al.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ms_s16x4 __attribute__((address_space(3))) *)(pa + yplane + (r0 + 4) * NS));
+                    ah.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pa + r0 * NS));
+                    ah.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pa + (r0 + 4) * NS));
+                    al.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pa + yplane + r0 * NS));
+                    al.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pa + yplane + (r0 + 4) * NS));
                     if (!ones) {
-                        bh.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ms_s16x4 __attribute__((address_space(3))) *)(pb + r0 * KS));
-                        bh.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ms_s16x4 __attribute__((address_space(3))) *)(pb + (r0 + 4) * KS));
-                        bl.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ms_s16x4 __attribute__((address_space(3))) *)(pb + xplane + r0 * KS));
-                        bl.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ms_s16x4 __attribute__((address_space(3))) *)(pb + xplane + (r0 + 4) * KS));
+                        bh.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb + r0 * KS));
+                        bh.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb + (r0 + 4) * KS));
+                        bl.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb + xplane + r0 * KS));
+                        bl.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb + xplane + (r0 + 4) * KS));
                         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah.v, bl.v, acc[t], 0, 0, 0);
                         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al.v, bh.v, acc[t], 0, 0, 0);
                         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah.v, bh.v, acc[t], 0, 0, 0);
@@ -758,7 +700,7 @@ __global__ __launch_bounds__(1024) void rows_wgrad_split_reduce_kernel(const flo
                                                                        const float *__restrict__ dy_amax, const float *__restrict__ x_amax,
                                                                        const float *__restrict__ x_amax2, float *__restrict__ out, int split_k)
 {
-    const float inv_y = 1.f / ms_scale_of(ms_amax(dy_amax, nullptr)), inv_yx = inv_y / ms_scale_of(ms_amax(x_amax, x_amax2));
+    const float inv_y = 1.f / x3_scale_of(x3_amax(dy_amax, nullptr)), inv_yx = inv_y / x3_scale_of(x3_amax(x_amax, x_amax2));
     pcacc_reduce_partials<EL>(partial, n_parts, elems, [&](int e, float v) {
         const int row = e / ka, col = e % ka;
         int o = e;

@@ -16,10 +16,7 @@
 // step, so the only workgroup barriers are around tile staging and the output tile.
 #include "common.h"
 
-typedef __bf16 pb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float pb_f32x16 __attribute__((ext_vector_type(16)));
-typedef short pb_s16x4 __attribute__((ext_vector_type(4)));
-union pb_frag { pb_bf16x8 v; pb_s16x4 h[2]; uint32_t u[4]; uint4 q; };
+union pb_frag { pcacc_bf16x8 v; pcacc_s16x4 h[2]; uint32_t u[4]; uint4 q; };
 
 #define PB_TILE 128
 #define PB_THREADS 256
@@ -35,14 +32,9 @@ struct PbPieces {                 // second half of x: b[idx[row]] (32 columns);
     const int32_t *idx;
 };
 
-__device__ __forceinline__ uint32_t pb_relu2(uint32_t v)
-{
-    const uint32_t neg = (v >> 15) & 0x00010001u;
-    return v & ~(neg * 0xffffu);
-}
 __device__ __forceinline__ pb_frag pb_relu(pb_frag f)
 {
-    f.u[0] = pb_relu2(f.u[0]); f.u[1] = pb_relu2(f.u[1]); f.u[2] = pb_relu2(f.u[2]); f.u[3] = pb_relu2(f.u[3]);
+    f.u[0] = pcacc_relu2(f.u[0]); f.u[1] = pcacc_relu2(f.u[1]); f.u[2] = pcacc_relu2(f.u[2]); f.u[3] = pcacc_relu2(f.u[3]);
     return f;
 }
 __device__ __forceinline__ bool pb_pos(uint32_t half) { return half != 0 && half <= 0x7f80u; }       // bf16 > 0 (not NaN)
@@ -123,7 +115,7 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
         if (tile + gridDim.x < n_tiles) fetch(tile + gridDim.x);              // in flight during the rest of this tile
         fetch_rows(tile + 2 * (int64_t)gridDim.x);
 
-        pb_f32x16 acc_h, acc_o;
+        pcacc_f32x16 acc_h, acc_o;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc_h[r] = 0.f; acc_o[r] = 0.f; }
         const uint16_t *xrow = xs + myrow * XS + lh * 8;
@@ -132,8 +124,8 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
             pb_frag bx;
             bx.q = *reinterpret_cast<const uint4 *>(xrow + kc * 16);
             const pb_frag br = pb_relu(bx);
-            const pb_bf16x8 a0 = *reinterpret_cast<const pb_bf16x8 *>(w0s + lp * XS + lh * 8 + kc * 16);
-            const pb_bf16x8 as = *reinterpret_cast<const pb_bf16x8 *>(wss + lp * XS + lh * 8 + kc * 16);
+            const pcacc_bf16x8 a0 = *reinterpret_cast<const pcacc_bf16x8 *>(w0s + lp * XS + lh * 8 + kc * 16);
+            const pcacc_bf16x8 as = *reinterpret_cast<const pcacc_bf16x8 *>(wss + lp * XS + lh * 8 + kc * 16);
             acc_h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, br.v, acc_h, 0, 0, 0);
             acc_o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as, bx.v, acc_o, 0, 0, 0);
         }
@@ -149,8 +141,8 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
         __syncthreads();                                                      // relu(h) complete; every wave is done reading xs
 #pragma unroll
         for (int kc = 0; kc < 2; ++kc) {
-            const pb_bf16x8 bh = *reinterpret_cast<const pb_bf16x8 *>(hrow + lh * 8 + kc * 16);
-            const pb_bf16x8 a1 = *reinterpret_cast<const pb_bf16x8 *>(w1s + lp * HS + lh * 8 + kc * 16);
+            const pcacc_bf16x8 bh = *reinterpret_cast<const pcacc_bf16x8 *>(hrow + lh * 8 + kc * 16);
+            const pcacc_bf16x8 a1 = *reinterpret_cast<const pcacc_bf16x8 *>(w1s + lp * HS + lh * 8 + kc * 16);
             acc_o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bh, acc_o, 0, 0, 0);
         }
         uint16_t *orow = xs + myrow * HS;
@@ -179,7 +171,7 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-#define PB_TR(p) __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_s16x4 __attribute__((address_space(3))) *)(p))
+#define PB_TR(p) __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(p))
 
 template <bool GATHER>
 __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void pfn_block_bwd_kernel(const uint16_t *__restrict__ xa, PbPieces xp, const uint16_t *__restrict__ hr,
@@ -202,7 +194,7 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     pb_stage_weights(W0, 32, 64, w0t, WS, true);
     pb_stage_weights(Ws, 32, 64, wst, WS, true);
 
-    pb_f32x16 acc_w1, acc_ws0, acc_ws1, acc_w00, acc_w01;
+    pcacc_f32x16 acc_w1, acc_ws0, acc_ws1, acc_w00, acc_w01;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc_w1[r] = 0.f; acc_ws0[r] = 0.f; acc_ws1[r] = 0.f; acc_w00[r] = 0.f; acc_w01[r] = 0.f; }
     float bias_sum = 0.f;                  // lane l < 32: column l of d(out), l >= 32: column l - 32 of d(h), over this wave's rows
@@ -260,14 +252,14 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         fetch_rows(tile + 2 * (int64_t)gridDim.x);
 
         // A. d(h) = (d(out) W1) where h > 0
-        pb_bf16x8 bg[2];
-        pb_f32x16 acc;
+        pcacc_bf16x8 bg[2];
+        pcacc_f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
         for (int kc = 0; kc < 2; ++kc) {
-            bg[kc] = *reinterpret_cast<const pb_bf16x8 *>(gs + myrow * GS + lh * 8 + kc * 16);
-            const pb_bf16x8 a = *reinterpret_cast<const pb_bf16x8 *>(w1t + lp * WS + lh * 8 + kc * 16);
+            bg[kc] = *reinterpret_cast<const pcacc_bf16x8 *>(gs + myrow * GS + lh * 8 + kc * 16);
+            const pcacc_bf16x8 a = *reinterpret_cast<const pcacc_bf16x8 *>(w1t + lp * WS + lh * 8 + kc * 16);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bg[kc], acc, 0, 0, 0);
         }
 #pragma unroll
@@ -310,14 +302,14 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         uint2 pk[2][4];
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-            pb_f32x16 a1, a2;
+            pcacc_f32x16 a1, a2;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { a1[r] = 0.f; a2[r] = 0.f; }
 #pragma unroll
             for (int kc = 0; kc < 2; ++kc) {
-                const pb_bf16x8 bgh = *reinterpret_cast<const pb_bf16x8 *>(ghs + myrow * GS + lh * 8 + kc * 16);
-                const pb_bf16x8 a0 = *reinterpret_cast<const pb_bf16x8 *>(w0t + (nt * 32 + lp) * WS + lh * 8 + kc * 16);
-                const pb_bf16x8 as = *reinterpret_cast<const pb_bf16x8 *>(wst + (nt * 32 + lp) * WS + lh * 8 + kc * 16);
+                const pcacc_bf16x8 bgh = *reinterpret_cast<const pcacc_bf16x8 *>(ghs + myrow * GS + lh * 8 + kc * 16);
+                const pcacc_bf16x8 a0 = *reinterpret_cast<const pcacc_bf16x8 *>(w0t + (nt * 32 + lp) * WS + lh * 8 + kc * 16);
+                const pcacc_bf16x8 as = *reinterpret_cast<const pcacc_bf16x8 *>(wst + (nt * 32 + lp) * WS + lh * 8 + kc * 16);
                 a1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bgh, a1, 0, 0, 0);
                 a2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as, bg[kc], a2, 0, 0, 0);
             }

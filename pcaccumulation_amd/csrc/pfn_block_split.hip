@@ -1,5 +1,5 @@
 // A ResnetBlockFC of the pillar encoder (models/pillar_encoder.py:13-55, sizes 64 -> 32 -> 32 with a linear shortcut) in the fp32x3
-// compute mode: fp32 point rows, every product on the 16-bit matrix cores from scaled fp16 hi / lo halves (conv_split.hip has the
+// compute mode: fp32 point rows, every product on the 16-bit matrix cores from scaled fp16 hi / lo halves (fp32x3.h has the
 // arithmetic).  The fp32 twin of pfn_block.hip's forward, and of the data half of its backward:
 //     h   = relu(x) W0^T + b0            [rows, 32]
 //     out = relu(h) W1^T + b1 + x Ws^T   [rows, 32]
@@ -14,11 +14,9 @@
 // wave (a wave's 32 rows are the only consumers of its intermediate: the exact maximum is at hand in the accumulators); each weight
 // matrix gets one scale when a workgroup stages it.
 #include "common.h"
+#include "fp32x3.h"
 
-typedef _Float16 pbs_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 pbs_f16x2 __attribute__((ext_vector_type(2)));
-typedef float pbs_f32x16 __attribute__((ext_vector_type(16)));
-union pbs_frag { pbs_f16x8 v; uint4 q; uint32_t u[4]; };
+union pbs_frag { x3_f16x8 v; uint4 q; uint32_t u[4]; };
 
 #define PBS_TILE 128
 #define PBS_THREADS 256
@@ -28,61 +26,9 @@ struct PbsPieces {                // second half of x: b[idx[row]] (32 columns);
     const int32_t *idx;
 };
 
-__device__ __forceinline__ float pbs_scale_of(float amax)
-{
-    if (!(amax > 0.f) || !(amax < __builtin_inff())) return 1.f;
-    int k;
-    frexpf(amax, &k);
-    return ldexpf(1.f, 14 - k);
-}
-__device__ __forceinline__ float pbs_amax(const float *__restrict__ parts, const float *__restrict__ parts2)
-{
-    const int lane = threadIdx.x & 63;
-    float m = fmaxf(fmaxf(parts[lane], parts[lane + 64]), fmaxf(parts[lane + 128], parts[lane + 192]));
-    if (parts2) m = fmaxf(m, fmaxf(fmaxf(parts2[lane], parts2[lane + 64]), fmaxf(parts2[lane + 128], parts2[lane + 192])));
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
-    return m;
-}
-__device__ __forceinline__ float pbs_wave_max(float m)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
-    return m;
-}
-__device__ __forceinline__ uint32_t pbs_pack(float a, float b)
-{
-    const pcacc_f32x2 f = {a, b};
-    const pbs_f16x2 r = __builtin_convertvector(f, pbs_f16x2);
-    return *reinterpret_cast<const uint32_t *>(&r);
-}
 #ifdef PCACC_X3_EXPERIMENT
-__device__ int pbs_xword;                                    // common.h: precision-map experiment build
-extern "C" int pcacc_x3_experiment_pfn(int word, void *stream)
-{
-    if (hipStreamSynchronize(pcacc_stream(stream)) != hipSuccess) return PCACC_E_LAUNCH;     // kernels already queued keep the word they were launched under
-    return hipMemcpyToSymbol(HIP_SYMBOL(pbs_xword), &word, sizeof(int)) == hipSuccess ? PCACC_OK : PCACC_E_LAUNCH;
-}
+extern "C" int pcacc_x3_experiment_pfn(int word, void *stream) { return x3_set_word(word, stream); }
 #endif
-__device__ __forceinline__ void pbs_split2(float a, float b, uint32_t &hi, uint32_t &lo)
-{
-#ifdef PCACC_X3_EXPERIMENT
-    const bool drop = pcacc_x_apply(PCACC_X_ACT(pbs_xword), a, b);
-#endif
-    hi = pbs_pack(a, b);
-    const pcacc_f32x2 back = __builtin_convertvector(*reinterpret_cast<const pbs_f16x2 *>(&hi), pcacc_f32x2);
-    lo = pbs_pack(a - back[0], b - back[1]);
-#ifdef PCACC_X3_EXPERIMENT
-    if (drop) lo = 0u;
-#endif
-}
-__device__ __forceinline__ void pbs_split8(const float4 &a, const float4 &b, float s, uint4 &hi, uint4 &lo)
-{
-    pbs_split2(a.x * s, a.y * s, hi.x, lo.x);
-    pbs_split2(a.z * s, a.w * s, hi.y, lo.y);
-    pbs_split2(b.x * s, b.y * s, hi.z, lo.z);
-    pbs_split2(b.z * s, b.w * s, hi.w, lo.w);
-}
 // max(x, 0) on a split fragment: the sign of x is the sign of its hi half (rounding keeps the sign, a lo half never outweighs its hi)
 __device__ __forceinline__ void pbs_relu(pbs_frag &hi, pbs_frag &lo)
 {
@@ -110,14 +56,14 @@ __device__ __forceinline__ float pbs_stage_weights(const float *__restrict__ src
     }
     atomicMax(wmax, m);
     __syncthreads();
-    const float t = pbs_scale_of(__uint_as_float(*wmax));
+    const float t = x3_scale_of(__uint_as_float(*wmax));
     for (int e = threadIdx.x; e < n * k; e += PBS_THREADS) {
         const int sr = e / k, sc = e % k;
         const int r = transposed ? sc : sr, c = transposed ? sr : sc;
         float v = src[e] * t;
 #ifdef PCACC_X3_EXPERIMENT
         float v2 = v;
-        const bool xdrop = pcacc_x_apply(PCACC_X_W(pbs_xword), v, v2);
+        const bool xdrop = pcacc_x_apply(PCACC_X_W(x3_xword), v, v2);
 #endif
         const _Float16 hi = (_Float16)v;
         _Float16 lo = (_Float16)(v - (float)hi);
@@ -165,7 +111,7 @@ __global__ __launch_bounds__(PBS_THREADS, 2) void pfn_block_split_fwd_kernel(con
     const float its = pbs_stage_weights(Ws, 32, 64, false, wss, XS, W64, wmax);
     const float it1 = pbs_stage_weights(W1, 32, 32, false, w1s, HS, W32, wmax);
     if (threadIdx.x < 32) { b0s[threadIdx.x] = b0 ? b0[threadIdx.x] : 0.f; b1s[threadIdx.x] = b1 ? b1[threadIdx.x] : 0.f; }
-    const float sx = pbs_scale_of(pbs_amax(xa_amax, GATHER ? xb_amax : nullptr));
+    const float sx = x3_scale_of(x3_amax(xa_amax, GATHER ? xb_amax : nullptr));
     const float k0 = it0 / sx, ks = its / sx;
     __syncthreads();
 
@@ -208,7 +154,7 @@ __global__ __launch_bounds__(PBS_THREADS, 2) void pfn_block_split_fwd_kernel(con
         for (int q = 0; q < 4; ++q) {
             const int c = threadIdx.x + q * PBS_THREADS;
             uint4 hi, lo;
-            pbs_split8(xreg[q][0], xreg[q][1], sx, hi, lo);
+            x3_split8(xreg[q][0], xreg[q][1], sx, hi, lo);
             uint16_t *dst = xs + (c >> 3) * XS + (c & 7) * 8;
             *reinterpret_cast<uint4 *>(dst) = hi;
             *reinterpret_cast<uint4 *>(dst + XPL) = lo;
@@ -217,7 +163,7 @@ __global__ __launch_bounds__(PBS_THREADS, 2) void pfn_block_split_fwd_kernel(con
         if (tile + gridDim.x < n_tiles) fetch(tile + gridDim.x);              // in flight during the rest of this tile
         fetch_rows(tile + 2 * (int64_t)gridDim.x);
 
-        pbs_f32x16 acc_h, acc_s, acc_1;
+        x3_f32x16 acc_h, acc_s, acc_1;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc_h[r] = 0.f; acc_s[r] = 0.f; acc_1[r] = 0.f; }
         const uint16_t *xrow = xs + myrow * XS + lh * 8;
@@ -236,10 +182,10 @@ __global__ __launch_bounds__(PBS_THREADS, 2) void pfn_block_split_fwd_kernel(con
                 if (kc < 2) xlo |= two << (kc * 16 + 2 * i);
                 else xhi |= two << ((kc - 2) * 16 + 2 * i);
             }
-            const pbs_f16x8 a0h = *reinterpret_cast<const pbs_f16x8 *>(w0s + lp * XS + lh * 8 + kc * 16);
-            const pbs_f16x8 a0l = *reinterpret_cast<const pbs_f16x8 *>(w0s + W64 + lp * XS + lh * 8 + kc * 16);
-            const pbs_f16x8 ash = *reinterpret_cast<const pbs_f16x8 *>(wss + lp * XS + lh * 8 + kc * 16);
-            const pbs_f16x8 asl = *reinterpret_cast<const pbs_f16x8 *>(wss + W64 + lp * XS + lh * 8 + kc * 16);
+            const x3_f16x8 a0h = *reinterpret_cast<const x3_f16x8 *>(w0s + lp * XS + lh * 8 + kc * 16);
+            const x3_f16x8 a0l = *reinterpret_cast<const x3_f16x8 *>(w0s + W64 + lp * XS + lh * 8 + kc * 16);
+            const x3_f16x8 ash = *reinterpret_cast<const x3_f16x8 *>(wss + lp * XS + lh * 8 + kc * 16);
+            const x3_f16x8 asl = *reinterpret_cast<const x3_f16x8 *>(wss + W64 + lp * XS + lh * 8 + kc * 16);
             acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, rl.v, acc_h, 0, 0, 0);
             acc_s = __builtin_amdgcn_mfma_f32_32x32x16_f16(ash, bl.v, acc_s, 0, 0, 0);
             acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0l, rh.v, acc_h, 0, 0, 0);
@@ -268,25 +214,25 @@ __global__ __launch_bounds__(PBS_THREADS, 2) void pfn_block_split_fwd_kernel(con
             }
         hbits <<= 4 * lh;
         hbits |= __shfl_xor(hbits, 32, 64);
-        hm = pbs_wave_max(hm);
+        hm = x3_wave_max(hm);
         hmax_all = fmaxf(hmax_all, hm);
-        const float sh = pbs_scale_of(hm), k1 = it1 / sh;
+        const float sh = x3_scale_of(hm), k1 = it1 / sh;
         uint16_t *hrow = hs + myrow * HS;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             uint2 ph, pl;
-            pbs_split2(hv[4 * g] * sh, hv[4 * g + 1] * sh, ph.x, pl.x);
-            pbs_split2(hv[4 * g + 2] * sh, hv[4 * g + 3] * sh, ph.y, pl.y);
+            x3_split2(hv[4 * g] * sh, hv[4 * g + 1] * sh, ph.x, pl.x);
+            x3_split2(hv[4 * g + 2] * sh, hv[4 * g + 3] * sh, ph.y, pl.y);
             *reinterpret_cast<uint2 *>(hrow + 8 * g + 4 * lh) = ph;
             *reinterpret_cast<uint2 *>(hrow + HPL + 8 * g + 4 * lh) = pl;
         }
         __syncthreads();                                                      // relu(h) planes complete; every wave is done reading the x planes
 #pragma unroll
         for (int kc = 0; kc < 2; ++kc) {
-            const pbs_f16x8 bh = *reinterpret_cast<const pbs_f16x8 *>(hrow + lh * 8 + kc * 16);
-            const pbs_f16x8 bl = *reinterpret_cast<const pbs_f16x8 *>(hrow + HPL + lh * 8 + kc * 16);
-            const pbs_f16x8 a1h = *reinterpret_cast<const pbs_f16x8 *>(w1s + lp * HS + lh * 8 + kc * 16);
-            const pbs_f16x8 a1l = *reinterpret_cast<const pbs_f16x8 *>(w1s + W32 + lp * HS + lh * 8 + kc * 16);
+            const x3_f16x8 bh = *reinterpret_cast<const x3_f16x8 *>(hrow + lh * 8 + kc * 16);
+            const x3_f16x8 bl = *reinterpret_cast<const x3_f16x8 *>(hrow + HPL + lh * 8 + kc * 16);
+            const x3_f16x8 a1h = *reinterpret_cast<const x3_f16x8 *>(w1s + lp * HS + lh * 8 + kc * 16);
+            const x3_f16x8 a1l = *reinterpret_cast<const x3_f16x8 *>(w1s + W32 + lp * HS + lh * 8 + kc * 16);
             acc_1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, bl, acc_1, 0, 0, 0);
             acc_1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1l, bh, acc_1, 0, 0, 0);
             acc_1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, bh, acc_1, 0, 0, 0);
@@ -328,7 +274,7 @@ __global__ __launch_bounds__(PBS_THREADS, 2) void pfn_block_split_fwd_kernel(con
             }
         }
     }
-    omax = pbs_wave_max(omax);
+    omax = x3_wave_max(omax);
     if (lane == 0) {
         if (out_amax) atomicMax(reinterpret_cast<unsigned *>(out_amax) + (blockIdx.x & 255), __float_as_uint(omax));
         if (hr_amax) atomicMax(reinterpret_cast<unsigned *>(hr_amax) + (blockIdx.x & 255), __float_as_uint(hmax_all));
@@ -358,7 +304,7 @@ __global__ __launch_bounds__(PBS_THREADS, 2) void pfn_block_split_dgrad_kernel(c
     const float it1 = pbs_stage_weights(W1, 32, 32, true, w1t, GS, W32, wmax);
     const float it0 = pbs_stage_weights(W0, 32, 64, true, w0t, GS, W64, wmax);
     const float its = pbs_stage_weights(Ws, 32, 64, true, wst, GS, W64, wmax);
-    const float sg = pbs_scale_of(pbs_amax(g_amax, nullptr));
+    const float sg = x3_scale_of(x3_amax(g_amax, nullptr));
     const float k1 = it1 / sg, ks = its / sg;
 
     const int64_t n_tiles = (rows + PBS_TILE - 1) / PBS_TILE;
@@ -388,7 +334,7 @@ __global__ __launch_bounds__(PBS_THREADS, 2) void pfn_block_split_dgrad_kernel(c
         for (int q = 0; q < 2; ++q) {
             const int c = threadIdx.x + q * PBS_THREADS;
             uint4 hi, lo;
-            pbs_split8(greg[q][0], greg[q][1], sg, hi, lo);
+            x3_split8(greg[q][0], greg[q][1], sg, hi, lo);
             uint16_t *dst = gs + (c >> 2) * GS + (c & 3) * 8;
             *reinterpret_cast<uint4 *>(dst) = hi;
             *reinterpret_cast<uint4 *>(dst + GPL) = lo;
@@ -400,16 +346,16 @@ __global__ __launch_bounds__(PBS_THREADS, 2) void pfn_block_split_dgrad_kernel(c
         if (tile + gridDim.x < n_tiles) fetch(tile + gridDim.x);
 
         // A. d(h) = (d(out) W1) where h > 0
-        pbs_f16x8 gh[2], gl[2];
-        pbs_f32x16 acc;
+        x3_f16x8 gh[2], gl[2];
+        x3_f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
         for (int kc = 0; kc < 2; ++kc) {
-            gh[kc] = *reinterpret_cast<const pbs_f16x8 *>(gs + myrow * GS + lh * 8 + kc * 16);
-            gl[kc] = *reinterpret_cast<const pbs_f16x8 *>(gs + GPL + myrow * GS + lh * 8 + kc * 16);
-            const pbs_f16x8 ah = *reinterpret_cast<const pbs_f16x8 *>(w1t + lp * GS + lh * 8 + kc * 16);
-            const pbs_f16x8 al = *reinterpret_cast<const pbs_f16x8 *>(w1t + W32 + lp * GS + lh * 8 + kc * 16);
+            gh[kc] = *reinterpret_cast<const x3_f16x8 *>(gs + myrow * GS + lh * 8 + kc * 16);
+            gl[kc] = *reinterpret_cast<const x3_f16x8 *>(gs + GPL + myrow * GS + lh * 8 + kc * 16);
+            const x3_f16x8 ah = *reinterpret_cast<const x3_f16x8 *>(w1t + lp * GS + lh * 8 + kc * 16);
+            const x3_f16x8 al = *reinterpret_cast<const x3_f16x8 *>(w1t + W32 + lp * GS + lh * 8 + kc * 16);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, gl[kc], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, gh[kc], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, gh[kc], acc, 0, 0, 0);
@@ -424,15 +370,15 @@ __global__ __launch_bounds__(PBS_THREADS, 2) void pfn_block_split_dgrad_kernel(c
                 dm = fmaxf(dm, fabsf(v));
                 if (v != v) dm = __builtin_inff();
             }
-        dm = pbs_wave_max(dm);
+        dm = x3_wave_max(dm);
         dmax_all = fmaxf(dmax_all, dm);
-        const float sd = pbs_scale_of(dm), k0 = it0 / sd;
+        const float sd = x3_scale_of(dm), k0 = it0 / sd;
         uint16_t *drow = ds + myrow * GS;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             uint2 ph, pl;
-            pbs_split2(dv[4 * g] * sd, dv[4 * g + 1] * sd, ph.x, pl.x);
-            pbs_split2(dv[4 * g + 2] * sd, dv[4 * g + 3] * sd, ph.y, pl.y);
+            x3_split2(dv[4 * g] * sd, dv[4 * g + 1] * sd, ph.x, pl.x);
+            x3_split2(dv[4 * g + 2] * sd, dv[4 * g + 3] * sd, ph.y, pl.y);
             *reinterpret_cast<uint2 *>(drow + 8 * g + 4 * lh) = ph;
             *reinterpret_cast<uint2 *>(drow + GPL + 8 * g + 4 * lh) = pl;
         }
@@ -442,17 +388,17 @@ __global__ __launch_bounds__(PBS_THREADS, 2) void pfn_block_split_dgrad_kernel(c
         float4 ox[2][4];
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-            pbs_f32x16 a1, a2;
+            x3_f32x16 a1, a2;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { a1[r] = 0.f; a2[r] = 0.f; }
 #pragma unroll
             for (int kc = 0; kc < 2; ++kc) {
-                const pbs_f16x8 dhh = *reinterpret_cast<const pbs_f16x8 *>(drow + lh * 8 + kc * 16);
-                const pbs_f16x8 dhl = *reinterpret_cast<const pbs_f16x8 *>(drow + GPL + lh * 8 + kc * 16);
-                const pbs_f16x8 a0h = *reinterpret_cast<const pbs_f16x8 *>(w0t + (nt * 32 + lp) * GS + lh * 8 + kc * 16);
-                const pbs_f16x8 a0l = *reinterpret_cast<const pbs_f16x8 *>(w0t + W64 + (nt * 32 + lp) * GS + lh * 8 + kc * 16);
-                const pbs_f16x8 ash = *reinterpret_cast<const pbs_f16x8 *>(wst + (nt * 32 + lp) * GS + lh * 8 + kc * 16);
-                const pbs_f16x8 asl = *reinterpret_cast<const pbs_f16x8 *>(wst + W64 + (nt * 32 + lp) * GS + lh * 8 + kc * 16);
+                const x3_f16x8 dhh = *reinterpret_cast<const x3_f16x8 *>(drow + lh * 8 + kc * 16);
+                const x3_f16x8 dhl = *reinterpret_cast<const x3_f16x8 *>(drow + GPL + lh * 8 + kc * 16);
+                const x3_f16x8 a0h = *reinterpret_cast<const x3_f16x8 *>(w0t + (nt * 32 + lp) * GS + lh * 8 + kc * 16);
+                const x3_f16x8 a0l = *reinterpret_cast<const x3_f16x8 *>(w0t + W64 + (nt * 32 + lp) * GS + lh * 8 + kc * 16);
+                const x3_f16x8 ash = *reinterpret_cast<const x3_f16x8 *>(wst + (nt * 32 + lp) * GS + lh * 8 + kc * 16);
+                const x3_f16x8 asl = *reinterpret_cast<const x3_f16x8 *>(wst + W64 + (nt * 32 + lp) * GS + lh * 8 + kc * 16);
                 a1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, dhl, a1, 0, 0, 0);
                 a2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ash, gl[kc], a2, 0, 0, 0);
                 a1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0l, dhh, a1, 0, 0, 0);
@@ -505,7 +451,7 @@ __global__ __launch_bounds__(PBS_THREADS, 2) void pfn_block_split_dgrad_kernel(c
                               *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(smem) + (c >> 3) * HO + (c & 7) * 4);
         }
     }
-    xmax = pbs_wave_max(xmax);
+    xmax = x3_wave_max(xmax);
     if (lane == 0) {
         if (gx_amax) atomicMax(reinterpret_cast<unsigned *>(gx_amax) + (blockIdx.x & 255), __float_as_uint(xmax));
         if (dh_amax) atomicMax(reinterpret_cast<unsigned *>(dh_amax) + (blockIdx.x & 255), __float_as_uint(dmax_all));

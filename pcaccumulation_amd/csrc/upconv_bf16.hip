@@ -11,10 +11,7 @@
 // map (the decoder's concatenation gradient): `pitch` = elements between pixels.
 #include "common.h"
 
-typedef __bf16 ub_bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float ub_f32x16_t __attribute__((ext_vector_type(16)));
-typedef short ub_s16x4 __attribute__((ext_vector_type(4)));
-union ub_frag { ub_bf16x8_t v; ub_s16x4 h[2]; };
+union ub_frag { pcacc_bf16x8 v; pcacc_s16x4 h[2]; };
 
 #define UB_ROWS 128
 #define UB_KC 64
@@ -109,7 +106,7 @@ __global__ __launch_bounds__(256) void upconv_bf16_kernel(const uint16_t *__rest
         }
     };
 
-    ub_f32x16_t acc[CT];
+    pcacc_f32x16 acc[CT];
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
@@ -134,10 +131,10 @@ __global__ __launch_bounds__(256) void upconv_bf16_kernel(const uint16_t *__rest
         const uint16_t *wrow = ws + lp * UB_XS + lh * 8;
 #pragma unroll
         for (int kc = 0; kc < UB_KC / 16; ++kc) {
-            const ub_bf16x8_t b = *reinterpret_cast<const ub_bf16x8_t *>(xrow + kc * 16);
+            const pcacc_bf16x8 b = *reinterpret_cast<const pcacc_bf16x8 *>(xrow + kc * 16);
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
-                const ub_bf16x8_t a = *reinterpret_cast<const ub_bf16x8_t *>(wrow + ct * 32 * UB_XS + kc * 16);
+                const pcacc_bf16x8 a = *reinterpret_cast<const pcacc_bf16x8 *>(wrow + ct * 32 * UB_XS + kc * 16);
                 acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[ct], 0, 0, 0);
             }
         }
@@ -218,7 +215,7 @@ __global__ __launch_bounds__(256) void upconv_bf16_wgrad_kernel(const uint16_t *
     const int64_t r_begin = (int64_t)split * rows_per_split, r_end = min(P, r_begin + rows_per_split);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lp = lane & 31, lh = lane >> 5;
-    ub_f32x16_t acc[2];
+    pcacc_f32x16 acc[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -280,12 +277,12 @@ __global__ __launch_bounds__(256) void upconv_bf16_wgrad_kernel(const uint16_t *
 #pragma unroll
         for (int r0 = 0; r0 < UW_ROWS; r0 += 16) {
             ub_frag a, b0, b1;
-            a.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ub_s16x4 __attribute__((address_space(3))) *)(pa + r0 * NS));
-            a.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ub_s16x4 __attribute__((address_space(3))) *)(pa + (r0 + 4) * NS));
-            b0.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ub_s16x4 __attribute__((address_space(3))) *)(pb + r0 * KS));
-            b0.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ub_s16x4 __attribute__((address_space(3))) *)(pb + (r0 + 4) * KS));
-            b1.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ub_s16x4 __attribute__((address_space(3))) *)(pb + 32 + r0 * KS));
-            b1.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ub_s16x4 __attribute__((address_space(3))) *)(pb + 32 + (r0 + 4) * KS));
+            a.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pa + r0 * NS));
+            a.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pa + (r0 + 4) * NS));
+            b0.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb + r0 * KS));
+            b0.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb + (r0 + 4) * KS));
+            b1.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb + 32 + r0 * KS));
+            b1.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pcacc_s16x4 __attribute__((address_space(3))) *)(pb + 32 + (r0 + 4) * KS));
             acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, b0.v, acc[0], 0, 0, 0);
             acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, b1.v, acc[1], 0, 0, 0);
         }

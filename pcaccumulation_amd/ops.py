@@ -1184,7 +1184,6 @@ def tube_pose(pose_vec, rows, plan, remaining, total, slot_centre, weights, n_fr
                            int(n_frames))
 
 
-_PREPARED = {}
 _WEIGHT_EPOCH = 0
 
 
@@ -1215,26 +1214,15 @@ def _weight_key(weight):
     return (weight._version, weight.data_ptr(), _WEIGHT_EPOCH)
 
 
-def _weight_ref(cache, key, weight):
-    """A weak reference that removes the weight's entry (and frees its device copies) when the weight dies."""
-    return weakref.ref(weight, lambda _r, c=cache, k=key: c.pop(k, None))
-
-
 # ---- every prepared form a step needs, in one launch --------------------------------------------------------------------------------
-# The per-weight caches below miss once per weight and optimizer step: ~90 host calls and launches of 10-20 us kernels at the start of a
+# The per-weight caches (_PreparedForms below) miss once per weight and optimizer step: ~90 host calls and launches of 10-20 us kernels at the start of a
 # 'mixed' training step.  The first miss after the weights changed (a new weight epoch) instead re-prepares EVERY form the process has
 # asked for so far (weights still alive, fp32, on that device) with one launch into buffers that stay allocated
-# (native.prepare_weights_batch), and fills all three caches; a miss for any other reason (a version change inside an epoch, a weight
+# (native.prepare_weights_batch), and fills all four caches; a miss for any other reason (a version change inside an epoch, a weight
 # seen for the first time) takes the per-weight path as before.  PCACC_BATCH_PREPARE=0 switches it off.
 _BATCH_ON = os.environ.get('PCACC_BATCH_PREPARE', '1') != '0'
 _BATCH_SEEN = {}            # (id(weight), kind) -> weak reference; kind 0 = split 3x3, 1 = split transposed 2x2, 2 = bf16 3x3, 3 = bf16 transposed 2x2
 _BATCH_STATE = {}           # device index -> {'sig', 'jobs', 'n', 'blocks', 'forms': [(ref, kind, fwd, bwd)], 'epoch'}
-
-
-def _batch_note(weight, kind):
-    k = (id(weight), kind)
-    if _BATCH_ON and k not in _BATCH_SEEN and weight.is_cuda and weight.dtype == torch.float32:
-        _BATCH_SEEN[k] = weakref.ref(weight, lambda _r, k=k: _BATCH_SEEN.pop(k, None))
 
 
 def _batch_build(dev, live):
@@ -1290,44 +1278,81 @@ def _batch_refresh(dev):
         _BATCH_STATE[dev.index] = state
     native.prepare_weights_batch(state['jobs'], state['n'], state['blocks'])
     state['epoch'] = _WEIGHT_EPOCH
-    caches = (_PREPARED_SPLIT, _PREPARED_UP, _PREPARED, _PREPARED_UPB)
     for ref, kind, fwd, bwd in state['forms']:
         w = ref()
         if w is not None:
-            caches[kind][id(w)] = (_weight_ref(caches[kind], id(w), w), _weight_key(w), fwd, bwd)
+            _FORMS[kind].put(w, fwd, bwd)
     return True
 
 
-def _batch_hit(cache, weight, kind):
-    """The prepared forms of `weight` out of a batch refresh, or None (the caller then prepares this weight alone)."""
-    if not (_BATCH_ON and (id(weight), kind) in _BATCH_SEEN and _batch_refresh(weight.device)):
-        return None
-    hit = cache.get(id(weight))
-    if hit is not None and hit[0]() is weight and hit[1] == _weight_key(weight):
-        return hit[2], hit[3]
-    return None
+class _PreparedForms:
+    """The (forward form, data-gradient form) of every weight asked for in one prepared layout, made once per weight VERSION and weight epoch
+    (weights_may_have_changed): the forward of a training step and its backward share one preparation, evaluation passes reuse the forms until the
+    optimizer (or a load_state_dict) writes the parameter again.  `kind` is the layout's number in the job rows of native.prepare_weights_batch
+    (see _BATCH_SEEN), `prepare(weight) -> (fwd, bwd)` prepares one weight alone.  An entry goes with its weight (no device copies of dead
+    parameters), and a cache of more than 4096 entries is emptied."""
+    __slots__ = ('kind', 'prepare', 'entries')
+
+    def __init__(self, kind, prepare):
+        self.kind, self.prepare, self.entries = kind, prepare, {}      # id(weight) -> (weak reference, _weight_key, fwd, bwd)
+
+    def forms(self, weight):
+        hit = self.entries.get(id(weight))
+        if hit is not None and hit[0]() is weight and hit[1] == _weight_key(weight):
+            return hit[2], hit[3]
+        return self._miss(weight)
+
+    def put(self, weight, fwd, bwd):
+        key, entries = id(weight), self.entries
+        entries[key] = (weakref.ref(weight, lambda _r: entries.pop(key, None)), _weight_key(weight), fwd, bwd)
+
+    def _miss(self, weight):
+        seen = (id(weight), self.kind)
+        if _BATCH_ON and seen in _BATCH_SEEN and _batch_refresh(weight.device):      # the batch has just filled every cache: look again
+            hit = self.entries.get(id(weight))
+            if hit is not None and hit[0]() is weight and hit[1] == _weight_key(weight):
+                return hit[2], hit[3]
+        if _BATCH_ON and seen not in _BATCH_SEEN and weight.is_cuda and weight.dtype == torch.float32:
+            _BATCH_SEEN[seen] = weakref.ref(weight, lambda _r: _BATCH_SEEN.pop(seen, None))
+        fwd, bwd = self.prepare(weight)
+        if len(self.entries) > 4096:
+            self.entries.clear()
+        self.put(weight, fwd, bwd)
+        return fwd, bwd
+
+
+def _detached_f32(weight):
+    w = weight.detach()
+    return w if w.dtype == torch.float32 else w.float()
+
+
+# the 3x3 preparers take fp32; the transposed 2x2 ones are handed the weight as it is
+_FORMS = {
+    0: _PreparedForms(0, lambda w: native.conv3x3_split_prepare_weights(_detached_f32(w))),
+    1: _PreparedForms(1, lambda w: native.upconv2x2_split_prepare_weights(w.detach())),
+    2: _PreparedForms(2, lambda w: native.conv3x3_prepare_weights_pair(_detached_f32(w))),
+    3: _PreparedForms(3, lambda w: native.upconv2x2_bf16_prepare_weights(w.detach())),
+}
 
 
 def prepared_conv_weights(weight):
-    """(forward form, data-gradient form) of a 3x3 / 3x3x3 weight for the MFMA kernels, prepared once per weight VERSION and weight
-    epoch (weights_may_have_changed): the forward of a training step and its backward share one launch, evaluation passes reuse the forms
-    until the optimizer (or a load_state_dict) writes the parameter again."""
-    key = id(weight)
-    hit = _PREPARED.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == _weight_key(weight):
-        return hit[2], hit[3]
-    got = _batch_hit(_PREPARED, weight, 2)
-    if got is not None:
-        return got
-    _batch_note(weight, 2)
-    w = weight.detach()
-    if w.dtype != torch.float32:
-        w = w.float()
-    fwd, bwd = native.conv3x3_prepare_weights_pair(w)
-    if len(_PREPARED) > 4096:
-        _PREPARED.clear()
-    _PREPARED[key] = (_weight_ref(_PREPARED, key, weight), _weight_key(weight), fwd, bwd)
-    return fwd, bwd
+    """(forward form, data-gradient form) of a 3x3 / 3x3x3 weight for the bf16 MFMA kernels (csrc/conv.hip, conv_deep.hip)."""
+    return _FORMS[2].forms(weight)
+
+
+def prepared_conv_weights_split(weight):
+    """(forward form, data-gradient form) of a 3x3 / 3x3x3 weight as fp16 hi / lo planes + row scales (fp32x3 mode)."""
+    return _FORMS[0].forms(weight)
+
+
+def prepared_upconv_weights_split(weight):
+    """The same for a transposed 2 x 2 weight (csrc/conv_split.hip, 1-tap kernels)."""
+    return _FORMS[1].forms(weight)
+
+
+def prepared_upconv_weights_bf16(weight):
+    """(forward form bf16 [4 c_up, c_in], data-gradient form bf16 [c_in, 4 c_up]) of a transposed 2 x 2 weight (csrc/upconv_bf16.hip)."""
+    return _FORMS[3].forms(weight)
 
 
 class _Conv3x3(torch.autograd.Function):
@@ -1404,29 +1429,6 @@ class _Conv3x3(torch.autograd.Function):
         if input_relu and gx is not None and not gx_masked:                               # the producer relies on it: mask here if the kernel did not
             gx = torch.ops.aten.threshold_backward(gx, x_rows, 0)
         return gx, gw, gb, None, None, None, None
-
-
-_PREPARED_SPLIT = {}
-
-
-def prepared_conv_weights_split(weight):
-    """(forward form, data-gradient form) of a 3x3 / 3x3x3 weight as fp16 hi / lo planes + row scales (fp32x3 mode), once per weight version."""
-    key = id(weight)
-    hit = _PREPARED_SPLIT.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == _weight_key(weight):
-        return hit[2], hit[3]
-    got = _batch_hit(_PREPARED_SPLIT, weight, 0)
-    if got is not None:
-        return got
-    _batch_note(weight, 0)
-    w = weight.detach()
-    if w.dtype != torch.float32:
-        w = w.float()
-    fwd, bwd = native.conv3x3_split_prepare_weights(w)
-    if len(_PREPARED_SPLIT) > 4096:
-        _PREPARED_SPLIT.clear()
-    _PREPARED_SPLIT[key] = (_weight_ref(_PREPARED_SPLIT, key, weight), _weight_key(weight), fwd, bwd)
-    return fwd, bwd
 
 
 class _Conv3x3Split(torch.autograd.Function):
@@ -1532,25 +1534,6 @@ def conv3x3_cat(a, b, conv, relu=False, premasked=False):
     return conv3x3(cat_maps((a, b), 1), conv, relu=relu, premasked=premasked)
 
 
-_PREPARED_UP = {}
-
-
-def prepared_upconv_weights_split(weight):
-    key = id(weight)
-    hit = _PREPARED_UP.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == _weight_key(weight):
-        return hit[2], hit[3]
-    got = _batch_hit(_PREPARED_UP, weight, 1)
-    if got is not None:
-        return got
-    _batch_note(weight, 1)
-    fwd, bwd = native.upconv2x2_split_prepare_weights(weight.detach())
-    if len(_PREPARED_UP) > 4096:
-        _PREPARED_UP.clear()
-    _PREPARED_UP[key] = (_weight_ref(_PREPARED_UP, key, weight), _weight_key(weight), fwd, bwd)
-    return fwd, bwd
-
-
 class _UpConv2x2Split(torch.autograd.Function):
     """nn.ConvTranspose2d(kernel 2, stride 2) on fp32 channels-last rows in the fp32x3 mode (csrc/conv_split.hip, 1-tap kernels):
     [n,h,w,c_in] -> [n,2h,2w,c_up]."""
@@ -1580,26 +1563,6 @@ class _UpConv2x2Split(torch.autograd.Function):
             gw = gw.to(weight.dtype)
             gb = gb if ctx.has_bias and ctx.needs_input_grad[2] else None
         return gx, gw, gb
-
-
-_PREPARED_UPB = {}
-
-
-def prepared_upconv_weights_bf16(weight):
-    """(forward form bf16 [4 c_up, c_in], data-gradient form bf16 [c_in, 4 c_up]) of a transposed 2 x 2 weight (csrc/upconv_bf16.hip)."""
-    key = id(weight)
-    hit = _PREPARED_UPB.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == _weight_key(weight):
-        return hit[2], hit[3]
-    got = _batch_hit(_PREPARED_UPB, weight, 3)
-    if got is not None:
-        return got
-    _batch_note(weight, 3)
-    fwd, bwd = native.upconv2x2_bf16_prepare_weights(weight.detach())
-    if len(_PREPARED_UPB) > 4096:
-        _PREPARED_UPB.clear()
-    _PREPARED_UPB[key] = (_weight_ref(_PREPARED_UPB, key, weight), _weight_key(weight), fwd, bwd)
-    return fwd, bwd
 
 
 def _upconv_bf16_backward(ctx, gy, x_rows, weight):

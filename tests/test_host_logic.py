@@ -111,13 +111,50 @@ def test_prepared_weight_copies_are_keyed_on_the_weight_epoch_too():
     assert ops._WEIGHT_EPOCH == e + 1
     # an entry goes with its weight (no device copies of dead parameters until the 4096-entry sweep)
     import gc
-    cache = {}
+    cache = ops._PreparedForms(0, lambda w: (None, None))
     w2 = torch.nn.Parameter(torch.randn(2, 2, 3, 3))
-    cache[id(w2)] = (ops._weight_ref(cache, id(w2), w2), ops._weight_key(w2), None, None)
-    assert len(cache) == 1
+    cache.forms(w2)
+    assert len(cache.entries) == 1
     del w2
     gc.collect()
-    assert len(cache) == 0
+    assert len(cache.entries) == 0
+
+
+def test_prepared_forms_cache_prepares_once_per_version_and_epoch():
+    """ops._PreparedForms, the one cache behind the four ops.prepared_*_weights*: a weight's forms are prepared once and handed out again until the
+    weight is written in place (version) or weights_may_have_changed() is called (epoch); more live weights than the 4096-entry sweep allows never
+    leave more than 4096 + 1 entries and never get another weight's forms.  CPU parameters: the batched refresh only ever notes CUDA weights."""
+    from pcaccumulation_amd import ops
+    calls = []
+
+    def prepare(w):
+        calls.append(w)
+        return ('fwd', len(calls)), ('bwd', len(calls))
+
+    cache = ops._PreparedForms(0, prepare)
+    w = torch.nn.Parameter(torch.randn(4, 4, 3, 3))
+    fwd, bwd = cache.forms(w)
+    assert len(calls) == 1 and calls[0] is w
+    again = cache.forms(w)
+    assert again[0] is fwd and again[1] is bwd and len(calls) == 1
+    with torch.no_grad():
+        w.add_(1.0)                                             # a version bump
+    fwd2, bwd2 = cache.forms(w)
+    assert len(calls) == 2 and fwd2 is not fwd and cache.forms(w)[0] is fwd2 and len(calls) == 2
+    ops.weights_may_have_changed()                              # what a fused optimizer's step leaves as the only trace
+    fwd3, _ = cache.forms(w)
+    assert len(calls) == 3 and fwd3 is not fwd2 and cache.forms(w)[0] is fwd3 and len(calls) == 3
+    assert len(cache.entries) == 1 and not ops._BATCH_SEEN.get((id(w), 0))
+    many = [torch.nn.Parameter(torch.zeros(1)) for _ in range(4097)]
+    del calls[:]
+    forms = []
+    for p in many:
+        forms.append(cache.forms(p))
+        assert len(cache.entries) <= 4096 + 1
+    assert len(calls) == 4097 and all(a is b for a, b in zip(calls, many))
+    assert len({f[0] for f in forms}) == 4097                   # every weight its own forms
+    assert cache.forms(many[-1])[0] is forms[-1][0] and len(calls) == 4097      # prepared after the sweep: still held
+    assert cache.forms(many[0])[0] is not forms[0][0] and calls[-1] is many[0]   # swept: prepared again, for itself
 
 
 
