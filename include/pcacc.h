@@ -669,6 +669,49 @@ int pcacc_accum_register(const float *points, int64_t n, const uint8_t *moving, 
                          int32_t *out_status, int32_t *out_correspondences, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C7. Rays through the accumulated scene cloud: for every voxel of a map, the number of measured laser rays that pass straight through it -- the
+ * geometric (visibility) signal beside the network's per-point moving flag: a voxel that was occupied and that later rays pierce was not static.
+ * Replaces the copy of every scan and of up to 8 M keys to the host and a ray cast there.  Removes no row, keeps no free-space map and
+ * does not modify the map's records.
+ * Inputs
+ *   points [n,3] f32, 0 <= n <= 2^30          the scan's points (scan frame);  moving [n] u8 or NULL (non-zero = predicted moving)
+ *   origins [S,3] f64, S >= 1                 sensor positions (scan frame);  origin_index [n] i32 or NULL (= all 0): the row of a point's origin
+ *   pose [4,4] f64                            scan-to-world, rows 0-2 are read; NULL = identity
+ *   voxel_size                                of the map;  margin >= 0, finite;  max_range: < 0 = none;  use_stamp, stamp;  max_steps in [1, 2^16]
+ *   keys, stamps, capacity, m                 the first m rows of a map, as for pcacc_accum_extract
+ * Per ray, all float64 with no FMA contraction, only + - * / and sqrt, in the order csrc/accum_pierce.h writes down and no other:
+ *   End points: e = pose . p, o = pose . origin with C4's transform ((r0 x + r1 y) + r2 z) + t.  The ray is DROPPED when origin_index lies
+ *   outside [0, S) or a coordinate w of o or e is not finite, has |w| >= 32768 or floor(w / voxel_size) outside [-2^20, 2^20): it is never
+ *   clamped and forms no key and no address.
+ *   Eligibility (after the drop rule): a point flagged moving is SKIPPED (the network has moved it: its ray is no measured ray).
+ *   d = e - o, L = sqrt((d_x^2 + d_y^2) + d_z^2), t_end = 1 - margin / L, with a max_range t_end = min(t_end, max_range / L);
+ *   !(L > 0) or !(t_end > 0): SKIPPED.  The margin keeps a ray away from the surface it measured.  Every other ray is WALKED.
+ *   Walk: i_a = floor(o_a / voxel_size); visit i; for every axis with d_a != 0, b_a = double(i_a + (d_a > 0 ? 1 : 0)) * voxel_size and
+ *   t_a = (b_a - o_a) / d_a, both afresh at every step; the smallest t_a by strict < (ties to x, then y, then z); !(t_a < t_end) ends the walk;
+ *   otherwise i_a +-= 1, and an index that leaves [-2^20, 2^20) ends the walk.  A walk that would make visit number max_steps + 1 ends instead
+ *   and the ray is TRUNCATED (the visits made stay): max_steps bounds the work of one ray.
+ *   Visit: the row of key(i) by binary search; on a hit, and with use_stamp != 0 only when t_last < stamp or t_first > stamp (the voxel was not
+ *   being filled at that time), pierced[row] += 1 and hits += 1.  Rows are not filtered by count or moving fraction.
+ * Outputs, both in/out (the call ADDS): pierced [capacity] i32;  counters [PCACC_PIERCE_COUNTERS] i64: rays walked, dropped, skipped,
+ * truncated, hits.  Everything is an integer added with integer atomics: the result is a function of the SET of rays -- not of their order,
+ * of how they were split over calls, or of the run.  No workspace is needed today (the query answers 0).
+ * Return value: PCACC_E_ARG for n outside [0, 2^30], S < 1, m outside [0, capacity], a margin that is negative or not finite, a NaN max_range,
+ * max_steps outside [1, 2^16], a voxel size that is not positive and finite or a NULL table of non-zero size; nothing is launched then.
+ * n = 0 launches nothing; m = 0 walks the rays for the counters and addresses no table.
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_PIERCE_COUNTERS 5
+#define PCACC_PIERCE_WALKED 0
+#define PCACC_PIERCE_DROPPED 1
+#define PCACC_PIERCE_SKIPPED 2
+#define PCACC_PIERCE_TRUNCATED 3
+#define PCACC_PIERCE_HITS 4
+int pcacc_accum_pierce_workspace_bytes(int64_t n, int64_t m, size_t *bytes /*host*/);
+int pcacc_accum_pierce(const float *points, int64_t n, const uint8_t *moving, const double *origins, int64_t n_origins,
+                       const int32_t *origin_index, const double *pose, double voxel_size, double margin, double max_range,
+                       int32_t use_stamp, int32_t stamp, int32_t max_steps, const int64_t *keys, const int32_t *stamps, int64_t capacity,
+                       int64_t m, int32_t *pierced, int64_t *counters, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

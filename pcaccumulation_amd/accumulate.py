@@ -9,8 +9,10 @@ coordinate sums), so the map does not depend on the order of the points, on the 
     for k, (results, input_dict, pose) in enumerate(windows):
         if k:                                                    # refine the (drifting) pose against the map so far: C6, section 9e
             pose = m.register_results(results, input_dict, init_pose=pose, min_count=2, max_moving_fraction=0.0)['pose']
+            m.see_through_results(results, input_dict, pose=pose, stamp=k)    # count the rays that pass through the map so far: C7, section 9f
         m.add_results(results, input_dict, pose=pose, stamp=k)
     static = m.extract(min_count=2, max_moving_fraction=0.0)     # dict of device tensors
+    keep = m.pierced(min_count=2, max_moving_fraction=0.0) < 2   # rows aligned with `static`: False where later rays went straight through the voxel
     nrm = m.normals(radius=1, min_count=2, max_moving_fraction=0.0, viewpoints=sensor_positions)   # rows aligned with `static` (C5, section 9d)
     m.save_ply('scene.ply', min_count=2, max_moving_fraction=0.0, viewpoints=sensor_positions)
 
@@ -46,6 +48,7 @@ class AccumulatedCloud(object):
         self._cur = self._alt = self._state = None           # device memory is taken at the first add
         self._n = 0
         self._dropped = 0
+        self._pierced = self._pierce_counters = None          # the sidecar of see_through: taken at its first call
 
     # ---- state -------------------------------------------------------------------------------------------------------------------------
     @property
@@ -66,6 +69,7 @@ class AccumulatedCloud(object):
 
     def clear(self):
         self._n = self._dropped = 0
+        self._pierced = self._pierce_counters = None
         if self._state is not None:
             self._state.zero_()
 
@@ -119,6 +123,8 @@ class AccumulatedCloud(object):
                 out_cap = min(2 * out_cap, native.ACCUM_MAX_CAPACITY)
         self._cur, self._alt = self._alt, self._cur
         self.capacity = out_cap
+        if self._pierced is not None:                              # carry the sidecar: the old map sits untouched in self._alt
+            self._pierced = self._carry(self._pierced, self._alt[0], self._n, self._cur[0], state[native.ACCUM_NUM_VOXELS])
         self._n = state[native.ACCUM_NUM_VOXELS]
         self._dropped = state[native.ACCUM_DROPPED]
         return self
@@ -142,6 +148,15 @@ class AccumulatedCloud(object):
         if n_batches != 1:
             raise ValueError('add_results: %d samples in the batch need one pose per sample, [B,4,4]' % n_batches)
         return self.add(points, pose, moving, stamp)
+
+    @staticmethod
+    def _carry(pierced, old_keys, n_old, new_keys, n_new):
+        """The sidecar of the merged map: every old key is present among the new ones and keys are below 2^63, so int64 order is key order and
+        searchsorted names the new row of every old row.  New voxels start at 0."""
+        out = torch.zeros((new_keys.shape[0],), dtype=torch.int32, device=pierced.device)
+        if n_old:
+            out[torch.searchsorted(new_keys[:n_new], old_keys[:n_old])] = pierced[:n_old]
+        return out
 
     # ---- extract -----------------------------------------------------------------------------------------------------------------------
     def extract(self, min_count=1, max_moving_fraction=None):
@@ -228,12 +243,88 @@ class AccumulatedCloud(object):
             raise ValueError('register_results: one sample per batch, got %d' % n_batches)
         return self.register(results['rec_est'], init_pose, results['mos_est'].argmax(1) == 1, **kw)
 
+    # ---- see through -------------------------------------------------------------------------------------------------------------------
+    def see_through(self, points, origins, origin_index=None, pose=None, moving=None, stamp=None, margin=None, max_range=None, max_steps=4096):
+        """Count, for every voxel of the map, the measured rays of a scan that pass straight through it (include/pcacc.h C7): a voxel that was occupied
+        and that later rays pierce was not static, whatever `moving` said when it was filled.  The map's records are not modified.
+        points [n,3] f32 (device, scan frame); origins [3] or [S,3] (tensor or array, scan frame): sensor positions; origin_index [n] integers (device;
+        None = row 0): the origin of every point; pose [4,4] scan-to-world (None = identity); moving [n] (non-zero = predicted moving: the network
+        has moved the point, its ray is skipped); stamp: with one, a voxel counts only when t_last < stamp or t_first > stamp (it was not being filled
+        at that time); margin (None = 2 voxel_size): the ray stops this far in front of the point it measured; max_range: rays are cut there;
+        max_steps in [1, 2^16]: the most voxels one ray visits.
+        Adds to a sidecar, int32 per row of the map, that add() carries along, and -> the counters (rays walked, dropped, skipped, truncated, hits)
+        as one int64 device tensor, cumulative since clear().  Nothing is read back."""
+        if not torch.is_tensor(points) or not points.is_cuda:
+            raise native.NativeError('see_through: points must be a tensor on the GPU; the HIP path has no CPU fallback')
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError('points must be [n,3], got %s' % (tuple(points.shape),))
+        n = points.shape[0]
+        if n > native.ACCUM_MAX_POINTS:
+            raise ValueError('at most 2^30 points per see_through, got %d' % n)
+        for name, t in (('moving', moving), ('origin_index', origin_index)):
+            if t is not None:
+                if not torch.is_tensor(t) or not t.is_cuda:
+                    raise native.NativeError('see_through: %s must live on the GPU' % name)
+                if tuple(t.shape) != (n,):
+                    raise ValueError('%s must be [n], got %s' % (name, tuple(t.shape)))
+        if not torch.is_tensor(origins):
+            origins = torch.from_numpy(np.ascontiguousarray(origins, dtype=np.float64))
+        if origins.dim() == 1:
+            origins = origins.reshape(1, -1)
+        if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape[0] < 1:
+            raise ValueError('origins must be [3] or [S,3] with S >= 1, got %s' % (tuple(origins.shape),))
+        margin = 2.0 * self.voxel_size if margin is None else float(margin)
+        if not (margin >= 0.0 and np.isfinite(margin)):
+            raise ValueError('margin must be a finite number >= 0, got %r' % margin)
+        if max_range is not None and not float(max_range) >= 0.0:
+            raise ValueError('max_range must be >= 0 or None, got %r' % max_range)
+        if not 1 <= int(max_steps) <= native.PIERCE_MAX_STEPS:
+            raise ValueError('max_steps must lie in [1, 2^16], got %r' % max_steps)
+        pose = self._pose(pose)
+        self._ensure()
+        if self._pierced is None:
+            self._pierced = torch.zeros((self.capacity,), dtype=torch.int32, device=self.device)
+            self._pierce_counters = torch.zeros((native.PIERCE_COUNTERS,), dtype=torch.int64, device=self.device)
+        native.accum_pierce(points.detach().float().contiguous(), (moving != 0).to(torch.uint8).contiguous() if moving is not None else None,
+                            origins.to(device=self.device, dtype=torch.float64).contiguous(),
+                            # the entry point takes int32 rows: a row outside [0, S) stays outside after the cast
+                            origin_index.clamp(-1, origins.shape[0]).to(torch.int32).contiguous() if origin_index is not None else None, pose, self.voxel_size, margin,
+                            max_range, stamp, int(max_steps), self._cur, self._n, self._pierced, self._pierce_counters)
+        return self._pierce_counters.clone()
+
+    def see_through_results(self, results, input_dict, pose=None, sensor_offset=(0, 0, 0), **kw):
+        """see_through() of a test / val-mode forward: the points are results['rec_est'] with results['mos_est'].argmax(1) == 1 as `moving`, the origin of
+        a point is the sensor position of its frame (input_dict['time_indice'][:, 1]) in the anchor frame, results['ego_motion_est'][0, t] applied to
+        sensor_offset (the sensor in its own frame).  One sample per batch."""
+        batch = input_dict['time_indice'][:, 0]
+        n_batches = results.get('_n_batches')
+        if n_batches is None:
+            n_batches = int(batch.max()) + 1 if batch.numel() else 1
+        if n_batches != 1:
+            raise ValueError('see_through_results: one sample per batch, got %d' % n_batches)
+        ego = results['ego_motion_est'][0].detach().to(torch.float64)                       # [T,4,4]
+        sx, sy, sz = (float(v) for v in sensor_offset)
+        origins = ((ego[:, :3, 0] * sx + ego[:, :3, 1] * sy) + ego[:, :3, 2] * sz) + ego[:, :3, 3]
+        return self.see_through(results['rec_est'], origins, input_dict['time_indice'][:, 1], pose, results['mos_est'].argmax(1) == 1, **kw)
+
+    def pierced(self, min_count=1, max_moving_fraction=None):
+        """[V] int32: the rays see_through counted through every voxel that extract(min_count, max_moving_fraction) returns, row for row; all zeros before
+        any see_through.  A key join: extract's coords -> keys -> their rows in the map."""
+        coords = self.extract(min_count, max_moving_fraction)['coords'].to(torch.int64)
+        if self._pierced is None or coords.shape[0] == 0:
+            return torch.zeros((coords.shape[0],), dtype=torch.int32, device=self.device)
+        keys = ((coords[:, 0] + native.ACCUM_IDX_BIAS) << 42) | ((coords[:, 1] + native.ACCUM_IDX_BIAS) << 21) | (coords[:, 2] + native.ACCUM_IDX_BIAS)
+        return self._pierced[torch.searchsorted(self._cur[0][:self._n], keys)]
+
     def save_ply(self, path, normals=True, min_count=1, max_moving_fraction=None, **normal_args):
         """extract(min_count, max_moving_fraction) as a binary PLY: x y z, with normals=True nx ny nz of normals(**normal_args) under the same filter
-        (rows without a valid normal are kept, with a zero normal), then count, moving, t_first, t_last."""
+        (rows without a valid normal are kept, with a zero normal), then count, moving, t_first, t_last and, once see_through has run, pierced."""
         cloud = self.extract(min_count, max_moving_fraction)
         nrm = self.normals(min_count=min_count, max_moving_fraction=max_moving_fraction, **normal_args)['normals'] if normals else None
-        write_ply(path, cloud['points'], nrm, [(k, cloud[k]) for k in ('count', 'moving', 't_first', 't_last')])
+        fields = [(k, cloud[k]) for k in ('count', 'moving', 't_first', 't_last')]
+        if self._pierced is not None:
+            fields.append(('pierced', self.pierced(min_count, max_moving_fraction)))
+        write_ply(path, cloud['points'], nrm, fields)
 
     # ---- persistence -------------------------------------------------------------------------------------------------------------------
     def records(self):
@@ -245,19 +336,27 @@ class AccumulatedCloud(object):
 
     def save(self, path):
         keys, acc, stamps = self.records()
+        extra = {}
+        if self._pierced is not None:                              # a map that was never pierced saves what it always saved
+            extra = {'pierced': self._pierced[:self._n].cpu().numpy(), 'pierce_counters': self._pierce_counters.cpu().numpy()}
         with open(path, 'wb') as f:
-            np.savez(f, keys=keys, acc=acc, stamps=stamps, voxel_size=np.float64(self.voxel_size), dropped=np.int64(self._dropped))
+            np.savez(f, keys=keys, acc=acc, stamps=stamps, voxel_size=np.float64(self.voxel_size), dropped=np.int64(self._dropped), **extra)
 
     @classmethod
     def load(cls, path, device='cuda'):
         with np.load(path, allow_pickle=False) as z:
             keys, acc, stamps = z['keys'], z['acc'], z['stamps']
             voxel_size, dropped = float(z['voxel_size']), int(z['dropped'])
+            pierced = z['pierced'] if 'pierced' in z.files else None
+            counters = z['pierce_counters'] if 'pierce_counters' in z.files else None
         m = keys.shape[0]
         if keys.dtype != np.int64 or acc.dtype != np.int64 or stamps.dtype != np.int32 or acc.shape != (native.ACCUM_FIELDS, m) or stamps.shape != (2, m):
             raise ValueError('%s does not hold the records of an AccumulatedCloud' % path)
         if m and (np.any(keys[1:] <= keys[:-1]) or keys[0] < 0):
             raise ValueError('%s: the keys are not ascending' % path)
+        if (pierced is None) != (counters is None) or (pierced is not None and (pierced.dtype != np.int32 or pierced.shape != (m,) or counters.dtype != np.int64
+                                                                                 or counters.shape != (native.PIERCE_COUNTERS,))):
+            raise ValueError('%s does not hold the ray counts of an AccumulatedCloud' % path)
         capacity = 64
         while capacity < m:
             capacity *= 2
@@ -271,6 +370,10 @@ class AccumulatedCloud(object):
         host[native.ACCUM_NUM_VOXELS], host[native.ACCUM_DROPPED] = m, dropped
         self._state.copy_(torch.tensor(host, dtype=torch.int64))
         self._n, self._dropped = m, dropped
+        if pierced is not None:
+            self._pierced = torch.zeros((capacity,), dtype=torch.int32, device=self.device)
+            self._pierced[:m] = torch.from_numpy(pierced).to(self.device)
+            self._pierce_counters = torch.from_numpy(counters).to(self.device)
         return self
 
 

@@ -686,6 +686,7 @@ ACCUM_STATE_WORDS, ACCUM_FIELDS = 8, 5
 ACCUM_NUM_VOXELS, ACCUM_DROPPED, ACCUM_STATUS, ACCUM_NEEDED, ACCUM_WINDOW_VOXELS, ACCUM_WINDOW_DROPPED = 0, 1, 2, 3, 4, 5
 ACCUM_OK, ACCUM_TOO_SMALL, ACCUM_BAD_STATE = 0, 1, 2
 ACCUM_MAX_POINTS = ACCUM_MAX_CAPACITY = 1 << 30
+ACCUM_IDX_BIAS = 1 << 20                    # key of voxel (x, y, z): (x + 2^20) << 42 | (y + 2^20) << 21 | (z + 2^20)
 
 
 def _accum_tables(tables, what):
@@ -801,6 +802,39 @@ def accum_register(points, moving, init_pose, voxel_size, max_distance, max_iter
                                       _dev(pose), _dev(stats[0:1]), _dev(stats[1:2]), _dev(words[0:1]), _dev(words[1:2]), _dev(words[2:3]),
                                       _dev(ws), ws.numel(), _stream()), 'accum_register')
     return pose, stats[0], stats[1], words[0], words[1], words[2]
+
+
+PIERCE_COUNTERS, PIERCE_MAX_STEPS = 5, 1 << 16
+PIERCE_WALKED, PIERCE_DROPPED, PIERCE_SKIPPED, PIERCE_TRUNCATED, PIERCE_HITS = 0, 1, 2, 3, 4
+
+
+def accum_pierce(points, moving, origins, origin_index, pose, voxel_size, margin, max_range, stamp, max_steps, tables, m, pierced, counters):
+    """The rays origin -> point through the first m rows of a map; see include/pcacc.h (C7).  points [n,3] f32, moving [n] u8 or None, origins [S,3] f64,
+    origin_index [n] i32 or None (all 0), pose [4,4] f64 or None, max_range / stamp None = none.  ADDS to pierced [cap] i32 and counters [5] i64
+    (walked, dropped, skipped, truncated, hits) on the device; nothing is read back."""
+    keys, _, stamps, cap = _accum_tables(tables, 'accum_pierce')
+    n, m = points.shape[0], int(m)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise NativeError('accum_pierce: points must be [n,3], got %s' % (tuple(points.shape),))
+    if moving is not None and tuple(moving.shape) != (n,):
+        raise NativeError('accum_pierce: moving must be [n], got %s' % (tuple(moving.shape),))
+    if origins.dim() != 2 or origins.shape[1] != 3:
+        raise NativeError('accum_pierce: origins must be [S,3], got %s' % (tuple(origins.shape),))
+    if origin_index is not None and tuple(origin_index.shape) != (n,):
+        raise NativeError('accum_pierce: origin_index must be [n], got %s' % (tuple(origin_index.shape),))
+    if pose is not None and tuple(pose.shape) != (4, 4):
+        raise NativeError('accum_pierce: pose must be [4,4], got %s' % (tuple(pose.shape),))
+    if tuple(pierced.shape) != (cap,) or tuple(counters.shape) != (PIERCE_COUNTERS,):
+        raise NativeError('accum_pierce: pierced [cap] and counters [%d] expected, got %s %s' % (PIERCE_COUNTERS, tuple(pierced.shape), tuple(counters.shape)))
+    pts = _dev(points, torch.float32, 'points')
+    ws = _workspace(lib().pcacc_accum_pierce_workspace_bytes, points.device, n, m)
+    _check(lib().pcacc_accum_pierce(pts if n else None, n, _dev(moving, torch.uint8, 'moving') if moving is not None and n else None,
+                                    _dev(origins, torch.float64, 'origins') if origins.shape[0] else None, origins.shape[0],
+                                    _dev(origin_index, torch.int32, 'origin_index') if origin_index is not None and n else None,
+                                    _dev(pose, torch.float64, 'pose') if pose is not None else None, float(voxel_size), float(margin),
+                                    -1.0 if max_range is None else float(max_range), 0 if stamp is None else 1, 0 if stamp is None else int(stamp),
+                                    int(max_steps), keys, stamps, cap, m, _dev(pierced, torch.int32, 'pierced'), _dev(counters, torch.int64, 'counters'),
+                                    _dev(ws), ws.numel(), _stream()), 'accum_pierce')
 
 
 def conv3x3_supported(c_in, c_out):

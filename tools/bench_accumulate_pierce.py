@@ -1,0 +1,153 @@
+"""Time the ray count of the accumulated scene cloud (include/pcacc.h C7, AccumulatedCloud.see_through) on the 40-window drifting scene of
+tools/bench_accumulate.py (5 x 160 k points per window, 0.1 m, the sensor 1.8 m above the window's origin) and, beside it on the same machine and
+inputs, what a user does without it: the copy of the scan and of the keys to the host and a ray cast there.
+  GPU leg    every window runs see_through(stamp=k) against the map of the windows before it, then add(stamp=k); device events around each call, one
+             warm-up; once without a max_range and once at --max-range; max_steps 4096.  The same scene once more with add alone (no sidecar: the
+             add of the revision before C7), for the cost of carrying the sidecar inside add.
+  host leg   a sub-sample of the last window's rays: the walk of tests/accumulate_pierce_reference.py in plain Python, the rows by np.searchsorted in
+             the copied keys.  It also gives the visits per ray (the kernel counts hits, not visits), and its hits are compared with the kernel's on
+             the same rays.
+The windows of this scene are INDEPENDENT random clouds (synthetic.make_sequence draws range points along the beams of a sensor, not surfaces): the
+figures give sizes and memory behaviour, not a ghost-removal rate (tests/test_accumulate_pierce.py has the scene with a known ghost).
+Results go to --out.  Nothing is gated on them.
+Usage: python tools/bench_accumulate_pierce.py [--windows 40] [--max-range 30] [--sample 2000] [--no-baseline] [--out profiles/accum_pierce_bench.txt]"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+
+SENSOR = np.array([[0.0, 0.0, 1.8]])                                             # synthetic.make_sequence: the beams start here
+
+
+def timed(torch, fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1), out
+
+
+def stats(t):
+    return 'median %.2f ms, min %.2f, max %.2f' % (float(np.median(t)), min(t), max(t))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--windows', type=int, default=40)
+    ap.add_argument('--frames', type=int, default=5)
+    ap.add_argument('--pts-per-frame', type=int, default=160000)
+    ap.add_argument('--voxel', type=float, default=0.1)
+    ap.add_argument('--max-range', type=float, default=30.0)
+    ap.add_argument('--max-steps', type=int, default=4096)
+    ap.add_argument('--sample', type=int, default=2000)
+    ap.add_argument('--no-baseline', action='store_true')
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'accum_pierce_bench.txt'))
+    a = ap.parse_args()
+    import torch
+    from bench_accumulate import drift
+    from pcaccumulation_amd.accumulate import AccumulatedCloud
+    from pcaccumulation_amd.config import default_config
+    from pcaccumulation_amd.synthetic import make_sequence
+    dev = torch.device('cuda:0')
+    cfg = default_config('waymo', 'test', n_sweeps=a.frames)
+    lines = ['tools/bench_accumulate_pierce.py --windows %d --frames %d --pts-per-frame %d --voxel %g --max-range %g --max-steps %d   (%s; GPU: device events '
+             'around each call, one warm-up; host: perf_counter)' % (a.windows, a.frames, a.pts_per_frame, a.voxel, a.max_range, a.max_steps,
+                                                                      torch.cuda.get_device_name(0))]
+
+    def emit(line):
+        lines.append(line)
+        print(line, flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:                                              # rewritten line by line: a run that is cut short leaves what it measured
+            f.write('\n'.join(lines) + '\n')
+
+    rng = np.random.RandomState(0)
+    windows = []
+    for k in range(a.windows):
+        s = make_sequence(500 + k, a.frames, a.pts_per_frame, cfg, mode='lidar_scan')
+        pts = np.ascontiguousarray(s['input_points'][:, :3], np.float32)
+        windows.append((torch.from_numpy(pts).to(dev), torch.from_numpy(rng.rand(pts.shape[0]) < 0.1).to(dev), drift(k)))
+    n = windows[0][0].shape[0]
+    warm = AccumulatedCloud(a.voxel, dev, 1 << 20)                               # warm-up: code objects, allocator
+    warm.add(windows[0][0], windows[0][2], windows[0][1], 0)
+    warm.see_through(windows[0][0], SENSOR, pose=windows[0][2], moving=windows[0][1], stamp=1, max_steps=a.max_steps)
+    warm.add(windows[0][0], windows[0][2], windows[0][1], 1)
+    del warm
+    torch.cuda.synchronize()
+
+    # add alone: no sidecar, the code path of the revision before C7
+    plain = AccumulatedCloud(a.voxel, dev, 1 << 20)
+    t_add_plain = [timed(torch, lambda: plain.add(pts, T, mv, k))[0] for k, (pts, mv, T) in enumerate(windows)]
+    del plain
+    last = None
+    for max_range in (None, a.max_range):
+        m = AccumulatedCloud(a.voxel, dev, 1 << 20)
+        t_see, t_add, sizes = [], [], []
+        for k, (pts, mv, T) in enumerate(windows):
+            sizes.append(m.num_voxels)
+            t_see.append(timed(torch, lambda: m.see_through(pts, SENSOR, pose=T, moving=mv, stamp=k, max_range=max_range, max_steps=a.max_steps))[0])
+            t_add.append(timed(torch, lambda: m.add(pts, T, mv, k))[0])
+        c = m._pierce_counters.tolist()
+        emit('GPU, max_range %s: %d see_through calls of %d rays against a map of %d .. %d voxels: %s; rays walked %d, dropped %d, skipped %d, truncated %d, '
+             'hits %d (%.2f per walked ray); voxels with a count >= 1: %d of %d'
+             % (max_range, len(t_see), n, sizes[0], sizes[-1], stats(t_see[1:]), c[0], c[1], c[2], c[3], c[4], c[4] / max(c[0], 1),
+                int((m.pierced() > 0).sum()), m.num_voxels))
+        q = max(1, len(t_see) // 4)
+        for lo in range(0, len(t_see), q):
+            emit('  windows %2d-%2d: map %8d -> %8d voxels, see_through median %.2f ms, add with the carry median %.2f ms, add alone median %.2f ms'
+                 % (lo, min(lo + q, len(t_see)) - 1, sizes[lo], sizes[min(lo + q, len(t_see)) - 1], float(np.median(t_see[lo:lo + q])),
+                    float(np.median(t_add[lo:lo + q])), float(np.median(t_add_plain[lo:lo + q]))))
+        emit('  add with the sidecar carry (zero-fill, searchsorted of the old keys, scatter): %s; add alone on the same scene: %s'
+             % (stats(t_add[1:]), stats(t_add_plain[1:])))
+        if max_range is None:
+            last = m
+    m = last
+    if not a.no_baseline:
+        baseline(a, torch, m, windows[-1], emit)
+    emit('not measured: the split of a call between the walk arithmetic, the searches and the atomics; achieved bandwidth; any counter run')
+
+
+def baseline(a, torch, m, window, emit):
+    import accumulate_pierce_reference as pref
+    pts, mv, T = window
+    t0 = time.perf_counter()
+    scan, flag = pts.cpu().numpy(), mv.cpu().numpy()                             # the copies a user makes today
+    keys = m.records()[0]
+    t_copy = time.perf_counter() - t0
+    pick = np.random.RandomState(1).choice(scan.shape[0], min(a.sample, scan.shape[0]), replace=False)
+    pick.sort()
+    Tl = [[float(v) for v in row] for row in T]
+    t0 = time.perf_counter()
+    visits = hits = walked = 0
+    for i in pick:
+        status, _, visited, _ = pref.ray(Tl, scan[i], SENSOR[0], bool(flag[i]), a.voxel, 2.0 * a.voxel, None, a.max_steps)
+        if status != pref.WALKED:
+            continue
+        walked += 1
+        visits += len(visited)
+        v = np.array(visited, np.int64) + pref.BIAS
+        k = (v[:, 0] << 42) | (v[:, 1] << 21) | v[:, 2]
+        pos = np.minimum(np.searchsorted(keys, k), keys.shape[0] - 1)
+        hits += int((keys[pos] == k).sum())
+    t_host = time.perf_counter() - t0
+    before = m._pierce_counters.clone()
+    sel = torch.from_numpy(pick).to(pts.device)
+    t_gpu, after = timed(torch, lambda: m.see_through(pts[sel], SENSOR, pose=T, moving=mv[sel], max_steps=a.max_steps))
+    got = (after - before).tolist()
+    emit('host, a sub-sample of %d rays of the last window (%d walked): copy of the scan (%d points) and of %d keys %.2f s; the walk in plain Python and '
+         'np.searchsorted %.2f s = %.2f ms per ray (%.0f s for the whole window at that rate); %.1f visits per walked ray, %d hits; the kernel on the same '
+         'rays: %d walked, %d hits (%s), %.2f ms for the call'
+         % (pick.shape[0], walked, scan.shape[0], keys.shape[0], t_copy, t_host, 1e3 * t_host / pick.shape[0], t_host / pick.shape[0] * scan.shape[0],
+            visits / max(walked, 1), hits, got[0], got[4], 'equal' if (got[0], got[4]) == (walked, hits) else 'DIFFERENT', t_gpu))
+
+
+if __name__ == '__main__':
+    main()
