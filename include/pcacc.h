@@ -712,6 +712,51 @@ int pcacc_accum_pierce(const float *points, int64_t n, const uint8_t *moving, co
                        int64_t m, int32_t *pierced, int64_t *counters, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C8. Removing rows from the accumulated scene cloud: voxels that rays pierced, that nothing has touched for a while, that lie outside a box or
+ * that have too few neighbours leave the map, on the device, by a predicate on the records.  Replaces the copy of the records to the host, a
+ * mask there and a load.  Merges no maps, shrinks no table, is not iterated and returns no removed row.
+ * Inputs
+ *   in_keys, in_acc, in_stamps, in_capacity, m        the first m rows of a map, as for pcacc_accum_extract
+ *   in_pierced [in_capacity] i32 or NULL              the sidecar of pcacc_accum_pierce
+ *   min_count, use_fraction, max_moving_fraction      extract's filter
+ *   use_stamp, before_stamp;  use_box, lo_x .. hi_z (voxel indices, inclusive);  min_pierced, use_ratio, ratio;  min_neighbors, radius
+ * Stage A, per row, from that row's record alone; the tests run in this order and the first that holds is the row's reason:
+ *   FILTER    extract does not keep the row (count < min_count, count <= 0 or, when use_fraction != 0, float64(moving) / float64(count) >
+ *             max_moving_fraction or unordered)
+ *   STALE     use_stamp != 0 and t_last < before_stamp
+ *   BOX       use_box != 0 and a voxel index of the row lies outside [lo_a, hi_a]
+ *   PIERCED   min_pierced > 0, in_pierced given, p = in_pierced[row] >= min_pierced and, when use_ratio != 0, float64(p) / float64(count) > ratio
+ *             (one IEEE division, strict).  Without a sidecar no row leaves for this reason.
+ * Stage B, when min_neighbors > 0, per stage-A survivor: k = the stage-A survivors with |delta|_inf <= radius, itself included, found as C5
+ * finds neighbours (offsets that leave [-2^20, 2^20) are skipped before a key is formed).  ISOLATED iff k < min_neighbors.  One pass: k counts
+ * stage-A survivors, never stage-B survivors, so the result is a function of the map alone.
+ * Outputs
+ *   out_keys, out_acc, out_stamps, out_pierced (out_capacity rows, distinct buffers): the surviving rows in key order, every record
+ *   bit-identical to what it was; out_pierced is written iff in_pierced is given.
+ *   counters [PCACC_PRUNE_COUNTERS] i64 (written, not added to): rows kept and rows removed per reason; they sum to m.
+ *   dry_run != 0 computes only the counters: no table and no state word is written, and the out_* tables and state may be NULL.
+ *   Otherwise state[PCACC_ACCUM_NUM_VOXELS] = rows kept, on the device; every other state word is left alone.
+ * Return value: PCACC_E_ARG, and nothing is launched, for m outside [0, in_capacity], out_capacity < m (there is no "too small" path), an
+ * output table that shares memory with an input table, min_neighbors outside [0, 343], radius outside 1..3 while min_neighbors > 0, a ratio
+ * that is NaN or negative while use_ratio != 0, lo_a > hi_a or a bound outside [-2^20, 2^20) while use_box != 0, or a NULL table of non-zero
+ * size.  m = 0 writes the zero counters and launches nothing else.
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_PRUNE_COUNTERS 6
+#define PCACC_PRUNE_KEPT 0
+#define PCACC_PRUNE_FILTER 1
+#define PCACC_PRUNE_STALE 2
+#define PCACC_PRUNE_BOX 3
+#define PCACC_PRUNE_PIERCED 4
+#define PCACC_PRUNE_ISOLATED 5
+int pcacc_accum_prune_workspace_bytes(int64_t m, size_t *bytes /*host*/);
+int pcacc_accum_prune(const int64_t *in_keys, const int64_t *in_acc, const int32_t *in_stamps, const int32_t *in_pierced, int64_t in_capacity,
+                      int64_t m, int64_t min_count, int32_t use_fraction, double max_moving_fraction, int32_t use_stamp, int32_t before_stamp,
+                      int32_t use_box, int32_t lo_x, int32_t lo_y, int32_t lo_z, int32_t hi_x, int32_t hi_y, int32_t hi_z, int32_t min_pierced,
+                      int32_t use_ratio, double ratio, int32_t min_neighbors, int32_t radius, int32_t dry_run, int64_t *out_keys,
+                      int64_t *out_acc, int32_t *out_stamps, int32_t *out_pierced, int64_t out_capacity, int64_t *counters, int64_t *state,
+                      void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

@@ -11,6 +11,9 @@ coordinate sums), so the map does not depend on the order of the points, on the 
             pose = m.register_results(results, input_dict, init_pose=pose, min_count=2, max_moving_fraction=0.0)['pose']
             m.see_through_results(results, input_dict, pose=pose, stamp=k)    # count the rays that pass through the map so far: C7, section 9f
         m.add_results(results, input_dict, pose=pose, stamp=k)
+        if k % 5 == 4:                                           # every few windows, drop what rays went through, what is 20 windows old and
+            x, y, z = pose[:3, 3].tolist()                       # what lies more than 50 m from the sensor: C8, section 9g
+            m.prune(min_pierced=2, before_stamp=k - 20, box=((x - 50, y - 50, z - 50), (x + 50, y + 50, z + 50)))
     static = m.extract(min_count=2, max_moving_fraction=0.0)     # dict of device tensors
     keep = m.pierced(min_count=2, max_moving_fraction=0.0) < 2   # rows aligned with `static`: False where later rays went straight through the voxel
     nrm = m.normals(radius=1, min_count=2, max_moving_fraction=0.0, viewpoints=sensor_positions)   # rows aligned with `static` (C5, section 9d)
@@ -25,6 +28,7 @@ from . import native
 _FIELDS = ('points', 'coords', 'count', 'moving', 't_first', 't_last')
 _NORMAL_FIELDS = ('normals', 'eigenvalues', 'neighbors', 'flags')
 _REGISTER_FIELDS = ('pose', 'fitness', 'rmse', 'iterations', 'status', 'correspondences')
+_PRUNE_FIELDS = ('kept', 'filter', 'stale', 'box', 'pierced', 'isolated')
 _PLY_TYPES = {'float32': 'float', 'float64': 'double', 'int8': 'char', 'uint8': 'uchar', 'int16': 'short', 'uint16': 'ushort', 'int32': 'int',
               'uint32': 'uint'}
 
@@ -315,6 +319,76 @@ class AccumulatedCloud(object):
             return torch.zeros((coords.shape[0],), dtype=torch.int32, device=self.device)
         keys = ((coords[:, 0] + native.ACCUM_IDX_BIAS) << 42) | ((coords[:, 1] + native.ACCUM_IDX_BIAS) << 21) | (coords[:, 2] + native.ACCUM_IDX_BIAS)
         return self._pierced[torch.searchsorted(self._cur[0][:self._n], keys)]
+
+    # ---- prune -------------------------------------------------------------------------------------------------------------------------
+    def _box_indices(self, box):
+        """(lo [3], hi [3]) in metres of the world frame -> inclusive voxel indices floor(bound / voxel_size), float64 (the map's own division),
+        clamped into the grid."""
+        try:
+            lo, hi = box
+            lo, hi = [float(v) for v in lo], [float(v) for v in hi]
+        except (TypeError, ValueError):
+            raise ValueError('box must be (lo [3], hi [3]) in metres, got %r' % (box,))
+        if len(lo) != 3 or len(hi) != 3:
+            raise ValueError('box must be (lo [3], hi [3]) in metres, got %r' % (box,))
+        if not all(np.isfinite(v) for v in lo + hi):
+            raise ValueError('box: every bound must be finite, got %r' % (box,))
+        if any(l > h for l, h in zip(lo, hi)):
+            raise ValueError('box: lo must not lie above hi, got %r' % (box,))
+        grid_lo, grid_hi = float(-native.ACCUM_IDX_BIAS), float(native.ACCUM_IDX_BIAS - 1)
+        index = lambda v: int(min(max(np.floor(np.float64(v) / np.float64(self.voxel_size)), grid_lo), grid_hi))
+        return [index(v) for v in lo], [index(v) for v in hi]
+
+    def prune(self, min_pierced=None, pierced_ratio=None, before_stamp=None, min_count=1, max_moving_fraction=None, box=None, min_neighbors=None,
+              radius=1, dry_run=False):
+        """Remove rows from the map, on the device (include/pcacc.h C8).  A row leaves for the first reason that holds:
+        filter: extract(min_count, max_moving_fraction) would not return it; stale: its last stamp is below before_stamp; box: its voxel lies outside
+        box = (lo [3], hi [3]), metres of the world frame, both faces' voxels included; pierced: see_through counted at least min_pierced rays through
+        it and, with pierced_ratio, rays / count > pierced_ratio (a wall of 1000 points outlives two grazing rays; without a see_through nothing leaves
+        for this reason).  Then, with min_neighbors, isolated: fewer than min_neighbors of the rows that are left so far lie within `radius` voxels
+        (1, 2 or 3; Chebyshev, the voxel itself included) -- one pass, not iterated.
+        The surviving records are unchanged, and extract, normals, register, pierced, save and save_ply see the pruned map.  The capacity stays.
+        -> {'kept', 'filter', 'stale', 'box', 'pierced', 'isolated'}: Python integers that sum to the rows before the call -- the one read-back.
+        dry_run=True counts and changes nothing."""
+        min_pierced = 0 if min_pierced is None else int(min_pierced)
+        min_neighbors = 0 if min_neighbors is None else int(min_neighbors)
+        radius, min_count = int(radius), int(min_count)
+        if min_pierced < 0 or min_pierced > 0x7fffffff:
+            raise ValueError('min_pierced must be None or lie in [0, 2^31), got %r' % min_pierced)
+        if pierced_ratio is not None:
+            if min_pierced < 1:
+                raise ValueError('pierced_ratio needs min_pierced >= 1')
+            if not float(pierced_ratio) >= 0.0:
+                raise ValueError('pierced_ratio must be >= 0, got %r' % pierced_ratio)
+        if before_stamp is not None and not -0x80000000 <= int(before_stamp) <= 0x7fffffff:
+            raise ValueError('before_stamp must fit 32 bits, got %r' % before_stamp)
+        if max_moving_fraction is not None and np.isnan(float(max_moving_fraction)):
+            raise ValueError('max_moving_fraction must be a number or None')
+        if not 0 <= min_neighbors <= native.PRUNE_MAX_NEIGHBORS:
+            raise ValueError('min_neighbors must be None or lie in [0, %d], got %r' % (native.PRUNE_MAX_NEIGHBORS, min_neighbors))
+        if min_neighbors and not 1 <= radius <= 3:
+            raise ValueError('radius must be 1, 2 or 3 voxels, got %r' % radius)
+        if box is not None:
+            box = self._box_indices(box)
+        self._ensure()
+        counters = torch.empty((native.PRUNE_COUNTERS,), dtype=torch.int64, device=self.device)
+        out = pierced_out = None
+        if not dry_run:
+            if self._alt is None or self._alt[0].shape[0] != self.capacity:
+                self._alt = None                                   # release before taking the tables
+                self._alt = _tables(self.capacity, self.device)
+            out = self._alt
+            if self._pierced is not None:
+                pierced_out = torch.zeros((self.capacity,), dtype=torch.int32, device=self.device)
+        native.accum_prune(self._cur, self._n, self._pierced, min_count, max_moving_fraction, before_stamp, box, min_pierced, pierced_ratio,
+                           min_neighbors, radius, dry_run, out, pierced_out, counters, None if dry_run else self._state)
+        res = dict(zip(_PRUNE_FIELDS, counters.tolist()))          # the one read-back of a prune
+        if not dry_run and self._n:                                # the map before the prune stays in self._alt, which the next add overwrites
+            self._cur, self._alt = self._alt, self._cur
+            if self._pierced is not None:
+                self._pierced = pierced_out
+            self._n = res['kept']
+        return res
 
     def save_ply(self, path, normals=True, min_count=1, max_moving_fraction=None, **normal_args):
         """extract(min_count, max_moving_fraction) as a binary PLY: x y z, with normals=True nx ny nz of normals(**normal_args) under the same filter

@@ -837,6 +837,46 @@ def accum_pierce(points, moving, origins, origin_index, pose, voxel_size, margin
                                     _dev(ws), ws.numel(), _stream()), 'accum_pierce')
 
 
+PRUNE_COUNTERS, PRUNE_MAX_NEIGHBORS = 6, 343
+PRUNE_KEPT, PRUNE_FILTER, PRUNE_STALE, PRUNE_BOX, PRUNE_PIERCED, PRUNE_ISOLATED = 0, 1, 2, 3, 4, 5
+
+
+def accum_prune(tables_in, m, pierced_in, min_count, max_moving_fraction, before_stamp, box, min_pierced, ratio, min_neighbors, radius, dry_run,
+                tables_out, pierced_out, counters, state):
+    """The first m rows of a map without the rows a predicate removes, out of place; see include/pcacc.h (C8).  pierced_in [cap] i32 or None;
+    max_moving_fraction, before_stamp, ratio None = not used; box None or (lo [3], hi [3]) integer voxel indices, inclusive; min_pierced,
+    min_neighbors 0 = not used.  tables_out = (keys, acc, stamps) and pierced_out [cap] i32 (with pierced_in), or None with dry_run; state [8] i64.
+    Writes counters [6] i64 (kept, filter, stale, box, pierced, isolated) and, unless dry_run, the tables and state[ACCUM_NUM_VOXELS]; nothing is
+    read back."""
+    ik, ia, is_, icap = _accum_tables(tables_in, 'accum_prune input')
+    if pierced_in is not None and tuple(pierced_in.shape) != (icap,):
+        raise NativeError('accum_prune: pierced_in must be [cap], got %s' % (tuple(pierced_in.shape),))
+    if tuple(counters.shape) != (PRUNE_COUNTERS,):
+        raise NativeError('accum_prune: counters must be [%d] int64' % PRUNE_COUNTERS)
+    ok = oa = os_ = op = st = None
+    ocap = icap
+    if tables_out is not None:
+        ok, oa, os_, ocap = _accum_tables(tables_out, 'accum_prune output')
+        if pierced_out is not None:
+            if tuple(pierced_out.shape) != (ocap,):
+                raise NativeError('accum_prune: pierced_out must be [cap], got %s' % (tuple(pierced_out.shape),))
+            op = _dev(pierced_out, torch.int32, 'pierced_out')
+    if state is not None:
+        if tuple(state.shape) != (ACCUM_STATE_WORDS,):
+            raise NativeError('accum_prune: state must be [%d] int64' % ACCUM_STATE_WORDS)
+        st = _dev(state, torch.int64, 'state')
+    lo, hi = ((0, 0, 0), (0, 0, 0)) if box is None else box
+    m = int(m)
+    ws = _workspace(lib().pcacc_accum_prune_workspace_bytes, tables_in[0].device, m)
+    _check(lib().pcacc_accum_prune(ik, ia, is_, _dev(pierced_in, torch.int32, 'pierced_in') if pierced_in is not None else None, icap, m, int(min_count),
+                                   0 if max_moving_fraction is None else 1, 0.0 if max_moving_fraction is None else float(max_moving_fraction),
+                                   0 if before_stamp is None else 1, 0 if before_stamp is None else int(before_stamp), 0 if box is None else 1,
+                                   int(lo[0]), int(lo[1]), int(lo[2]), int(hi[0]), int(hi[1]), int(hi[2]), int(min_pierced),
+                                   0 if ratio is None else 1, 0.0 if ratio is None else float(ratio), int(min_neighbors), int(radius),
+                                   1 if dry_run else 0, ok, oa, os_, op, ocap, _dev(counters, torch.int64, 'counters'), st, _dev(ws), ws.numel(),
+                                   _stream()), 'accum_prune')
+
+
 def conv3x3_supported(c_in, c_out):
     return c_in >= 32 and c_out >= 32 and c_in % 32 == 0 and c_out % 32 == 0
 
