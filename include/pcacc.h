@@ -757,6 +757,64 @@ int pcacc_accum_prune(const int64_t *in_keys, const int64_t *in_acc, const int32
                       void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C9. Looking a scan's points up in the accumulated scene cloud: for every point, what the map knows at that place -- the record of the point's
+ * own voxel, the nearest kept centroid among the 27 voxels around it and the signed distance to that voxel's plane.  Replaces the copy of up to
+ * 8 M centroids to the host and a KD-tree there.  Answers one nearest neighbour within one voxel, not k and not a radius; does not modify the map.
+ * Inputs
+ *   points [n,3] f32, 0 <= n <= 2^30;  pose [4,4] f64 scan-to-world, rows 0-2 are read; NULL = identity
+ *   voxel_size                of the map;  max_distance in (0, voxel_size]
+ *   keys, acc, stamps, capacity, m; min_count, use_fraction, max_moving_fraction     the map and extract's filter, as for pcacc_accum_normals
+ *   pierced [capacity] i32 or NULL                the sidecar of pcacc_accum_pierce
+ *   normals [n_rows,3] f32, flags [n_rows] u8     out_normals / out_flags of pcacc_accum_normals on this map under this filter, or both NULL
+ *   require_normal            non-zero: only rows with a valid normal are candidates (C6's candidate set); needs the tables
+ * Per point, all float64 with no FMA contraction, only + - * / and sqrt, in the order csrc/accum_query.h writes down and no other:
+ *   World: w = pose . p with C4's transform and C4's validity rule.  An invalid point gets PCACC_QUERY_INVALID and every other output at its
+ *   default: it is never clamped and forms no key and no address.
+ *   Own voxel: the map row whose key is the key of the point's voxel, if there is one: PCACC_QUERY_OCCUPIED; count, moving, t_first, t_last are
+ *   the row's, pierced the sidecar's entry (0 without a sidecar); PCACC_QUERY_KEPT iff extract's filter keeps the row.  Without a row all are 0.
+ *   Nearest kept centroid: C6's search -- the rows the filter keeps (with require_normal: that also have neither PCACC_NORMAL_FEW_NEIGHBORS nor
+ *   PCACC_NORMAL_DEGENERATE) in the 3 x 3 x 3 voxels around the point's voxel, visited in ascending key order; offsets that leave [-2^20, 2^20)
+ *   are skipped before a key is formed; d2 = (e_x e_x + e_y e_y) + e_z e_z against the float64 centroid, strict < (ties to the lowest key),
+ *   accepted iff d2 <= max_distance^2.  On a match PCACC_QUERY_MATCHED, row = the row of pcacc_accum_extract under this filter (valid until the
+ *   map changes), nearest = the float32 of the centroid (extract's point), distance = sqrt(d2).
+ *   A centroid lies within 2^-17 m of its voxel, so one outside the 27 voxels is farther than voxel_size - 2^-17 from the point: for
+ *   max_distance <= 0.9 voxel_size (voxel sizes of 1e-4 m and up) the match is the global nearest kept centroid within max_distance.  At
+ *   max_distance = voxel_size the 27-voxel search itself is the contract, as in C6.
+ *   Plane distance: with the tables and a matched row whose normal has neither flag: PCACC_QUERY_NORMAL and
+ *   plane_distance = (n_x e_x + n_y e_y) + n_z e_z, n the float32 normal widened to double, e = w - centroid: C6's residual, signed.
+ *   Defaults: row -1, nearest 0, distance and plane_distance +inf.
+ * Outputs (device, n rows each, every row written once): out_status u8 (a sum of the bits below), out_count, out_moving i64, out_t_first,
+ * out_t_last, out_pierced, out_row i32, out_nearest [n,3] f32, out_distance, out_plane_distance f64;
+ * counters [PCACC_QUERY_COUNTERS] i64 (written, not added to): points, invalid, occupied, kept, matched, with a normal, and BAD_TABLE (0 / 1).
+ * BAD_TABLE = 1: tables were given and n_rows differs from the rows the filter keeps (decided on the device): no normal table is addressed and
+ * no point is MATCHED; world and own voxel are reported as always.  Every table index is range-checked against m, n_rows and capacity.
+ * Return value: PCACC_E_ARG, and nothing is launched, for n outside [0, 2^30], m outside [0, capacity], a voxel size that is not positive and
+ * finite, a max_distance that is NaN or outside (0, voxel_size], exactly one of normals / flags, require_normal without them, n_rows outside
+ * [0, m] (or > 0 without tables), a NULL table or output of non-zero size, or a workspace that is too small.  n = 0 writes the zero counters and
+ * launches nothing else; m = 0 launches only the point kernel: every valid point gets status 0.
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_QUERY_INVALID 1
+#define PCACC_QUERY_OCCUPIED 2
+#define PCACC_QUERY_KEPT 4
+#define PCACC_QUERY_MATCHED 8
+#define PCACC_QUERY_NORMAL 16
+#define PCACC_QUERY_COUNTERS 7
+#define PCACC_QUERY_N_POINTS 0
+#define PCACC_QUERY_N_INVALID 1
+#define PCACC_QUERY_N_OCCUPIED 2
+#define PCACC_QUERY_N_KEPT 3
+#define PCACC_QUERY_N_MATCHED 4
+#define PCACC_QUERY_N_NORMAL 5
+#define PCACC_QUERY_BAD_TABLE 6
+int pcacc_accum_query_workspace_bytes(int64_t m, size_t *bytes /*host*/);
+int pcacc_accum_query(const float *points, int64_t n, const double *pose, double voxel_size, double max_distance, const int64_t *keys,
+                      const int64_t *acc, const int32_t *stamps, const int32_t *pierced, int64_t capacity, int64_t m, int64_t min_count,
+                      int32_t use_fraction, double max_moving_fraction, const float *normals, const uint8_t *flags, int64_t n_rows,
+                      int32_t require_normal, uint8_t *out_status, int64_t *out_count, int64_t *out_moving, int32_t *out_t_first,
+                      int32_t *out_t_last, int32_t *out_pierced, int32_t *out_row, float *out_nearest, double *out_distance,
+                      double *out_plane_distance, int64_t *counters, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

@@ -10,6 +10,8 @@ coordinate sums), so the map does not depend on the order of the points, on the 
         if k:                                                    # refine the (drifting) pose against the map so far: C6, section 9e
             pose = m.register_results(results, input_dict, init_pose=pose, min_count=2, max_moving_fraction=0.0)['pose']
             m.see_through_results(results, input_dict, pose=pose, stamp=k)    # count the rays that pass through the map so far: C7, section 9f
+            seen = m.query_results(results, input_dict, pose=pose, max_distance=0.05)   # per point: its voxel's record, nearest centroid: C9, section 9h
+            novelty = 1.0 - seen['counters'][native.QUERY_N_OCCUPIED] / seen['counters'][native.QUERY_N_POINTS]   # share of the window the map lacks
         m.add_results(results, input_dict, pose=pose, stamp=k)
         if k % 5 == 4:                                           # every few windows, drop what rays went through, what is 20 windows old and
             x, y, z = pose[:3, 3].tolist()                       # what lies more than 50 m from the sensor: C8, section 9g
@@ -246,6 +248,58 @@ class AccumulatedCloud(object):
         if n_batches != 1:
             raise ValueError('register_results: one sample per batch, got %d' % n_batches)
         return self.register(results['rec_est'], init_pose, results['mos_est'].argmax(1) == 1, **kw)
+
+    # ---- query -------------------------------------------------------------------------------------------------------------------------
+    def query(self, points, pose=None, max_distance=None, min_count=1, max_moving_fraction=None, normals=False, require_normal=False, radius=1,
+              min_neighbors=5, viewpoints=None, stamp_base=0):
+        """What the map knows at every point of a scan (include/pcacc.h C9).  The map is not modified.
+        points [n,3] f32 (device), pose [4,4] scan-to-world (tensor or array; None = identity), max_distance in (0, voxel_size] (None = voxel_size).
+        -> dict of device tensors, one row per point in the caller's order:
+        status [n] u8, a sum of native.QUERY_* bits: INVALID (the point is not finite or lies outside the grid: every other field at its default),
+        OCCUPIED (the map has the point's voxel), KEPT (extract(min_count, max_moving_fraction) returns that voxel), MATCHED, NORMAL;
+        count, moving [n] i64, t_first, t_last [n] i32: the record of the point's own voxel, pierced [n] i32: its see_through count (all 0 without one);
+        row [n] i32, nearest [n,3] f32, distance [n] f64: the nearest centroid extract(min_count, max_moving_fraction) returns among the 3 x 3 x 3 voxels
+        around the point, if within max_distance -- its row there (valid until the next add or prune), extract's point, the distance to the float64
+        centroid; -1, 0, +inf without a match.  For max_distance <= 0.9 voxel_size this is the nearest kept centroid of the whole map.
+        normals=True computes normals(radius, min_neighbors, ..., viewpoints, stamp_base) under the same filter, as register() does, and adds
+        plane_distance [n] f64: the signed distance of the point to the plane through the matched centroid (+inf without a valid normal there);
+        require_normal=True matches only centroids with a valid normal: register()'s correspondences.
+        counters [7] i64: points, invalid, occupied, kept, matched, with a normal, and native.QUERY_BAD_TABLE (always 0 from here).
+        Nothing is read back beyond the kept count normals() reads when normals=True."""
+        if not torch.is_tensor(points) or not points.is_cuda:
+            raise native.NativeError('query: points must be a tensor on the GPU; the HIP path has no CPU fallback')
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError('points must be [n,3], got %s' % (tuple(points.shape),))
+        n = points.shape[0]
+        if n > native.QUERY_MAX_POINTS:
+            raise ValueError('at most 2^30 points per query, got %d' % n)
+        max_distance = self.voxel_size if max_distance is None else float(max_distance)
+        if not 0.0 < max_distance <= self.voxel_size:
+            raise ValueError('max_distance must lie in (0, voxel_size = %r], got %r' % (self.voxel_size, max_distance))
+        if not 1 <= int(radius) <= 3:
+            raise ValueError('radius must be 1, 2 or 3 voxels, got %r' % radius)
+        if int(min_neighbors) < 3:
+            raise ValueError('min_neighbors must be at least 3, got %r' % min_neighbors)
+        if require_normal and not normals:
+            raise ValueError('require_normal=True needs normals=True')
+        pose = self._pose(pose)
+        self._ensure()
+        nrm = flags = None
+        if normals:
+            res = self.normals(radius, min_neighbors, min_count, max_moving_fraction, viewpoints, stamp_base)
+            nrm, flags = res['normals'], res['flags']
+        return native.accum_query(points.detach().float().contiguous(), pose, self.voxel_size, max_distance, self._cur, self._n, self._pierced, min_count,
+                                  max_moving_fraction, nrm, flags, bool(require_normal) and nrm.shape[0] > 0)   # no kept row: nothing can match
+
+    def query_results(self, results, input_dict, pose=None, **kw):
+        """query() of a test / val-mode forward: results['rec_est'].  One sample per batch."""
+        batch = input_dict['time_indice'][:, 0]
+        n_batches = results.get('_n_batches')
+        if n_batches is None:
+            n_batches = int(batch.max()) + 1 if batch.numel() else 1
+        if n_batches != 1:
+            raise ValueError('query_results: one sample per batch, got %d' % n_batches)
+        return self.query(results['rec_est'], pose, **kw)
 
     # ---- see through -------------------------------------------------------------------------------------------------------------------
     def see_through(self, points, origins, origin_index=None, pose=None, moving=None, stamp=None, margin=None, max_range=None, max_steps=4096):

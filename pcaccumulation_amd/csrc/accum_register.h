@@ -66,11 +66,13 @@ PCACC_HD bool accr_world(const double *T, const float *p, double voxel_size, dou
     return true;
 }
 
-// Output row of map row p when it is a candidate, else -1: dst[p] in [0, n_rows) and neither flag 1 nor flag 2 on it.
+// Output row of map row p when it is a candidate, else -1: dst[p] in [0, n_rows) and neither flag 1 nor flag 2 on it.  flags == NULL (C9 only): every
+// row the filter keeps is a candidate.
 PCACC_HD int64_t accr_candidate(const int *dst, const uint8_t *flags, int64_t n_rows, int64_t p)
 {
     const int64_t j = dst[p];
     if (j < 0) return -1;
+    if (!flags) return j;                                                                    // register never passes NULL
     if (accn_index(j, n_rows) < 0) return -1;
     return (flags[j] & (ACCN_FEW_NEIGHBORS | ACCN_DEGENERATE)) ? -1 : j;
 }

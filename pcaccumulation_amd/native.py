@@ -877,6 +877,59 @@ def accum_prune(tables_in, m, pierced_in, min_count, max_moving_fraction, before
                                    _stream()), 'accum_prune')
 
 
+QUERY_INVALID, QUERY_OCCUPIED, QUERY_KEPT, QUERY_MATCHED, QUERY_NORMAL = 1, 2, 4, 8, 16
+QUERY_COUNTERS = 7
+QUERY_N_POINTS, QUERY_N_INVALID, QUERY_N_OCCUPIED, QUERY_N_KEPT, QUERY_N_MATCHED, QUERY_N_NORMAL, QUERY_BAD_TABLE = 0, 1, 2, 3, 4, 5, 6
+QUERY_MAX_POINTS = 1 << 30
+QUERY_FIELDS = (('status', torch.uint8, ()), ('count', torch.int64, ()), ('moving', torch.int64, ()), ('t_first', torch.int32, ()),
+                ('t_last', torch.int32, ()), ('pierced', torch.int32, ()), ('row', torch.int32, ()), ('nearest', torch.float32, (3,)),
+                ('distance', torch.float64, ()), ('plane_distance', torch.float64, ()))
+
+
+def accum_query(points, pose, voxel_size, max_distance, tables, m, pierced, min_count, max_moving_fraction, normals, flags, require_normal,
+                out=None, counters=None):
+    """What the first m rows of a map know at every point of a scan; see include/pcacc.h (C9).  points [n,3] f32, pose [4,4] f64 or None, pierced
+    [cap] i32 or None, normals [V,3] f32 / flags [V] u8 = accum_normals' rows on this map under the same filter, or both None.  out: a dict of the
+    QUERY_FIELDS tensors to write into (None = new ones), counters [7] i64 likewise.  -> out with 'counters' added; nothing is read back."""
+    keys, acc, stamps, cap = _accum_tables(tables, 'accum_query')
+    dev = tables[0].device
+    n, m = points.shape[0], int(m)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise NativeError('accum_query: points must be [n,3], got %s' % (tuple(points.shape),))
+    if pose is not None and tuple(pose.shape) != (4, 4):
+        raise NativeError('accum_query: pose must be [4,4], got %s' % (tuple(pose.shape),))
+    if pierced is not None and tuple(pierced.shape) != (cap,):
+        raise NativeError('accum_query: pierced must be [cap], got %s' % (tuple(pierced.shape),))
+    v = 0
+    if normals is not None and flags is not None:
+        v = normals.shape[0]
+        if tuple(normals.shape) != (v, 3) or tuple(flags.shape) != (v,):
+            raise NativeError('accum_query: normals [V,3] and flags [V] expected, got %s %s' % (tuple(normals.shape), tuple(flags.shape)))
+    pts = _dev(points, torch.float32, 'points')
+    nrm = _dev(normals, torch.float32, 'normals') if normals is not None else None
+    flg = _dev(flags, torch.uint8, 'flags') if flags is not None else None
+    if out is None:
+        out = {name: torch.empty((n,) + shape, dtype=dtype, device=dev) for name, dtype, shape in QUERY_FIELDS}
+    for name, dtype, shape in QUERY_FIELDS:
+        if tuple(out[name].shape) != (n,) + shape:
+            raise NativeError('accum_query: out[%r] must be %s, got %s' % (name, (n,) + shape, tuple(out[name].shape)))
+    if counters is None:
+        counters = torch.empty((QUERY_COUNTERS,), dtype=torch.int64, device=dev)
+    if tuple(counters.shape) != (QUERY_COUNTERS,):
+        raise NativeError('accum_query: counters must be [%d] int64' % QUERY_COUNTERS)
+    o_status, o_count, o_moving, o_first, o_last, o_pierced, o_row, o_nearest, o_distance, o_plane = [_dev(out[name], dtype, name) if n else None
+                                                                                                      for name, dtype, _ in QUERY_FIELDS]
+    ws = _workspace(lib().pcacc_accum_query_workspace_bytes, dev, m)
+    _check(lib().pcacc_accum_query(pts if n else None, n, _dev(pose, torch.float64, 'pose') if pose is not None else None, float(voxel_size),
+                                   float(max_distance), keys, acc, stamps, _dev(pierced, torch.int32, 'pierced') if pierced is not None else None, cap, m,
+                                   int(min_count), 0 if max_moving_fraction is None else 1,
+                                   0.0 if max_moving_fraction is None else float(max_moving_fraction), nrm, flg, v, 1 if require_normal else 0,
+                                   o_status, o_count, o_moving, o_first, o_last, o_pierced, o_row, o_nearest, o_distance, o_plane, _dev(counters, torch.int64, 'counters'), _dev(ws), ws.numel(), _stream()), 'accum_query')
+    res = dict(out)
+    res['counters'] = counters
+    return res
+
+
 def conv3x3_supported(c_in, c_out):
     return c_in >= 32 and c_out >= 32 and c_in % 32 == 0 and c_out % 32 == 0
 
