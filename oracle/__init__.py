@@ -536,7 +536,8 @@ def cluster_labels(points, eps, min_samples, min_p_cluster, estimator=None):
 
 
 def cluster_per_batch(mos, offset, points, eps, min_samples, min_p_cluster, use_offset=True, estimator=None):
-    """models/cluster.py:52-84 with fb_labels=None.  mos [N], offset [N,2], points [N,3] (float32)."""
+    """models/cluster.py:52-84 with fb_labels=None.  mos [N], offset [N,2], points [N,3] (float32).
+    The voxel sizes are the reference's constants, not the config's: 5 cm with the offsets added, 15 cm without."""
     mos, offset, points = np.asarray(mos), np.asarray(offset, np.float32), np.asarray(points, np.float32)
     sel = mos == 1
     full = np.zeros(mos.shape[0], np.int64)

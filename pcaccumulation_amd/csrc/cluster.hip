@@ -1,5 +1,5 @@
-// Test-mode instance clustering on the device (models/cluster.py:9-111): 5 cm voxel down-sampling of the points
-// predicted moving, DBSCAN in the horizontal plane, small clusters dropped, labels canonicalised per sample.
+// Test-mode instance clustering on the device (models/cluster.py:9-111): voxel down-sampling of the points predicted moving
+// (5 cm voxels with the offsets added, 15 cm without), DBSCAN in the horizontal plane, small clusters dropped, labels per sample.
 // The reference does this on the host (torchsparse sparse_quantize + scikit-learn DBSCAN) behind a
 // device->host->device round trip; here every sample of the batch is clustered in one set of launches and the
 // result is bit-identical to that host path:

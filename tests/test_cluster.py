@@ -3,7 +3,8 @@
 Golden vectors: tests/golden/cluster.npz -- the reference's models/cluster.py:Cluster run on synthetic scenes with the real
 scikit-learn DBSCAN (tests/golden/make_golden_cluster.py); model_tiny_test.npz -- the reference MotionNet in misc.mode='test'.
 CPU leg: the oracle's restated DBSCAN / sparse_quantize against the fixture and against scikit-learn itself.
-GPU leg: pcacc_cluster through the C ABI, bit-exact against the fixture and against scikit-learn on random scenes."""
+GPU leg: pcacc_cluster through the C ABI, bit-exact against the fixture and against scikit-learn on random scenes.
+Geometry built to break the kernel's invariants (exact-eps pairs, shared border points, rounding ties, ...): test_cluster_edges.py."""
 import numpy as np
 import pytest
 import torch
