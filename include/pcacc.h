@@ -815,6 +815,63 @@ int pcacc_accum_query(const float *points, int64_t n, const double *pose, double
                       double *out_plane_distance, int64_t *counters, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C10. Casting rays into the accumulated scene cloud: looking from an origin towards a target, the first voxel the map keeps and how far away it
+ * is -- a range image of the map from a sensor pose, the range the map predicts along a measured beam, visibility between two places.
+ * Replaces the copy of up to 8 M keys to the host and a ray cast there.  Intersects no surfel or plane (the answer is a voxel and its centroid),
+ * skips no empty space with a coarser structure, takes no stamp and does not modify the map.
+ * Inputs
+ *   targets [n,3] f32, 0 <= n <= 2^30         where the rays point (caller's frame)
+ *   origins [S,3] f64, S >= 1                 where they start (caller's frame);  origin_index [n] i32 or NULL (= all 0): the row of a ray's origin
+ *   pose [4,4] f64                            caller's frame to world, rows 0-2 are read; NULL = identity
+ *   voxel_size                                of the map;  min_range >= 0, finite;  max_range: < 0 = none;  margin >= 0, finite, read only
+ *                                             without a max_range;  max_steps in [1, 2^16]
+ *   keys, acc, capacity, m; min_count, use_fraction, max_moving_fraction     the map and extract's filter, as for pcacc_accum_normals
+ * Per ray, all float64 with no FMA contraction, only + - * / and sqrt, in the order csrc/accum_raycast.h writes down and no other:
+ *   End points: o = pose . origin, e = pose . p with C4's transform.  PCACC_RAYCAST_DROPPED when origin_index lies outside [0, S) or a
+ *   coordinate of o or e fails C4's validity rule: the ray is never clamped and forms no key and no address.
+ *   Extent: d = e - o, L = sqrt((d_x^2 + d_y^2) + d_z^2), t_start = min_range / L; t_end = max_range / L with a max_range (the ray may run past
+ *   its target), else 1 - margin / L (C7's formula: the ray runs to its target).  !(L > 0), !(t_end > 0) or !(t_start < t_end):
+ *   PCACC_RAYCAST_SKIPPED.
+ *   Walk: C7's, bit for bit.  The start voxel floor(o_a / voxel_size) has t_in = 0; per step b_a and t_a afresh, the smallest t_a by strict <
+ *   (ties to x, then y, then z); !(t_a < t_end) ends the walk; otherwise the index moves, an index that leaves [-2^20, 2^20) ends the walk, and
+ *   the entered voxel has t_in = t_a.  A walk that would make visit number max_steps + 1 ends instead: PCACC_RAYCAST_TRUNCATED.
+ *   Visit: visits += 1.  A voxel with t_in < t_start is walked without a search.  Every other voxel is looked up by binary search; it is the
+ *   HIT iff the map has its row and extract's filter keeps that row.  The walk stops at the first HIT; a walk that ends without one is a MISS.
+ * Outputs (device, n rows each, every row written once): out_status u8 (one of the codes below); out_row i32: the row of pcacc_accum_extract
+ * under this filter (valid until the map changes); out_coords [n,3] i32: the hit voxel; out_point [n,3] f32: the float32 of its float64 centroid
+ * c (extract's point); out_range_in f64 = t_in L, where the ray enters the voxel; out_depth f64 = (((c_x - o_x) d_x + (c_y - o_y) d_y) +
+ * (c_z - o_z) d_z) / L, the centroid's range along the ray; out_length f64 = L (0 for DROPPED); out_visits i32.  Without a HIT: row -1, coords
+ * and point 0, range_in and depth +inf.  |depth - range_in| <= sqrt(3) voxel_size + 2^-17 plus rounding: a centroid lies within 2^-17 m of its
+ * voxel.
+ * counters [PCACC_RAYCAST_COUNTERS] i64 (written, not added to): rays, dropped, skipped, hit, missed, truncated -- the first is the sum of the
+ * next five -- and the visits of all rays.
+ * Return value: PCACC_E_ARG, and nothing is launched, for n outside [0, 2^30], S < 1, m outside [0, capacity], a voxel size that is not positive
+ * and finite, a min_range or margin that is negative or not finite, a NaN max_range, max_steps outside [1, 2^16], a NULL table or output of
+ * non-zero size, or a workspace that is too small.  n = 0 writes the zero counters and launches nothing else; m = 0 walks the rays and
+ * addresses no table: every valid ray is MISS or TRUNCATED.
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_RAYCAST_MISS 0
+#define PCACC_RAYCAST_HIT 1
+#define PCACC_RAYCAST_TRUNCATED 2
+#define PCACC_RAYCAST_SKIPPED 3
+#define PCACC_RAYCAST_DROPPED 4
+#define PCACC_RAYCAST_COUNTERS 7
+#define PCACC_RAYCAST_N_RAYS 0
+#define PCACC_RAYCAST_N_DROPPED 1
+#define PCACC_RAYCAST_N_SKIPPED 2
+#define PCACC_RAYCAST_N_HIT 3
+#define PCACC_RAYCAST_N_MISSED 4
+#define PCACC_RAYCAST_N_TRUNCATED 5
+#define PCACC_RAYCAST_N_VISITS 6
+int pcacc_accum_raycast_workspace_bytes(int64_t m, size_t *bytes /*host*/);
+int pcacc_accum_raycast(const float *targets, int64_t n, const double *origins, int64_t n_origins, const int32_t *origin_index,
+                        const double *pose, double voxel_size, double min_range, double max_range, double margin, int32_t max_steps,
+                        const int64_t *keys, const int64_t *acc, int64_t capacity, int64_t m, int64_t min_count, int32_t use_fraction,
+                        double max_moving_fraction, uint8_t *out_status, int32_t *out_row, int32_t *out_coords, float *out_point,
+                        double *out_range_in, double *out_depth, double *out_length, int32_t *out_visits, int64_t *counters, void *workspace,
+                        size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

@@ -19,6 +19,7 @@ coordinate sums), so the map does not depend on the order of the points, on the 
     static = m.extract(min_count=2, max_moving_fraction=0.0)     # dict of device tensors
     keep = m.pierced(min_count=2, max_moving_fraction=0.0) < 2   # rows aligned with `static`: False where later rays went straight through the voxel
     nrm = m.normals(radius=1, min_count=2, max_moving_fraction=0.0, viewpoints=sensor_positions)   # rows aligned with `static` (C5, section 9d)
+    image = m.render_range_image(pose, 64, 2048, 0.05, -0.43, max_range=80.0, min_count=2)['depth']   # [64,2048] f64, +inf = nothing there: C10, section 9i
     m.save_ply('scene.ply', min_count=2, max_moving_fraction=0.0, viewpoints=sensor_positions)
 
 There is no CPU path: a CPU tensor raises native.NativeError."""
@@ -364,6 +365,99 @@ class AccumulatedCloud(object):
         sx, sy, sz = (float(v) for v in sensor_offset)
         origins = ((ego[:, :3, 0] * sx + ego[:, :3, 1] * sy) + ego[:, :3, 2] * sz) + ego[:, :3, 3]
         return self.see_through(results['rec_est'], origins, input_dict['time_indice'][:, 1], pose, results['mos_est'].argmax(1) == 1, **kw)
+
+    # ---- raycast -----------------------------------------------------------------------------------------------------------------------
+    def raycast(self, targets, origins, origin_index=None, pose=None, max_range=None, min_range=0.0, margin=0.0, min_count=1, max_moving_fraction=None,
+                max_steps=4096):
+        """Looking from an origin towards a target: the first voxel extract(min_count, max_moving_fraction) returns along the ray, and how far away it
+        is (include/pcacc.h C10).  The map is not modified.
+        targets [n,3] f32 (device, caller's frame); origins [3] or [S,3] (tensor or array, caller's frame); origin_index [n] integers (device; None =
+        row 0); pose [4,4] caller's frame to world (None = identity).  With max_range the ray runs that far along its direction, past its target if
+        need be; with max_range=None it ends margin in front of the target (see_through's ray).  Voxels the ray enters before min_range are passed
+        over; max_steps in [1, 2^16]: the most voxels one ray visits.
+        -> dict of device tensors, one row per ray in the caller's order:
+        status [n] u8: native.RAYCAST_MISS, _HIT, _TRUNCATED (max_steps voxels without a hit), _SKIPPED (a ray of no length, or min_range >= its
+        end), _DROPPED (an end point that is not finite or lies outside the grid, or an origin_index outside [0, S));
+        row [n] i32: the hit voxel's row of extract(min_count, max_moving_fraction), valid until the next add or prune; coords [n,3] i32 its voxel,
+        point [n,3] f32 its centroid (extract's point); range_in [n] f64: where the ray enters that voxel; depth [n] f64: the centroid's range
+        along the ray, within sqrt(3) voxel_size + 2^-17 of range_in; length [n] f64: origin to target; visits [n] i32: voxels visited.
+        Without a hit row = -1, coords = point = 0 and range_in = depth = +inf.
+        counters [7] i64: rays, dropped, skipped, hit, missed, truncated, visits of all rays.  Nothing is read back."""
+        if not torch.is_tensor(targets) or not targets.is_cuda:
+            raise native.NativeError('raycast: targets must be a tensor on the GPU; the HIP path has no CPU fallback')
+        if targets.dim() != 2 or targets.shape[1] != 3:
+            raise ValueError('targets must be [n,3], got %s' % (tuple(targets.shape),))
+        n = targets.shape[0]
+        if n > native.RAYCAST_MAX_RAYS:
+            raise ValueError('at most 2^30 rays per raycast, got %d' % n)
+        if origin_index is not None:
+            if not torch.is_tensor(origin_index) or not origin_index.is_cuda:
+                raise native.NativeError('raycast: origin_index must live on the GPU')
+            if tuple(origin_index.shape) != (n,):
+                raise ValueError('origin_index must be [n], got %s' % (tuple(origin_index.shape),))
+        if not torch.is_tensor(origins):
+            origins = torch.from_numpy(np.ascontiguousarray(origins, dtype=np.float64))
+        if origins.dim() == 1:
+            origins = origins.reshape(1, -1)
+        if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape[0] < 1:
+            raise ValueError('origins must be [3] or [S,3] with S >= 1, got %s' % (tuple(origins.shape),))
+        min_range, margin = float(min_range), float(margin)
+        if not (min_range >= 0.0 and np.isfinite(min_range)):
+            raise ValueError('min_range must be a finite number >= 0, got %r' % min_range)
+        if not (margin >= 0.0 and np.isfinite(margin)):
+            raise ValueError('margin must be a finite number >= 0, got %r' % margin)
+        if max_range is not None:
+            max_range = float(max_range)
+            if not max_range >= 0.0:
+                raise ValueError('max_range must be >= 0 or None, got %r' % max_range)
+            if margin != 0.0:
+                raise ValueError('margin is measured from the target: it cannot be combined with a max_range')
+        if not 1 <= int(max_steps) <= native.RAYCAST_MAX_STEPS:
+            raise ValueError('max_steps must lie in [1, 2^16], got %r' % max_steps)
+        pose = self._pose(pose)
+        self._ensure()
+        return native.accum_raycast(targets.detach().float().contiguous(), origins.to(device=self.device, dtype=torch.float64).contiguous(),
+                                    # the entry point takes int32 rows: a row outside [0, S) stays outside after the cast
+                                    origin_index.clamp(-1, origins.shape[0]).to(torch.int32).contiguous() if origin_index is not None else None, pose,
+                                    self.voxel_size, min_range, max_range, margin, int(max_steps), self._cur, self._n, min_count, max_moving_fraction)
+
+    def raycast_results(self, results, input_dict, pose=None, sensor_offset=(0, 0, 0), **kw):
+        """raycast() of a test / val-mode forward: the targets are results['rec_est'], the origin of a target is the sensor position of its frame, built
+        as see_through_results builds it.  One sample per batch."""
+        batch = input_dict['time_indice'][:, 0]
+        n_batches = results.get('_n_batches')
+        if n_batches is None:
+            n_batches = int(batch.max()) + 1 if batch.numel() else 1
+        if n_batches != 1:
+            raise ValueError('raycast_results: one sample per batch, got %d' % n_batches)
+        ego = results['ego_motion_est'][0].detach().to(torch.float64)                       # [T,4,4]
+        sx, sy, sz = (float(v) for v in sensor_offset)
+        origins = ((ego[:, :3, 0] * sx + ego[:, :3, 1] * sy) + ego[:, :3, 2] * sz) + ego[:, :3, 3]
+        return self.raycast(results['rec_est'], origins, input_dict['time_indice'][:, 1], pose, **kw)
+
+    def render_range_image(self, pose, height, width, fov_up, fov_down, max_range, **kw):
+        """A range image of the map from a sensor at `pose` ([4,4] sensor-to-world; None = identity): one ray per pixel from the sensor's origin.  Row r
+        looks at elevation fov_up - (r + 0.5)(fov_up - fov_down) / height, column c at azimuth pi - (c + 0.5) 2 pi / width (radians; the image's
+        middle column looks along +x), direction (cos el cos az, cos el sin az, sin el), computed on the host in float64 and cast to float32.
+        -> raycast(directions, (0, 0, 0), pose=pose, max_range=max_range, **kw) with every column reshaped to [height, width, ...] (depth is the range
+        image; +inf where nothing was hit) and 'directions' [height, width, 3] f32."""
+        height, width = int(height), int(width)
+        if height < 1 or width < 1 or height * width > native.RAYCAST_MAX_RAYS:
+            raise ValueError('height and width must be at least 1 and height * width at most 2^30, got %r x %r' % (height, width))
+        fov_up, fov_down = float(fov_up), float(fov_down)
+        if not (np.isfinite(fov_up) and np.isfinite(fov_down)):
+            raise ValueError('fov_up and fov_down must be finite, got %r %r' % (fov_up, fov_down))
+        if max_range is None:
+            raise ValueError('render_range_image needs a max_range: a direction has no target to stop at')
+        el = fov_up - (np.arange(height, dtype=np.float64) + 0.5) * (fov_up - fov_down) / height
+        az = np.pi - (np.arange(width, dtype=np.float64) + 0.5) * 2.0 * np.pi / width
+        d = np.stack([np.cos(el)[:, None] * np.cos(az)[None, :], np.cos(el)[:, None] * np.sin(az)[None, :],
+                      np.sin(el)[:, None] * np.ones_like(az)[None, :]], -1).astype(np.float32)
+        directions = torch.from_numpy(d).to(self.device)
+        res = self.raycast(directions.reshape(-1, 3), np.zeros((1, 3)), None, pose, max_range, **kw)
+        out = {k: (v if k == 'counters' else v.reshape((height, width) + tuple(v.shape[1:]))) for k, v in res.items()}
+        out['directions'] = directions
+        return out
 
     def pierced(self, min_count=1, max_moving_fraction=None):
         """[V] int32: the rays see_through counted through every voxel that extract(min_count, max_moving_fraction) returns, row for row; all zeros before

@@ -48,6 +48,28 @@ PCACC_HD bool accp_end_point(const double *T, double x, double y, double z, doub
     return true;
 }
 
+// One step of the walk, the choice C7 and C10 (accum_raycast.h) share: for every axis with d_a != 0 the plane b_a and t_a = (b_a - o_a) / d_a afresh, the
+// smallest t_a by strict < (ties: x, y, z).  false: the walk ends -- no axis, !(t_best < t_end), or the moved index left [-2^20, 2^20) (i has moved then).
+// true: i moved by one voxel along the winning axis and the ray enters that voxel at *t_in = t_best.
+PCACC_HD bool accp_step(const double o[3], const double d[3], double voxel_size, double t_end, int64_t i[3], double *t_in)
+{
+    PCACC_NO_CONTRACT
+    int best = -1;
+    double t_best = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        if (d[a] == 0.0) continue;
+        const double b = (double)(i[a] + (d[a] > 0.0 ? 1 : 0)) * voxel_size;
+        const double t = (b - o[a]) / d[a];
+        if (best < 0 || t < t_best) { best = a; t_best = t; }
+    }
+    if (best < 0 || !(t_best < t_end)) return false;
+    bool inside = true;
+    for (int a = 0; a < 3; ++a)                                                  // no run-time index into i: the three stay in registers
+        if (a == best) { i[a] += d[a] > 0.0 ? 1 : -1; inside = accp_in_range(i[a]); }
+    *t_in = t_best;
+    return inside;
+}
+
 // The whole of one ray.  T: 12 doubles of the pose; p: the scan point; origin: its row of the origin table, read only when origin_ok (origin_index in range);
 // stamps [2][capacity]; t_end's max_range is used when use_range.  hit(pos) is called for every counted visit, pos in [0, m): the kernel adds with an
 // integer atomic, the host build with ++.
@@ -77,6 +99,7 @@ PCACC_HD AccpRay accp_ray(const double *T, const float *p, const double *origin,
     if (!(t_end > 0.0)) return r;
     r.status = ACCP_WALKED;
     const double d[3] = {dx, dy, dz};
+    double t_in = 0.0;
     for (;;) {
         const unsigned long long key = accum_key(i[0], i[1], i[2]);
         const int64_t pos = accum_lower_bound(keys, m, key);                     // in [0, m]; m = 0: no load
@@ -85,19 +108,7 @@ PCACC_HD AccpRay accp_ray(const double *T, const float *p, const double *origin,
             PCACC_BOUND(pos, m);
             if (keys[pos] == key && (!use_stamp || stamps[capacity + pos] < stamp || stamps[pos] > stamp)) { hit(pos); ++r.hits; }
         }
-        int best = -1;
-        double t_best = 0.0;
-        for (int a = 0; a < 3; ++a) {
-            if (d[a] == 0.0) continue;
-            const double b = (double)(i[a] + (d[a] > 0.0 ? 1 : 0)) * voxel_size;
-            const double t = (b - o[a]) / d[a];
-            if (best < 0 || t < t_best) { best = a; t_best = t; }
-        }
-        if (best < 0 || !(t_best < t_end)) break;
-        bool inside = true;
-        for (int a = 0; a < 3; ++a)                                              // no run-time index into i: the three stay in registers
-            if (a == best) { i[a] += d[a] > 0.0 ? 1 : -1; inside = accp_in_range(i[a]); }
-        if (!inside) break;
+        if (!accp_step(o, d, voxel_size, t_end, i, &t_in)) break;
         if (r.visits >= max_steps) { r.truncated = 1; break; }
     }
     return r;

@@ -930,6 +930,54 @@ def accum_query(points, pose, voxel_size, max_distance, tables, m, pierced, min_
     return res
 
 
+RAYCAST_MISS, RAYCAST_HIT, RAYCAST_TRUNCATED, RAYCAST_SKIPPED, RAYCAST_DROPPED = 0, 1, 2, 3, 4
+RAYCAST_COUNTERS = 7
+RAYCAST_N_RAYS, RAYCAST_N_DROPPED, RAYCAST_N_SKIPPED, RAYCAST_N_HIT, RAYCAST_N_MISSED, RAYCAST_N_TRUNCATED, RAYCAST_N_VISITS = 0, 1, 2, 3, 4, 5, 6
+RAYCAST_MAX_RAYS, RAYCAST_MAX_STEPS = 1 << 30, 1 << 16
+RAYCAST_FIELDS = (('status', torch.uint8, ()), ('row', torch.int32, ()), ('coords', torch.int32, (3,)), ('point', torch.float32, (3,)),
+                  ('range_in', torch.float64, ()), ('depth', torch.float64, ()), ('length', torch.float64, ()), ('visits', torch.int32, ()))
+
+
+def accum_raycast(targets, origins, origin_index, pose, voxel_size, min_range, max_range, margin, max_steps, tables, m, min_count, max_moving_fraction,
+                  out=None, counters=None):
+    """The first kept voxel of the first m rows of a map along every ray origin -> target; see include/pcacc.h (C10).  targets [n,3] f32, origins [S,3]
+    f64, origin_index [n] i32 or None (all 0), pose [4,4] f64 or None, max_range None = none (the ray ends margin in front of its target).  out: a dict
+    of the RAYCAST_FIELDS tensors to write into (None = new ones), counters [7] i64 likewise.  -> out with 'counters' added; nothing is read back."""
+    keys, acc, _, cap = _accum_tables(tables, 'accum_raycast')
+    dev = tables[0].device
+    n, m = targets.shape[0], int(m)
+    if targets.dim() != 2 or targets.shape[1] != 3:
+        raise NativeError('accum_raycast: targets must be [n,3], got %s' % (tuple(targets.shape),))
+    if origins.dim() != 2 or origins.shape[1] != 3:
+        raise NativeError('accum_raycast: origins must be [S,3], got %s' % (tuple(origins.shape),))
+    if origin_index is not None and tuple(origin_index.shape) != (n,):
+        raise NativeError('accum_raycast: origin_index must be [n], got %s' % (tuple(origin_index.shape),))
+    if pose is not None and tuple(pose.shape) != (4, 4):
+        raise NativeError('accum_raycast: pose must be [4,4], got %s' % (tuple(pose.shape),))
+    pts = _dev(targets, torch.float32, 'targets')
+    if out is None:
+        out = {name: torch.empty((n,) + shape, dtype=dtype, device=dev) for name, dtype, shape in RAYCAST_FIELDS}
+    for name, dtype, shape in RAYCAST_FIELDS:
+        if tuple(out[name].shape) != (n,) + shape:
+            raise NativeError('accum_raycast: out[%r] must be %s, got %s' % (name, (n,) + shape, tuple(out[name].shape)))
+    if counters is None:
+        counters = torch.empty((RAYCAST_COUNTERS,), dtype=torch.int64, device=dev)
+    if tuple(counters.shape) != (RAYCAST_COUNTERS,):
+        raise NativeError('accum_raycast: counters must be [%d] int64' % RAYCAST_COUNTERS)
+    o_status, o_row, o_coords, o_point, o_range_in, o_depth, o_length, o_visits = [_dev(out[name], dtype, name) if n else None for name, dtype, _ in RAYCAST_FIELDS]
+    ws = _workspace(lib().pcacc_accum_raycast_workspace_bytes, dev, m)
+    _check(lib().pcacc_accum_raycast(pts if n else None, n, _dev(origins, torch.float64, 'origins') if origins.shape[0] else None, origins.shape[0],
+                                     _dev(origin_index, torch.int32, 'origin_index') if origin_index is not None and n else None,
+                                     _dev(pose, torch.float64, 'pose') if pose is not None else None, float(voxel_size), float(min_range),
+                                     -1.0 if max_range is None else float(max_range), float(margin), int(max_steps), keys, acc, cap, m, int(min_count),
+                                     0 if max_moving_fraction is None else 1, 0.0 if max_moving_fraction is None else float(max_moving_fraction),
+                                     o_status, o_row, o_coords, o_point, o_range_in, o_depth, o_length, o_visits, _dev(counters, torch.int64, 'counters'),
+                                     _dev(ws), ws.numel(), _stream()), 'accum_raycast')
+    res = dict(out)
+    res['counters'] = counters
+    return res
+
+
 def conv3x3_supported(c_in, c_out):
     return c_in >= 32 and c_out >= 32 and c_in % 32 == 0 and c_out % 32 == 0
 
