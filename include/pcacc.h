@@ -872,6 +872,69 @@ int pcacc_accum_raycast(const float *targets, int64_t n, const double *origins, 
                         size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C11. Connected components of the accumulated scene cloud: which voxels belong together, with the size, box, centroid and stamps of every
+ * connected set, and the removal of the small ones -- floating blobs that every per-voxel neighbour count lets through.  Replaces the copy of the
+ * records to the host, a flood fill there and a load.  26-connectivity widened by a radius only: no 6- or 18-connectivity, no edge conditioned on
+ * a distance or a normal, no label column stored in the map, no incremental relabelling.
+ * pcacc_accum_components: inputs
+ *   keys, acc, stamps, capacity, m; min_count, use_fraction, max_moving_fraction     the map and extract's filter, as for pcacc_accum_normals
+ *   mask [mask_rows] u8 or NULL      over the rows of pcacc_accum_extract under the same filter; radius 1, 2 or 3
+ * Map row i takes part iff the filter keeps it (extract row j) and, with a mask, mask[j] != 0.  Two rows that take part are adjacent iff
+ * |delta|_inf <= radius; neighbours are found as C5 finds them (offsets that leave [-2^20, 2^20) are skipped before a key is formed).  The
+ * components of that graph are numbered 0 .. K-1 in ascending order of their smallest key = their smallest extract row: a function of the map.
+ * Outputs (device; every table has room for m rows)
+ *   out_label [kept] i32             aligned with extract: the component of the row, -1 where the mask excludes it
+ *   per component, K rows, each a function of the member set alone (integer sums, minima and maxima):
+ *   out_voxels i32; out_points, out_moving i64 (sums of count and moving); out_sum_q [K,3] i64 (sums of the records' sum q; |.| < 2^62);
+ *   out_centroid [K,3] f32 = float32(((double)sum_q_a / (double)points) * 2^-16); out_lo, out_hi [K,3] i32 (voxel indices, inclusive);
+ *   out_t_first (minimum), out_t_last (maximum), out_first_row (extract row of the smallest key) i32
+ *   counters [PCACC_COMPONENTS_COUNTERS] i64 (written, not added to): map rows = rows that take part + rows outside the filter + rows masked
+ *   out; K; voxels of the largest component; status.
+ * Status PCACC_COMPONENTS_BAD_MASK: a mask was given and mask_rows differs from the rows the filter keeps (decided on the device): no row takes
+ * part, every label is -1, K = 0, every kept row counts as masked out.  PCACC_COMPONENTS_GAVE_UP: a join lost its compare-and-swap
+ * 1024 times in a row against other lanes and was abandoned; the labels are then not to be used.  Rows of a table behind K (behind kept for
+ * out_label) are not written.  The map is not modified.
+ * pcacc_accum_remove_components: the second stage.  label, voxels, points, components_counters are out_label, out_voxels, out_points and counters
+ * of pcacc_accum_components on this map under this filter, still on the device.  A row that takes part (label >= 0) is SMALL iff its component
+ * has voxels < min_voxels or points < min_points (a threshold of 0 is off); rows that do not take part stay.  The surviving rows go, in key
+ * order and every record bit-identical, to out_keys, out_acc, out_stamps and (iff in_pierced is given) out_pierced, as for pcacc_accum_prune.
+ *   counters [PCACC_COMPONENTS_REMOVE_COUNTERS] i64 (written): rows kept, rows SMALL, components removed, components kept.
+ *   dry_run != 0, or a first-stage status other than OK, computes only the counters: no table and no state word is written.
+ *   Otherwise state[PCACC_ACCUM_NUM_VOXELS] = rows kept, on the device; every other state word is left alone.
+ * Return value: PCACC_E_ARG, and nothing is launched, for m outside [0, capacity], radius outside 1..3, a negative threshold, mask_rows < 0, a
+ * NULL table or output of non-zero size, a workspace that is too small and, for the removal, out_capacity < m or an output table that shares
+ * memory with an input table.  m = 0 writes the zero counters and launches nothing else.  One workspace size serves both entries.
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_COMPONENTS_COUNTERS 7
+#define PCACC_COMPONENTS_ROWS 0
+#define PCACC_COMPONENTS_PARTICIPATING 1
+#define PCACC_COMPONENTS_OUTSIDE 2
+#define PCACC_COMPONENTS_MASKED 3
+#define PCACC_COMPONENTS_K 4
+#define PCACC_COMPONENTS_LARGEST 5
+#define PCACC_COMPONENTS_STATUS 6
+#define PCACC_COMPONENTS_OK 0
+#define PCACC_COMPONENTS_BAD_MASK 1
+#define PCACC_COMPONENTS_GAVE_UP 2
+#define PCACC_COMPONENTS_REMOVE_COUNTERS 4
+#define PCACC_COMPONENTS_REMOVE_KEPT 0
+#define PCACC_COMPONENTS_REMOVE_SMALL 1
+#define PCACC_COMPONENTS_REMOVED 2
+#define PCACC_COMPONENTS_SURVIVED 3
+int pcacc_accum_components_workspace_bytes(int64_t m, size_t *bytes /*host*/);
+int pcacc_accum_components(const int64_t *keys, const int64_t *acc, const int32_t *stamps, int64_t capacity, int64_t m, int64_t min_count,
+                           int32_t use_fraction, double max_moving_fraction, const uint8_t *mask, int64_t mask_rows, int32_t radius,
+                           int32_t *out_label, int32_t *out_voxels, int64_t *out_points, int64_t *out_moving, int64_t *out_sum_q,
+                           float *out_centroid, int32_t *out_lo, int32_t *out_hi, int32_t *out_t_first, int32_t *out_t_last,
+                           int32_t *out_first_row, int64_t *counters, void *workspace, size_t workspace_bytes, void *stream);
+int pcacc_accum_remove_components(const int64_t *in_keys, const int64_t *in_acc, const int32_t *in_stamps, const int32_t *in_pierced,
+                                  int64_t in_capacity, int64_t m, int64_t min_count, int32_t use_fraction, double max_moving_fraction,
+                                  const int32_t *label, const int32_t *voxels, const int64_t *points, const int64_t *components_counters,
+                                  int64_t min_voxels, int64_t min_points, int32_t dry_run, int64_t *out_keys, int64_t *out_acc,
+                                  int32_t *out_stamps, int32_t *out_pierced, int64_t out_capacity, int64_t *counters, int64_t *state,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

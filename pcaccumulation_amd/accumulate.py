@@ -20,6 +20,9 @@ coordinate sums), so the map does not depend on the order of the points, on the 
     keep = m.pierced(min_count=2, max_moving_fraction=0.0) < 2   # rows aligned with `static`: False where later rays went straight through the voxel
     nrm = m.normals(radius=1, min_count=2, max_moving_fraction=0.0, viewpoints=sensor_positions)   # rows aligned with `static` (C5, section 9d)
     image = m.render_range_image(pose, 64, 2048, 0.05, -0.43, max_range=80.0, min_count=2)['depth']   # [64,2048] f64, +inf = nothing there: C10, section 9i
+    objects = m.components(min_count=2, max_moving_fraction=0.0, mask=static['points'][:, 2] > ground_z)   # a label per row of `static`, and per connected
+                                                                 # set above the ground its size, box and centroid: C11, section 9j
+    m.remove_components(min_voxels=30, min_count=2, max_moving_fraction=0.0)   # drop the floating blobs that a per-voxel neighbour count lets through
     m.save_ply('scene.ply', min_count=2, max_moving_fraction=0.0, viewpoints=sensor_positions)
 
 There is no CPU path: a CPU tensor raises native.NativeError."""
@@ -32,6 +35,8 @@ _FIELDS = ('points', 'coords', 'count', 'moving', 't_first', 't_last')
 _NORMAL_FIELDS = ('normals', 'eigenvalues', 'neighbors', 'flags')
 _REGISTER_FIELDS = ('pose', 'fitness', 'rmse', 'iterations', 'status', 'correspondences')
 _PRUNE_FIELDS = ('kept', 'filter', 'stale', 'box', 'pierced', 'isolated')
+_COMPONENT_FIELDS = ('voxels', 'points', 'moving', 'sum_q', 'centroid', 'lo', 'hi', 't_first', 't_last', 'first_row')
+_REMOVE_FIELDS = ('kept', 'small', 'components_removed', 'components_kept', 'rows', 'participating', 'outside', 'masked', 'components', 'largest')
 _PLY_TYPES = {'float32': 'float', 'float64': 'double', 'int8': 'char', 'uint8': 'uchar', 'int16': 'short', 'uint16': 'ushort', 'int32': 'int',
               'uint32': 'uint'}
 
@@ -532,6 +537,84 @@ class AccumulatedCloud(object):
                            min_neighbors, radius, dry_run, out, pierced_out, counters, None if dry_run else self._state)
         res = dict(zip(_PRUNE_FIELDS, counters.tolist()))          # the one read-back of a prune
         if not dry_run and self._n:                                # the map before the prune stays in self._alt, which the next add overwrites
+            self._cur, self._alt = self._alt, self._cur
+            if self._pierced is not None:
+                self._pierced = pierced_out
+            self._n = res['kept']
+        return res
+
+    # ---- connected components ----------------------------------------------------------------------------------------------------------
+    def _components_args(self, what, radius, min_count, max_moving_fraction, mask):
+        radius, min_count = int(radius), int(min_count)
+        if not 1 <= radius <= 3:
+            raise ValueError('radius must be 1, 2 or 3 voxels, got %r' % radius)
+        if max_moving_fraction is not None and np.isnan(float(max_moving_fraction)):
+            raise ValueError('max_moving_fraction must be a number or None')
+        if mask is not None:
+            if not torch.is_tensor(mask) or mask.dim() != 1 or mask.dtype not in (torch.bool, torch.uint8):
+                raise ValueError('mask must be a 1-D bool / uint8 tensor over the rows of extract()')
+            if not mask.is_cuda:
+                raise native.NativeError('%s: mask must live on the GPU; the HIP path has no CPU fallback' % what)
+            mask = (mask.to(torch.uint8) if mask.dtype == torch.bool else mask).contiguous()
+        return radius, min_count, mask
+
+    @staticmethod
+    def _components_status(counters):
+        status = counters[native.COMPONENTS_STATUS]
+        if status == native.COMPONENTS_BAD_MASK:
+            raise ValueError('mask must have one entry per row of extract() under the same filter (%d rows)'
+                             % (counters[native.COMPONENTS_ROWS] - counters[native.COMPONENTS_OUTSIDE]))
+        if status != native.COMPONENTS_OK:
+            raise native.NativeError('accum_components: a join was abandoned under contention (status %d); the labels are not valid' % status)
+
+    def components(self, radius=1, min_count=1, max_moving_fraction=None, mask=None):
+        """Which voxels belong together (include/pcacc.h C11).  The voxels extract(min_count, max_moving_fraction) keeps -- with mask [V] bool / uint8
+        (device) over its rows: those whose entry is non-zero -- are joined when they lie within `radius` voxels of each other (1, 2 or 3; Chebyshev);
+        the connected sets are numbered 0 .. K-1 in ascending order of their smallest (x, y, z) voxel.
+        -> label [V] i32 aligned with extract (-1 where the mask excludes the row); per component voxels [K] i32, points, moving [K] i64 (sums of count
+        and moving), sum_q [K,3] i64 (the records' fixed-point coordinate sums), centroid [K,3] f32, lo, hi [K,3] i32 (box in voxel indices, inclusive), t_first, t_last [K] i32, first_row [K] i32 (extract row
+        of the smallest voxel); counters [7] i64: native.COMPONENTS_*.  Device tensors; only the counters are read back.  The map is not modified."""
+        radius, min_count, mask = self._components_args('components', radius, min_count, max_moving_fraction, mask)
+        self._ensure()
+        res = native.accum_components(self._cur, self._n, min_count, max_moving_fraction, mask, radius)
+        counters = res['counters'].tolist()                        # the one read-back
+        self._components_status(counters)
+        kept, k = counters[native.COMPONENTS_ROWS] - counters[native.COMPONENTS_OUTSIDE], counters[native.COMPONENTS_K]
+        out = {name: res[name][:k] for name in _COMPONENT_FIELDS}
+        out['label'] = res['label'][:kept]
+        out['counters'] = res['counters']
+        return out
+
+    def remove_components(self, min_voxels=None, min_points=None, radius=1, min_count=1, max_moving_fraction=None, mask=None, dry_run=False):
+        """Remove the small connected sets from the map, on the device (include/pcacc.h C11): every voxel that takes part in components(radius,
+        min_count, max_moving_fraction, mask) and whose component has fewer than min_voxels voxels or fewer than min_points points.  Voxels that do
+        not take part (outside the filter or the mask) stay: prune() applies a filter.  The surviving records and ray counts are unchanged.
+        -> {'kept', 'small', 'components_removed', 'components_kept', 'rows', 'participating', 'outside', 'masked', 'components', 'largest'}: Python
+        integers -- the one read-back.  dry_run=True counts and changes nothing."""
+        if min_voxels is None and min_points is None:
+            raise ValueError('remove_components needs min_voxels or min_points')
+        min_voxels = 0 if min_voxels is None else int(min_voxels)
+        min_points = 0 if min_points is None else int(min_points)
+        if min_voxels < 0 or min_points < 0:
+            raise ValueError('min_voxels and min_points must not be negative, got %r %r' % (min_voxels, min_points))
+        radius, min_count, mask = self._components_args('remove_components', radius, min_count, max_moving_fraction, mask)
+        self._ensure()
+        counters = torch.empty((native.COMPONENTS_COUNTERS + native.COMPONENTS_REMOVE_COUNTERS,), dtype=torch.int64, device=self.device)
+        first = native.accum_components(self._cur, self._n, min_count, max_moving_fraction, mask, radius, counters=counters[:native.COMPONENTS_COUNTERS])
+        out = pierced_out = None
+        if not dry_run:
+            if self._alt is None or self._alt[0].shape[0] != self.capacity:
+                self._alt = None                                   # release before taking the tables
+                self._alt = _tables(self.capacity, self.device)
+            out = self._alt
+            if self._pierced is not None:
+                pierced_out = torch.zeros((self.capacity,), dtype=torch.int32, device=self.device)
+        native.accum_remove_components(self._cur, self._n, self._pierced, min_count, max_moving_fraction, first, min_voxels, min_points, dry_run, out,
+                                       pierced_out, counters[native.COMPONENTS_COUNTERS:], None if dry_run else self._state)
+        host = counters.tolist()                                   # the one read-back, of both stages
+        self._components_status(host)                              # a stage that did not end OK has left the tables and the state word alone
+        res = dict(zip(_REMOVE_FIELDS, host[native.COMPONENTS_COUNTERS:] + host[:native.COMPONENTS_STATUS]))
+        if not dry_run and self._n:                                # the map before the call stays in self._alt, which the next add overwrites
             self._cur, self._alt = self._alt, self._cur
             if self._pierced is not None:
                 self._pierced = pierced_out

@@ -28,6 +28,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "scan.h"
+#include "union_find.h"
 
 #define CL_BLOCK 256
 #define CL_INVALID 0xffffffffffffffffull
@@ -243,31 +244,7 @@ __global__ __launch_bounds__(CL_BLOCK) void cluster_core(const float *__restrict
 }
 
 // ---- 4. union-find over core-core edges, on grid positions ----------------------------------------------------------------
-__device__ __forceinline__ int uf_load(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int uf_find(int *parent, int x)
-{
-    int p = uf_load(&parent[x]);
-    while (p != x) {
-        const int gp = uf_load(&parent[p]);
-        if (gp != p) __hip_atomic_store(&parent[x], gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // path halving
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-
-// joins the sets of a and b; returns the surviving (smaller) root
-__device__ __forceinline__ int uf_union(int *parent, int a, int b)
-{
-    for (;;) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return a;
-        if (a < b) { const int t = a; a = b; b = t; }
-        if (atomicCAS(&parent[a], a, b) == a) return b;                       // larger root goes under the smaller one
-    }
-}
+// uf_load / uf_find / uf_union: union_find.h, the one copy that accum_components.hip shares.
 
 // 4a. the core points of one cell are mutually in range: hang each under the cell's first core point (no atomics: a point
 //     only writes its own, still untouched, slot)
@@ -325,7 +302,7 @@ __global__ __launch_bounds__(CL_BLOCK) void cluster_flatten(const int *__restric
     for (int k = blockIdx.x * CL_BLOCK + threadIdx.x; k < m; k += gridDim.x * CL_BLOCK)
         if (core_g[k]) {
             const int r = uf_find(parent, k);
-            if (r != k) __hip_atomic_store(&parent[k], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (r != k) uf_store(&parent[k], r);
         }
 }
 

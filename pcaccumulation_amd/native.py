@@ -930,6 +930,88 @@ def accum_query(points, pose, voxel_size, max_distance, tables, m, pierced, min_
     return res
 
 
+COMPONENTS_COUNTERS, COMPONENTS_REMOVE_COUNTERS = 7, 4
+COMPONENTS_ROWS, COMPONENTS_PARTICIPATING, COMPONENTS_OUTSIDE, COMPONENTS_MASKED, COMPONENTS_K, COMPONENTS_LARGEST, COMPONENTS_STATUS = 0, 1, 2, 3, 4, 5, 6
+COMPONENTS_OK, COMPONENTS_BAD_MASK, COMPONENTS_GAVE_UP = 0, 1, 2
+COMPONENTS_REMOVE_KEPT, COMPONENTS_REMOVE_SMALL, COMPONENTS_REMOVED, COMPONENTS_SURVIVED = 0, 1, 2, 3
+COMPONENTS_FIELDS = (('label', torch.int32, ()), ('voxels', torch.int32, ()), ('points', torch.int64, ()), ('moving', torch.int64, ()),
+                     ('sum_q', torch.int64, (3,)), ('centroid', torch.float32, (3,)), ('lo', torch.int32, (3,)), ('hi', torch.int32, (3,)),
+                     ('t_first', torch.int32, ()), ('t_last', torch.int32, ()), ('first_row', torch.int32, ()))
+
+
+def accum_components(tables, m, min_count, max_moving_fraction, mask, radius, out=None, counters=None):
+    """The connected components of the first m rows of a map; see include/pcacc.h (C11).  mask [V] u8 over accum_extract's rows under the same filter,
+    or None.  out: a dict of the COMPONENTS_FIELDS tensors (m rows each) to write into (None = new ones), counters [7] i64 likewise.
+    -> out with 'counters' added: the caller reads the counters and slices label to the kept count, the tables to K.  Nothing is read back."""
+    keys, acc, stamps, cap = _accum_tables(tables, 'accum_components')
+    dev = tables[0].device
+    m = int(m)
+    if mask is not None and mask.dim() != 1:
+        raise NativeError('accum_components: mask must be [V], got %s' % (tuple(mask.shape),))
+    if out is None:
+        out = {name: torch.empty((m,) + shape, dtype=dtype, device=dev) for name, dtype, shape in COMPONENTS_FIELDS}
+    for name, dtype, shape in COMPONENTS_FIELDS:
+        if tuple(out[name].shape) != (m,) + shape:
+            raise NativeError('accum_components: out[%r] must be %s, got %s' % (name, (m,) + shape, tuple(out[name].shape)))
+    if counters is None:
+        counters = torch.empty((COMPONENTS_COUNTERS,), dtype=torch.int64, device=dev)
+    if tuple(counters.shape) != (COMPONENTS_COUNTERS,):
+        raise NativeError('accum_components: counters must be [%d] int64' % COMPONENTS_COUNTERS)
+    (o_label, o_voxels, o_points, o_moving, o_sum_q, o_centroid, o_lo, o_hi, o_first, o_last,
+     o_row) = [_dev(out[name], dtype, name) if m else None for name, dtype, _ in COMPONENTS_FIELDS]
+    mask_rows = 0 if mask is None else mask.shape[0]
+    ws = _workspace(lib().pcacc_accum_components_workspace_bytes, dev, m)
+    _check(lib().pcacc_accum_components(keys, acc, stamps, cap, m, int(min_count), 0 if max_moving_fraction is None else 1,
+                                        0.0 if max_moving_fraction is None else float(max_moving_fraction),
+                                        _dev(mask, torch.uint8, 'mask') if mask is not None else None, mask_rows, int(radius), o_label, o_voxels, o_points,
+                                        o_moving, o_sum_q, o_centroid, o_lo, o_hi, o_first, o_last, o_row,
+                                        _dev(counters, torch.int64, 'counters'), _dev(ws), ws.numel(), _stream()), 'accum_components')
+    res = dict(out)
+    res['counters'] = counters
+    return res
+
+
+def accum_remove_components(tables_in, m, pierced_in, min_count, max_moving_fraction, first, min_voxels, min_points, dry_run, tables_out, pierced_out,
+                            counters, state):
+    """The first m rows of a map without the rows of its small components, out of place; see include/pcacc.h (C11).  first: what accum_components
+    returned on this map under this filter (label, voxels, points, counters are read, on the device).  tables_out, pierced_out, state as for
+    accum_prune.  Writes counters [4] i64 (kept, small, components removed, components kept) and, unless dry_run, the tables and
+    state[ACCUM_NUM_VOXELS]; nothing is read back."""
+    ik, ia, is_, icap = _accum_tables(tables_in, 'accum_remove_components input')
+    m = int(m)
+    if pierced_in is not None and tuple(pierced_in.shape) != (icap,):
+        raise NativeError('accum_remove_components: pierced_in must be [cap], got %s' % (tuple(pierced_in.shape),))
+    if tuple(counters.shape) != (COMPONENTS_REMOVE_COUNTERS,):
+        raise NativeError('accum_remove_components: counters must be [%d] int64' % COMPONENTS_REMOVE_COUNTERS)
+    for name, dtype in (('label', torch.int32), ('voxels', torch.int32), ('points', torch.int64)):
+        if tuple(first[name].shape) != (m,):
+            raise NativeError('accum_remove_components: first[%r] must be [%d], got %s' % (name, m, tuple(first[name].shape)))
+    if tuple(first['counters'].shape) != (COMPONENTS_COUNTERS,):
+        raise NativeError('accum_remove_components: first[\'counters\'] must be [%d] int64' % COMPONENTS_COUNTERS)
+    ok = oa = os_ = op = st = None
+    ocap = icap
+    if tables_out is not None:
+        ok, oa, os_, ocap = _accum_tables(tables_out, 'accum_remove_components output')
+        if pierced_out is not None:
+            if tuple(pierced_out.shape) != (ocap,):
+                raise NativeError('accum_remove_components: pierced_out must be [cap], got %s' % (tuple(pierced_out.shape),))
+            op = _dev(pierced_out, torch.int32, 'pierced_out')
+    if state is not None:
+        if tuple(state.shape) != (ACCUM_STATE_WORDS,):
+            raise NativeError('accum_remove_components: state must be [%d] int64' % ACCUM_STATE_WORDS)
+        st = _dev(state, torch.int64, 'state')
+    ws = _workspace(lib().pcacc_accum_components_workspace_bytes, tables_in[0].device, m)
+    _check(lib().pcacc_accum_remove_components(ik, ia, is_, _dev(pierced_in, torch.int32, 'pierced_in') if pierced_in is not None else None, icap, m,
+                                               int(min_count), 0 if max_moving_fraction is None else 1,
+                                               0.0 if max_moving_fraction is None else float(max_moving_fraction),
+                                               _dev(first['label'], torch.int32, 'label') if m else None,
+                                               _dev(first['voxels'], torch.int32, 'voxels') if m else None,
+                                               _dev(first['points'], torch.int64, 'points') if m else None,
+                                               _dev(first['counters'], torch.int64, 'components counters'), int(min_voxels), int(min_points),
+                                               1 if dry_run else 0, ok, oa, os_, op, ocap, _dev(counters, torch.int64, 'counters'), st, _dev(ws),
+                                               ws.numel(), _stream()), 'accum_remove_components')
+
+
 RAYCAST_MISS, RAYCAST_HIT, RAYCAST_TRUNCATED, RAYCAST_SKIPPED, RAYCAST_DROPPED = 0, 1, 2, 3, 4
 RAYCAST_COUNTERS = 7
 RAYCAST_N_RAYS, RAYCAST_N_DROPPED, RAYCAST_N_SKIPPED, RAYCAST_N_HIT, RAYCAST_N_MISSED, RAYCAST_N_TRUNCATED, RAYCAST_N_VISITS = 0, 1, 2, 3, 4, 5, 6
