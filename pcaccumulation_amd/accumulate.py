@@ -47,6 +47,67 @@ def _tables(capacity, device):
             torch.empty((2, capacity), dtype=torch.int32, device=device))
 
 
+# ---- what the methods that take a scan share: one copy of each check and of each piece of host arithmetic -----------------------------------
+def _scan_points(what, name, points, limit, items='points'):
+    """points (or targets) is a GPU tensor [n,3] of at most `limit` (a power of two) rows -> n."""
+    if not torch.is_tensor(points) or not points.is_cuda:
+        raise native.NativeError('%s: %s must be a tensor on the GPU; the HIP path has no CPU fallback' % (what, name))
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError('%s must be [n,3], got %s' % (name, tuple(points.shape)))
+    n = points.shape[0]
+    if n > limit:
+        raise ValueError('at most 2^%d %s per %s, got %d' % (limit.bit_length() - 1, items, what, n))
+    return n
+
+
+def _scan_rows(what, name, t, n):
+    """moving or origin_index: None, or [n] on the GPU."""
+    if t is not None:
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise native.NativeError('%s: %s must live on the GPU' % (what, name))
+        if tuple(t.shape) != (n,):
+            raise ValueError('%s must be [n], got %s' % (name, tuple(t.shape)))
+
+
+def _origins(origins):
+    """[3] or [S,3], tensor or array -> tensor [S,3], S >= 1."""
+    if not torch.is_tensor(origins):
+        origins = torch.from_numpy(np.ascontiguousarray(origins, dtype=np.float64))
+    if origins.dim() == 1:
+        origins = origins.reshape(1, -1)
+    if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape[0] < 1:
+        raise ValueError('origins must be [3] or [S,3] with S >= 1, got %s' % (tuple(origins.shape),))
+    return origins
+
+
+def _origin_rows(origin_index, n_origins):
+    if origin_index is None:
+        return None
+    # the entry point takes int32 rows: a row outside [0, S) stays outside after the cast
+    return origin_index.clamp(-1, n_origins).to(torch.int32).contiguous()
+
+
+def _n_batches(results, input_dict):
+    batch = input_dict['time_indice'][:, 0]
+    n_batches = results.get('_n_batches')
+    if n_batches is None:
+        n_batches = int(batch.max()) + 1 if batch.numel() else 1
+    return n_batches
+
+
+def _one_sample(results, input_dict, what):
+    n_batches = _n_batches(results, input_dict)
+    if n_batches != 1:
+        raise ValueError('%s: one sample per batch, got %d' % (what, n_batches))
+
+
+def _sensor_origins(results, sensor_offset):
+    """The sensor position of every frame in the anchor frame: results['ego_motion_est'][0, t] applied to sensor_offset, float64, ((a + b) + c) + d."""
+    ego = results['ego_motion_est'][0].detach().to(torch.float64)                       # [T,4,4]
+    sx, sy, sz = (float(v) for v in sensor_offset)
+    return ((ego[:, :3, 0] * sx + ego[:, :3, 1] * sy) + ego[:, :3, 2] * sz) + ego[:, :3, 3]
+
+
 class AccumulatedCloud(object):
     def __init__(self, voxel_size, device='cuda', capacity=1 << 20):
         voxel_size = float(voxel_size)
@@ -98,18 +159,8 @@ class AccumulatedCloud(object):
     def add(self, points, pose=None, moving=None, stamp=0):
         """points [n,3] f32 (device), pose [4,4] window-to-world (tensor or array; None = identity), moving [n] bool / integer (non-zero = predicted
         moving; None = none), stamp: one integer for the call.  Only the map's eight state words are read back."""
-        if not torch.is_tensor(points) or not points.is_cuda:
-            raise native.NativeError('add: points must be a tensor on the GPU; the HIP path has no CPU fallback')
-        if points.dim() != 2 or points.shape[1] != 3:
-            raise ValueError('points must be [n,3], got %s' % (tuple(points.shape),))
-        n = points.shape[0]
-        if n > native.ACCUM_MAX_POINTS:
-            raise ValueError('at most 2^30 points per add, got %d' % n)
-        if moving is not None:
-            if not moving.is_cuda:
-                raise native.NativeError('add: moving must live on the GPU')
-            if tuple(moving.shape) != (n,):
-                raise ValueError('moving must be [n], got %s' % (tuple(moving.shape),))
+        n = _scan_points('add', 'points', points, native.ACCUM_MAX_POINTS)
+        _scan_rows('add', 'moving', moving, n)
         if n == 0:
             return self
         self._ensure()
@@ -148,15 +199,13 @@ class AccumulatedCloud(object):
         moving = results['mos_est'].argmax(1) == 1
         if pose is not None and not torch.is_tensor(pose):
             pose = torch.from_numpy(np.ascontiguousarray(pose, dtype=np.float64))
-        batch = input_dict['time_indice'][:, 0]
         if pose is not None and pose.dim() == 3:
+            batch = input_dict['time_indice'][:, 0]
             for b in range(pose.shape[0]):
                 rows = torch.nonzero(batch == b).reshape(-1)
                 self.add(points.index_select(0, rows), pose[b], moving.index_select(0, rows), stamp)
             return self
-        n_batches = results.get('_n_batches')
-        if n_batches is None:
-            n_batches = int(batch.max()) + 1 if batch.numel() else 1
+        n_batches = _n_batches(results, input_dict)
         if n_batches != 1:
             raise ValueError('add_results: %d samples in the batch need one pose per sample, [B,4,4]' % n_batches)
         return self.add(points, pose, moving, stamp)
@@ -220,18 +269,8 @@ class AccumulatedCloud(object):
         Every call computes the normals anew, because the rows move with every add: the cost of one normals() call (profiles/accum_normals_bench.txt:
         2.78 ms at 8.0 M voxels and r = 1 without a filter, 1.07 ms with min_count=2, max_moving_fraction=0.0) comes on top of the rounds (profiles/accum_register_bench.txt: about
         2 ms per round at 800 k points against 2 - 8 M voxels).  Only the kept count that normals() reads is read back."""
-        if not torch.is_tensor(points) or not points.is_cuda:
-            raise native.NativeError('register: points must be a tensor on the GPU; the HIP path has no CPU fallback')
-        if points.dim() != 2 or points.shape[1] != 3:
-            raise ValueError('points must be [n,3], got %s' % (tuple(points.shape),))
-        n = points.shape[0]
-        if n > native.REGISTER_MAX_POINTS:
-            raise ValueError('at most 2^24 points per register, got %d' % n)
-        if moving is not None:
-            if not moving.is_cuda:
-                raise native.NativeError('register: moving must live on the GPU')
-            if tuple(moving.shape) != (n,):
-                raise ValueError('moving must be [n], got %s' % (tuple(moving.shape),))
+        n = _scan_points('register', 'points', points, native.REGISTER_MAX_POINTS)
+        _scan_rows('register', 'moving', moving, n)
         max_distance = self.voxel_size if max_distance is None else float(max_distance)
         if not 0.0 < max_distance <= self.voxel_size:
             raise ValueError('max_distance must lie in (0, voxel_size = %r], got %r' % (self.voxel_size, max_distance))
@@ -247,12 +286,7 @@ class AccumulatedCloud(object):
 
     def register_results(self, results, input_dict, init_pose=None, **kw):
         """register() of a test / val-mode forward: results['rec_est'], with results['mos_est'].argmax(1) == 1 as `moving`.  One sample per batch."""
-        batch = input_dict['time_indice'][:, 0]
-        n_batches = results.get('_n_batches')
-        if n_batches is None:
-            n_batches = int(batch.max()) + 1 if batch.numel() else 1
-        if n_batches != 1:
-            raise ValueError('register_results: one sample per batch, got %d' % n_batches)
+        _one_sample(results, input_dict, 'register_results')
         return self.register(results['rec_est'], init_pose, results['mos_est'].argmax(1) == 1, **kw)
 
     # ---- query -------------------------------------------------------------------------------------------------------------------------
@@ -272,13 +306,7 @@ class AccumulatedCloud(object):
         require_normal=True matches only centroids with a valid normal: register()'s correspondences.
         counters [7] i64: points, invalid, occupied, kept, matched, with a normal, and native.QUERY_BAD_TABLE (always 0 from here).
         Nothing is read back beyond the kept count normals() reads when normals=True."""
-        if not torch.is_tensor(points) or not points.is_cuda:
-            raise native.NativeError('query: points must be a tensor on the GPU; the HIP path has no CPU fallback')
-        if points.dim() != 2 or points.shape[1] != 3:
-            raise ValueError('points must be [n,3], got %s' % (tuple(points.shape),))
-        n = points.shape[0]
-        if n > native.QUERY_MAX_POINTS:
-            raise ValueError('at most 2^30 points per query, got %d' % n)
+        _scan_points('query', 'points', points, native.QUERY_MAX_POINTS)
         max_distance = self.voxel_size if max_distance is None else float(max_distance)
         if not 0.0 < max_distance <= self.voxel_size:
             raise ValueError('max_distance must lie in (0, voxel_size = %r], got %r' % (self.voxel_size, max_distance))
@@ -299,12 +327,7 @@ class AccumulatedCloud(object):
 
     def query_results(self, results, input_dict, pose=None, **kw):
         """query() of a test / val-mode forward: results['rec_est'].  One sample per batch."""
-        batch = input_dict['time_indice'][:, 0]
-        n_batches = results.get('_n_batches')
-        if n_batches is None:
-            n_batches = int(batch.max()) + 1 if batch.numel() else 1
-        if n_batches != 1:
-            raise ValueError('query_results: one sample per batch, got %d' % n_batches)
+        _one_sample(results, input_dict, 'query_results')
         return self.query(results['rec_est'], pose, **kw)
 
     # ---- see through -------------------------------------------------------------------------------------------------------------------
@@ -318,25 +341,10 @@ class AccumulatedCloud(object):
         max_steps in [1, 2^16]: the most voxels one ray visits.
         Adds to a sidecar, int32 per row of the map, that add() carries along, and -> the counters (rays walked, dropped, skipped, truncated, hits)
         as one int64 device tensor, cumulative since clear().  Nothing is read back."""
-        if not torch.is_tensor(points) or not points.is_cuda:
-            raise native.NativeError('see_through: points must be a tensor on the GPU; the HIP path has no CPU fallback')
-        if points.dim() != 2 or points.shape[1] != 3:
-            raise ValueError('points must be [n,3], got %s' % (tuple(points.shape),))
-        n = points.shape[0]
-        if n > native.ACCUM_MAX_POINTS:
-            raise ValueError('at most 2^30 points per see_through, got %d' % n)
-        for name, t in (('moving', moving), ('origin_index', origin_index)):
-            if t is not None:
-                if not torch.is_tensor(t) or not t.is_cuda:
-                    raise native.NativeError('see_through: %s must live on the GPU' % name)
-                if tuple(t.shape) != (n,):
-                    raise ValueError('%s must be [n], got %s' % (name, tuple(t.shape)))
-        if not torch.is_tensor(origins):
-            origins = torch.from_numpy(np.ascontiguousarray(origins, dtype=np.float64))
-        if origins.dim() == 1:
-            origins = origins.reshape(1, -1)
-        if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape[0] < 1:
-            raise ValueError('origins must be [3] or [S,3] with S >= 1, got %s' % (tuple(origins.shape),))
+        n = _scan_points('see_through', 'points', points, native.ACCUM_MAX_POINTS)
+        _scan_rows('see_through', 'moving', moving, n)
+        _scan_rows('see_through', 'origin_index', origin_index, n)
+        origins = _origins(origins)
         margin = 2.0 * self.voxel_size if margin is None else float(margin)
         if not (margin >= 0.0 and np.isfinite(margin)):
             raise ValueError('margin must be a finite number >= 0, got %r' % margin)
@@ -350,26 +358,16 @@ class AccumulatedCloud(object):
             self._pierced = torch.zeros((self.capacity,), dtype=torch.int32, device=self.device)
             self._pierce_counters = torch.zeros((native.PIERCE_COUNTERS,), dtype=torch.int64, device=self.device)
         native.accum_pierce(points.detach().float().contiguous(), (moving != 0).to(torch.uint8).contiguous() if moving is not None else None,
-                            origins.to(device=self.device, dtype=torch.float64).contiguous(),
-                            # the entry point takes int32 rows: a row outside [0, S) stays outside after the cast
-                            origin_index.clamp(-1, origins.shape[0]).to(torch.int32).contiguous() if origin_index is not None else None, pose, self.voxel_size, margin,
-                            max_range, stamp, int(max_steps), self._cur, self._n, self._pierced, self._pierce_counters)
+                            origins.to(device=self.device, dtype=torch.float64).contiguous(), _origin_rows(origin_index, origins.shape[0]), pose,
+                            self.voxel_size, margin, max_range, stamp, int(max_steps), self._cur, self._n, self._pierced, self._pierce_counters)
         return self._pierce_counters.clone()
 
     def see_through_results(self, results, input_dict, pose=None, sensor_offset=(0, 0, 0), **kw):
         """see_through() of a test / val-mode forward: the points are results['rec_est'] with results['mos_est'].argmax(1) == 1 as `moving`, the origin of
         a point is the sensor position of its frame (input_dict['time_indice'][:, 1]) in the anchor frame, results['ego_motion_est'][0, t] applied to
         sensor_offset (the sensor in its own frame).  One sample per batch."""
-        batch = input_dict['time_indice'][:, 0]
-        n_batches = results.get('_n_batches')
-        if n_batches is None:
-            n_batches = int(batch.max()) + 1 if batch.numel() else 1
-        if n_batches != 1:
-            raise ValueError('see_through_results: one sample per batch, got %d' % n_batches)
-        ego = results['ego_motion_est'][0].detach().to(torch.float64)                       # [T,4,4]
-        sx, sy, sz = (float(v) for v in sensor_offset)
-        origins = ((ego[:, :3, 0] * sx + ego[:, :3, 1] * sy) + ego[:, :3, 2] * sz) + ego[:, :3, 3]
-        return self.see_through(results['rec_est'], origins, input_dict['time_indice'][:, 1], pose, results['mos_est'].argmax(1) == 1, **kw)
+        _one_sample(results, input_dict, 'see_through_results')
+        return self.see_through(results['rec_est'], _sensor_origins(results, sensor_offset), input_dict['time_indice'][:, 1], pose, results['mos_est'].argmax(1) == 1, **kw)
 
     # ---- raycast -----------------------------------------------------------------------------------------------------------------------
     def raycast(self, targets, origins, origin_index=None, pose=None, max_range=None, min_range=0.0, margin=0.0, min_count=1, max_moving_fraction=None,
@@ -388,24 +386,9 @@ class AccumulatedCloud(object):
         along the ray, within sqrt(3) voxel_size + 2^-17 of range_in; length [n] f64: origin to target; visits [n] i32: voxels visited.
         Without a hit row = -1, coords = point = 0 and range_in = depth = +inf.
         counters [7] i64: rays, dropped, skipped, hit, missed, truncated, visits of all rays.  Nothing is read back."""
-        if not torch.is_tensor(targets) or not targets.is_cuda:
-            raise native.NativeError('raycast: targets must be a tensor on the GPU; the HIP path has no CPU fallback')
-        if targets.dim() != 2 or targets.shape[1] != 3:
-            raise ValueError('targets must be [n,3], got %s' % (tuple(targets.shape),))
-        n = targets.shape[0]
-        if n > native.RAYCAST_MAX_RAYS:
-            raise ValueError('at most 2^30 rays per raycast, got %d' % n)
-        if origin_index is not None:
-            if not torch.is_tensor(origin_index) or not origin_index.is_cuda:
-                raise native.NativeError('raycast: origin_index must live on the GPU')
-            if tuple(origin_index.shape) != (n,):
-                raise ValueError('origin_index must be [n], got %s' % (tuple(origin_index.shape),))
-        if not torch.is_tensor(origins):
-            origins = torch.from_numpy(np.ascontiguousarray(origins, dtype=np.float64))
-        if origins.dim() == 1:
-            origins = origins.reshape(1, -1)
-        if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape[0] < 1:
-            raise ValueError('origins must be [3] or [S,3] with S >= 1, got %s' % (tuple(origins.shape),))
+        n = _scan_points('raycast', 'targets', targets, native.RAYCAST_MAX_RAYS, 'rays')
+        _scan_rows('raycast', 'origin_index', origin_index, n)
+        origins = _origins(origins)
         min_range, margin = float(min_range), float(margin)
         if not (min_range >= 0.0 and np.isfinite(min_range)):
             raise ValueError('min_range must be a finite number >= 0, got %r' % min_range)
@@ -422,23 +405,13 @@ class AccumulatedCloud(object):
         pose = self._pose(pose)
         self._ensure()
         return native.accum_raycast(targets.detach().float().contiguous(), origins.to(device=self.device, dtype=torch.float64).contiguous(),
-                                    # the entry point takes int32 rows: a row outside [0, S) stays outside after the cast
-                                    origin_index.clamp(-1, origins.shape[0]).to(torch.int32).contiguous() if origin_index is not None else None, pose,
-                                    self.voxel_size, min_range, max_range, margin, int(max_steps), self._cur, self._n, min_count, max_moving_fraction)
+                                    _origin_rows(origin_index, origins.shape[0]), pose, self.voxel_size, min_range, max_range, margin, int(max_steps), self._cur, self._n, min_count, max_moving_fraction)
 
     def raycast_results(self, results, input_dict, pose=None, sensor_offset=(0, 0, 0), **kw):
         """raycast() of a test / val-mode forward: the targets are results['rec_est'], the origin of a target is the sensor position of its frame, built
         as see_through_results builds it.  One sample per batch."""
-        batch = input_dict['time_indice'][:, 0]
-        n_batches = results.get('_n_batches')
-        if n_batches is None:
-            n_batches = int(batch.max()) + 1 if batch.numel() else 1
-        if n_batches != 1:
-            raise ValueError('raycast_results: one sample per batch, got %d' % n_batches)
-        ego = results['ego_motion_est'][0].detach().to(torch.float64)                       # [T,4,4]
-        sx, sy, sz = (float(v) for v in sensor_offset)
-        origins = ((ego[:, :3, 0] * sx + ego[:, :3, 1] * sy) + ego[:, :3, 2] * sz) + ego[:, :3, 3]
-        return self.raycast(results['rec_est'], origins, input_dict['time_indice'][:, 1], pose, **kw)
+        _one_sample(results, input_dict, 'raycast_results')
+        return self.raycast(results['rec_est'], _sensor_origins(results, sensor_offset), input_dict['time_indice'][:, 1], pose, **kw)
 
     def render_range_image(self, pose, height, width, fov_up, fov_down, max_range, **kw):
         """A range image of the map from a sensor at `pose` ([4,4] sensor-to-world; None = identity): one ray per pixel from the sensor's origin.  Row r

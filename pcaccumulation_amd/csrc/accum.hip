@@ -19,11 +19,11 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "scan.h"
-#include "accum_grid.h"
+#include "accum_launch.h"
 
 #define ACC_BLOCK 256
 #define ACC_MAX_POINTS ((int64_t)1 << 30)         // int scans and int row numbers
-#define ACC_MAX_CAPACITY ((int64_t)1 << 30)
+static_assert(ACC_BLOCK == ACCUM_KEEP_BLOCK, "extract launches accum_keep_kernel on its own grid");
 
 struct AccHdr {                                     // device words of one call, zeroed first
     unsigned long long dropped;                     // invalid points of this call
@@ -87,14 +87,6 @@ static __global__ __launch_bounds__(ACC_BLOCK) void accum_heads_kernel(const uns
         const unsigned long long k = keys[i];
         head[i] = (k != ACC_INVALID_KEY && (i == 0 || keys[i - 1] != k)) ? 1 : 0;
     }
-}
-
-static void acc_scan(const int *in, int64_t n, int *chunk, int *out, hipStream_t st)       // out[0..n] exclusive, out[n] = total
-{
-    const int nc = pcacc_chunks(n);
-    hipLaunchKernelGGL(chunk_sums_i32, dim3(nc), dim3(256), 0, st, in, n, chunk);
-    hipLaunchKernelGGL(scan_chunk_sums, dim3(1), dim3(1024), 0, st, chunk, nc, (int *)nullptr, -1);
-    hipLaunchKernelGGL(chunk_scan_i32, dim3(nc), dim3(256), 0, st, in, n, (const int *)chunk, out, 1, (int *)nullptr);
 }
 
 // window tables [ACC_FIELDS][n]: rows below the number of window voxels cleared
@@ -307,7 +299,7 @@ extern "C" int pcacc_accum_add(const float *points, int64_t n, const double *pos
 {
     if (n < 1 || n > ACC_MAX_POINTS || !points || !state || !workspace) return PCACC_E_ARG;
     if (!(voxel_size > 0.0) || !(voxel_size - voxel_size == 0.0)) return PCACC_E_ARG;
-    if (in_capacity < 0 || in_capacity > ACC_MAX_CAPACITY || out_capacity < 1 || out_capacity > ACC_MAX_CAPACITY) return PCACC_E_ARG;
+    if (in_capacity < 0 || in_capacity > ACCUM_MAX_CAPACITY || out_capacity < 1 || out_capacity > ACCUM_MAX_CAPACITY) return PCACC_E_ARG;
     if (in_capacity > 0 && (!in_keys || !in_acc || !in_stamps)) return PCACC_E_ARG;
     if (!out_keys || !out_acc || !out_stamps) return PCACC_E_ARG;
     if (out_keys == in_keys || out_acc == in_acc || out_stamps == in_stamps) return PCACC_E_ARG;     // the merge is out of place
@@ -326,14 +318,14 @@ extern "C" int pcacc_accum_add(const float *points, int64_t n, const double *pos
     if (rocprim::radix_sort_pairs(w.sort_tmp, w.sort_tmp_bytes, w.key_a, w.key_b, w.idx_a, w.idx_b, (size_t)n, 0, 64, st) != hipSuccess)
         return PCACC_E_LAUNCH;
     hipLaunchKernelGGL(accum_heads_kernel, dim3(grid), dim3(ACC_BLOCK), 0, st, (const unsigned long long *)w.key_b, n, w.head);
-    acc_scan(w.head, n, w.chunk, w.vox, st);                                                  // vox[n] = window voxels
+    pcacc_scan_i32(w.head, n, w.chunk, w.vox, st);                                                  // vox[n] = window voxels
     hipLaunchKernelGGL(accum_zero_kernel, dim3(pcacc_grid(n * ACC_FIELDS, ACC_BLOCK)), dim3(ACC_BLOCK), 0, st, w.wacc, (const int *)(w.vox + n), n);
     hipLaunchKernelGGL(accum_reduce_kernel, dim3(grid), dim3(ACC_BLOCK), 0, st, points, n, pose, moving, voxel_size,
                        (const unsigned long long *)w.key_b, (const int *)w.idx_b, (const int *)w.head, (const int *)w.vox, w.wkey, w.wacc);
     PCACC_CHECK_LAUNCH();
     hipLaunchKernelGGL(accum_search_kernel, dim3(grid), dim3(ACC_BLOCK), 0, st, (const unsigned long long *)w.wkey, (const int *)(w.vox + n), n,
                        (const unsigned long long *)in_keys, (const AccHdr *)w.hdr, w.miss, w.pos);
-    acc_scan(w.miss, n, w.chunk, w.mrank, st);                                                // mrank[n] = misses
+    pcacc_scan_i32(w.miss, n, w.chunk, w.mrank, st);                                                // mrank[n] = misses
     hipLaunchKernelGGL(accum_decide_kernel, dim3(1), dim3(1), 0, st, state, w.hdr, (const int *)w.vox, (const int *)w.mrank, n, out_capacity);
     PCACC_CHECK_LAUNCH();
     if (in_capacity > 0)
@@ -349,13 +341,6 @@ extern "C" int pcacc_accum_add(const float *points, int64_t n, const double *pos
 }
 
 // ---- extract ---------------------------------------------------------------------------------------------------------------------------
-static __global__ __launch_bounds__(ACC_BLOCK) void accum_keep_kernel(const long long *__restrict__ acc, int64_t capacity, int64_t m, int64_t min_count,
-                                                                       int use_fraction, double max_moving_fraction, int *__restrict__ keep)
-{
-    for (int64_t i = (int64_t)blockIdx.x * ACC_BLOCK + threadIdx.x; i < m; i += (int64_t)gridDim.x * ACC_BLOCK)
-        keep[i] = accum_keep(acc[accum_field(0, i, capacity)], acc[accum_field(1, i, capacity)], min_count, use_fraction != 0, max_moving_fraction) ? 1 : 0;
-}
-
 static __global__ __launch_bounds__(ACC_BLOCK) void accum_compact_kernel(const unsigned long long *__restrict__ keys, const long long *__restrict__ acc,
                                                                           const int32_t *__restrict__ stamps, int64_t capacity, int64_t m,
                                                                           const int *__restrict__ keep, const int *__restrict__ kpos,
@@ -396,7 +381,7 @@ static size_t acc_extract_ws(int64_t m, int **keep, int **kpos, int **chunk, cha
 
 extern "C" int pcacc_accum_extract_workspace_bytes(int64_t m, size_t *bytes)
 {
-    if (!bytes || m < 0 || m > ACC_MAX_CAPACITY) return PCACC_E_ARG;
+    if (!bytes || m < 0 || m > ACCUM_MAX_CAPACITY) return PCACC_E_ARG;
     int *a, *b, *c;
     *bytes = acc_extract_ws(m > 0 ? m : 1, &a, &b, &c, nullptr);
     return PCACC_OK;
@@ -407,16 +392,16 @@ extern "C" int pcacc_accum_extract(const int64_t *keys, const int64_t *acc, cons
                                    int64_t *out_moving, int32_t *out_t_first, int32_t *out_t_last, int64_t *out_n,
                                    void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (m < 0 || capacity < m || capacity > ACC_MAX_CAPACITY || !out_n) return PCACC_E_ARG;
+    if (m < 0 || capacity < m || capacity > ACCUM_MAX_CAPACITY || !out_n) return PCACC_E_ARG;
     hipStream_t st = pcacc_stream(stream);
     if (m == 0) return hipMemsetAsync(out_n, 0, sizeof(int64_t), st) == hipSuccess ? PCACC_OK : PCACC_E_LAUNCH;
     if (!keys || !acc || !stamps || !out_points || !out_coords || !out_count || !out_moving || !out_t_first || !out_t_last || !workspace) return PCACC_E_ARG;
     int *keep, *kpos, *chunk;
     if (workspace_bytes < acc_extract_ws(m, &keep, &kpos, &chunk, (char *)workspace)) return PCACC_E_WORKSPACE;
     const int grid = pcacc_grid(m, ACC_BLOCK);
-    hipLaunchKernelGGL(accum_keep_kernel, dim3(grid), dim3(ACC_BLOCK), 0, st, (const long long *)acc, capacity, m, min_count, (int)use_fraction,
+    hipLaunchKernelGGL(accum_keep_kernel, dim3(grid), dim3(ACC_BLOCK), 0, st, acc, capacity, m, min_count, (int)use_fraction,
                        max_moving_fraction, keep);
-    acc_scan(keep, m, chunk, kpos, st);
+    pcacc_scan_i32(keep, m, chunk, kpos, st);
     hipLaunchKernelGGL(accum_compact_kernel, dim3(grid), dim3(ACC_BLOCK), 0, st, (const unsigned long long *)keys, (const long long *)acc, stamps, capacity, m,
                        (const int *)keep, (const int *)kpos, out_points, out_coords, out_count, out_moving, out_t_first, out_t_last, out_n);
     PCACC_CHECK_LAUNCH();

@@ -22,10 +22,10 @@
 // the scan's, no inline assembly.
 #include "scan.h"
 #include "accum_components.h"
+#include "accum_launch.h"
 #include "accum_rows.h"
 
 #define ACCC_BLOCK 256
-#define ACCC_MAX_CAPACITY ((int64_t)1 << 30)        // as accum.hip: int scans and int row numbers
 
 static_assert(ACCC_COUNTERS == PCACC_COMPONENTS_COUNTERS && ACCC_C_ROWS == PCACC_COMPONENTS_ROWS && ACCC_C_PARTICIPATING == PCACC_COMPONENTS_PARTICIPATING &&
               ACCC_C_OUTSIDE == PCACC_COMPONENTS_OUTSIDE && ACCC_C_MASKED == PCACC_COMPONENTS_MASKED && ACCC_C_COMPONENTS == PCACC_COMPONENTS_K &&
@@ -60,13 +60,6 @@ static __device__ __forceinline__ int64_t accc_kept(const AcccMap &M)
     return kept > M.m ? M.m : (kept < 0 ? 0 : kept);
 }
 
-static __device__ __forceinline__ long long accc_wave_sum(long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 static __global__ __launch_bounds__(ACCC_BLOCK) void accc_init_kernel(int64_t m, int *__restrict__ parent)
 {
     for (int64_t j = (int64_t)blockIdx.x * ACCC_BLOCK + threadIdx.x; j < m; j += (int64_t)gridDim.x * ACCC_BLOCK) parent[j] = (int)j;
@@ -97,11 +90,8 @@ static __global__ __launch_bounds__(ACCC_BLOCK) void accc_link_kernel(AcccMap M,
         });
     }
     // every lane of the wave arrives here: one atomic per wave and non-zero counter
-    c_part = accc_wave_sum(c_part); c_masked = accc_wave_sum(c_masked);
-    if (lane_id() == 0) {
-        if (c_part) atomicAdd(&counters[ACCC_C_PARTICIPATING], (unsigned long long)c_part);
-        if (c_masked) atomicAdd(&counters[ACCC_C_MASKED], (unsigned long long)c_masked);
-    }
+    accum_wave_count(counters, ACCC_C_PARTICIPATING, c_part);
+    accum_wave_count(counters, ACCC_C_MASKED, c_masked);
     if (gave_up) atomicMax(&counters[ACCC_C_STATUS], (unsigned long long)ACCC_GAVE_UP);
 }
 
@@ -271,11 +261,8 @@ static __global__ __launch_bounds__(ACCC_BLOCK) void accc_compact_kernel(const u
                       accum_merge_dst(kpos[i], 0, kept));
     }
     // every lane of the wave arrives here: one atomic per wave and non-zero counter
-    c_kept = accc_wave_sum(c_kept); c_small = accc_wave_sum(c_small);
-    if (lane_id() == 0) {
-        if (c_kept) atomicAdd(&counters[ACCC_R_KEPT], (unsigned long long)c_kept);
-        if (c_small) atomicAdd(&counters[ACCC_R_SMALL], (unsigned long long)c_small);
-    }
+    accum_wave_count(counters, ACCC_R_KEPT, c_kept);
+    accum_wave_count(counters, ACCC_R_SMALL, c_small);
     if (!dry && blockIdx.x == 0 && threadIdx.x == 0) state[PCACC_ACCUM_NUM_VOXELS] = kept;
 }
 
@@ -288,21 +275,17 @@ static __global__ __launch_bounds__(ACCC_BLOCK) void accc_component_count_kernel
         const bool small = ok && accc_small(R.voxels[c], R.points[c], R.min_voxels, R.min_points);
         c_removed += small; c_kept += !small;
     }
-    c_removed = accc_wave_sum(c_removed); c_kept = accc_wave_sum(c_kept);
-    if (lane_id() == 0) {
-        if (c_removed) atomicAdd(&counters[ACCC_R_COMPONENTS_REMOVED], (unsigned long long)c_removed);
-        if (c_kept) atomicAdd(&counters[ACCC_R_COMPONENTS_KEPT], (unsigned long long)c_kept);
-    }
+    accum_wave_count(counters, ACCC_R_COMPONENTS_REMOVED, c_removed);
+    accum_wave_count(counters, ACCC_R_COMPONENTS_KEPT, c_kept);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------------------
-struct AcccWs { AccnRows rows; int64_t *kept; int *parent, *flag, *cid, *chunk; unsigned long long *vox64; };
+struct AcccWs : AccnRowsWs { int *parent, *flag, *cid, *chunk; unsigned long long *vox64; };
 
 static size_t accc_carve(AcccWs *w, char *base, int64_t m)                                   // m >= 1
 {
-    size_t off = accn_rows_carve(m, &w->rows, base);
+    size_t off = accn_rows_ws_carve(m, w, base);
     auto take = [&](size_t bytes) { char *p = base + off; off += pcacc_align(bytes); return p; };
-    w->kept = (int64_t *)take(sizeof(int64_t));
     w->parent = (int *)take((size_t)m * 4);
     w->flag = (int *)take((size_t)m * 4);
     w->cid = (int *)take((size_t)(m + 1) * 4);
@@ -311,25 +294,9 @@ static size_t accc_carve(AcccWs *w, char *base, int64_t m)                      
     return off;
 }
 
-static void accc_scan(const int *in, int64_t n, int *chunk, int *out, hipStream_t st)      // out[0..n] exclusive, out[n] = total -- as acc_scan of accum.hip
-{
-    const int nc = pcacc_chunks(n);
-    hipLaunchKernelGGL(chunk_sums_i32, dim3(nc), dim3(256), 0, st, in, n, chunk);
-    hipLaunchKernelGGL(scan_chunk_sums, dim3(1), dim3(1024), 0, st, chunk, nc, (int *)nullptr, -1);
-    hipLaunchKernelGGL(chunk_scan_i32, dim3(nc), dim3(256), 0, st, in, n, (const int *)chunk, out, 1, (int *)nullptr);
-}
-
-// [a, a + na) and [b, b + nb) share a byte; a NULL table shares nothing.
-static bool accc_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 extern "C" int pcacc_accum_components_workspace_bytes(int64_t m, size_t *bytes)
 {
-    if (!bytes || m < 0 || m > ACCC_MAX_CAPACITY) return PCACC_E_ARG;
+    if (!bytes || m < 0 || m > ACCUM_MAX_CAPACITY) return PCACC_E_ARG;
     AcccWs w;
     *bytes = accc_carve(&w, nullptr, m > 0 ? m : 1);
     return PCACC_OK;
@@ -341,7 +308,7 @@ extern "C" int pcacc_accum_components(const int64_t *keys, const int64_t *acc, c
                                       float *out_centroid, int32_t *out_lo, int32_t *out_hi, int32_t *out_t_first, int32_t *out_t_last,
                                       int32_t *out_first_row, int64_t *counters, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (m < 0 || capacity < m || capacity > ACCC_MAX_CAPACITY || radius < 1 || radius > ACCN_MAX_RADIUS || mask_rows < 0 || !counters) return PCACC_E_ARG;
+    if (m < 0 || capacity < m || capacity > ACCUM_MAX_CAPACITY || radius < 1 || radius > ACCN_MAX_RADIUS || mask_rows < 0 || !counters) return PCACC_E_ARG;
     AcccWs w;
     if (m > 0) {
         if (!keys || !acc || !stamps || !workspace || (mask_rows > 0 && !mask)) return PCACC_E_ARG;
@@ -366,7 +333,7 @@ extern "C" int pcacc_accum_components(const int64_t *keys, const int64_t *acc, c
     hipLaunchKernelGGL(accc_flatten_kernel, dim3(grid), dim3(ACCC_BLOCK), 0, st, M, w.parent);
     hipLaunchKernelGGL(accc_root_kernel, dim3(grid), dim3(ACCC_BLOCK), 0, st, M, (const int *)w.parent, w.flag);
     PCACC_CHECK_LAUNCH();
-    accc_scan(w.flag, m, w.chunk, w.cid, st);                                                // cid[m] = K
+    pcacc_scan_i32(w.flag, m, w.chunk, w.cid, st);                                                // cid[m] = K
     hipLaunchKernelGGL(accc_label_kernel, dim3(grid), dim3(ACCC_BLOCK), 0, st, M, (const int *)w.parent, (const int *)w.cid, out, w.vox64);
     hipLaunchKernelGGL(accc_stats_kernel, dim3(grid), dim3(ACCC_BLOCK), 0, st, M, out, w.vox64);
     hipLaunchKernelGGL(accc_finish_kernel, dim3(grid), dim3(ACCC_BLOCK), 0, st, m, out, (const unsigned long long *)w.vox64);
@@ -381,14 +348,9 @@ extern "C" int pcacc_accum_remove_components(const int64_t *in_keys, const int64
                                              int32_t *out_stamps, int32_t *out_pierced, int64_t out_capacity, int64_t *counters, int64_t *state,
                                              void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (m < 0 || in_capacity < m || in_capacity > ACCC_MAX_CAPACITY || out_capacity < m || out_capacity > ACCC_MAX_CAPACITY || !counters) return PCACC_E_ARG;
+    if (m < 0 || in_capacity < m || in_capacity > ACCUM_MAX_CAPACITY || out_capacity < m || out_capacity > ACCUM_MAX_CAPACITY || !counters) return PCACC_E_ARG;
     if (min_voxels < 0 || min_points < 0) return PCACC_E_ARG;
-    const int64_t *in_tab[4] = {in_keys, in_acc, (const int64_t *)in_stamps, (const int64_t *)in_pierced};
-    const int64_t *out_tab[4] = {out_keys, out_acc, (const int64_t *)out_stamps, (const int64_t *)out_pierced};
-    const size_t row_bytes[4] = {8, 8 * ACC_FIELDS, 4 * 2, 4};
-    for (int a = 0; a < 4; ++a)
-        for (int b = 0; b < 4; ++b)
-            if (accc_overlap(in_tab[a], row_bytes[a] * (size_t)in_capacity, out_tab[b], row_bytes[b] * (size_t)out_capacity)) return PCACC_E_ARG;
+    if (accum_tables_overlap(in_keys, in_acc, in_stamps, in_pierced, in_capacity, out_keys, out_acc, out_stamps, out_pierced, out_capacity)) return PCACC_E_ARG;
     AcccWs w;
     if (m > 0) {
         if (!in_keys || !in_acc || !in_stamps || !workspace || !label || !voxels || !points || !components_counters) return PCACC_E_ARG;
@@ -404,7 +366,7 @@ extern "C" int pcacc_accum_remove_components(const int64_t *in_keys, const int64
     R.m = m; R.min_voxels = min_voxels; R.min_points = min_points; R.dry_run = dry_run != 0 ? 1 : 0;
     const int grid = pcacc_grid(m, ACCC_BLOCK);
     hipLaunchKernelGGL(accc_small_kernel, dim3(grid), dim3(ACCC_BLOCK), 0, st, R, w.flag);
-    accc_scan(w.flag, m, w.chunk, w.cid, st);                                                // cid[m] = rows kept
+    pcacc_scan_i32(w.flag, m, w.chunk, w.cid, st);                                                // cid[m] = rows kept
     PCACC_CHECK_LAUNCH();
     hipLaunchKernelGGL(accc_compact_kernel, dim3(grid), dim3(ACCC_BLOCK), 0, st, (const unsigned long long *)in_keys, in_acc, in_stamps, in_pierced,
                        in_capacity, R, (const int *)w.flag, (const int *)w.cid, (unsigned long long *)out_keys, out_acc, out_stamps,

@@ -9,17 +9,11 @@
 // Everything a result depends on is the set of integer records, visited in key order: two runs give the same bits.
 #include "scan.h"
 #include "accum_normals.h"
+#include "accum_launch.h"
 #include "accum_rows.h"
 
 #define ACCN_BLOCK 256
-#define ACCN_MAX_CAPACITY ((int64_t)1 << 30)        // as accum.hip: int scans and int row numbers
-
-static __global__ __launch_bounds__(ACCN_BLOCK) void accn_keep_kernel(const int64_t *__restrict__ acc, int64_t capacity, int64_t m, int64_t min_count,
-                                                                       int use_fraction, double max_moving_fraction, int *__restrict__ keep)
-{
-    for (int64_t i = (int64_t)blockIdx.x * ACCN_BLOCK + threadIdx.x; i < m; i += (int64_t)gridDim.x * ACCN_BLOCK)
-        keep[i] = accum_keep(acc[accum_field(0, i, capacity)], acc[accum_field(1, i, capacity)], min_count, use_fraction != 0, max_moving_fraction) ? 1 : 0;
-}
+static_assert(ACCN_BLOCK == ACCUM_KEEP_BLOCK, "accn_rows_launch launches accum_keep_kernel on the grid of accn_dst_kernel");
 
 // keep[i] (0 / 1) becomes dst[i] in place; rows[dst[i]] = i.
 static __global__ __launch_bounds__(ACCN_BLOCK) void accn_dst_kernel(int *__restrict__ keep_dst, const int *__restrict__ kpos, int64_t m, int *__restrict__ rows,
@@ -71,11 +65,8 @@ int accn_rows_launch(const int64_t *acc, int64_t capacity, int64_t m, int64_t mi
                      int64_t *out_n, hipStream_t st)
 {
     const int grid = pcacc_grid(m, ACCN_BLOCK);
-    const int nc = pcacc_chunks(m);
-    hipLaunchKernelGGL(accn_keep_kernel, dim3(grid), dim3(ACCN_BLOCK), 0, st, acc, capacity, m, min_count, use_fraction, max_moving_fraction, t.dst);
-    hipLaunchKernelGGL(chunk_sums_i32, dim3(nc), dim3(256), 0, st, (const int *)t.dst, m, t.chunk);
-    hipLaunchKernelGGL(scan_chunk_sums, dim3(1), dim3(1024), 0, st, t.chunk, nc, (int *)nullptr, -1);
-    hipLaunchKernelGGL(chunk_scan_i32, dim3(nc), dim3(256), 0, st, (const int *)t.dst, m, (const int *)t.chunk, t.kpos, 1, (int *)nullptr);     // kpos[m] = kept
+    hipLaunchKernelGGL(accum_keep_kernel, dim3(grid), dim3(ACCN_BLOCK), 0, st, acc, capacity, m, min_count, use_fraction, max_moving_fraction, t.dst);
+    pcacc_scan_i32(t.dst, m, t.chunk, t.kpos, st);                                           // kpos[m] = kept
     PCACC_CHECK_LAUNCH();
     hipLaunchKernelGGL(accn_dst_kernel, dim3(grid), dim3(ACCN_BLOCK), 0, st, t.dst, (const int *)t.kpos, m, t.rows, out_n);
     PCACC_CHECK_LAUNCH();
@@ -84,7 +75,7 @@ int accn_rows_launch(const int64_t *acc, int64_t capacity, int64_t m, int64_t mi
 
 extern "C" int pcacc_accum_normals_workspace_bytes(int64_t m, size_t *bytes)
 {
-    if (!bytes || m < 0 || m > ACCN_MAX_CAPACITY) return PCACC_E_ARG;
+    if (!bytes || m < 0 || m > ACCUM_MAX_CAPACITY) return PCACC_E_ARG;
     AccnRows t;
     *bytes = accn_rows_carve(m > 0 ? m : 1, &t, nullptr);
     return PCACC_OK;
@@ -95,7 +86,7 @@ extern "C" int pcacc_accum_normals(const int64_t *keys, const int64_t *acc, cons
                                    int64_t n_viewpoints, int64_t stamp_base, float *out_normals, float *out_eigenvalues, int32_t *out_neighbors,
                                    uint8_t *out_flags, int64_t *out_n, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (m < 0 || capacity < m || capacity > ACCN_MAX_CAPACITY || !out_n) return PCACC_E_ARG;
+    if (m < 0 || capacity < m || capacity > ACCUM_MAX_CAPACITY || !out_n) return PCACC_E_ARG;
     if (radius < 1 || radius > ACCN_MAX_RADIUS || min_neighbors < ACCN_MIN_NEIGHBORS || n_viewpoints < 0) return PCACC_E_ARG;
     if (n_viewpoints > 0 && !viewpoints) return PCACC_E_ARG;
     hipStream_t st = pcacc_stream(stream);

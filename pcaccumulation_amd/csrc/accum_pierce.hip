@@ -5,22 +5,15 @@
 // counted visit on pierced[row], and one per wave and counter after a reduction over the 64 lanes.  No floating-point atomics, no LDS, no inline assembly.
 #include "common.h"
 #include "accum_pierce.h"
+#include "accum_launch.h"
 
 #define ACCP_BLOCK 256
 #define ACCP_MAX_POINTS ((int64_t)1 << 30)
-#define ACCP_MAX_CAPACITY ((int64_t)1 << 30)        // as accum.hip
 
 struct AccpHit {
     int32_t *pierced;
     __device__ __forceinline__ void operator()(int64_t pos) const { atomicAdd(&pierced[pos], 1); }
 };
-
-static __device__ __forceinline__ long long accp_wave_sum(long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 static __global__ __launch_bounds__(ACCP_BLOCK) void accp_pierce_kernel(const float *__restrict__ points, int64_t n, const uint8_t *__restrict__ moving,
                                                                          const double *__restrict__ origins, int64_t n_origins,
@@ -46,21 +39,17 @@ static __global__ __launch_bounds__(ACCP_BLOCK) void accp_pierce_kernel(const fl
         c_truncated += r.truncated; c_hits += r.hits;
     }
     // every lane of the wave arrives here: one atomic per wave and counter
-    c_walked = accp_wave_sum(c_walked); c_dropped = accp_wave_sum(c_dropped); c_skipped = accp_wave_sum(c_skipped);
-    c_truncated = accp_wave_sum(c_truncated); c_hits = accp_wave_sum(c_hits);
-    if (lane_id() == 0) {
-        if (c_walked) atomicAdd(&counters[PCACC_PIERCE_WALKED], (unsigned long long)c_walked);
-        if (c_dropped) atomicAdd(&counters[PCACC_PIERCE_DROPPED], (unsigned long long)c_dropped);
-        if (c_skipped) atomicAdd(&counters[PCACC_PIERCE_SKIPPED], (unsigned long long)c_skipped);
-        if (c_truncated) atomicAdd(&counters[PCACC_PIERCE_TRUNCATED], (unsigned long long)c_truncated);
-        if (c_hits) atomicAdd(&counters[PCACC_PIERCE_HITS], (unsigned long long)c_hits);
-    }
+    accum_wave_count(counters, PCACC_PIERCE_WALKED, c_walked);
+    accum_wave_count(counters, PCACC_PIERCE_DROPPED, c_dropped);
+    accum_wave_count(counters, PCACC_PIERCE_SKIPPED, c_skipped);
+    accum_wave_count(counters, PCACC_PIERCE_TRUNCATED, c_truncated);
+    accum_wave_count(counters, PCACC_PIERCE_HITS, c_hits);
 }
 
 // No launch of C7 takes scratch memory today; the pair of entry points keeps the calling convention of C4 - C6.
 extern "C" int pcacc_accum_pierce_workspace_bytes(int64_t n, int64_t m, size_t *bytes)
 {
-    if (!bytes || n < 0 || n > ACCP_MAX_POINTS || m < 0 || m > ACCP_MAX_CAPACITY) return PCACC_E_ARG;
+    if (!bytes || n < 0 || n > ACCP_MAX_POINTS || m < 0 || m > ACCUM_MAX_CAPACITY) return PCACC_E_ARG;
     *bytes = 0;
     return PCACC_OK;
 }
@@ -71,7 +60,7 @@ extern "C" int pcacc_accum_pierce(const float *points, int64_t n, const uint8_t 
                                   int64_t m, int32_t *pierced, int64_t *counters, void *workspace, size_t workspace_bytes, void *stream)
 {
     (void)workspace; (void)workspace_bytes;
-    if (n < 0 || n > ACCP_MAX_POINTS || n_origins < 1 || m < 0 || capacity < m || capacity > ACCP_MAX_CAPACITY) return PCACC_E_ARG;
+    if (n < 0 || n > ACCP_MAX_POINTS || n_origins < 1 || m < 0 || capacity < m || capacity > ACCUM_MAX_CAPACITY) return PCACC_E_ARG;
     if (!(voxel_size > 0.0) || !(voxel_size - voxel_size == 0.0)) return PCACC_E_ARG;
     if (!(margin >= 0.0) || !(margin - margin == 0.0) || max_range != max_range) return PCACC_E_ARG;
     if (max_steps < 1 || max_steps > ACCP_MAX_STEPS || !counters) return PCACC_E_ARG;

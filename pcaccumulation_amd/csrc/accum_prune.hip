@@ -12,9 +12,9 @@
 // assembly; nothing is read back.
 #include "scan.h"
 #include "accum_prune.h"
+#include "accum_launch.h"
 
 #define ACCR_BLOCK 256
-#define ACCR_MAX_CAPACITY ((int64_t)1 << 30)        // as accum.hip: int scans and int row numbers
 
 static __global__ __launch_bounds__(ACCR_BLOCK) void accr_reason_kernel(const unsigned long long *__restrict__ keys, const int64_t *__restrict__ acc,
                                                                          const int32_t *__restrict__ stamps, const int32_t *__restrict__ pierced,
@@ -56,13 +56,6 @@ static __global__ __launch_bounds__(ACCR_BLOCK) void accr_isolated_kernel(const 
     }
 }
 
-static __device__ __forceinline__ long long accr_wave_sum(long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 static __global__ __launch_bounds__(ACCR_BLOCK) void accr_compact_kernel(const unsigned long long *__restrict__ in_keys, const int64_t *__restrict__ in_acc,
                                                                           const int32_t *__restrict__ in_stamps, const int32_t *__restrict__ in_pierced,
                                                                           int64_t in_capacity, int64_t m, const int *__restrict__ flag,
@@ -83,16 +76,12 @@ static __global__ __launch_bounds__(ACCR_BLOCK) void accr_compact_kernel(const u
                       accum_merge_dst(kpos[i], 0, kept));
     }
     // every lane of the wave arrives here: one atomic per wave and non-zero counter
-    c_kept = accr_wave_sum(c_kept); c_filter = accr_wave_sum(c_filter); c_stale = accr_wave_sum(c_stale); c_box = accr_wave_sum(c_box);
-    c_pierced = accr_wave_sum(c_pierced); c_isolated = accr_wave_sum(c_isolated);
-    if (lane_id() == 0) {
-        if (c_kept) atomicAdd(&counters[PCACC_PRUNE_KEPT], (unsigned long long)c_kept);
-        if (c_filter) atomicAdd(&counters[PCACC_PRUNE_FILTER], (unsigned long long)c_filter);
-        if (c_stale) atomicAdd(&counters[PCACC_PRUNE_STALE], (unsigned long long)c_stale);
-        if (c_box) atomicAdd(&counters[PCACC_PRUNE_BOX], (unsigned long long)c_box);
-        if (c_pierced) atomicAdd(&counters[PCACC_PRUNE_PIERCED], (unsigned long long)c_pierced);
-        if (c_isolated) atomicAdd(&counters[PCACC_PRUNE_ISOLATED], (unsigned long long)c_isolated);
-    }
+    accum_wave_count(counters, PCACC_PRUNE_KEPT, c_kept);
+    accum_wave_count(counters, PCACC_PRUNE_FILTER, c_filter);
+    accum_wave_count(counters, PCACC_PRUNE_STALE, c_stale);
+    accum_wave_count(counters, PCACC_PRUNE_BOX, c_box);
+    accum_wave_count(counters, PCACC_PRUNE_PIERCED, c_pierced);
+    accum_wave_count(counters, PCACC_PRUNE_ISOLATED, c_isolated);
     if (!dry_run && blockIdx.x == 0 && threadIdx.x == 0) state[PCACC_ACCUM_NUM_VOXELS] = kept;
 }
 
@@ -111,25 +100,9 @@ static size_t accr_carve(int64_t m, AccrWs *t, char *base)
     return off;
 }
 
-static void accr_scan(const int *in, int64_t n, int *chunk, int *out, hipStream_t st)      // out[0..n] exclusive, out[n] = total -- as acc_scan of accum.hip
-{
-    const int nc = pcacc_chunks(n);
-    hipLaunchKernelGGL(chunk_sums_i32, dim3(nc), dim3(256), 0, st, in, n, chunk);
-    hipLaunchKernelGGL(scan_chunk_sums, dim3(1), dim3(1024), 0, st, chunk, nc, (int *)nullptr, -1);
-    hipLaunchKernelGGL(chunk_scan_i32, dim3(nc), dim3(256), 0, st, in, n, (const int *)chunk, out, 1, (int *)nullptr);
-}
-
-// [a, a + na) and [b, b + nb) share a byte; a NULL table shares nothing.
-static bool accr_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 extern "C" int pcacc_accum_prune_workspace_bytes(int64_t m, size_t *bytes)
 {
-    if (!bytes || m < 0 || m > ACCR_MAX_CAPACITY) return PCACC_E_ARG;
+    if (!bytes || m < 0 || m > ACCUM_MAX_CAPACITY) return PCACC_E_ARG;
     AccrWs t;
     *bytes = accr_carve(m > 0 ? m : 1, &t, nullptr);
     return PCACC_OK;
@@ -142,7 +115,7 @@ extern "C" int pcacc_accum_prune(const int64_t *in_keys, const int64_t *in_acc, 
                                  int64_t *out_acc, int32_t *out_stamps, int32_t *out_pierced, int64_t out_capacity, int64_t *counters, int64_t *state,
                                  void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (m < 0 || in_capacity < m || in_capacity > ACCR_MAX_CAPACITY || out_capacity < m || out_capacity > ACCR_MAX_CAPACITY || !counters) return PCACC_E_ARG;
+    if (m < 0 || in_capacity < m || in_capacity > ACCUM_MAX_CAPACITY || out_capacity < m || out_capacity > ACCUM_MAX_CAPACITY || !counters) return PCACC_E_ARG;
     if (min_neighbors < 0 || min_neighbors > ACCR_MAX_NEIGHBORS) return PCACC_E_ARG;
     if (min_neighbors > 0 && (radius < 1 || radius > ACCN_MAX_RADIUS)) return PCACC_E_ARG;
     if (use_ratio && !(ratio >= 0.0)) return PCACC_E_ARG;                                    // NaN or negative
@@ -151,12 +124,7 @@ extern "C" int pcacc_accum_prune(const int64_t *in_keys, const int64_t *in_acc, 
         for (int a = 0; a < 3; ++a)
             if (lo[a] > hi[a] || !accn_in_range(lo[a]) || !accn_in_range(hi[a])) return PCACC_E_ARG;
     }
-    const int64_t *in_tab[4] = {in_keys, in_acc, (const int64_t *)in_stamps, (const int64_t *)in_pierced};
-    const int64_t *out_tab[4] = {out_keys, out_acc, (const int64_t *)out_stamps, (const int64_t *)out_pierced};
-    const size_t row_bytes[4] = {8, 8 * ACC_FIELDS, 4 * 2, 4};
-    for (int a = 0; a < 4; ++a)
-        for (int b = 0; b < 4; ++b)
-            if (accr_overlap(in_tab[a], row_bytes[a] * (size_t)in_capacity, out_tab[b], row_bytes[b] * (size_t)out_capacity)) return PCACC_E_ARG;
+    if (accum_tables_overlap(in_keys, in_acc, in_stamps, in_pierced, in_capacity, out_keys, out_acc, out_stamps, out_pierced, out_capacity)) return PCACC_E_ARG;
     hipStream_t st = pcacc_stream(stream);
     AccrWs t;
     if (m > 0) {
@@ -173,14 +141,14 @@ extern "C" int pcacc_accum_prune(const int64_t *in_keys, const int64_t *in_acc, 
     const unsigned long long *keys = (const unsigned long long *)in_keys;
     const int grid = pcacc_grid(m, ACCR_BLOCK);
     hipLaunchKernelGGL(accr_reason_kernel, dim3(grid), dim3(ACCR_BLOCK), 0, st, keys, in_acc, in_stamps, in_pierced, in_capacity, m, P, t.flag, t.reason);
-    accr_scan(t.flag, m, t.chunk, t.kpos, st);                                               // kpos[m] = stage-A survivors
+    pcacc_scan_i32(t.flag, m, t.chunk, t.kpos, st);                                               // kpos[m] = stage-A survivors
     PCACC_CHECK_LAUNCH();
     if (min_neighbors > 0) {
         hipLaunchKernelGGL(accr_dst_kernel, dim3(grid), dim3(ACCR_BLOCK), 0, st, (const int *)t.flag, (const int *)t.kpos, m, t.dst, t.rows);
         // a lane runs (2r+1)^2 serial searches: many small workgroups spread over the CUs, as accum_normals.hip
         hipLaunchKernelGGL(accr_isolated_kernel, dim3(pcacc_grid(m, ACCR_BLOCK, 1 << 22)), dim3(ACCR_BLOCK), 0, st, keys, m, (const int *)t.dst,
                            (const int *)t.rows, (const int *)(t.kpos + m), (int)radius, (int)min_neighbors, t.flag, t.reason);
-        accr_scan(t.flag, m, t.chunk, t.kpos, st);                                           // kpos[m] = survivors of both stages
+        pcacc_scan_i32(t.flag, m, t.chunk, t.kpos, st);                                           // kpos[m] = survivors of both stages
         PCACC_CHECK_LAUNCH();
     }
     hipLaunchKernelGGL(accr_compact_kernel, dim3(grid), dim3(ACCR_BLOCK), 0, st, keys, in_acc, in_stamps, in_pierced, in_capacity, m, (const int *)t.flag,

@@ -10,32 +10,16 @@
 // inline assembly.  Every result is an integer, a copied record or a float64 computed in one order: two runs give the same bits.
 #include "scan.h"
 #include "accum_query.h"
+#include "accum_launch.h"
 #include "accum_rows.h"
 
 #define ACCQ_BLOCK 256
 #define ACCQ_MAX_POINTS ((int64_t)1 << 30)
-#define ACCQ_MAX_CAPACITY ((int64_t)1 << 30)        // as accum.hip
 
 static_assert(ACCQ_INVALID == PCACC_QUERY_INVALID && ACCQ_OCCUPIED == PCACC_QUERY_OCCUPIED && ACCQ_KEPT == PCACC_QUERY_KEPT &&
               ACCQ_MATCHED == PCACC_QUERY_MATCHED && ACCQ_NORMAL == PCACC_QUERY_NORMAL && ACCQ_COUNTERS == PCACC_QUERY_COUNTERS &&
               ACCQ_C_POINTS == PCACC_QUERY_N_POINTS && ACCQ_C_NORMAL == PCACC_QUERY_N_NORMAL && ACCQ_C_BAD_TABLE == PCACC_QUERY_BAD_TABLE,
               "accum_query.h and include/pcacc.h name the same bits and counters");
-
-struct AccqWs { AccnRows rows; int64_t *kept; };
-
-static size_t accq_carve(AccqWs *w, char *base, int64_t m)
-{
-    size_t off = accn_rows_carve(m > 0 ? m : 1, &w->rows, base);
-    w->kept = (int64_t *)(base + off);
-    return off + pcacc_align(sizeof(int64_t));
-}
-
-static __device__ __forceinline__ long long accq_wave_sum(long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 static __global__ __launch_bounds__(ACCQ_BLOCK) void accq_point_kernel(const float *__restrict__ points, int64_t n, const double *__restrict__ pose,
                                                                         AccqParams P, const int64_t *__restrict__ kept_ptr, AccqOut out,
@@ -56,24 +40,20 @@ static __global__ __launch_bounds__(ACCQ_BLOCK) void accq_point_kernel(const flo
         c_matched += (r.status & ACCQ_MATCHED) != 0; c_normal += (r.status & ACCQ_NORMAL) != 0;
     }
     // every lane of the wave arrives here: one atomic per wave and non-zero counter
-    c_points = accq_wave_sum(c_points); c_invalid = accq_wave_sum(c_invalid); c_occupied = accq_wave_sum(c_occupied); c_kept = accq_wave_sum(c_kept);
-    c_matched = accq_wave_sum(c_matched); c_normal = accq_wave_sum(c_normal);
-    if (lane_id() == 0) {
-        if (c_points) atomicAdd(&counters[ACCQ_C_POINTS], (unsigned long long)c_points);
-        if (c_invalid) atomicAdd(&counters[ACCQ_C_INVALID], (unsigned long long)c_invalid);
-        if (c_occupied) atomicAdd(&counters[ACCQ_C_OCCUPIED], (unsigned long long)c_occupied);
-        if (c_kept) atomicAdd(&counters[ACCQ_C_KEPT], (unsigned long long)c_kept);
-        if (c_matched) atomicAdd(&counters[ACCQ_C_MATCHED], (unsigned long long)c_matched);
-        if (c_normal) atomicAdd(&counters[ACCQ_C_NORMAL], (unsigned long long)c_normal);
-    }
+    accum_wave_count(counters, ACCQ_C_POINTS, c_points);
+    accum_wave_count(counters, ACCQ_C_INVALID, c_invalid);
+    accum_wave_count(counters, ACCQ_C_OCCUPIED, c_occupied);
+    accum_wave_count(counters, ACCQ_C_KEPT, c_kept);
+    accum_wave_count(counters, ACCQ_C_MATCHED, c_matched);
+    accum_wave_count(counters, ACCQ_C_NORMAL, c_normal);
     if (blockIdx.x == 0 && threadIdx.x == 0 && tables == ACCQ_BAD_TABLES) counters[ACCQ_C_BAD_TABLE] = 1;   // the memset left 0; no lane adds to this one
 }
 
 extern "C" int pcacc_accum_query_workspace_bytes(int64_t m, size_t *bytes)
 {
-    if (!bytes || m < 0 || m > ACCQ_MAX_CAPACITY) return PCACC_E_ARG;
-    AccqWs w;
-    *bytes = accq_carve(&w, nullptr, m);
+    if (!bytes || m < 0 || m > ACCUM_MAX_CAPACITY) return PCACC_E_ARG;
+    AccnRowsWs w;
+    *bytes = accn_rows_ws_carve(m, &w, nullptr);
     return PCACC_OK;
 }
 
@@ -84,15 +64,15 @@ extern "C" int pcacc_accum_query(const float *points, int64_t n, const double *p
                                  int32_t *out_t_last, int32_t *out_pierced, int32_t *out_row, float *out_nearest, double *out_distance,
                                  double *out_plane_distance, int64_t *counters, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (n < 0 || n > ACCQ_MAX_POINTS || m < 0 || capacity < m || capacity > ACCQ_MAX_CAPACITY || n_rows < 0 || n_rows > m) return PCACC_E_ARG;
+    if (n < 0 || n > ACCQ_MAX_POINTS || m < 0 || capacity < m || capacity > ACCUM_MAX_CAPACITY || n_rows < 0 || n_rows > m) return PCACC_E_ARG;
     if (!(voxel_size > 0.0) || !(voxel_size < 1e300) || !(max_distance > 0.0) || !(max_distance <= voxel_size)) return PCACC_E_ARG;
     if ((normals != nullptr) != (flags != nullptr) || (require_normal && !normals) || (n_rows > 0 && !normals)) return PCACC_E_ARG;
     if (!counters || !workspace || (m > 0 && (!keys || !acc || !stamps))) return PCACC_E_ARG;
     if (n > 0 && (!points || !out_status || !out_count || !out_moving || !out_t_first || !out_t_last || !out_pierced || !out_row || !out_nearest ||
                   !out_distance || !out_plane_distance))
         return PCACC_E_ARG;
-    AccqWs w;
-    if (workspace_bytes < accq_carve(&w, (char *)workspace, m)) return PCACC_E_ARG;
+    AccnRowsWs w;
+    if (workspace_bytes < accn_rows_ws_carve(m, &w, (char *)workspace)) return PCACC_E_ARG;
     hipStream_t st = pcacc_stream(stream);
     if (hipMemsetAsync(counters, 0, ACCQ_COUNTERS * sizeof(int64_t), st) != hipSuccess) return PCACC_E_LAUNCH;
     if (n == 0) return PCACC_OK;

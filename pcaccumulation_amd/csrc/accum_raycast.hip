@@ -9,11 +9,11 @@
 // inline assembly.  Every result is an integer, a copied value or a float64 computed in one order: two runs give the same bits.
 #include "scan.h"
 #include "accum_raycast.h"
+#include "accum_launch.h"
 #include "accum_rows.h"
 
 #define ACCY_BLOCK 256
 #define ACCY_MAX_RAYS ((int64_t)1 << 30)
-#define ACCY_MAX_CAPACITY ((int64_t)1 << 30)        // as accum.hip
 
 static_assert(ACCY_MISS == PCACC_RAYCAST_MISS && ACCY_HIT == PCACC_RAYCAST_HIT && ACCY_TRUNCATED == PCACC_RAYCAST_TRUNCATED &&
               ACCY_SKIPPED == PCACC_RAYCAST_SKIPPED && ACCY_DROPPED == PCACC_RAYCAST_DROPPED && ACCY_COUNTERS == PCACC_RAYCAST_COUNTERS &&
@@ -21,22 +21,6 @@ static_assert(ACCY_MISS == PCACC_RAYCAST_MISS && ACCY_HIT == PCACC_RAYCAST_HIT &
               ACCY_C_HIT == PCACC_RAYCAST_N_HIT && ACCY_C_MISSED == PCACC_RAYCAST_N_MISSED && ACCY_C_TRUNCATED == PCACC_RAYCAST_N_TRUNCATED &&
               ACCY_C_VISITS == PCACC_RAYCAST_N_VISITS,
               "accum_raycast.h and include/pcacc.h name the same codes and counters");
-
-struct AccyWs { AccnRows rows; int64_t *kept; };
-
-static size_t accy_carve(AccyWs *w, char *base, int64_t m)
-{
-    size_t off = accn_rows_carve(m > 0 ? m : 1, &w->rows, base);
-    w->kept = (int64_t *)(base + off);
-    return off + pcacc_align(sizeof(int64_t));
-}
-
-static __device__ __forceinline__ long long accy_wave_sum(long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 static __global__ __launch_bounds__(ACCY_BLOCK) void accy_ray_kernel(const float *__restrict__ targets, int64_t n, const double *__restrict__ origins,
                                                                       int64_t n_origins, const int32_t *__restrict__ origin_index,
@@ -61,24 +45,20 @@ static __global__ __launch_bounds__(ACCY_BLOCK) void accy_ray_kernel(const float
         c_missed += r.status == ACCY_MISS; c_truncated += r.status == ACCY_TRUNCATED; c_visits += r.visits;
     }
     // every lane of the wave arrives here: one atomic per wave and non-zero counter
-    c_rays = accy_wave_sum(c_rays); c_dropped = accy_wave_sum(c_dropped); c_skipped = accy_wave_sum(c_skipped); c_hit = accy_wave_sum(c_hit);
-    c_missed = accy_wave_sum(c_missed); c_truncated = accy_wave_sum(c_truncated); c_visits = accy_wave_sum(c_visits);
-    if (lane_id() == 0) {
-        if (c_rays) atomicAdd(&counters[ACCY_C_RAYS], (unsigned long long)c_rays);
-        if (c_dropped) atomicAdd(&counters[ACCY_C_DROPPED], (unsigned long long)c_dropped);
-        if (c_skipped) atomicAdd(&counters[ACCY_C_SKIPPED], (unsigned long long)c_skipped);
-        if (c_hit) atomicAdd(&counters[ACCY_C_HIT], (unsigned long long)c_hit);
-        if (c_missed) atomicAdd(&counters[ACCY_C_MISSED], (unsigned long long)c_missed);
-        if (c_truncated) atomicAdd(&counters[ACCY_C_TRUNCATED], (unsigned long long)c_truncated);
-        if (c_visits) atomicAdd(&counters[ACCY_C_VISITS], (unsigned long long)c_visits);
-    }
+    accum_wave_count(counters, ACCY_C_RAYS, c_rays);
+    accum_wave_count(counters, ACCY_C_DROPPED, c_dropped);
+    accum_wave_count(counters, ACCY_C_SKIPPED, c_skipped);
+    accum_wave_count(counters, ACCY_C_HIT, c_hit);
+    accum_wave_count(counters, ACCY_C_MISSED, c_missed);
+    accum_wave_count(counters, ACCY_C_TRUNCATED, c_truncated);
+    accum_wave_count(counters, ACCY_C_VISITS, c_visits);
 }
 
 extern "C" int pcacc_accum_raycast_workspace_bytes(int64_t m, size_t *bytes)
 {
-    if (!bytes || m < 0 || m > ACCY_MAX_CAPACITY) return PCACC_E_ARG;
-    AccyWs w;
-    *bytes = accy_carve(&w, nullptr, m);
+    if (!bytes || m < 0 || m > ACCUM_MAX_CAPACITY) return PCACC_E_ARG;
+    AccnRowsWs w;
+    *bytes = accn_rows_ws_carve(m, &w, nullptr);
     return PCACC_OK;
 }
 
@@ -89,15 +69,15 @@ extern "C" int pcacc_accum_raycast(const float *targets, int64_t n, const double
                                    double *out_range_in, double *out_depth, double *out_length, int32_t *out_visits, int64_t *counters, void *workspace,
                                    size_t workspace_bytes, void *stream)
 {
-    if (n < 0 || n > ACCY_MAX_RAYS || n_origins < 1 || m < 0 || capacity < m || capacity > ACCY_MAX_CAPACITY) return PCACC_E_ARG;
+    if (n < 0 || n > ACCY_MAX_RAYS || n_origins < 1 || m < 0 || capacity < m || capacity > ACCUM_MAX_CAPACITY) return PCACC_E_ARG;
     if (!(voxel_size > 0.0) || !(voxel_size - voxel_size == 0.0)) return PCACC_E_ARG;
     if (!(min_range >= 0.0) || !(min_range - min_range == 0.0) || !(margin >= 0.0) || !(margin - margin == 0.0) || max_range != max_range) return PCACC_E_ARG;
     if (max_steps < 1 || max_steps > ACCY_MAX_STEPS) return PCACC_E_ARG;
     if (!counters || !workspace || (m > 0 && (!keys || !acc))) return PCACC_E_ARG;
     if (n > 0 && (!targets || !origins || !out_status || !out_row || !out_coords || !out_point || !out_range_in || !out_depth || !out_length || !out_visits))
         return PCACC_E_ARG;
-    AccyWs w;
-    if (workspace_bytes < accy_carve(&w, (char *)workspace, m)) return PCACC_E_ARG;
+    AccnRowsWs w;
+    if (workspace_bytes < accn_rows_ws_carve(m, &w, (char *)workspace)) return PCACC_E_ARG;
     hipStream_t st = pcacc_stream(stream);
     if (hipMemsetAsync(counters, 0, ACCY_COUNTERS * sizeof(int64_t), st) != hipSuccess) return PCACC_E_LAUNCH;
     if (n == 0) return PCACC_OK;

@@ -12,10 +12,10 @@
 // Everything a result depends on is added in an order the header fixes: two runs give the same bits.
 #include "scan.h"
 #include "accum_register.h"
+#include "accum_launch.h"
 #include "accum_rows.h"
 
 #define ACCR_MAX_POINTS ((int64_t)1 << 24)          // 65 536 slots: the update wave adds them one after the other
-#define ACCR_MAX_CAPACITY ((int64_t)1 << 30)        // as accum.hip
 #define ACCR_MAX_ITERATIONS 10000
 
 struct AccrWs {
@@ -122,7 +122,7 @@ static __global__ __launch_bounds__(64) void accr_update_kernel(const double *__
     if (threadIdx.x == 0) accr_round(st, sums, round, max_iter, &o);
 }
 
-static bool accr_sizes_ok(int64_t n, int64_t m) { return n >= 0 && n <= ACCR_MAX_POINTS && m >= 0 && m <= ACCR_MAX_CAPACITY; }
+static bool accr_sizes_ok(int64_t n, int64_t m) { return n >= 0 && n <= ACCR_MAX_POINTS && m >= 0 && m <= ACCUM_MAX_CAPACITY; }
 
 extern "C" int pcacc_accum_register_workspace_bytes(int64_t n, int64_t m, size_t *bytes)
 {
@@ -138,7 +138,7 @@ extern "C" int pcacc_accum_register(const float *points, int64_t n, const uint8_
                                     int64_t n_rows, double *out_pose, double *out_fitness, double *out_rmse, int32_t *out_iterations,
                                     int32_t *out_status, int32_t *out_correspondences, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!accr_sizes_ok(n, m) || capacity < m || capacity > ACCR_MAX_CAPACITY || n_rows < 0 || n_rows > m) return PCACC_E_ARG;
+    if (!accr_sizes_ok(n, m) || capacity < m || capacity > ACCUM_MAX_CAPACITY || n_rows < 0 || n_rows > m) return PCACC_E_ARG;
     if (!(voxel_size > 0.0) || !(voxel_size < 1e300) || !(max_distance > 0.0) || !(max_distance <= voxel_size)) return PCACC_E_ARG;
     if (max_iter < 0 || max_iter > ACCR_MAX_ITERATIONS) return PCACC_E_ARG;
     if (!out_pose || !out_fitness || !out_rmse || !out_iterations || !out_status || !out_correspondences || !workspace) return PCACC_E_ARG;

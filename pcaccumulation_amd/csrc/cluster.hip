@@ -433,14 +433,6 @@ __global__ __launch_bounds__(CL_BLOCK) void cluster_expand(const uint64_t *__res
     }
 }
 
-static void cluster_scan(const int *in, int64_t n, int *chunk, int *out, hipStream_t st)
-{
-    const int chunks = pcacc_chunks(n);
-    hipLaunchKernelGGL(chunk_sums_i32, dim3(chunks), dim3(256), 0, st, in, n, chunk);
-    hipLaunchKernelGGL(scan_chunk_sums, dim3(1), dim3(1024), 0, st, chunk, chunks, (int *)nullptr, -1);
-    hipLaunchKernelGGL(chunk_scan_i32, dim3(chunks), dim3(256), 0, st, in, n, chunk, out, 1);
-}
-
 extern "C" int pcacc_cluster(const float *points, const float *offset, const uint8_t *sel, const int32_t *batch, int64_t n,
                              int32_t n_batches, float voxel_size, double eps, int32_t min_samples, int32_t min_p_cluster,
                              int64_t *labels, void *ws, size_t ws_bytes, void *stream)
@@ -460,7 +452,7 @@ extern "C" int pcacc_cluster(const float *points, const float *offset, const uin
     if (rocprim::radix_sort_pairs(w.sort_tmp, w.sort_tmp_bytes, w.key_a, w.key_b, w.idx_a, w.idx_b, (size_t)n, 0, 64, st) != hipSuccess)
         return PCACC_E_LAUNCH;
     hipLaunchKernelGGL(cluster_heads, dim3(grid), dim3(CL_BLOCK), 0, st, w.key_b, n, w.head);
-    cluster_scan(w.head, n, w.chunk, w.vox, st);                                   // vox[n] = M
+    pcacc_scan_i32(w.head, n, w.chunk, w.vox, st);                                   // vox[n] = M
     hipLaunchKernelGGL(cluster_reset, dim3(grid), dim3(CL_BLOCK), 0, st, n, w.gk_a, w.gi_a, w.parent, w.size, w.root_min);
     hipLaunchKernelGGL(cluster_sub_points_fill, dim3(grid), dim3(CL_BLOCK), 0, st, points, offset, w.key_b, w.idx_b, w.head, w.vox, n,
                        cell, w.sx, w.sy, w.gk_a);
@@ -481,7 +473,7 @@ extern "C" int pcacc_cluster(const float *points, const float *offset, const uin
     hipLaunchKernelGGL(cluster_assign, dim3(grid), dim3(CL_BLOCK), 0, st, w.gpx, w.gpy, w.gi_b, w.cell_hi, w.far_lo, w.far_hi, w.core,
                        w.root_min, m_ptr, n, r2, w.parent, w.comp, w.size);
     hipLaunchKernelGGL(cluster_survivors, dim3(grid), dim3(CL_BLOCK), 0, st, w.size, m_ptr, n, min_p_cluster, w.flag);
-    cluster_scan(w.flag, n, w.chunk, w.rank, st);                                  // rank[n] = survivors in the whole batch
+    pcacc_scan_i32(w.flag, n, w.chunk, w.rank, st);                                  // rank[n] = survivors in the whole batch
     hipLaunchKernelGGL(cluster_sample_bases, dim3(1), dim3(64), 0, st, w.key_b, w.vox, w.rank, n, n_batches, min_p_cluster, w.base,
                        w.gate);
     hipLaunchKernelGGL(cluster_expand, dim3(grid), dim3(CL_BLOCK), 0, st, w.key_b, w.idx_b, w.head, w.vox, w.comp, w.flag, w.rank, w.base,

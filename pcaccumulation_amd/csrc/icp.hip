@@ -205,10 +205,7 @@ extern "C" int pcacc_icp_point_to_point(const float *points, int64_t n, const in
     const int setup_items = n_jobs > n_seg + 1 ? n_jobs : n_seg + 1;
     hipLaunchKernelGGL(icp_setup, dim3((setup_items + ICP_BLOCK - 1) / ICP_BLOCK), dim3(ICP_BLOCK), 0, st, seg_offsets, n_seg, jobs, n_jobs, n, init, w);
     if (n > 0) hipLaunchKernelGGL(icp_insert, dim3(pcacc_grid(n, ICP_BLOCK)), dim3(ICP_BLOCK), 0, st, points, n, seg_offsets, n_seg, threshold, w);
-    const int chunks = pcacc_chunks(w.slots);
-    hipLaunchKernelGGL(chunk_sums_i32, dim3(chunks), dim3(256), 0, st, w.cnt, (int64_t)w.slots, w.sums);
-    hipLaunchKernelGGL(scan_chunk_sums, dim3(1), dim3(1024), 0, st, w.sums, chunks, (int *)nullptr, -1);
-    hipLaunchKernelGGL(chunk_scan_i32, dim3(chunks), dim3(256), 0, st, w.cnt, (int64_t)w.slots, w.sums, w.start, 1, w.cnt);
+    pcacc_scan_i32(w.cnt, (int64_t)w.slots, w.sums, w.start, st, w.cnt);                    // the histogram becomes the cursor array of the fill pass
     if (n > 0) hipLaunchKernelGGL(icp_fill, dim3(pcacc_grid(n, ICP_BLOCK)), dim3(ICP_BLOCK), 0, st, n, w);
     PCACC_CHECK_LAUNCH();
     const double thr2 = threshold * threshold;

@@ -80,3 +80,12 @@ static __global__ __launch_bounds__(256) void chunk_scan_i32(const int *in, int6
         carry += tot;
     }
 }
+
+// The three launches of an int scan: out[0..n] exclusive, out[n] = total.  chunk: pcacc_chunks(n) ints of scratch.
+static inline void pcacc_scan_i32(const int *in, int64_t n, int *chunk, int *out, hipStream_t st, int *clear_in = nullptr)
+{
+    const int nc = pcacc_chunks(n);
+    hipLaunchKernelGGL(chunk_sums_i32, dim3(nc), dim3(256), 0, st, in, n, chunk);
+    hipLaunchKernelGGL(scan_chunk_sums, dim3(1), dim3(1024), 0, st, chunk, nc, (int *)nullptr, -1);
+    hipLaunchKernelGGL(chunk_scan_i32, dim3(nc), dim3(256), 0, st, in, n, (const int *)chunk, out, 1, clear_in);
+}

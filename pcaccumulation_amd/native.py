@@ -101,6 +101,10 @@ def _dev(t, dtype=None, what='tensor'):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _opt(t, dtype, what):
+    return _dev(t, dtype, what) if t is not None else None
+
+
 _raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None)
 _cur_device = getattr(torch._C, '_cuda_getDevice', None)
 
@@ -699,6 +703,50 @@ def _accum_tables(tables, what):
     return _dev(keys, torch.int64, what + ' keys'), _dev(acc, torch.int64, what + ' acc'), _dev(stamps, torch.int32, what + ' stamps'), cap
 
 
+# What the accum_* bindings below share.  Each helper only prepares arguments: every lib().pcacc_* call stays a direct call with positional arguments
+# (tests/test_abi.py counts them), so a helper returns values that its caller unpacks into names.
+def _given(value, number):
+    """An optional number as the entry points take it, a flag and a value: None -> (0, number()), otherwise (1, number(value))."""
+    return (0, number()) if value is None else (1, number(value))
+
+
+def _fraction(max_moving_fraction):
+    return _given(max_moving_fraction, float)
+
+
+def _shaped(what, name, t, shape):
+    """t (None passes) has the dimensions of `shape`: an integer entry is the size, a string entry stands for any size and names it in the message."""
+    if t is not None and (t.dim() != len(shape) or any(not isinstance(s, str) and s != d for s, d in zip(shape, t.shape))):
+        raise NativeError('%s: %s must be [%s], got %s' % (what, name, ','.join(str(s) for s in shape), tuple(t.shape)))
+
+
+def _out_columns(what, fields, rows, out, counters, n_counters, device):
+    """The outputs of a call that writes one row per point, ray or map row: out, a dict of the `fields` tensors of `rows` rows each (None = new ones), and
+    counters [n_counters] i64 likewise -> (out, counters, the pointers of the columns in the order of `fields`: None each without a row)."""
+    if out is None:
+        out = {name: torch.empty((rows,) + shape, dtype=dtype, device=device) for name, dtype, shape in fields}
+    for name, _, shape in fields:
+        _shaped(what, 'out[%r]' % name, out[name], (rows,) + shape)
+    if counters is None:
+        counters = torch.empty((n_counters,), dtype=torch.int64, device=device)
+    _shaped(what, 'counters', counters, (n_counters,))
+    return out, counters, [_dev(out[name], dtype, name) if rows else None for name, dtype, _ in fields]
+
+
+def _out_tables(what, tables_out, pierced_out, state, in_capacity):
+    """The output side of an out-of-place call: tables_out = (keys, acc, stamps) with pierced_out [cap] i32, and state [8] i64, each None with dry_run
+    -> (keys, acc, stamps, pierced, capacity, state) as the entry points take them; without tables the capacity is the input's."""
+    ok = oa = os_ = op = None
+    ocap = in_capacity
+    if tables_out is not None:
+        ok, oa, os_, ocap = _accum_tables(tables_out, what + ' output')
+        if pierced_out is not None:
+            _shaped(what, 'pierced_out', pierced_out, (ocap,))
+            op = _dev(pierced_out, torch.int32, 'pierced_out')
+    _shaped(what, 'state', state, (ACCUM_STATE_WORDS,))
+    return ok, oa, os_, op, ocap, _opt(state, torch.int64, 'state')
+
+
 def accum_add(points, pose, moving, stamp, voxel_size, tables_in, tables_out, state):
     """One window into a voxel map, out of place; see include/pcacc.h (C4).  points [n,3] f32 (n >= 1), pose [4,4] f64 or None, moving [n] u8 or None,
     tables_in / tables_out = (keys, acc, stamps) of the map before and after, state [8] i64.  Nothing is read back: the caller looks at `state`."""
@@ -706,17 +754,13 @@ def accum_add(points, pose, moving, stamp, voxel_size, tables_in, tables_out, st
     if points.dim() != 2 or points.shape[1] != 3 or n < 1:
         raise NativeError('accum_add: points must be [n,3] with n >= 1, got %s' % (tuple(points.shape),))
     pts = _dev(points, torch.float32, 'points')
-    if moving is not None and tuple(moving.shape) != (n,):
-        raise NativeError('accum_add: moving must be [n], got %s' % (tuple(moving.shape),))
-    if pose is not None and tuple(pose.shape) != (4, 4):
-        raise NativeError('accum_add: pose must be [4,4], got %s' % (tuple(pose.shape),))
-    if tuple(state.shape) != (ACCUM_STATE_WORDS,):
-        raise NativeError('accum_add: state must be [%d] int64' % ACCUM_STATE_WORDS)
+    _shaped('accum_add', 'moving', moving, (n,))
+    _shaped('accum_add', 'pose', pose, (4, 4))
+    _shaped('accum_add', 'state', state, (ACCUM_STATE_WORDS,))
     ik, ia, is_, icap = _accum_tables(tables_in, 'accum_add input')
     ok, oa, os_, ocap = _accum_tables(tables_out, 'accum_add output')
     ws = _workspace(lib().pcacc_accum_add_workspace_bytes, points.device, n)
-    _check(lib().pcacc_accum_add(pts, n, _dev(pose, torch.float64, 'pose') if pose is not None else None,
-                                 _dev(moving, torch.uint8, 'moving') if moving is not None else None, int(stamp), float(voxel_size),
+    _check(lib().pcacc_accum_add(pts, n, _opt(pose, torch.float64, 'pose'), _opt(moving, torch.uint8, 'moving'), int(stamp), float(voxel_size),
                                  ik, ia, is_, icap, ok, oa, os_, ocap, _dev(state, torch.int64, 'state'), _dev(ws), ws.numel(), _stream()), 'accum_add')
 
 
@@ -733,9 +777,9 @@ def accum_extract(tables, m, min_count, max_moving_fraction):
     t_first = torch.empty((m,), dtype=torch.int32, device=dev)
     t_last = torch.empty((m,), dtype=torch.int32, device=dev)
     kept = torch.empty((1,), dtype=torch.int64, device=dev)
+    use_f, f = _fraction(max_moving_fraction)
     ws = _workspace(lib().pcacc_accum_extract_workspace_bytes, dev, m)
-    _check(lib().pcacc_accum_extract(keys, acc, stamps, cap, m, int(min_count), 0 if max_moving_fraction is None else 1,
-                                     0.0 if max_moving_fraction is None else float(max_moving_fraction), _dev(points), _dev(coords), _dev(count),
+    _check(lib().pcacc_accum_extract(keys, acc, stamps, cap, m, int(min_count), use_f, f, _dev(points), _dev(coords), _dev(count),
                                      _dev(moving), _dev(t_first), _dev(t_last), _dev(kept), _dev(ws), ws.numel(), _stream()), 'accum_extract')
     return points, coords, count, moving, t_first, t_last, kept
 
@@ -750,19 +794,16 @@ def accum_normals(tables, m, min_count, max_moving_fraction, radius, min_neighbo
     keys, acc, stamps, cap = _accum_tables(tables, 'accum_normals')
     dev = tables[0].device
     m = int(m)
-    n_view = 0
-    if viewpoints is not None:
-        if viewpoints.dim() != 2 or viewpoints.shape[1] != 3:
-            raise NativeError('accum_normals: viewpoints must be [S,3], got %s' % (tuple(viewpoints.shape),))
-        n_view = viewpoints.shape[0]
+    _shaped('accum_normals', 'viewpoints', viewpoints, ('S', 3))
+    n_view = 0 if viewpoints is None else viewpoints.shape[0]
     normals = torch.empty((m, 3), dtype=torch.float32, device=dev)
     eigenvalues = torch.empty((m, 3), dtype=torch.float32, device=dev)
     neighbors = torch.empty((m,), dtype=torch.int32, device=dev)
     flags = torch.empty((m,), dtype=torch.uint8, device=dev)
     kept = torch.empty((1,), dtype=torch.int64, device=dev)
+    use_f, f = _fraction(max_moving_fraction)
     ws = _workspace(lib().pcacc_accum_normals_workspace_bytes, dev, m)
-    _check(lib().pcacc_accum_normals(keys, acc, stamps, cap, m, int(min_count), 0 if max_moving_fraction is None else 1,
-                                     0.0 if max_moving_fraction is None else float(max_moving_fraction), int(radius), int(min_neighbors),
+    _check(lib().pcacc_accum_normals(keys, acc, stamps, cap, m, int(min_count), use_f, f, int(radius), int(min_neighbors),
                                      _dev(viewpoints, torch.float64, 'viewpoints') if n_view else None, n_view, int(stamp_base), _dev(normals),
                                      _dev(eigenvalues), _dev(neighbors), _dev(flags), _dev(kept), _dev(ws), ws.numel(), _stream()), 'accum_normals')
     return normals, eigenvalues, neighbors, flags, kept
@@ -779,26 +820,23 @@ def accum_register(points, moving, init_pose, voxel_size, max_distance, max_iter
     keys, acc, _, cap = _accum_tables(tables, 'accum_register')
     dev = tables[0].device
     n, m = points.shape[0], int(m)
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise NativeError('accum_register: points must be [n,3], got %s' % (tuple(points.shape),))
-    if moving is not None and tuple(moving.shape) != (n,):
-        raise NativeError('accum_register: moving must be [n], got %s' % (tuple(moving.shape),))
-    if init_pose is not None and tuple(init_pose.shape) != (4, 4):
-        raise NativeError('accum_register: init_pose must be [4,4], got %s' % (tuple(init_pose.shape),))
+    _shaped('accum_register', 'points', points, ('n', 3))
+    _shaped('accum_register', 'moving', moving, (n,))
+    _shaped('accum_register', 'init_pose', init_pose, (4, 4))
     v = normals.shape[0]
-    if tuple(normals.shape) != (v, 3) or tuple(flags.shape) != (v,):
-        raise NativeError('accum_register: normals [V,3] and flags [V] expected, got %s %s' % (tuple(normals.shape), tuple(flags.shape)))
+    _shaped('accum_register', 'normals', normals, ('V', 3))
+    _shaped('accum_register', 'flags', flags, (v,))
     pts = _dev(points, torch.float32, 'points')
-    mv = _dev(moving, torch.uint8, 'moving') if moving is not None else None
-    init = _dev(init_pose, torch.float64, 'init_pose') if init_pose is not None else None
+    mv = _opt(moving, torch.uint8, 'moving')
+    init = _opt(init_pose, torch.float64, 'init_pose')
     nrm, flg = _dev(normals, torch.float32, 'normals'), _dev(flags, torch.uint8, 'flags')
+    use_f, f = _fraction(max_moving_fraction)
     pose = torch.empty((4, 4), dtype=torch.float64, device=dev)
     stats = torch.empty((2,), dtype=torch.float64, device=dev)
     words = torch.empty((3,), dtype=torch.int32, device=dev)
     ws = _workspace(lib().pcacc_accum_register_workspace_bytes, dev, n, m)
     _check(lib().pcacc_accum_register(pts if n else None, n, mv if n else None, init, float(voxel_size), float(max_distance), int(max_iter), keys, acc, cap, m,
-                                      int(min_count), 0 if max_moving_fraction is None else 1,
-                                      0.0 if max_moving_fraction is None else float(max_moving_fraction), nrm if v else None, flg if v else None, v,
+                                      int(min_count), use_f, f, nrm if v else None, flg if v else None, v,
                                       _dev(pose), _dev(stats[0:1]), _dev(stats[1:2]), _dev(words[0:1]), _dev(words[1:2]), _dev(words[2:3]),
                                       _dev(ws), ws.numel(), _stream()), 'accum_register')
     return pose, stats[0], stats[1], words[0], words[1], words[2]
@@ -814,26 +852,21 @@ def accum_pierce(points, moving, origins, origin_index, pose, voxel_size, margin
     (walked, dropped, skipped, truncated, hits) on the device; nothing is read back."""
     keys, _, stamps, cap = _accum_tables(tables, 'accum_pierce')
     n, m = points.shape[0], int(m)
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise NativeError('accum_pierce: points must be [n,3], got %s' % (tuple(points.shape),))
-    if moving is not None and tuple(moving.shape) != (n,):
-        raise NativeError('accum_pierce: moving must be [n], got %s' % (tuple(moving.shape),))
-    if origins.dim() != 2 or origins.shape[1] != 3:
-        raise NativeError('accum_pierce: origins must be [S,3], got %s' % (tuple(origins.shape),))
-    if origin_index is not None and tuple(origin_index.shape) != (n,):
-        raise NativeError('accum_pierce: origin_index must be [n], got %s' % (tuple(origin_index.shape),))
-    if pose is not None and tuple(pose.shape) != (4, 4):
-        raise NativeError('accum_pierce: pose must be [4,4], got %s' % (tuple(pose.shape),))
-    if tuple(pierced.shape) != (cap,) or tuple(counters.shape) != (PIERCE_COUNTERS,):
-        raise NativeError('accum_pierce: pierced [cap] and counters [%d] expected, got %s %s' % (PIERCE_COUNTERS, tuple(pierced.shape), tuple(counters.shape)))
+    _shaped('accum_pierce', 'points', points, ('n', 3))
+    _shaped('accum_pierce', 'moving', moving, (n,))
+    _shaped('accum_pierce', 'origins', origins, ('S', 3))
+    _shaped('accum_pierce', 'origin_index', origin_index, (n,))
+    _shaped('accum_pierce', 'pose', pose, (4, 4))
+    _shaped('accum_pierce', 'pierced', pierced, (cap,))
+    _shaped('accum_pierce', 'counters', counters, (PIERCE_COUNTERS,))
     pts = _dev(points, torch.float32, 'points')
+    use_stamp, at = _given(stamp, int)
     ws = _workspace(lib().pcacc_accum_pierce_workspace_bytes, points.device, n, m)
-    _check(lib().pcacc_accum_pierce(pts if n else None, n, _dev(moving, torch.uint8, 'moving') if moving is not None and n else None,
+    _check(lib().pcacc_accum_pierce(pts if n else None, n, _opt(moving if n else None, torch.uint8, 'moving'),
                                     _dev(origins, torch.float64, 'origins') if origins.shape[0] else None, origins.shape[0],
-                                    _dev(origin_index, torch.int32, 'origin_index') if origin_index is not None and n else None,
-                                    _dev(pose, torch.float64, 'pose') if pose is not None else None, float(voxel_size), float(margin),
-                                    -1.0 if max_range is None else float(max_range), 0 if stamp is None else 1, 0 if stamp is None else int(stamp),
-                                    int(max_steps), keys, stamps, cap, m, _dev(pierced, torch.int32, 'pierced'), _dev(counters, torch.int64, 'counters'),
+                                    _opt(origin_index if n else None, torch.int32, 'origin_index'),
+                                    _opt(pose, torch.float64, 'pose'), float(voxel_size), float(margin),
+                                    -1.0 if max_range is None else float(max_range), use_stamp, at, int(max_steps), keys, stamps, cap, m, _dev(pierced, torch.int32, 'pierced'), _dev(counters, torch.int64, 'counters'),
                                     _dev(ws), ws.numel(), _stream()), 'accum_pierce')
 
 
@@ -849,30 +882,19 @@ def accum_prune(tables_in, m, pierced_in, min_count, max_moving_fraction, before
     Writes counters [6] i64 (kept, filter, stale, box, pierced, isolated) and, unless dry_run, the tables and state[ACCUM_NUM_VOXELS]; nothing is
     read back."""
     ik, ia, is_, icap = _accum_tables(tables_in, 'accum_prune input')
-    if pierced_in is not None and tuple(pierced_in.shape) != (icap,):
-        raise NativeError('accum_prune: pierced_in must be [cap], got %s' % (tuple(pierced_in.shape),))
-    if tuple(counters.shape) != (PRUNE_COUNTERS,):
-        raise NativeError('accum_prune: counters must be [%d] int64' % PRUNE_COUNTERS)
-    ok = oa = os_ = op = st = None
-    ocap = icap
-    if tables_out is not None:
-        ok, oa, os_, ocap = _accum_tables(tables_out, 'accum_prune output')
-        if pierced_out is not None:
-            if tuple(pierced_out.shape) != (ocap,):
-                raise NativeError('accum_prune: pierced_out must be [cap], got %s' % (tuple(pierced_out.shape),))
-            op = _dev(pierced_out, torch.int32, 'pierced_out')
-    if state is not None:
-        if tuple(state.shape) != (ACCUM_STATE_WORDS,):
-            raise NativeError('accum_prune: state must be [%d] int64' % ACCUM_STATE_WORDS)
-        st = _dev(state, torch.int64, 'state')
+    _shaped('accum_prune', 'pierced_in', pierced_in, (icap,))
+    _shaped('accum_prune', 'counters', counters, (PRUNE_COUNTERS,))
+    ok, oa, os_, op, ocap, st = _out_tables('accum_prune', tables_out, pierced_out, state, icap)
     lo, hi = ((0, 0, 0), (0, 0, 0)) if box is None else box
     m = int(m)
+    use_f, f = _fraction(max_moving_fraction)
+    use_stamp, before = _given(before_stamp, int)
+    use_ratio, r = _given(ratio, float)
     ws = _workspace(lib().pcacc_accum_prune_workspace_bytes, tables_in[0].device, m)
-    _check(lib().pcacc_accum_prune(ik, ia, is_, _dev(pierced_in, torch.int32, 'pierced_in') if pierced_in is not None else None, icap, m, int(min_count),
-                                   0 if max_moving_fraction is None else 1, 0.0 if max_moving_fraction is None else float(max_moving_fraction),
-                                   0 if before_stamp is None else 1, 0 if before_stamp is None else int(before_stamp), 0 if box is None else 1,
+    _check(lib().pcacc_accum_prune(ik, ia, is_, _opt(pierced_in, torch.int32, 'pierced_in'), icap, m, int(min_count), use_f, f,
+                                   use_stamp, before, 0 if box is None else 1,
                                    int(lo[0]), int(lo[1]), int(lo[2]), int(hi[0]), int(hi[1]), int(hi[2]), int(min_pierced),
-                                   0 if ratio is None else 1, 0.0 if ratio is None else float(ratio), int(min_neighbors), int(radius),
+                                   use_ratio, r, int(min_neighbors), int(radius),
                                    1 if dry_run else 0, ok, oa, os_, op, ocap, _dev(counters, torch.int64, 'counters'), st, _dev(ws), ws.numel(),
                                    _stream()), 'accum_prune')
 
@@ -894,36 +916,24 @@ def accum_query(points, pose, voxel_size, max_distance, tables, m, pierced, min_
     keys, acc, stamps, cap = _accum_tables(tables, 'accum_query')
     dev = tables[0].device
     n, m = points.shape[0], int(m)
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise NativeError('accum_query: points must be [n,3], got %s' % (tuple(points.shape),))
-    if pose is not None and tuple(pose.shape) != (4, 4):
-        raise NativeError('accum_query: pose must be [4,4], got %s' % (tuple(pose.shape),))
-    if pierced is not None and tuple(pierced.shape) != (cap,):
-        raise NativeError('accum_query: pierced must be [cap], got %s' % (tuple(pierced.shape),))
+    _shaped('accum_query', 'points', points, ('n', 3))
+    _shaped('accum_query', 'pose', pose, (4, 4))
+    _shaped('accum_query', 'pierced', pierced, (cap,))
     v = 0
     if normals is not None and flags is not None:
         v = normals.shape[0]
-        if tuple(normals.shape) != (v, 3) or tuple(flags.shape) != (v,):
-            raise NativeError('accum_query: normals [V,3] and flags [V] expected, got %s %s' % (tuple(normals.shape), tuple(flags.shape)))
+        _shaped('accum_query', 'normals', normals, ('V', 3))
+        _shaped('accum_query', 'flags', flags, (v,))
     pts = _dev(points, torch.float32, 'points')
-    nrm = _dev(normals, torch.float32, 'normals') if normals is not None else None
-    flg = _dev(flags, torch.uint8, 'flags') if flags is not None else None
-    if out is None:
-        out = {name: torch.empty((n,) + shape, dtype=dtype, device=dev) for name, dtype, shape in QUERY_FIELDS}
-    for name, dtype, shape in QUERY_FIELDS:
-        if tuple(out[name].shape) != (n,) + shape:
-            raise NativeError('accum_query: out[%r] must be %s, got %s' % (name, (n,) + shape, tuple(out[name].shape)))
-    if counters is None:
-        counters = torch.empty((QUERY_COUNTERS,), dtype=torch.int64, device=dev)
-    if tuple(counters.shape) != (QUERY_COUNTERS,):
-        raise NativeError('accum_query: counters must be [%d] int64' % QUERY_COUNTERS)
-    o_status, o_count, o_moving, o_first, o_last, o_pierced, o_row, o_nearest, o_distance, o_plane = [_dev(out[name], dtype, name) if n else None
-                                                                                                      for name, dtype, _ in QUERY_FIELDS]
+    nrm = _opt(normals, torch.float32, 'normals')
+    flg = _opt(flags, torch.uint8, 'flags')
+    out, counters, (o_status, o_count, o_moving, o_first, o_last, o_pierced, o_row, o_nearest, o_distance,
+                    o_plane) = _out_columns('accum_query', QUERY_FIELDS, n, out, counters, QUERY_COUNTERS, dev)
+    use_f, f = _fraction(max_moving_fraction)
     ws = _workspace(lib().pcacc_accum_query_workspace_bytes, dev, m)
-    _check(lib().pcacc_accum_query(pts if n else None, n, _dev(pose, torch.float64, 'pose') if pose is not None else None, float(voxel_size),
-                                   float(max_distance), keys, acc, stamps, _dev(pierced, torch.int32, 'pierced') if pierced is not None else None, cap, m,
-                                   int(min_count), 0 if max_moving_fraction is None else 1,
-                                   0.0 if max_moving_fraction is None else float(max_moving_fraction), nrm, flg, v, 1 if require_normal else 0,
+    _check(lib().pcacc_accum_query(pts if n else None, n, _opt(pose, torch.float64, 'pose'), float(voxel_size),
+                                   float(max_distance), keys, acc, stamps, _opt(pierced, torch.int32, 'pierced'), cap, m,
+                                   int(min_count), use_f, f, nrm, flg, v, 1 if require_normal else 0,
                                    o_status, o_count, o_moving, o_first, o_last, o_pierced, o_row, o_nearest, o_distance, o_plane, _dev(counters, torch.int64, 'counters'), _dev(ws), ws.numel(), _stream()), 'accum_query')
     res = dict(out)
     res['counters'] = counters
@@ -946,24 +956,14 @@ def accum_components(tables, m, min_count, max_moving_fraction, mask, radius, ou
     keys, acc, stamps, cap = _accum_tables(tables, 'accum_components')
     dev = tables[0].device
     m = int(m)
-    if mask is not None and mask.dim() != 1:
-        raise NativeError('accum_components: mask must be [V], got %s' % (tuple(mask.shape),))
-    if out is None:
-        out = {name: torch.empty((m,) + shape, dtype=dtype, device=dev) for name, dtype, shape in COMPONENTS_FIELDS}
-    for name, dtype, shape in COMPONENTS_FIELDS:
-        if tuple(out[name].shape) != (m,) + shape:
-            raise NativeError('accum_components: out[%r] must be %s, got %s' % (name, (m,) + shape, tuple(out[name].shape)))
-    if counters is None:
-        counters = torch.empty((COMPONENTS_COUNTERS,), dtype=torch.int64, device=dev)
-    if tuple(counters.shape) != (COMPONENTS_COUNTERS,):
-        raise NativeError('accum_components: counters must be [%d] int64' % COMPONENTS_COUNTERS)
-    (o_label, o_voxels, o_points, o_moving, o_sum_q, o_centroid, o_lo, o_hi, o_first, o_last,
-     o_row) = [_dev(out[name], dtype, name) if m else None for name, dtype, _ in COMPONENTS_FIELDS]
+    _shaped('accum_components', 'mask', mask, ('V',))
+    out, counters, (o_label, o_voxels, o_points, o_moving, o_sum_q, o_centroid, o_lo, o_hi, o_first, o_last,
+                    o_row) = _out_columns('accum_components', COMPONENTS_FIELDS, m, out, counters, COMPONENTS_COUNTERS, dev)
     mask_rows = 0 if mask is None else mask.shape[0]
+    use_f, f = _fraction(max_moving_fraction)
     ws = _workspace(lib().pcacc_accum_components_workspace_bytes, dev, m)
-    _check(lib().pcacc_accum_components(keys, acc, stamps, cap, m, int(min_count), 0 if max_moving_fraction is None else 1,
-                                        0.0 if max_moving_fraction is None else float(max_moving_fraction),
-                                        _dev(mask, torch.uint8, 'mask') if mask is not None else None, mask_rows, int(radius), o_label, o_voxels, o_points,
+    _check(lib().pcacc_accum_components(keys, acc, stamps, cap, m, int(min_count), use_f, f,
+                                        _opt(mask, torch.uint8, 'mask'), mask_rows, int(radius), o_label, o_voxels, o_points,
                                         o_moving, o_sum_q, o_centroid, o_lo, o_hi, o_first, o_last, o_row,
                                         _dev(counters, torch.int64, 'counters'), _dev(ws), ws.numel(), _stream()), 'accum_components')
     res = dict(out)
@@ -979,31 +979,16 @@ def accum_remove_components(tables_in, m, pierced_in, min_count, max_moving_frac
     state[ACCUM_NUM_VOXELS]; nothing is read back."""
     ik, ia, is_, icap = _accum_tables(tables_in, 'accum_remove_components input')
     m = int(m)
-    if pierced_in is not None and tuple(pierced_in.shape) != (icap,):
-        raise NativeError('accum_remove_components: pierced_in must be [cap], got %s' % (tuple(pierced_in.shape),))
-    if tuple(counters.shape) != (COMPONENTS_REMOVE_COUNTERS,):
-        raise NativeError('accum_remove_components: counters must be [%d] int64' % COMPONENTS_REMOVE_COUNTERS)
-    for name, dtype in (('label', torch.int32), ('voxels', torch.int32), ('points', torch.int64)):
-        if tuple(first[name].shape) != (m,):
-            raise NativeError('accum_remove_components: first[%r] must be [%d], got %s' % (name, m, tuple(first[name].shape)))
-    if tuple(first['counters'].shape) != (COMPONENTS_COUNTERS,):
-        raise NativeError('accum_remove_components: first[\'counters\'] must be [%d] int64' % COMPONENTS_COUNTERS)
-    ok = oa = os_ = op = st = None
-    ocap = icap
-    if tables_out is not None:
-        ok, oa, os_, ocap = _accum_tables(tables_out, 'accum_remove_components output')
-        if pierced_out is not None:
-            if tuple(pierced_out.shape) != (ocap,):
-                raise NativeError('accum_remove_components: pierced_out must be [cap], got %s' % (tuple(pierced_out.shape),))
-            op = _dev(pierced_out, torch.int32, 'pierced_out')
-    if state is not None:
-        if tuple(state.shape) != (ACCUM_STATE_WORDS,):
-            raise NativeError('accum_remove_components: state must be [%d] int64' % ACCUM_STATE_WORDS)
-        st = _dev(state, torch.int64, 'state')
+    _shaped('accum_remove_components', 'pierced_in', pierced_in, (icap,))
+    _shaped('accum_remove_components', 'counters', counters, (COMPONENTS_REMOVE_COUNTERS,))
+    for name in ('label', 'voxels', 'points'):
+        _shaped('accum_remove_components', 'first[%r]' % name, first[name], (m,))
+    _shaped('accum_remove_components', "first['counters']", first['counters'], (COMPONENTS_COUNTERS,))
+    ok, oa, os_, op, ocap, st = _out_tables('accum_remove_components', tables_out, pierced_out, state, icap)
+    use_f, f = _fraction(max_moving_fraction)
     ws = _workspace(lib().pcacc_accum_components_workspace_bytes, tables_in[0].device, m)
-    _check(lib().pcacc_accum_remove_components(ik, ia, is_, _dev(pierced_in, torch.int32, 'pierced_in') if pierced_in is not None else None, icap, m,
-                                               int(min_count), 0 if max_moving_fraction is None else 1,
-                                               0.0 if max_moving_fraction is None else float(max_moving_fraction),
+    _check(lib().pcacc_accum_remove_components(ik, ia, is_, _opt(pierced_in, torch.int32, 'pierced_in'), icap, m,
+                                               int(min_count), use_f, f,
                                                _dev(first['label'], torch.int32, 'label') if m else None,
                                                _dev(first['voxels'], torch.int32, 'voxels') if m else None,
                                                _dev(first['points'], torch.int64, 'points') if m else None,
@@ -1028,32 +1013,20 @@ def accum_raycast(targets, origins, origin_index, pose, voxel_size, min_range, m
     keys, acc, _, cap = _accum_tables(tables, 'accum_raycast')
     dev = tables[0].device
     n, m = targets.shape[0], int(m)
-    if targets.dim() != 2 or targets.shape[1] != 3:
-        raise NativeError('accum_raycast: targets must be [n,3], got %s' % (tuple(targets.shape),))
-    if origins.dim() != 2 or origins.shape[1] != 3:
-        raise NativeError('accum_raycast: origins must be [S,3], got %s' % (tuple(origins.shape),))
-    if origin_index is not None and tuple(origin_index.shape) != (n,):
-        raise NativeError('accum_raycast: origin_index must be [n], got %s' % (tuple(origin_index.shape),))
-    if pose is not None and tuple(pose.shape) != (4, 4):
-        raise NativeError('accum_raycast: pose must be [4,4], got %s' % (tuple(pose.shape),))
+    _shaped('accum_raycast', 'targets', targets, ('n', 3))
+    _shaped('accum_raycast', 'origins', origins, ('S', 3))
+    _shaped('accum_raycast', 'origin_index', origin_index, (n,))
+    _shaped('accum_raycast', 'pose', pose, (4, 4))
     pts = _dev(targets, torch.float32, 'targets')
-    if out is None:
-        out = {name: torch.empty((n,) + shape, dtype=dtype, device=dev) for name, dtype, shape in RAYCAST_FIELDS}
-    for name, dtype, shape in RAYCAST_FIELDS:
-        if tuple(out[name].shape) != (n,) + shape:
-            raise NativeError('accum_raycast: out[%r] must be %s, got %s' % (name, (n,) + shape, tuple(out[name].shape)))
-    if counters is None:
-        counters = torch.empty((RAYCAST_COUNTERS,), dtype=torch.int64, device=dev)
-    if tuple(counters.shape) != (RAYCAST_COUNTERS,):
-        raise NativeError('accum_raycast: counters must be [%d] int64' % RAYCAST_COUNTERS)
-    o_status, o_row, o_coords, o_point, o_range_in, o_depth, o_length, o_visits = [_dev(out[name], dtype, name) if n else None for name, dtype, _ in RAYCAST_FIELDS]
+    out, counters, (o_status, o_row, o_coords, o_point, o_range_in, o_depth, o_length,
+                    o_visits) = _out_columns('accum_raycast', RAYCAST_FIELDS, n, out, counters, RAYCAST_COUNTERS, dev)
+    use_f, f = _fraction(max_moving_fraction)
     ws = _workspace(lib().pcacc_accum_raycast_workspace_bytes, dev, m)
     _check(lib().pcacc_accum_raycast(pts if n else None, n, _dev(origins, torch.float64, 'origins') if origins.shape[0] else None, origins.shape[0],
-                                     _dev(origin_index, torch.int32, 'origin_index') if origin_index is not None and n else None,
-                                     _dev(pose, torch.float64, 'pose') if pose is not None else None, float(voxel_size), float(min_range),
+                                     _opt(origin_index if n else None, torch.int32, 'origin_index'),
+                                     _opt(pose, torch.float64, 'pose'), float(voxel_size), float(min_range),
                                      -1.0 if max_range is None else float(max_range), float(margin), int(max_steps), keys, acc, cap, m, int(min_count),
-                                     0 if max_moving_fraction is None else 1, 0.0 if max_moving_fraction is None else float(max_moving_fraction),
-                                     o_status, o_row, o_coords, o_point, o_range_in, o_depth, o_length, o_visits, _dev(counters, torch.int64, 'counters'),
+                                     use_f, f, o_status, o_row, o_coords, o_point, o_range_in, o_depth, o_length, o_visits, _dev(counters, torch.int64, 'counters'),
                                      _dev(ws), ws.numel(), _stream()), 'accum_raycast')
     res = dict(out)
     res['counters'] = counters
@@ -1661,10 +1634,6 @@ def sinkhorn_backward(grad_log_perm, log_alpha, lse_rows, lse_cols):
 
 
 # ---------------------------------------------------------------------------------------------------
-def _opt(t, dtype, what):
-    return _dev(t, dtype, what) if t is not None else None
-
-
 def seg_loss_forward(logits, plane, labels, rows, n):
     """L1 (include/pcacc.h): logits = the whole f32 / bf16 logit tensor ([n_total,2] rows when plane == 0, NCHW planes of
     `plane` cells otherwise), labels [n_total] i64, rows [n] i64 or None.  Returns (loss [2] f32 = cross entropy, Lovasz;

@@ -203,6 +203,28 @@ def test_header_binding_and_no_cpu_fallback():
         native.accum_extract((torch.zeros(4, dtype=torch.int64), torch.zeros(5, 4, dtype=torch.int64), torch.zeros(2, 4, dtype=torch.int32)), 0, 1, None)
 
 
+def test_one_copy_of_the_launcher_scaffolding():
+    """What the launchers of C4 - C11 share is defined once: the wave sum and extract's predicate in accum_launch.h, the three-launch int scan in scan.h.
+    A `_scan` that is a __device__ function is not meant (acc_seg_scan of accum.hip is K4's segmented sum over a wave, not a launcher).  voxelize.hip,
+    canvas.hip and segment.hip keep their own launches of scan_chunk_sums: the first two pair it with counting kernels of their own."""
+    import glob
+    import re
+    csrc = os.path.join(ROOT, 'pcaccumulation_amd', 'csrc')
+    text = {os.path.basename(p): open(p).read() for p in glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.h'))}
+    assert sum(t.count('long long accum_wave_sum(') for t in text.values()) == 1 and 'long long accum_wave_sum(' in text['accum_launch.h']
+    for name, t in text.items():
+        if name.startswith('accum') and name.endswith('.hip'):
+            for line, fn in re.findall(r'^(static [^\n;=]*?\b(\w+)\([^\n;]*)$', t, re.M):
+                assert not fn.endswith(('_wave_sum', '_overlap')), (name, fn)
+                assert not fn.endswith('_scan') or '__device__' in line, (name, fn)
+        if name.startswith('accum') or name in ('icp.hip', 'cluster.hip'):
+            assert not re.search(r'scan_chunk_sums|chunk_sums_i32|chunk_scan_i32', t), name
+    assert 'hipLaunchKernelGGL(scan_chunk_sums' in text['scan.h'] and 'void pcacc_scan_i32(' in text['scan.h']
+    assert not any('accn_keep_kernel' in t for t in text.values())
+    assert sum(t.count('void accum_keep_kernel(') for t in text.values()) == 1
+    assert open(os.path.join(ROOT, 'pcaccumulation_amd', 'native.py')).read().count('is None else 1') <= 1
+
+
 # ---- GPU -------------------------------------------------------------------------------------------------------------------------------
 def _one_add_case(name):
     if name == 'n1':

@@ -623,7 +623,8 @@ def test_header_binding_and_argument_checks():
     pierce = open(os.path.join(ROOT, 'pcaccumulation_amd', 'csrc', 'accum_pierce.h')).read()
     assert pierce.count('accp_step(') >= 2 and pierce.count('t < t_best') == 1     # one copy of the step: C7 walks with it too
     kernel = open(os.path.join(ROOT, 'pcaccumulation_amd', 'csrc', 'accum_raycast.hip')).read()
-    assert kernel.count('__global__') == 1 and 'accy_ray_kernel' in kernel and '__shfl_xor' in kernel and 'asm(' not in kernel and 'asm volatile' not in kernel
+    assert kernel.count('__global__') == 1 and 'accy_ray_kernel' in kernel and 'accum_wave_count(' in kernel and 'asm(' not in kernel and 'asm volatile' not in kernel
+    assert '__shfl_xor' in open(os.path.join(ROOT, 'pcaccumulation_amd', 'csrc', 'accum_launch.h')).read()      # the wave reduction behind accum_wave_count
     assert (native.RAYCAST_MISS, native.RAYCAST_HIT, native.RAYCAST_TRUNCATED, native.RAYCAST_SKIPPED, native.RAYCAST_DROPPED, native.RAYCAST_COUNTERS) == \
         (0, 1, 2, 3, 4, 7)
     for k, name in enumerate(('RAYS', 'DROPPED', 'SKIPPED', 'HIT', 'MISSED', 'TRUNCATED', 'VISITS')):
