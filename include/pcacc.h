@@ -935,6 +935,66 @@ int pcacc_accum_remove_components(const int64_t *in_keys, const int64_t *in_acc,
                                   void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C12. Two accumulated scene clouds into one, and a map under a rigid pose and / or a new voxel size.  Replaces the copy of both maps' records to
+ * the host, a numpy join there and a load.  Applies no filter to either map, takes two maps per call, merges out of place, shrinks no table, and
+ * computes no intersection or difference.
+ * pcacc_accum_merge: two maps on ONE grid, exact.  Inputs
+ *   a_keys, a_acc, a_stamps, a_capacity, ma           the first ma rows of map A;  b_*, b_capacity, mb: the first mb rows of map B
+ *   a_pierced, b_pierced [capacity] i32 or NULL       the sidecars of pcacc_accum_pierce
+ *   add_dropped                                       B's dropped points, which the host knows
+ * Both maps are ascending and duplicate-free.  A and B may be the same tables.  The result goes OUT OF PLACE to out_keys, out_acc, out_stamps
+ * (out_capacity rows) and, iff at least one sidecar is given, out_pierced: the keys are the ascending union.  A key in both maps gets count, moving
+ * and the three coordinate sums added (int64), t_first = the minimum, t_last = the maximum and pierced = min(int64(a) + int64(b), 2^31 - 1); a key in
+ * one map only is copied bit for bit, with a ray count of 0 when that side has no sidecar.  The result is the map one accumulator would hold had
+ * it been given every add of both.
+ *   counters [PCACC_MERGE_COUNTERS] i64 (written, not added to): status, rows of the union, keys in both maps, keys of B that A lacks, ray counts
+ *   that were clamped.
+ * Only the device knows ma + NEW.  If it exceeds out_capacity NOTHING is written to out_* or state, counters[STATUS] = PCACC_ACCUM_TOO_SMALL and
+ * counters[NEEDED] says what it takes; A and B are intact.  Otherwise counters[STATUS] = 0, state[PCACC_ACCUM_NUM_VOXELS] = NEEDED,
+ * state[PCACC_ACCUM_DROPPED] grows by add_dropped, and every other state word is left alone.
+ * Return value: PCACC_E_ARG, and nothing is launched, for ma or mb outside [0, capacity], a capacity above 2^30, a NULL table of non-zero size or
+ * an output table that shares memory with an input table; PCACC_E_WORKSPACE for a workspace that is too small.  ma = mb = 0 writes the zero
+ * counters and state[NUM_VOXELS] = 0 and launches nothing else.
+ * pcacc_accum_regrid: a map under a pose and / or on a grid of out_voxel_size.  A voxel is treated as `count` points at its centroid: LOSSY by
+ * design (the points of a voxel that the new grid would separate stay together).  Per input row i < m, all float64 with no FMA contraction:
+ *   usable iff 0 < count <= 2^31;  c_a = (float64(sum q_a) / float64(count)) * 2^-16, the centroid of C5
+ *   w_a = ((r_a0 * c_x + r_a1 * c_y) + r_a2 * c_z) + t_a from rows 0-2 of pose (NULL = identity, through the same arithmetic)
+ *   validity, i_a = floor(w_a / out_voxel_size), the key and q_a = llrint(w_a * 65536) exactly as C4 has them for a point
+ * A usable, valid row contributes count, moving, count * q_a (|.| < 2^62), t_first, t_last and its ray count to the row of its key.  An unusable
+ * or invalid row is never clamped and forms no address: it adds 1 to DROPPED_ROWS and max(count, 0) to DROPPED_POINTS.
+ * Output: a new sorted map in out_keys, out_acc, out_stamps (out_capacity >= m rows: the result never has more rows than the input, there is no
+ * "too small" path) and, iff in_pierced is given, out_pierced: rows with one key summed, stamps min / max, ray counts summed in int64 and stored
+ * as min(sum, 2^31 - 1).  All eight words of the new map's state are written: NUM_VOXELS = rows, DROPPED = carry_dropped + DROPPED_POINTS, the
+ * rest 0.  Integer sums commute: the result is bit-identical from run to run.
+ *   counters [PCACC_REGRID_COUNTERS] i64 (written): rows in, rows out, rows dropped, points dropped, ray counts that were clamped.
+ * Return value: PCACC_E_ARG, and nothing is launched, for m outside [0, in_capacity], out_capacity < m, a capacity above 2^30, an out_voxel_size
+ * that is not positive and finite, a NULL table of non-zero size or an output table that shares memory with an input table.
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_MERGE_COUNTERS 5
+#define PCACC_MERGE_STATUS 0           /* PCACC_ACCUM_OK or PCACC_ACCUM_TOO_SMALL */
+#define PCACC_MERGE_NEEDED 1           /* rows of the union */
+#define PCACC_MERGE_SHARED 2           /* keys in both maps */
+#define PCACC_MERGE_NEW 3              /* keys of B that A lacks */
+#define PCACC_MERGE_SATURATED 4        /* ray counts stored as 2^31 - 1 because the sum did not fit */
+#define PCACC_REGRID_COUNTERS 5
+#define PCACC_REGRID_ROWS_IN 0
+#define PCACC_REGRID_ROWS_OUT 1
+#define PCACC_REGRID_DROPPED_ROWS 2
+#define PCACC_REGRID_DROPPED_POINTS 3
+#define PCACC_REGRID_SATURATED 4
+int pcacc_accum_merge_workspace_bytes(int64_t ma, int64_t mb, size_t *bytes /*host*/);
+int pcacc_accum_merge(const int64_t *a_keys, const int64_t *a_acc, const int32_t *a_stamps, const int32_t *a_pierced, int64_t a_capacity,
+                      int64_t ma, const int64_t *b_keys, const int64_t *b_acc, const int32_t *b_stamps, const int32_t *b_pierced,
+                      int64_t b_capacity, int64_t mb, int64_t add_dropped, int64_t *out_keys, int64_t *out_acc, int32_t *out_stamps,
+                      int32_t *out_pierced, int64_t out_capacity, int64_t *counters, int64_t *state, void *workspace, size_t workspace_bytes,
+                      void *stream);
+int pcacc_accum_regrid_workspace_bytes(int64_t m, size_t *bytes /*host*/);
+int pcacc_accum_regrid(const int64_t *in_keys, const int64_t *in_acc, const int32_t *in_stamps, const int32_t *in_pierced, int64_t in_capacity,
+                       int64_t m, const double *pose, double out_voxel_size, int64_t carry_dropped, int64_t *out_keys, int64_t *out_acc,
+                       int32_t *out_stamps, int32_t *out_pierced, int64_t out_capacity, int64_t *counters, int64_t *state, void *workspace,
+                       size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

@@ -24,6 +24,8 @@ coordinate sums), so the map does not depend on the order of the points, on the 
                                                                  # set above the ground its size, box and centroid: C11, section 9j
     m.remove_components(min_voxels=30, min_count=2, max_moving_fraction=0.0)   # drop the floating blobs that a per-voxel neighbour count lets through
     m.save_ply('scene.ply', min_count=2, max_moving_fraction=0.0, viewpoints=sensor_positions)
+    m.merge(other_session)                                       # another map of the same place on the same grid, exactly as if m had seen its adds: C12,
+    m.merge(submap, pose=submap_to_world)                        # section 9l; a map in its own frame or at another voxel size goes through regrid()
 
 There is no CPU path: a CPU tensor raises native.NativeError."""
 import numpy as np
@@ -106,6 +108,14 @@ def _sensor_origins(results, sensor_offset):
     ego = results['ego_motion_est'][0].detach().to(torch.float64)                       # [T,4,4]
     sx, sy, sz = (float(v) for v in sensor_offset)
     return ((ego[:, :3, 0] * sx + ego[:, :3, 1] * sy) + ego[:, :3, 2] * sz) + ego[:, :3, 3]
+
+
+def _device_key(device):
+    """(type, index) with the index 'cuda' stands for: two maps on 'cuda' and 'cuda:0' share a device."""
+    index = device.index
+    if index is None and device.type == 'cuda':
+        index = torch.cuda.current_device() if torch.cuda.is_available() else 0
+    return device.type, index
 
 
 class AccumulatedCloud(object):
@@ -592,6 +602,110 @@ class AccumulatedCloud(object):
             if self._pierced is not None:
                 self._pierced = pierced_out
             self._n = res['kept']
+        return res
+
+    # ---- merge, regrid, copy -----------------------------------------------------------------------------------------------------------
+    def copy(self):
+        """An independent clone: device copies of the rows in use, of the ray counts and of the state words.  merge() mutates its map, so
+        `c = a.copy(); c.merge(b)` keeps a."""
+        c = AccumulatedCloud(self.voxel_size, self.device, self.capacity)
+        c._n, c._dropped = self._n, self._dropped
+        if self._cur is not None:
+            c._ensure()
+            n = self._n
+            for dst, src in zip(c._cur, self._cur):
+                dst[..., :n].copy_(src[..., :n])
+            c._state.copy_(self._state)
+            if self._pierced is not None:
+                c._pierced = torch.zeros((self.capacity,), dtype=torch.int32, device=self.device)
+                c._pierced[:n].copy_(self._pierced[:n])
+                c._pierce_counters = self._pierce_counters.clone()
+        return c
+
+    def _regrid(self, pose, voxel_size, capacity):
+        """-> (the new map, the counters of the call as Python integers: the one read-back)."""
+        if pose is None and voxel_size is None:
+            raise ValueError('regrid needs a pose, a voxel_size or both')
+        voxel_size = self.voxel_size if voxel_size is None else float(voxel_size)
+        capacity = self.capacity if capacity is None else int(capacity)
+        if capacity < max(self._n, 1):
+            raise ValueError('capacity must be at least the %d rows of the map (the result never has more), got %r' % (self._n, capacity))
+        new = AccumulatedCloud(voxel_size, self.device, capacity)              # checks voxel_size and capacity
+        pose = self._pose(pose)
+        self._ensure()
+        new._ensure()
+        if self._pierced is not None:
+            new._pierced = torch.zeros((capacity,), dtype=torch.int32, device=self.device)
+            new._pierce_counters = self._pierce_counters.clone()
+        counters = torch.empty((native.REGRID_COUNTERS,), dtype=torch.int64, device=self.device)
+        native.accum_regrid(self._cur, self._n, self._pierced, pose, voxel_size, self._dropped, new._cur, new._pierced, counters, new._state)
+        host = counters.tolist()                                   # the one read-back of a regrid
+        new._n = host[native.REGRID_ROWS_OUT]
+        new._dropped = self._dropped + host[native.REGRID_DROPPED_POINTS]
+        return new, host
+
+    def regrid(self, pose=None, voxel_size=None, capacity=None):
+        """This map under a rigid pose ([4,4] map-to-new-frame, tensor or array) and / or at another voxel size, as a NEW AccumulatedCloud on the same
+        device (include/pcacc.h C12); this map is not modified.  LOSSY by design: a voxel is treated as `count` points at its centroid, so points
+        that the new grid would separate stay together.  Counts, moving counts, stamps (min / max) and ray counts (clamped at 2^31 - 1) are summed per
+        new voxel.  A row whose centroid leaves the grid (or is not finite under the pose) is dropped, never clamped: its points are added to the
+        new map's `dropped`.  capacity (None = this map's) must hold this map's rows.  Only the five counters are read back."""
+        return self._regrid(pose, voxel_size, capacity)[0]
+
+    def merge(self, other, pose=None):
+        """Take another map's voxels into this one, on the device (include/pcacc.h C12); `other` is not modified.
+        pose=None is the exact path: both maps on one grid (other.voxel_size == self.voxel_size, the same device), and the result is, bit for bit, the
+        map one AccumulatedCloud would hold had it been given every add of both: counts, moving counts and coordinate sums added, first stamp the
+        minimum, last stamp the maximum, ray counts added (clamped at 2^31 - 1), `dropped` added.  With a pose ([4,4] other-to-world, tensor or array)
+        `other` is first regridded under it onto this map's voxel size (regrid: lossy by design) and the result merged.
+        The capacity grows as in add().  -> {'rows', 'shared', 'new', 'dropped_rows', 'dropped_points', 'saturated'}: rows of this map after the call,
+        voxels both maps held, voxels only `other` held, rows / points the regrid dropped, ray counts that were clamped -- Python integers, one
+        read-back of the counters per attempt.  An empty `other` changes nothing."""
+        if not isinstance(other, AccumulatedCloud):
+            raise TypeError('merge takes an AccumulatedCloud, got %s' % type(other).__name__)
+        if _device_key(other.device) != _device_key(self.device):
+            raise ValueError('merge: the maps live on %s and %s; save() / load() carries a map across' % (self.device, other.device))
+        if pose is None and other.voxel_size != self.voxel_size:
+            raise ValueError('merge: voxel sizes %r and %r differ; give pose= (np.eye(4) keeps the frame) or regrid() the other map first'
+                             % (self.voxel_size, other.voxel_size))
+        self._ensure()
+        other._ensure()
+        res = dict(rows=self._n, shared=0, new=0, dropped_rows=0, dropped_points=0, saturated=0)
+        if other._n == 0:
+            return res
+        if pose is not None:
+            other, host = other._regrid(pose, self.voxel_size, None)
+            res['dropped_rows'], res['dropped_points'] = host[native.REGRID_DROPPED_ROWS], host[native.REGRID_DROPPED_POINTS]
+            res['saturated'] = host[native.REGRID_SATURATED]
+        sidecar = self._pierced is not None or other._pierced is not None
+        counters = torch.empty((native.MERGE_COUNTERS,), dtype=torch.int64, device=self.device)
+        out_cap = self.capacity
+        while True:
+            if self._alt is None or self._alt[0].shape[0] != out_cap:
+                self._alt = None                                   # release before taking the larger tables
+                self._alt = _tables(out_cap, self.device)
+            pierced_out = torch.zeros((out_cap,), dtype=torch.int32, device=self.device) if sidecar else None
+            native.accum_merge(self._cur, self._n, self._pierced, other._cur, other._n, other._pierced, other._dropped, self._alt, pierced_out, counters,
+                               self._state)
+            host = counters.tolist()                               # the one read-back of an attempt
+            if host[native.MERGE_STATUS] == native.ACCUM_OK:
+                break
+            need = host[native.MERGE_NEEDED]
+            if need > native.ACCUM_MAX_CAPACITY:
+                raise native.NativeError('accum_merge: the map would take %d voxels, more than 2^30' % need)
+            while out_cap < need:                                  # growth by doubling; both maps are untouched
+                out_cap = min(2 * out_cap, native.ACCUM_MAX_CAPACITY)
+        self._cur, self._alt = self._alt, self._cur                # the map before the merge stays in self._alt, which the next add overwrites
+        self.capacity = out_cap
+        if sidecar:
+            if self._pierce_counters is None:
+                self._pierce_counters = other._pierce_counters.clone()
+            elif other._pierce_counters is not None:
+                self._pierce_counters = self._pierce_counters + other._pierce_counters
+            self._pierced = pierced_out
+        self._n = host[native.MERGE_NEEDED]
+        self._dropped += other._dropped
+        res.update(rows=self._n, shared=host[native.MERGE_SHARED], new=host[native.MERGE_NEW], saturated=res['saturated'] + host[native.MERGE_SATURATED])
         return res
 
     def save_ply(self, path, normals=True, min_count=1, max_moving_fraction=None, **normal_args):

@@ -99,17 +99,6 @@ static __global__ __launch_bounds__(ACC_BLOCK) void accum_zero_kernel(long long 
     }
 }
 
-static __device__ __forceinline__ long long acc_seg_scan(long long v, int r, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long t = __shfl_up(v, d, 64);
-        const int rr = __shfl_up(r, d, 64);
-        if (lane >= d && rr == r) v += t;                       // r ascends along the lanes: equal at distance d = equal all the way
-    }
-    return v;
-}
-
 // K4.  A wave takes 64 consecutive sorted positions per pass; all 64 lanes stay in the loop (the bound is wave-uniform).
 static __global__ __launch_bounds__(ACC_BLOCK) void accum_reduce_kernel(const float *__restrict__ points, int64_t n, const double *__restrict__ pose,
                                                                          const uint8_t *__restrict__ moving, double voxel_size,

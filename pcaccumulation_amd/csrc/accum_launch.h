@@ -22,6 +22,18 @@ static __device__ __forceinline__ void accum_wave_count(unsigned long long *coun
     if (lane_id() == 0 && v) atomicAdd(&counters[slot], (unsigned long long)v);
 }
 
+// The segmented sum over the 64 lanes of a wave (K4 of add, the reduction of regrid): lane's v plus the v of the lanes before it with the same run r.
+static __device__ __forceinline__ long long acc_seg_scan(long long v, int r, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const long long t = __shfl_up(v, d, 64);
+        const int rr = __shfl_up(r, d, 64);
+        if (lane >= d && rr == r) v += t;                       // r ascends along the lanes: equal at distance d = equal all the way
+    }
+    return v;
+}
+
 // Extract's predicate over the first m rows: pcacc_accum_extract and accn_rows_launch (pass 1 of C5) launch it.
 static __global__ __launch_bounds__(ACCUM_KEEP_BLOCK) void accum_keep_kernel(const int64_t *__restrict__ acc, int64_t capacity, int64_t m, int64_t min_count,
                                                                               int use_fraction, double max_moving_fraction, int *__restrict__ keep)

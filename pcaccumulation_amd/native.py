@@ -997,6 +997,46 @@ def accum_remove_components(tables_in, m, pierced_in, min_count, max_moving_frac
                                                ws.numel(), _stream()), 'accum_remove_components')
 
 
+MERGE_COUNTERS, REGRID_COUNTERS = 5, 5
+MERGE_STATUS, MERGE_NEEDED, MERGE_SHARED, MERGE_NEW, MERGE_SATURATED = 0, 1, 2, 3, 4
+REGRID_ROWS_IN, REGRID_ROWS_OUT, REGRID_DROPPED_ROWS, REGRID_DROPPED_POINTS, REGRID_SATURATED = 0, 1, 2, 3, 4
+
+
+def accum_merge(tables_a, ma, pierced_a, tables_b, mb, pierced_b, add_dropped, tables_out, pierced_out, counters, state):
+    """The first ma rows of map A and the first mb rows of map B, on one grid, as one map, out of place; see include/pcacc.h (C12).  pierced_a /
+    pierced_b [cap] i32 or None; add_dropped: B's dropped points; tables_out = (keys, acc, stamps), pierced_out [cap] i32 when either side has a
+    sidecar; state [8] i64: A's.  Writes counters [5] i64 (status, needed, shared, new, saturated) and, unless the status is ACCUM_TOO_SMALL, the
+    tables, state[ACCUM_NUM_VOXELS] and state[ACCUM_DROPPED]; nothing is read back."""
+    ak, aa, as_, acap = _accum_tables(tables_a, 'accum_merge A')
+    bk, ba, bs_, bcap = _accum_tables(tables_b, 'accum_merge B')
+    _shaped('accum_merge', 'pierced_a', pierced_a, (acap,))
+    _shaped('accum_merge', 'pierced_b', pierced_b, (bcap,))
+    _shaped('accum_merge', 'counters', counters, (MERGE_COUNTERS,))
+    ok, oa, os_, op, ocap, st = _out_tables('accum_merge', tables_out, pierced_out, state, acap)
+    ma, mb = int(ma), int(mb)
+    ws = _workspace(lib().pcacc_accum_merge_workspace_bytes, tables_a[0].device, ma, mb)
+    _check(lib().pcacc_accum_merge(ak, aa, as_, _opt(pierced_a, torch.int32, 'pierced_a'), acap, ma, bk, ba, bs_, _opt(pierced_b, torch.int32, 'pierced_b'),
+                                   bcap, mb, int(add_dropped), ok, oa, os_, op, ocap, _dev(counters, torch.int64, 'counters'), st, _dev(ws), ws.numel(),
+                                   _stream()), 'accum_merge')
+
+
+def accum_regrid(tables_in, m, pierced_in, pose, out_voxel_size, carry_dropped, tables_out, pierced_out, counters, state):
+    """The first m rows of a map under a pose ([4,4] f64 or None) on a grid of out_voxel_size, every voxel as `count` points at its centroid, out of
+    place; see include/pcacc.h (C12).  pierced_in [cap] i32 or None; tables_out = (keys, acc, stamps) of at least m rows, pierced_out [cap] i32 with
+    pierced_in; state [8] i64: the new map's, every word written.  Writes counters [5] i64 (rows in, rows out, dropped rows, dropped points,
+    saturated); nothing is read back."""
+    ik, ia, is_, icap = _accum_tables(tables_in, 'accum_regrid input')
+    _shaped('accum_regrid', 'pierced_in', pierced_in, (icap,))
+    _shaped('accum_regrid', 'pose', pose, (4, 4))
+    _shaped('accum_regrid', 'counters', counters, (REGRID_COUNTERS,))
+    ok, oa, os_, op, ocap, st = _out_tables('accum_regrid', tables_out, pierced_out, state, icap)
+    m = int(m)
+    ws = _workspace(lib().pcacc_accum_regrid_workspace_bytes, tables_in[0].device, m)
+    _check(lib().pcacc_accum_regrid(ik, ia, is_, _opt(pierced_in, torch.int32, 'pierced_in'), icap, m, _opt(pose, torch.float64, 'pose'),
+                                    float(out_voxel_size), int(carry_dropped), ok, oa, os_, op, ocap, _dev(counters, torch.int64, 'counters'), st,
+                                    _dev(ws), ws.numel(), _stream()), 'accum_regrid')
+
+
 RAYCAST_MISS, RAYCAST_HIT, RAYCAST_TRUNCATED, RAYCAST_SKIPPED, RAYCAST_DROPPED = 0, 1, 2, 3, 4
 RAYCAST_COUNTERS = 7
 RAYCAST_N_RAYS, RAYCAST_N_DROPPED, RAYCAST_N_SKIPPED, RAYCAST_N_HIT, RAYCAST_N_MISSED, RAYCAST_N_TRUNCATED, RAYCAST_N_VISITS = 0, 1, 2, 3, 4, 5, 6

@@ -1,0 +1,716 @@
+"""Two accumulated scene clouds into one, a map under a pose and / or at another voxel size (include/pcacc.h C12):
+AccumulatedCloud.merge, .regrid and .copy.
+
+Every result is an integer or a copied record, so every claim is an equality:
+  CPU   the g++ build of csrc/accum_merge.h (tests/accum_merge_host_driver.cpp: every table index asserted, poison behind the rows in use, every
+        destination written exactly once, keys ascending) against the plain-Python restatement (tests/accumulate_merge_reference.py);
+  GPU   merge against add itself (the map one accumulator holds after every add of both), the kernels against the g++ build on the same scenes, regrid
+        against add on points that are exact in float32 and in fixed point, and merge(other, pose) against regrid + merge."""
+import io
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import accumulate_merge_reference as mref
+import accumulate_reference as ref
+from helpers import build_host_driver
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEV = 'cuda:0'
+BIAS = 1 << 20
+I31 = (1 << 31) - 1
+
+
+def _key(c):
+    return ((c[0] + BIAS) << 42) | ((c[1] + BIAS) << 21) | (c[2] + BIAS)
+
+
+def _rot(axis, angle, t):
+    """Rodrigues: a rotation by `angle` about `axis` and a translation, [4,4] f64."""
+    a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    T = np.eye(4)
+    T[:3, :3] = np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * (K @ K)
+    T[:3, 3] = t
+    return T
+
+
+SKEW = _rot((0.3, -0.5, 0.8), 0.7, (1.37, -2.11, 0.53))
+
+
+# ---- scenes: (ReferenceMap, {key: rays} or None), built once and never modified ---------------------------------------------------------------------
+def _rows(coords, seed, rays=False, vs=0.1):
+    """Random records on the given voxels: counts 1..6, stamps 0..15, centroids inside the voxel; rays 0..4 with rays=True."""
+    rs = np.random.RandomState(seed)
+    r, p = ref.ReferenceMap(vs), ({} if rays else None)
+    for c in coords:
+        count = int(rs.randint(1, 7))
+        t_first = int(rs.randint(0, 11))
+        q = [int(np.rint((v + rs.uniform(0.1, 0.9)) * vs * 65536.0)) * count + int(rs.randint(0, count)) for v in c]
+        r.rec[_key(c)] = [count, int(rs.randint(0, count + 1))] + q + [t_first, t_first + int(rs.randint(0, 6))]
+        if rays:
+            p[_key(c)] = int(rs.randint(0, 5))
+    r.dropped = int(rs.randint(0, 9))
+    return r, p
+
+
+CELLS = [(x, y, z) for x in range(-2, 3) for y in range(-2, 3) for z in range(-2, 3)]
+ROW_COUNTS = (0, 1, 63, 64, 65)
+
+
+def _some(m, seed):
+    return [CELLS[i] for i in np.random.RandomState(seed).permutation(len(CELLS))[:m]]
+
+
+def _wavy(shift=0.0):
+    """test_accumulate_prune.py's sheet: 26 m x 26 m at 0.1 m, four points in every column, and one far voxel -- 76 661 voxels, more than one workgroup,
+    m mod 64 != 0, more than one scan chunk."""
+    g = np.arange(520) * 0.05 + 0.025 - 13.0
+    x, y = np.meshgrid(g, g, indexing='ij')
+    z = 0.4 * np.sin(0.9 * x) * np.cos(0.7 * y) + 0.013
+    pts = np.concatenate([np.stack([x, y, z], -1).reshape(-1, 3), [[40.0, 40.0, 40.0]]])
+    pts[:, 0] += shift
+    return pts.astype(np.float32)
+
+
+def _cloud_points(seed, n, lo=(-1, -1, -0.5), hi=(1, 1, 0.5)):
+    return np.random.RandomState(seed).uniform(lo, hi, (n, 3)).astype(np.float32)
+
+
+_scenes = {}
+
+
+def _build_scene(name):
+    if name.startswith('rows'):                                                  # rows<m>_<seed>: with a sidecar
+        m, seed = (int(v) for v in name[4:].split('_'))
+        return _rows(_some(m, seed), 50 + 7 * m + seed, rays=True)
+    line = lambda xs: [(x, 1, -1) for x in xs]
+    if name == 'low':
+        return _rows(line(range(-40, -10)), 1)
+    if name == 'high':
+        return _rows(line(range(10, 47)), 2)
+    if name == 'even':
+        return _rows(line(range(-20, 20, 2)), 3)
+    if name == 'odd':
+        return _rows(line(range(-19, 21, 2)), 4)
+    if name == 'outer':
+        return _rows(line(range(-30, 30)), 5)
+    if name == 'inner':
+        return _rows(line(range(-7, 9)), 6)
+    if name in ('plain_a', 'plain_b'):                                           # overlapping, no sidecar
+        return _rows(_some(70, 11 if name == 'plain_a' else 12), 13 if name == 'plain_a' else 14)
+    if name in ('rays_a', 'rays_b'):
+        return _rows(_some(70, 11 if name == 'rays_a' else 12), 15 if name == 'rays_a' else 16, rays=True)
+    if name in ('sat_a', 'sat_b'):                                               # (2^31 - 2) + 5, (2^31 - 1) + 0, (2^31 - 1) + (2^31 - 1), 7 + 8, one side only
+        r, _ = _rows(line(range(5)) if name == 'sat_a' else line(range(4)) + [(9, 1, -1)], 17)
+        rays = (I31 - 1, I31, I31, 7, I31) if name == 'sat_a' else (5, 0, I31, 8, I31)
+        return r, {k: v for k, v in zip(sorted(r.rec), rays)}
+    if name in ('grow_a', 'grow_b'):                                             # 1000 distinct voxels each, disjoint
+        return _rows([(x, y, 0 if name == 'grow_a' else 5) for x in range(40) for y in range(25)], 18)
+    if name in ('wavy', 'wavy_shifted'):
+        r = ref.ReferenceMap(0.1)
+        r.add(_wavy(0.0 if name == 'wavy' else 13.0), stamp=3 if name == 'wavy' else 8)
+        return r, None
+    if name in ('dense', 'dense_rays'):                                          # many points per voxel, three stamps, flags, dropped points
+        r = ref.ReferenceMap(0.1)
+        for k in range(3):
+            pts = _cloud_points(30 + k, 3000)
+            pts[::501] = np.nan
+            r.add(pts, None, np.random.RandomState(40 + k).uniform(0, 1, 3000) < 0.3, stamp=5 - 2 * k)
+        rs = np.random.RandomState(44)
+        return r, ({k: int(rs.randint(0, 9)) for k in r.rec} if name == 'dense_rays' else None)
+    if name == 'crafted':                                                        # unusable rows among usable ones: count 0, -3, 2^31 + 1; and 2^31
+        r, p = _rows(line(range(8)), 19, rays=True)
+        for k, count in zip(sorted(r.rec)[1::2], (0, -3, (1 << 31) + 1, 1 << 31)):
+            r.rec[k][0] = count
+            r.rec[k][2:5] = [0, 0, 0]
+        return r, p
+    assert name == 'sat_regrid'                                                  # two rows of one 0.2 m voxel whose ray counts do not fit together
+    r, _ = _rows([(0, 0, 0), (1, 0, 0), (4, 4, 4)], 20)
+    return r, {k: v for k, v in zip(sorted(r.rec), (I31 - 1, 5, 9))}
+
+
+def _scene(name):
+    if name not in _scenes:
+        _scenes[name] = _build_scene(name)
+    return _scenes[name]
+
+
+# ---- cases -----------------------------------------------------------------------------------------------------------------------------------------------
+MERGE_CASES = {'below': ('high', 'low'), 'above': ('low', 'high'), 'interleaved': ('even', 'odd'), 'contained': ('outer', 'inner'),
+               'contains': ('inner', 'outer'), 'identical': ('even', 'even'), 'self': ('rows65_1', None), 'no_sidecar': ('plain_a', 'plain_b'),
+               'sidecar_a': ('rays_a', 'plain_b'), 'sidecar_b': ('plain_a', 'rays_b'), 'sidecar_both': ('rays_a', 'rays_b'),
+               'saturation': ('sat_a', 'sat_b')}
+for _ma in ROW_COUNTS:
+    for _mb in ROW_COUNTS:
+        MERGE_CASES['rows_%d_%d' % (_ma, _mb)] = ('rows%d_1' % _ma, 'rows%d_2' % _mb)
+MERGE_NAMES = sorted(MERGE_CASES)
+
+FAR = np.eye(4)
+FAR[0, 3] = 32767.5                                                              # x >= 0.5 leaves |w| < 32768
+NAN_POSE = SKEW.copy()
+NAN_POSE[1, 2] = np.nan
+REGRID_CASES = {'pose': ('dense', SKEW, 0.1), 'pose_coarse': ('dense', SKEW, 0.25), 'pose_fine': ('dense', SKEW, 0.03), 'doubled': ('dense', None, 0.2),
+                'sidecar': ('dense_rays', SKEW, 0.3), 'far': ('dense_rays', FAR, 0.1), 'nan': ('dense', NAN_POSE, 0.1), 'crafted': ('crafted', SKEW, 0.1),
+                'crafted_identity': ('crafted', None, 0.1), 'saturation': ('sat_regrid', None, 0.2), 'index_limit': ('dense', None, 5e-7),
+                'empty': ('rows0_1', SKEW, 0.1), 'rows64': ('rows64_1', SKEW, 0.2), 'rows65': ('rows65_1', None, 0.35)}
+REGRID_NAMES = sorted(REGRID_CASES)
+
+
+# ---- the host build ----------------------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope='module')
+def host_exe(tmp_path_factory):
+    return build_host_driver(tmp_path_factory.mktemp('merge_host'), 'accum_merge_host_driver')
+
+
+def _map_bytes(r, pierced):
+    keys, acc, stamps = r.records()
+    raw = keys.tobytes() + np.ascontiguousarray(acc, np.int64).tobytes() + np.ascontiguousarray(stamps, np.int32).tobytes()
+    return raw + (b'' if pierced is None else mref.aligned(pierced, keys).tobytes())
+
+
+def _read_result(raw, sidecar, rows_word):
+    counters, state = np.frombuffer(raw, np.int64, 5).tolist(), np.frombuffer(raw, np.int64, 8, 40).tolist()
+    rows, off = counters[rows_word], 104
+    out = dict(counters=counters, state=state)
+    for name, dtype, shape in (('keys', np.int64, (rows,)), ('acc', np.int64, (5, rows)), ('stamps', np.int32, (2, rows)),
+                               ('pierced', np.int32, (rows if sidecar else 0,))):
+        n = int(np.prod(shape))
+        out[name] = np.frombuffer(raw, dtype, n, off).reshape(shape).copy()
+        off += n * np.dtype(dtype).itemsize
+    assert off == len(raw)
+    if not sidecar:
+        out['pierced'] = None
+    return out
+
+
+def _run_host_merge(exe, tmp_path, tag, a, b, out_capacity=None, spare=3):
+    """a, b = (ReferenceMap, rays); b None: B is A (a self-merge).  out_capacity None: the union's rows + 5."""
+    (ra, pa), (rb, pb) = a, (a if b is None else b)
+    ma, mb = ra.num_voxels, rb.num_voxels
+    if out_capacity is None:
+        out_capacity = len(set(ra.rec) | set(rb.rec)) + 5
+    head = [0, ma, ma + spare, 0 if pa is None else 1, mb, mb + spare, 0 if pb is None else 1, out_capacity,
+            1 if b is None else 0, rb.dropped]
+    src, dst = os.path.join(str(tmp_path), tag + '.in'), os.path.join(str(tmp_path), tag + '.out')
+    with open(src, 'wb') as f:
+        f.write(np.array(head, np.int64).tobytes() + _map_bytes(ra, pa) + (b'' if b is None else _map_bytes(rb, pb)))
+    subprocess.check_call([exe, src, dst])
+    res = _read_result(open(dst, 'rb').read(), pa is not None or pb is not None, 1)
+    if res['counters'][0] != 0:                                                  # TOO_SMALL: no map follows
+        res = dict(res, keys=res['keys'][:0])
+    return res
+
+
+def _run_host_regrid(exe, tmp_path, tag, a, pose, voxel_size, spare_in=3, spare_out=5):
+    r, p = a
+    m = r.num_voxels
+    head = [1, m, m + spare_in, 0 if p is None else 1, m + spare_out, 0 if pose is None else 1, r.dropped]
+    src, dst = os.path.join(str(tmp_path), tag + '.in'), os.path.join(str(tmp_path), tag + '.out')
+    with open(src, 'wb') as f:
+        f.write(np.array(head, np.int64).tobytes())
+        f.write(np.concatenate([[voxel_size], (np.eye(4) if pose is None else np.asarray(pose, np.float64)).reshape(-1)]).astype(np.float64).tobytes())
+        f.write(_map_bytes(r, p))
+    subprocess.check_call([exe, src, dst])
+    return _read_result(open(dst, 'rb').read(), p is not None, 1)
+
+
+def _too_small_result(exe, tmp_path, tag, a, b, out_capacity):
+    (ra, pa), (rb, pb) = a, b
+    head = [0, ra.num_voxels, ra.num_voxels + 3, 0 if pa is None else 1, rb.num_voxels, rb.num_voxels + 3, 0 if pb is None else 1, out_capacity, 0, rb.dropped]
+    src, dst = os.path.join(str(tmp_path), tag + '.in'), os.path.join(str(tmp_path), tag + '.out')
+    with open(src, 'wb') as f:
+        f.write(np.array(head, np.int64).tobytes() + _map_bytes(ra, pa) + _map_bytes(rb, pb))
+    subprocess.check_call([exe, src, dst])
+    raw = open(dst, 'rb').read()
+    assert len(raw) == 104                                                       # counters and state, no map
+    return np.frombuffer(raw, np.int64, 5).tolist(), np.frombuffer(raw, np.int64, 8, 40).tolist()
+
+
+_hosted = {}
+
+
+def _host_merge(exe, tmp_path, name):
+    if ('m', name) not in _hosted:
+        a, b = MERGE_CASES[name]
+        _hosted[('m', name)] = _run_host_merge(exe, tmp_path, name, _scene(a), None if b is None else _scene(b))
+    return _hosted[('m', name)]
+
+
+def _host_regrid(exe, tmp_path, name):
+    if ('g', name) not in _hosted:
+        scene, pose, vs = REGRID_CASES[name]
+        _hosted[('g', name)] = _run_host_regrid(exe, tmp_path, name, _scene(scene), pose, vs)
+    return _hosted[('g', name)]
+
+
+def _as_tables(r, pierced):
+    keys, acc, stamps = r.records()
+    return dict(keys=keys, acc=acc.reshape(5, -1), stamps=stamps.reshape(2, -1), pierced=None if pierced is None else mref.aligned(pierced, keys))
+
+
+def _assert_tables(got, want, what):
+    for f in ('keys', 'acc', 'stamps'):
+        assert got[f].dtype == want[f].dtype and np.array_equal(got[f], want[f]), (what, f)
+    assert (got['pierced'] is None) == (want['pierced'] is None), what
+    assert got['pierced'] is None or np.array_equal(got['pierced'], want['pierced']), what
+
+
+# ---- CPU: host build == restatement ----------------------------------------------------------------------------------------------------------------------
+def test_scenes_hold_what_they_are_for():
+    for m in ROW_COUNTS:
+        assert _scene('rows%d_1' % m)[0].num_voxels == m == _scene('rows%d_2' % m)[0].num_voxels
+    shared = lambda a, b: len(set(_scene(a)[0].rec) & set(_scene(b)[0].rec))
+    assert shared('rows65_1', 'rows65_2') not in (0, 65) and shared('even', 'odd') == 0 and shared('outer', 'inner') == 16 == _scene('inner')[0].num_voxels
+    assert max(_scene('low')[0].rec) < min(_scene('high')[0].rec) and shared('grow_a', 'grow_b') == 0 and _scene('grow_a')[0].num_voxels == 1000
+    assert _scene('wavy')[0].num_voxels == 76661 and 76661 % 64 != 0 and 76661 > 2048 and 0 < shared('wavy', 'wavy_shifted') < 76661
+    dense = _scene('dense')[0]
+    assert dense.num_voxels > 2000 and dense.dropped == 18 and max(v[0] for v in dense.rec.values()) >= 4
+    assert [v[0] for _, v in sorted(_scene('crafted')[0].rec.items())][1::2] == [0, -3, (1 << 31) + 1, 1 << 31]
+
+
+@pytest.mark.parametrize('name', MERGE_NAMES)
+def test_merge_host_build_equals_the_restatement(host_exe, tmp_path, name):
+    a, b = MERGE_CASES[name]
+    (ra, pa), (rb, pb) = _scene(a), _scene(a if b is None else b)
+    want, wp, res = mref.merge(ra, pa, rb, pb)
+    got = _host_merge(host_exe, tmp_path, name)
+    assert got['counters'] == [0, res['rows'], res['shared'], res['new'], res['saturated']], name
+    assert got['state'] == [res['rows'], 100 + rb.dropped] + [7] * 6, name     # NUM_VOXELS and DROPPED, every other word left alone
+    _assert_tables(got, _as_tables(want, wp), name)
+    assert res['rows'] == ra.num_voxels + res['new'] and res['shared'] + res['new'] == rb.num_voxels
+
+
+def test_merge_relations_and_saturation(host_exe, tmp_path):
+    count = lambda name: _host_merge(host_exe, tmp_path, name)['counters'][1:]
+    assert count('below') == [67, 0, 30, 0] and count('above') == [67, 0, 37, 0] and count('interleaved') == [40, 0, 20, 0]
+    assert count('contained') == [60, 16, 0, 0] and count('contains') == [60, 16, 44, 0] and count('identical') == [20, 20, 0, 0]
+    assert count('rows_0_0') == [0, 0, 0, 0] and count('rows_0_65') == [65, 0, 65, 0] and count('rows_65_0') == [65, 0, 0, 0]
+    below = _host_merge(host_exe, tmp_path, 'below')                             # every B row in front of every A row
+    assert below['keys'][:30].tolist() == sorted(_scene('low')[0].rec) and below['keys'][30:].tolist() == sorted(_scene('high')[0].rec)
+    # a.merge(a): every count and sum doubled, the stamps the same, the centroids bit-equal
+    r, p = _scene('rows65_1')
+    twice, once = _host_merge(host_exe, tmp_path, 'self'), _as_tables(r, p)
+    assert np.array_equal(twice['keys'], once['keys']) and np.array_equal(twice['acc'], 2 * once['acc']) and np.array_equal(twice['stamps'], once['stamps'])
+    assert np.array_equal(twice['pierced'], 2 * once['pierced']) and twice['counters'] == [0, 65, 65, 0, 0]
+    c = lambda t: ((t['acc'][2:5].astype(np.float64) / t['acc'][0].astype(np.float64)) * 2.0 ** -16).astype(np.float32)
+    assert c(twice).tobytes() == c(once).tobytes()
+    sat = _host_merge(host_exe, tmp_path, 'saturation')                          # (2^31 - 2) + 5 and 2 (2^31 - 1) clamp; (2^31 - 1) + 0 and 7 + 8 fit
+    assert sat['counters'] == [0, 6, 4, 1, 2] and sat['pierced'].tolist() == [I31, I31, I31, 15, I31, I31]
+    for name in ('sidecar_a', 'sidecar_b'):                                      # the side without a sidecar counts 0 rays
+        a, b = (_scene(s) for s in MERGE_CASES[name])
+        got = _host_merge(host_exe, tmp_path, name)
+        have = a[1] if a[1] is not None else b[1]
+        assert got['pierced'].tolist() == [have.get(int(k), 0) for k in got['keys'].tolist()], name
+    assert _host_merge(host_exe, tmp_path, 'no_sidecar')['pierced'] is None
+
+
+def test_merge_too_small_writes_nothing(host_exe, tmp_path):
+    """The driver asserts that every output row is still poison; the state words are those before the call."""
+    a, b = _scene('grow_a'), _scene('grow_b')
+    for cap in (1024, 1999):
+        counters, state = _too_small_result(host_exe, tmp_path, 'small%d' % cap, a, b, cap)
+        assert counters == [1, 2000, 0, 1000, 0] and state == [1000, 100] + [7] * 6, cap
+    got = _run_host_merge(host_exe, tmp_path, 'exact', a, b, out_capacity=2000)  # the smallest capacity that holds it
+    assert got['counters'] == [0, 2000, 0, 1000, 0] and got['keys'].shape[0] == 2000
+
+
+@pytest.mark.parametrize('name', REGRID_NAMES)
+def test_regrid_host_build_equals_the_restatement(host_exe, tmp_path, name):
+    scene, pose, vs = REGRID_CASES[name]
+    r, p = _scene(scene)
+    want, wp, res = mref.regrid(r, p, pose, vs)
+    got = _host_regrid(host_exe, tmp_path, name)
+    assert got['counters'] == [res['rows_in'], res['rows_out'], res['dropped_rows'], res['dropped_points'], res['saturated']], name
+    assert got['state'] == [res['rows_out'], r.dropped + res['dropped_points']] + [0] * 6 and want.dropped == got['state'][1], name
+    _assert_tables(got, _as_tables(want, wp), name)
+
+
+def test_regrid_drops_conserves_and_saturates(host_exe, tmp_path):
+    dense = _scene('dense')[0]
+    total = lambda t, f: int(t['acc'][f].sum())
+    src = _as_tables(dense, None)
+    doubled = _host_regrid(host_exe, tmp_path, 'doubled')                        # identity pose, twice the voxel size: nothing is lost but resolution
+    assert doubled['counters'][2:] == [0, 0, 0] and doubled['counters'][1] < doubled['counters'][0] == dense.num_voxels
+    assert total(doubled, 0) == total(src, 0) == 9000 - 18 and total(doubled, 1) == total(src, 1)
+    assert doubled['stamps'][0].min() == src['stamps'][0].min() == 1 and doubled['stamps'][1].max() == src['stamps'][1].max() == 5
+    far = _host_regrid(host_exe, tmp_path, 'far')                                # x + 32767.5 >= 32768 leaves: dropped whole, nothing clamped
+    r, p = _scene('dense_rays')
+    cx = {k: (np.float64(v[2]) / np.float64(v[0])) * 2.0 ** -16 + FAR[0, 3] for k, v in r.rec.items()}
+    gone = [k for k in r.rec if not abs(cx[k]) < 32768.0]
+    assert 0 < len(gone) < r.num_voxels and far['counters'] == [r.num_voxels, r.num_voxels - len(gone), len(gone), sum(r.rec[k][0] for k in gone), 0]
+    assert far['state'][1] == r.dropped + far['counters'][3] and ((far['keys'] >> 42) - BIAS).max() < 327680
+    assert int(far['pierced'].sum()) == sum(v for k, v in p.items() if k not in gone)
+    nan = _host_regrid(host_exe, tmp_path, 'nan')                                # one NaN in the pose: every row dropped, an empty map
+    assert nan['counters'] == [dense.num_voxels, 0, dense.num_voxels, 9000 - 18, 0] and nan['keys'].shape[0] == 0
+    limit = _host_regrid(host_exe, tmp_path, 'index_limit')                      # voxel size 5e-7: |w| / 5e-7 >= 2^20 beyond 0.52 m
+    assert 0 < limit['counters'][2] < dense.num_voxels
+    for name in ('crafted', 'crafted_identity'):                                 # count 0, -3 and 2^31 + 1 are unusable, 2^31 is not
+        got = _host_regrid(host_exe, tmp_path, name)
+        assert got['counters'][2:4] == [3, (1 << 31) + 1] and got['counters'][1] == 5, name
+    same = _host_regrid(host_exe, tmp_path, 'crafted_identity')                  # the identity at the same voxel size: a usable row stays in its voxel;
+    crafted = _scene('crafted')[0]                                               # the row of 2^31 points was given the sums 0: its centroid is the origin
+    assert set(same['keys'].tolist()) == set(sorted(crafted.rec)[0::2]) | {_key((0, 0, 0))}
+    assert same['acc'][:, same['keys'].tolist().index(_key((0, 0, 0)))].tolist() == [1 << 31, crafted.rec[sorted(crafted.rec)[7]][1], 0, 0, 0]
+    sat = _host_regrid(host_exe, tmp_path, 'saturation')
+    assert sat['counters'] == [3, 2, 0, 0, 1] and sat['pierced'].tolist() == [I31, 9]
+    assert _host_regrid(host_exe, tmp_path, 'empty')['counters'] == [0, 0, 0, 0, 0]
+
+
+def test_header_binding_and_argument_checks():
+    from pcaccumulation_amd import native
+    from pcaccumulation_amd.accumulate import AccumulatedCloud
+    header = open(os.path.join(ROOT, 'include', 'pcacc.h')).read()
+    for name in ('pcacc_accum_merge_workspace_bytes', 'pcacc_accum_merge', 'pcacc_accum_regrid_workspace_bytes', 'pcacc_accum_regrid'):
+        assert ('int %s(' % name) in header and name in native.EXPORTS
+    assert ' C12. ' in header and len(native._PROTOTYPES['pcacc_accum_merge']) == 23 and len(native._PROTOTYPES['pcacc_accum_regrid']) == 19
+    for word, value in (('MERGE_COUNTERS', 5), ('MERGE_STATUS', 0), ('MERGE_NEEDED', 1), ('MERGE_SHARED', 2), ('MERGE_NEW', 3), ('MERGE_SATURATED', 4),
+                        ('REGRID_COUNTERS', 5), ('REGRID_ROWS_IN', 0), ('REGRID_ROWS_OUT', 1), ('REGRID_DROPPED_ROWS', 2), ('REGRID_DROPPED_POINTS', 3),
+                        ('REGRID_SATURATED', 4)):
+        assert ('#define PCACC_%s %d' % (word, value)) in header and getattr(native, word) == value, word
+    csrc = os.path.join(ROOT, 'pcaccumulation_amd', 'csrc')
+    text = open(os.path.join(csrc, 'accum_merge.h')).read()
+    assert [l for l in text.split('\n') if l.startswith('#include')] == ['#include "accum_normals.h"']            # nothing of HIP
+    assert all(s in text for s in ('accum_lower_bound(', 'accum_merge_dst(', 'accum_field(', 'accn_centroid(', 'ACC_COORD_LIMIT', 'ACC_IDX_BIAS', 'ACC_FIXED_ONE'))
+    assert '32768' not in text.split('#pragma once')[1] and '1048576' not in text and '65536' not in text.split('#pragma once')[1]   # no bound restated
+    hip = open(os.path.join(csrc, 'accum_merge.hip')).read()
+    assert 'pcacc_scan_i32(' in hip and 'accum_wave_count(' in hip and 'accum_tables_overlap(' in hip and 'acc_seg_scan(' in hip
+    assert 'acc_seg_scan(long long' in open(os.path.join(csrc, 'accum_launch.h')).read() and 'acc_seg_scan(long long' not in open(os.path.join(csrc, 'accum.hip')).read()
+    assert 'accum_merge.hip' in open(os.path.join(csrc, 'Makefile')).read()
+    a, b = AccumulatedCloud(0.1, 'cpu', 64), AccumulatedCloud(0.2, 'cpu', 64)
+    with pytest.raises(ValueError, match='pose=.*regrid'):                       # before any call: the device is never asked
+        a.merge(b)
+    with pytest.raises(ValueError, match='pose=.*regrid'):
+        a.merge(AccumulatedCloud(np.nextafter(0.1, 1.0), 'cpu', 64))             # float equality
+    for bad in (5, None, 'map', (a,)):
+        with pytest.raises(TypeError):
+            a.merge(bad)
+    with pytest.raises(ValueError):
+        a.regrid()
+    for bad in (dict(voxel_size=0.0), dict(voxel_size=float('nan')), dict(voxel_size=-1.0), dict(pose=np.eye(3)), dict(voxel_size=0.2, capacity=0)):
+        with pytest.raises(ValueError):
+            a.regrid(**bad)
+    for call in (lambda: a.merge(AccumulatedCloud(0.1, 'cpu', 64)), lambda: a.merge(b, pose=np.eye(4)), lambda: a.regrid(voxel_size=0.2),
+                 lambda: a.regrid(pose=np.eye(4))):
+        with pytest.raises(native.NativeError):                                  # there is no CPU path
+            call()
+    c = a.copy()
+    assert c is not a and (c.voxel_size, c.capacity, c.num_voxels, c.dropped, c.device) == (0.1, 64, 0, 0, a.device)
+    cpu = (torch.zeros(4, dtype=torch.int64), torch.zeros(5, 4, dtype=torch.int64), torch.zeros(2, 4, dtype=torch.int32))
+    words = torch.zeros(5, dtype=torch.int64), torch.zeros(8, dtype=torch.int64)
+    with pytest.raises(native.NativeError):
+        native.accum_merge(cpu, 0, None, cpu, 0, None, 0, tuple(t.clone() for t in cpu), None, words[0], words[1])
+    with pytest.raises(native.NativeError):
+        native.accum_regrid(cpu, 0, None, None, 0.1, 0, tuple(t.clone() for t in cpu), None, words[0], words[1])
+
+
+# ---- GPU ---------------------------------------------------------------------------------------------------------------------------------------------------
+def _device_cloud(r, pierced, capacity=None):
+    """The restatement's map and ray counts as an AccumulatedCloud on the device, through load()."""
+    from pcaccumulation_amd.accumulate import AccumulatedCloud
+    keys, acc, stamps = r.records()
+    extra = {}
+    if pierced is not None:
+        extra = dict(pierced=mref.aligned(pierced, keys), pierce_counters=np.arange(5, dtype=np.int64) + r.num_voxels)
+    buf = io.BytesIO()
+    np.savez(buf, keys=keys, acc=acc.reshape(5, -1), stamps=stamps.reshape(2, -1), voxel_size=np.float64(r.voxel_size), dropped=np.int64(r.dropped), **extra)
+    buf.seek(0)
+    return AccumulatedCloud.load(buf, DEV)
+
+
+def _snapshot(m):
+    n = m.num_voxels
+    keys, acc, stamps = m._cur
+    return (n, m.capacity, m.dropped, keys[:n].clone(), acc[:, :n].clone(), stamps[:, :n].clone(), None if m._pierced is None else m._pierced[:n].clone(),
+            m._state.clone(), None if m._pierce_counters is None else m._pierce_counters.clone())
+
+
+def _assert_unchanged(m, snap, what):
+    now = _snapshot(m)
+    assert now[:3] == snap[:3], what
+    for a, b in zip(now[3:], snap[3:]):
+        assert (a is None and b is None) or torch.equal(a, b), what
+
+
+def _assert_same_map(a, b, what):
+    """Two device maps: rows, every record field, both stamp rows, dropped, the ray counts, and the state words the map owns."""
+    n = b.num_voxels
+    assert a.num_voxels == n and a.dropped == b.dropped and a.voxel_size == b.voxel_size, what
+    for x, y in zip(a._cur, b._cur):
+        assert torch.equal(x[..., :n], y[..., :n]), what
+    assert a._state[:2].tolist() == b._state[:2].tolist() == [n, b.dropped], what
+    assert (a._pierced is None) == (b._pierced is None), what
+    if a._pierced is not None:
+        assert a._pierced.shape[0] == a.capacity and torch.equal(a._pierced[:n], b._pierced[:n]), what
+
+
+def _assert_device_equals_host(m, host, what):
+    t = lambda a: torch.from_numpy(a).to(DEV)
+    n = host['keys'].shape[0]
+    assert m.num_voxels == n, what
+    keys, acc, stamps = m._cur
+    assert torch.equal(keys[:n], t(host['keys'])) and torch.equal(acc[:, :n], t(host['acc'])) and torch.equal(stamps[:, :n], t(host['stamps'])), what
+    assert (m._pierced is None) == (host['pierced'] is None), what
+    if host['pierced'] is not None:
+        assert m._pierced.shape[0] == m.capacity and torch.equal(m._pierced[:n], t(host['pierced'])), what
+
+
+def _saved(m, tmp_path, tag):
+    """The members of a save()d file, byte for byte (the zip container around them carries the time of day)."""
+    path = os.path.join(str(tmp_path), tag + '.npz')
+    m.save(path)
+    with np.load(path) as z:
+        return {k: (z[k].dtype.str, z[k].shape, z[k].tobytes()) for k in z.files}
+
+
+_windows = {}
+
+
+def _window(k):
+    """2049 random points in a 6 m x 6 m x 3 m box with flags, a stamp and a pose; two of them not finite."""
+    if k not in _windows:
+        rs = np.random.RandomState(70 + k)
+        pts = rs.uniform((-3, -3, -1.5), (3, 3, 1.5), (2049, 3)).astype(np.float32)
+        pts[5 + k] = np.nan
+        pts[900 + 7 * k, 1] = np.inf
+        _windows[k] = (pts, rs.uniform(0, 1, 2049) < 0.3, 10 - 3 * k if k % 2 else k, _rot((0.1 * k, 1.0, 0.3), 0.02 * k, (0.05 * k, -0.03 * k, 0.01)))
+    return _windows[k]
+
+
+def _added(ks, capacity=64, vs=0.1):
+    from pcaccumulation_amd.accumulate import AccumulatedCloud
+    m = AccumulatedCloud(vs, DEV, capacity)
+    for k in ks:
+        pts, mv, stamp, pose = _window(k)
+        m.add(torch.from_numpy(pts).to(DEV), pose, torch.from_numpy(mv).to(DEV), stamp)
+    return m
+
+
+@pytest.mark.gpu
+def test_merge_is_add_gpu(tmp_path):
+    A, B, C = _added((1, 3)), _added((2, 4)), _added((1, 2, 3, 4))
+    snap_a, snap_b = _snapshot(A), _snapshot(B)
+    ab = A.copy()
+    res = ab.merge(B)
+    _assert_unchanged(B, snap_b, 'other is not modified')
+    _assert_unchanged(A, snap_a, 'a copy is independent')
+    _assert_same_map(ab, C, 'A.merge(B)')
+    assert ab.dropped == C.dropped == 8 and _saved(ab, tmp_path, 'ab') == _saved(C, tmp_path, 'c')
+    assert res['rows'] == C.num_voxels == A.num_voxels + res['new'] and res['shared'] + res['new'] == B.num_voxels and res['shared'] > 0
+    assert (res['dropped_rows'], res['dropped_points'], res['saturated']) == (0, 0, 0) and all(type(v) is int for v in res.values())
+    assert ab.capacity >= C.num_voxels and ab._state[2:].tolist() == A._state[2:].tolist()      # every other state word is left alone
+    ba = B.copy()
+    ba.merge(A)
+    _assert_same_map(ba, C, 'B.merge(A)')
+    assert _saved(ba, tmp_path, 'ba') == _saved(C, tmp_path, 'c')
+    D = _added((5,))                                                             # grouping: (A u B) u D == A u (B u D)
+    left = ab.copy()
+    left.merge(D)
+    bd = B.copy()
+    bd.merge(D)
+    right = A.copy()
+    right.merge(bd)
+    _assert_same_map(left, right, 'grouping')
+    _assert_same_map(left, _added((1, 2, 3, 4, 5)), 'five windows')
+    pts, mv, stamp, pose = _window(6)                                            # an add onto the merged map: the buffer swap
+    ab.add(torch.from_numpy(pts).to(DEV), pose, torch.from_numpy(mv).to(DEV), stamp)
+    _assert_same_map(ab, _added((1, 2, 3, 4, 6)), 'add after merge')
+    empty = _added(())
+    before = _snapshot(ab)
+    assert ab.merge(empty) == dict(rows=ab.num_voxels, shared=0, new=0, dropped_rows=0, dropped_points=0, saturated=0)
+    _assert_unchanged(ab, before, 'an empty other changes nothing')
+    into = _added(())                                                            # a map that never saw an add takes another whole
+    into.merge(C)
+    _assert_same_map(into, C, 'empty.merge(C)')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', MERGE_NAMES)
+def test_merge_kernel_equals_the_host_build_gpu(host_exe, tmp_path, name):
+    from pcaccumulation_amd import native
+    a, b = MERGE_CASES[name]
+    host = _host_merge(host_exe, tmp_path, name)
+    A = _device_cloud(*_scene(a))
+    B = A if b is None else _device_cloud(*_scene(b))
+    snap_b, state, drop_a, drop_b = _snapshot(B), A._state.tolist(), A.dropped, B.dropped
+    counters = (None if A._pierce_counters is None else A._pierce_counters.clone(), None if B._pierce_counters is None else B._pierce_counters.clone())
+    res = A.merge(B)
+    assert [0, res['rows'], res['shared'], res['new'], res['saturated']] == host['counters'], name
+    _assert_device_equals_host(A, host, name)
+    if b is not None:
+        _assert_unchanged(B, snap_b, name)
+    if B.num_voxels or b is None:                                                # an empty other returns before the device is asked
+        state[native.ACCUM_NUM_VOXELS], state[native.ACCUM_DROPPED] = host['counters'][1], drop_a + drop_b
+    assert A._state.tolist() == state and A.dropped == state[native.ACCUM_DROPPED], name
+    if B.num_voxels and any(c is not None for c in counters):
+        want = sum(c for c in counters if c is not None)
+        assert torch.equal(A._pierce_counters, want), name
+    again = _device_cloud(*_scene(a))                                            # a second run gives the same map
+    assert again.merge(again if b is None else _device_cloud(*_scene(b))) == res
+    _assert_same_map(again, A, name)
+
+
+@pytest.mark.gpu
+def test_merge_kernel_on_76661_voxels_gpu(host_exe, tmp_path):
+    a, b = _scene('wavy'), _scene('wavy_shifted')
+    host = _run_host_merge(host_exe, tmp_path, 'wavy', a, b)
+    A, B = _device_cloud(*a), _device_cloud(*b)
+    assert A.num_voxels == 76661 and A.capacity == 131072
+    res = A.merge(B)
+    assert [0, res['rows'], res['shared'], res['new'], res['saturated']] == host['counters'] and 0 < res['shared'] < 76661 < res['rows']
+    assert A.capacity == 262144 and 131072 < res['rows']                         # the union outgrew the tables: one refused attempt, then the doubling
+    _assert_device_equals_host(A, host, 'wavy')
+    assert A._cur[1][0, :res['rows']].sum().item() == 2 * (270400 + 1)           # every point of both sheets
+
+
+@pytest.mark.gpu
+def test_merge_grows_by_the_devices_count_gpu(host_exe, tmp_path):
+    from pcaccumulation_amd import native
+    A, B = _device_cloud(*_scene('grow_a')), _device_cloud(*_scene('grow_b'))
+    assert (A.capacity, A.num_voxels, B.capacity, B.num_voxels) == (1024, 1000, 1024, 1000)
+    snap_a, snap_b = _snapshot(A), _snapshot(B)
+    # the refused attempt on its own: a capacity the host knows is too small, nothing overrun, nothing written
+    out = tuple(torch.full_like(t, 7) for t in A._cur)
+    counters = torch.full((5,), 7, dtype=torch.int64, device=DEV)
+    native.accum_merge(A._cur, 1000, None, B._cur, 1000, None, B.dropped, out, None, counters, A._state)
+    assert counters.tolist() == [native.ACCUM_TOO_SMALL, 2000, 0, 1000, 0] and all(bool((t == 7).all()) for t in out)
+    _assert_unchanged(A, snap_a, 'refused attempt')
+    _assert_unchanged(B, snap_b, 'refused attempt')
+    res = A.merge(B)
+    assert res == dict(rows=2000, shared=0, new=1000, dropped_rows=0, dropped_points=0, saturated=0) and (A.capacity, A.num_voxels) == (2048, 2000)
+    _assert_device_equals_host(A, _run_host_merge(host_exe, tmp_path, 'grow', _scene('grow_a'), _scene('grow_b')), 'grow')
+    _assert_unchanged(B, snap_b, 'other')
+    assert A._pierced is None and A._cur[0].shape[0] == 2048
+
+
+# ---- regrid ------------------------------------------------------------------------------------------------------------------------------------------------
+def _fine_points(index):
+    """Voxel indices at 2^-10 m -> one point inside each voxel on the 2^-16 grid: exact in float32 (|x| < 64: 22 bits) and in fixed point."""
+    index = np.asarray(index, np.int64)
+    sub = np.random.RandomState(len(index)).randint(0, 64, index.shape)
+    pts = ((index * 64 + sub).astype(np.float64) * 2.0 ** -16).astype(np.float32)
+    assert np.abs(pts).max() < 64 and np.array_equal(pts.astype(np.float64) * 65536.0, (index * 64 + sub).astype(np.float64))
+    return pts
+
+
+def _fine_case(name):
+    rs = np.random.RandomState(81)
+    if name == 'scattered':                                                      # 3000 voxels of a 6 m box
+        index = np.unique(rs.randint(-3000, 3000, (3000, 3)), axis=0)
+    elif name == 'one_voxel':                                                    # 5000 source voxels inside the pre-image of ONE 0.5 m voxel: a run longer than any tile
+        centre = np.linalg.inv(SKEW) @ np.array([1.25, -0.75, 2.25, 1.0])
+        index = np.unique(np.floor(centre[:3] * 1024).astype(np.int64) + rs.randint(-120, 121, (5200, 3)), axis=0)[:5000]
+    else:                                                                        # 4096 voxels 0.94 m apart or more (a 0.5 m voxel is 0.87 m across): 4096 distinct 0.5 m voxels under any rigid pose
+        assert name == 'distinct'
+        g = np.arange(16) - 8
+        index = np.stack(np.meshgrid(g, g, g, indexing='ij'), -1).reshape(-1, 3) * 1024 + rs.randint(0, 64, (4096, 3))
+    return _fine_points(index)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', ['scattered', 'one_voxel', 'distinct'])
+def test_regrid_is_add_gpu(name):
+    from pcaccumulation_amd.accumulate import AccumulatedCloud
+    pts = _fine_case(name)
+    n = pts.shape[0]
+    mv = np.random.RandomState(82).uniform(0, 1, n) < 0.4
+    cuts = [0, n // 3, n // 2, n]
+    src, want = AccumulatedCloud(2.0 ** -10, DEV, 8192), AccumulatedCloud(0.5, DEV, 8192)
+    for k, stamp in enumerate((7, 2, 11)):
+        sel = slice(cuts[k], cuts[k + 1])
+        p, f = torch.from_numpy(pts[sel]).to(DEV), torch.from_numpy(mv[sel]).to(DEV)
+        src.add(p, None, f, stamp)
+        want.add(p, SKEW, f, stamp)
+    assert src.num_voxels == n and src.dropped == 0                              # one point per source voxel
+    snap = _snapshot(src)
+    got = src.regrid(pose=SKEW, voxel_size=0.5)
+    _assert_unchanged(src, snap, name)
+    _assert_same_map(got, want, name)
+    assert got._state.tolist() == [want.num_voxels, 0, 0, 0, 0, 0, 0, 0] and got.capacity == src.capacity and got.device == src.device
+    assert want.num_voxels == {'scattered': want.num_voxels, 'one_voxel': 1, 'distinct': 4096}[name] and (want.num_voxels < n) == (name != 'distinct')
+    assert torch.equal(got.extract()['points'], want.extract()['points'])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', REGRID_NAMES)
+def test_regrid_kernel_equals_the_host_build_gpu(host_exe, tmp_path, name):
+    scene, pose, vs = REGRID_CASES[name]
+    r, p = _scene(scene)
+    host = _host_regrid(host_exe, tmp_path, name)
+    src = _device_cloud(r, p)                                                    # count 0 and 2^31 + 1 come in through load()
+    snap = _snapshot(src)
+    got, counters = src._regrid(pose, vs, None)
+    assert counters == host['counters'], name
+    _assert_unchanged(src, snap, name)
+    _assert_device_equals_host(got, host, name)
+    assert got._state.tolist() == host['state'] and got.dropped == host['state'][1] and got.voxel_size == vs, name
+    if p is not None:
+        assert torch.equal(got._pierce_counters, src._pierce_counters) and got._pierce_counters is not src._pierce_counters
+    small = src.regrid(pose, vs, capacity=max(src.num_voxels, 1))                # the smallest capacity the call takes
+    _assert_same_map(small, got, name)
+    with pytest.raises(ValueError):
+        src.regrid(pose, vs, capacity=src.num_voxels - 1)
+
+
+@pytest.mark.gpu
+def test_regrid_kernel_on_76661_voxels_gpu(host_exe, tmp_path):
+    a = _scene('wavy')
+    host = _run_host_regrid(host_exe, tmp_path, 'wavy', a, SKEW, 0.2)
+    got, counters = _device_cloud(*a)._regrid(SKEW, 0.2, None)
+    assert counters == host['counters'] and counters[0] == 76661 and 2048 < counters[1] < 76661
+    _assert_device_equals_host(got, host, 'wavy')
+
+
+@pytest.mark.gpu
+def test_merge_with_a_pose_is_regrid_then_merge_gpu():
+    for scene, pose, vs in (('dense_rays', SKEW, 0.1), ('dense', SKEW, 0.25), ('dense_rays', FAR, 0.1), ('crafted', None, 0.1)):
+        other = _device_cloud(*_scene(scene))
+        pose = np.eye(4) if pose is None else pose
+        snap = _snapshot(other)
+        a, b = _added((1, 2), vs=vs), _added((1, 2), vs=vs)
+        res = a.merge(other, pose=torch.from_numpy(pose))
+        _assert_unchanged(other, snap, scene)
+        tmp, counters = other._regrid(pose, vs, None)
+        want = b.merge(tmp)
+        _assert_same_map(a, b, scene)
+        assert res == dict(want, dropped_rows=counters[2], dropped_points=counters[3], saturated=want['saturated'] + counters[4]), scene
+        assert a.dropped == 4 + other.dropped + counters[3], scene
+        assert (a._pierced is None) == (other._pierced is None), scene
+
+
+@pytest.mark.gpu
+def test_bad_arguments_launch_nothing_gpu():
+    from pcaccumulation_amd import native
+    A, B = _device_cloud(*_scene('rays_a')), _device_cloud(*_scene('rays_b'))
+    assert (A.num_voxels, A.capacity, B.num_voxels, B.capacity) == (70, 128, 70, 128)
+    snap_a, snap_b = _snapshot(A), _snapshot(B)
+    out = tuple(torch.full_like(t, 7) for t in A._cur)                           # 128 rows: any of them may stand in for an input's table
+    pout = torch.full_like(A._pierced, 7)
+    small = tuple(t[..., :69].contiguous() for t in out)
+    mc, rc = (torch.full((5,), 7, dtype=torch.int64, device=DEV) for _ in range(2))
+    state = torch.full((8,), 7, dtype=torch.int64, device=DEV)
+    good = dict(tables_a=A._cur, ma=70, pierced_a=A._pierced, tables_b=B._cur, mb=70, pierced_b=B._pierced, add_dropped=0, tables_out=out,
+                pierced_out=pout, counters=mc, state=state)
+    for bad in (dict(tables_out=A._cur), dict(tables_out=B._cur), dict(pierced_out=A._pierced), dict(pierced_out=B._pierced),
+                dict(tables_out=(out[0], A._cur[1], out[2])), dict(tables_out=(out[0], out[1], B._cur[2])), dict(tables_out=(B._cur[0], out[1], out[2])),
+                dict(ma=129), dict(ma=-1), dict(mb=129), dict(mb=-1)):
+        with pytest.raises(native.NativeError, match='PCACC_E_ARG'):
+            native.accum_merge(**dict(good, **bad))
+    rgood = dict(tables_in=A._cur, m=70, pierced_in=A._pierced, pose=None, out_voxel_size=0.2, carry_dropped=0, tables_out=out, pierced_out=pout,
+                 counters=rc, state=state)
+    for bad in (dict(tables_out=A._cur), dict(pierced_out=A._pierced), dict(tables_out=(out[0], A._cur[1], out[2])),
+                dict(tables_out=small, pierced_out=pout[:69].contiguous()), dict(m=129), dict(m=-1), dict(out_voxel_size=0.0),
+                dict(out_voxel_size=float('nan'))):
+        with pytest.raises(native.NativeError, match='PCACC_E_ARG'):
+            native.accum_regrid(**dict(rgood, **bad))
+    torch.cuda.synchronize()
+    _assert_unchanged(A, snap_a, 'bad arguments')
+    _assert_unchanged(B, snap_b, 'bad arguments')
+    assert all(bool((t == 7).all()) for t in out + small + (pout, mc, rc, state))   # nothing was written
+    native.accum_merge(**dict(good, ma=0, mb=0))                                 # ma = mb = 0: the zero counters and NUM_VOXELS = 0, nothing else
+    assert mc.tolist() == [0] * 5 and state.tolist() == [0] + [7] * 7 and all(bool((t == 7).all()) for t in out + (pout,))
+    native.accum_regrid(**dict(rgood, m=0))                                      # m = 0: the zero counters and the state of an empty map
+    assert rc.tolist() == [0] * 5 and state.tolist() == [0] * 8 and all(bool((t == 7).all()) for t in out + (pout,))
