@@ -995,6 +995,74 @@ int pcacc_accum_regrid(const int64_t *in_keys, const int64_t *in_acc, const int3
                        size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C13. Two accumulated scene clouds compared -- what changed? -- and the rows of pcacc_accum_extract that a mask names as a new map.  Replaces the
+ * copy of both maps' records to the host and a numpy join there, and two one-way pcacc_accum_query calls on float32 centroids that name no row of
+ * the other map.  Takes no pose and one voxel size, finds one nearest centroid within one voxel, compares no normals or stamps, makes no
+ * free-space test, takes two maps per call and selects out of place.
+ * pcacc_accum_compare: both directions in one call.  Inputs
+ *   a_keys, a_acc, a_capacity, ma                      the first ma rows of map A;  b_*, b_capacity, mb: the first mb rows of map B
+ *   a_pierced, b_pierced [capacity] i32 or NULL        the sidecars of pcacc_accum_pierce
+ *   voxel_size; max_distance in (0, voxel_size]; min_count >= 1, use_fraction, max_moving_fraction: ONE filter for both maps, extract's
+ * Both maps are ascending and duplicate-free, on ONE grid.  A and B may be the same tables.  Neither is modified.
+ * Outputs (device), per side one row per row pcacc_accum_extract returns under the filter, in its order (every column has room for that side's
+ * m rows; rows behind KEPT are not written).  For own row i that the filter keeps, against the other map O, all float64 with no FMA contraction:
+ *   key = keys[i], idx = its voxel;  w_a = (float64(sum q_a) / float64(count)) * 2^-16, the centroid of C5
+ *   HELD iff O holds the key, at its row q;  out_pierced = O's ray count at q (0 without a sidecar or without HELD)
+ *   SAME iff HELD and the filter keeps O's row q;  out_same_row = that row's row of O's extract, else -1
+ *   NEAR iff C9's nearest search finds a centroid: the kept rows of O in the 3 x 3 x 3 voxels around idx in ascending key order,
+ *     d2 = (e_x e_x + e_y e_y) + e_z e_z, strict < (ties to the lowest key), accepted iff d2 <= max_distance^2;  out_row = its row of O's extract,
+ *     out_distance = sqrt(d2); -1 and +inf without one.  For max_distance <= 0.9 voxel_size this is the nearest kept centroid of the whole of O.
+ *   out_status u8 = a sum of PCACC_COMPARE_SAME, _HELD, _NEAR
+ *   counters [PCACC_COMPARE_COUNTERS] i64 (written, not added to): for A at 0 and for B at PCACC_COMPARE_SIDE_COUNTERS, map rows, rows the filter
+ *   keeps, and of those the rows with SAME, with HELD, with NEAR, and with neither SAME nor NEAR (ONLY).
+ * A side with 0 rows has KEPT = 0 and nothing of it is addressed; every kept row of the other side is then ONLY.  ma = mb = 0 writes the zero
+ * counters and launches nothing else.  Nothing is read back.
+ * Return value: PCACC_E_ARG, and nothing is launched, for ma or mb outside [0, capacity], a capacity above 2^30, min_count < 1, a voxel_size or
+ * max_distance that is not positive and finite, max_distance > voxel_size, a NULL table of non-zero size or an output column that is NULL while
+ * its side has rows; PCACC_E_WORKSPACE for a workspace that is too small.
+ * pcacc_accum_select: map row i is written iff the filter keeps it (extract row j) and (mask[j] != 0) != (invert != 0); mask [mask_rows] u8 over
+ * the rows of pcacc_accum_extract under the same filter.  The selected rows go, in key order and every record and ray count bit-identical, to
+ * out_keys, out_acc, out_stamps (out_capacity >= m rows: there is no "too small" path) and, iff in_pierced is given, out_pierced.  All eight words
+ * of the new map's state are written: NUM_VOXELS = SELECTED, the rest 0.  The input map is not modified.
+ *   counters [PCACC_SELECT_COUNTERS] i64 (written): status, map rows, rows the filter keeps, rows selected.
+ * Status PCACC_SELECT_BAD_MASK: mask_rows differs from the rows the filter keeps (decided on the device): no mask entry is addressed and nothing
+ * is written to the output tables or the state.
+ * Return value: PCACC_E_ARG, and nothing is launched, for m outside [0, in_capacity], out_capacity < m, a capacity above 2^30, min_count < 1,
+ * mask_rows < 0, a NULL table or mask of non-zero size, or an output table that shares memory with an input table; PCACC_E_WORKSPACE for a
+ * workspace that is too small.
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_COMPARE_SAME 1
+#define PCACC_COMPARE_HELD 2
+#define PCACC_COMPARE_NEAR 4
+#define PCACC_COMPARE_COUNTERS 12
+#define PCACC_COMPARE_SIDE_COUNTERS 6  /* side A at 0, side B at 6 */
+#define PCACC_COMPARE_ROWS 0           /* rows of the side's map */
+#define PCACC_COMPARE_KEPT 1           /* rows the filter keeps = rows of the side's columns */
+#define PCACC_COMPARE_N_SAME 2
+#define PCACC_COMPARE_N_HELD 3
+#define PCACC_COMPARE_N_NEAR 4
+#define PCACC_COMPARE_N_ONLY 5         /* kept rows with neither SAME nor NEAR */
+#define PCACC_SELECT_COUNTERS 4
+#define PCACC_SELECT_STATUS 0          /* PCACC_SELECT_OK or PCACC_SELECT_BAD_MASK */
+#define PCACC_SELECT_ROWS 1
+#define PCACC_SELECT_KEPT 2
+#define PCACC_SELECT_SELECTED 3
+#define PCACC_SELECT_OK 0
+#define PCACC_SELECT_BAD_MASK 1
+int pcacc_accum_compare_workspace_bytes(int64_t ma, int64_t mb, size_t *bytes /*host*/);
+int pcacc_accum_compare(const int64_t *a_keys, const int64_t *a_acc, const int32_t *a_pierced, int64_t a_capacity, int64_t ma,
+                        const int64_t *b_keys, const int64_t *b_acc, const int32_t *b_pierced, int64_t b_capacity, int64_t mb,
+                        double voxel_size, double max_distance, int64_t min_count, int32_t use_fraction, double max_moving_fraction,
+                        uint8_t *out_a_status, int32_t *out_a_same_row, int32_t *out_a_row, double *out_a_distance, int32_t *out_a_pierced,
+                        uint8_t *out_b_status, int32_t *out_b_same_row, int32_t *out_b_row, double *out_b_distance, int32_t *out_b_pierced,
+                        int64_t *counters, void *workspace, size_t workspace_bytes, void *stream);
+int pcacc_accum_select_workspace_bytes(int64_t m, size_t *bytes /*host*/);
+int pcacc_accum_select(const int64_t *in_keys, const int64_t *in_acc, const int32_t *in_stamps, const int32_t *in_pierced, int64_t in_capacity,
+                       int64_t m, int64_t min_count, int32_t use_fraction, double max_moving_fraction, const uint8_t *mask, int64_t mask_rows,
+                       int32_t invert, int64_t *out_keys, int64_t *out_acc, int32_t *out_stamps, int32_t *out_pierced, int64_t out_capacity,
+                       int64_t *counters, int64_t *state, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

@@ -26,6 +26,9 @@ coordinate sums), so the map does not depend on the order of the points, on the 
     m.save_ply('scene.ply', min_count=2, max_moving_fraction=0.0, viewpoints=sensor_positions)
     m.merge(other_session)                                       # another map of the same place on the same grid, exactly as if m had seen its adds: C12,
     m.merge(submap, pose=submap_to_world)                        # section 9l; a map in its own frame or at another voxel size goes through regrid()
+    changed = m.compare(last_week, max_distance=0.05)            # per row of extract(), both ways: does the other map hold the voxel, which row, the
+    gone = last_week.difference(m, max_distance=0.05)            # nearest centroid within a voxel; what one map has and the other has nothing near, as
+    ground = m.select(static['points'][:, 2] < ground_z, min_count=2, max_moving_fraction=0.0)   # a map; any rows of extract() as a map: C13, section 9m
 
 There is no CPU path: a CPU tensor raises native.NativeError."""
 import numpy as np
@@ -39,6 +42,7 @@ _REGISTER_FIELDS = ('pose', 'fitness', 'rmse', 'iterations', 'status', 'correspo
 _PRUNE_FIELDS = ('kept', 'filter', 'stale', 'box', 'pierced', 'isolated')
 _COMPONENT_FIELDS = ('voxels', 'points', 'moving', 'sum_q', 'centroid', 'lo', 'hi', 't_first', 't_last', 'first_row')
 _REMOVE_FIELDS = ('kept', 'small', 'components_removed', 'components_kept', 'rows', 'participating', 'outside', 'masked', 'components', 'largest')
+_COMPARE_COUNTERS = ('rows', 'kept', 'same', 'held', 'near', 'only')
 _PLY_TYPES = {'float32': 'float', 'float64': 'double', 'int8': 'char', 'uint8': 'uchar', 'int16': 'short', 'uint16': 'ushort', 'int32': 'int',
               'uint32': 'uint'}
 
@@ -116,6 +120,22 @@ def _device_key(device):
     if index is None and device.type == 'cuda':
         index = torch.cuda.current_device() if torch.cuda.is_available() else 0
     return device.type, index
+
+
+def _row_mask(what, mask):
+    """A mask over the rows of extract() (components, remove_components, select): None, or a 1-D bool / uint8 tensor on the GPU -> uint8, contiguous."""
+    if mask is not None:
+        if not torch.is_tensor(mask) or mask.dim() != 1 or mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError('mask must be a 1-D bool / uint8 tensor over the rows of extract()')
+        if not mask.is_cuda:
+            raise native.NativeError('%s: mask must live on the GPU; the HIP path has no CPU fallback' % what)
+        mask = (mask.to(torch.uint8) if mask.dtype == torch.bool else mask).contiguous()
+    return mask
+
+
+def _bad_mask(rows):
+    """The device found a mask whose length is not the number of rows the filter keeps."""
+    return ValueError('mask must have one entry per row of extract() under the same filter (%d rows)' % rows)
 
 
 class AccumulatedCloud(object):
@@ -533,20 +553,13 @@ class AccumulatedCloud(object):
             raise ValueError('radius must be 1, 2 or 3 voxels, got %r' % radius)
         if max_moving_fraction is not None and np.isnan(float(max_moving_fraction)):
             raise ValueError('max_moving_fraction must be a number or None')
-        if mask is not None:
-            if not torch.is_tensor(mask) or mask.dim() != 1 or mask.dtype not in (torch.bool, torch.uint8):
-                raise ValueError('mask must be a 1-D bool / uint8 tensor over the rows of extract()')
-            if not mask.is_cuda:
-                raise native.NativeError('%s: mask must live on the GPU; the HIP path has no CPU fallback' % what)
-            mask = (mask.to(torch.uint8) if mask.dtype == torch.bool else mask).contiguous()
-        return radius, min_count, mask
+        return radius, min_count, _row_mask(what, mask)
 
     @staticmethod
     def _components_status(counters):
         status = counters[native.COMPONENTS_STATUS]
         if status == native.COMPONENTS_BAD_MASK:
-            raise ValueError('mask must have one entry per row of extract() under the same filter (%d rows)'
-                             % (counters[native.COMPONENTS_ROWS] - counters[native.COMPONENTS_OUTSIDE]))
+            raise _bad_mask(counters[native.COMPONENTS_ROWS] - counters[native.COMPONENTS_OUTSIDE])
         if status != native.COMPONENTS_OK:
             raise native.NativeError('accum_components: a join was abandoned under contention (status %d); the labels are not valid' % status)
 
@@ -707,6 +720,84 @@ class AccumulatedCloud(object):
         self._dropped += other._dropped
         res.update(rows=self._n, shared=host[native.MERGE_SHARED], new=host[native.MERGE_NEW], saturated=res['saturated'] + host[native.MERGE_SATURATED])
         return res
+
+    # ---- compare, select, difference ---------------------------------------------------------------------------------------------------
+    def _filter_args(self, min_count, max_moving_fraction):
+        min_count = int(min_count)
+        if min_count < 1:
+            raise ValueError('min_count must be at least 1, got %r' % min_count)
+        if max_moving_fraction is not None and np.isnan(float(max_moving_fraction)):
+            raise ValueError('max_moving_fraction must be a number or None')
+        return min_count
+
+    def compare(self, other, max_distance=None, min_count=1, max_moving_fraction=None):
+        """What changed between this map and another, on the device, in both directions (include/pcacc.h C13).  Neither map is modified.
+        Both maps on one grid (other.voxel_size == self.voxel_size, the same device; regrid() brings a map onto another grid); `other` may be this
+        map.  max_distance in (0, voxel_size] (None = voxel_size); min_count, max_moving_fraction: ONE filter, extract's, for both maps.
+        -> {'self': {...}, 'other': {...}, 'counters': {...}}.  Each side has one row per row of that map's extract(min_count, max_moving_fraction),
+        in its order (normals() and components() align the same way), as device tensors:
+        status [V] u8, a sum of native.COMPARE_* bits: HELD (the other map has this voxel), SAME (and its extract under the filter returns it), NEAR
+        (a centroid the other's extract returns lies within max_distance of this row's float64 centroid, among the 3 x 3 x 3 voxels around it);
+        same_row [V] i32: the voxel's row of the other's extract (-1 without SAME); row [V] i32, distance [V] f64: the nearest such centroid's row
+        there and the distance to it (-1, +inf without NEAR; ties go to the lowest voxel; for max_distance <= 0.9 voxel_size it is the nearest of the
+        whole map); pierced [V] i32: the other's see_through count of this voxel (0 without HELD or without one).  The rows are valid until the
+        next add, prune or merge of the map they index.
+        counters: per side {'rows', 'kept', 'same', 'held', 'near', 'only'}, Python integers -- the one read-back; `only` counts kept rows with
+        neither SAME nor NEAR."""
+        if not isinstance(other, AccumulatedCloud):
+            raise TypeError('compare takes an AccumulatedCloud, got %s' % type(other).__name__)
+        if _device_key(other.device) != _device_key(self.device):
+            raise ValueError('compare: the maps live on %s and %s; save() / load() carries a map across' % (self.device, other.device))
+        if other.voxel_size != self.voxel_size:
+            raise ValueError('compare: voxel sizes %r and %r differ; regrid() one map onto the other\'s grid first' % (self.voxel_size, other.voxel_size))
+        max_distance = self.voxel_size if max_distance is None else float(max_distance)
+        if not 0.0 < max_distance <= self.voxel_size:
+            raise ValueError('max_distance must lie in (0, voxel_size = %r], got %r' % (self.voxel_size, max_distance))
+        min_count = self._filter_args(min_count, max_moving_fraction)
+        self._ensure()
+        other._ensure()
+        res = native.accum_compare(self._cur, self._n, self._pierced, other._cur, other._n, other._pierced, self.voxel_size, max_distance, min_count,
+                                   max_moving_fraction)
+        host = res['counters'].tolist()                            # the one read-back
+        out = {'counters': {}}
+        for side, key, at in (('self', 'a', 0), ('other', 'b', native.COMPARE_SIDE_COUNTERS)):
+            c = dict(zip(_COMPARE_COUNTERS, host[at:at + native.COMPARE_SIDE_COUNTERS]))
+            out[side] = {name: t[:c['kept']] for name, t in res[key].items()}
+            out['counters'][side] = c
+        return out
+
+    def select(self, mask, invert=False, min_count=1, max_moving_fraction=None, capacity=None):
+        """The rows of extract(min_count, max_moving_fraction) that mask [V] bool / uint8 (device) names -- with invert=True the rows it does not name
+        -- as a NEW AccumulatedCloud on the same device (include/pcacc.h C13); this map is not modified.  Rows outside the filter are never
+        selected.  Records, stamps and ray counts are copied bit for bit, the see_through counters are carried, `dropped` starts at 0.  capacity
+        (None = this map's) must hold this map's rows.  Only the four counters are read back."""
+        if mask is None:
+            raise ValueError('select needs a mask over the rows of extract()')
+        mask = _row_mask('select', mask)
+        min_count = self._filter_args(min_count, max_moving_fraction)
+        capacity = self.capacity if capacity is None else int(capacity)
+        if capacity < max(self._n, 1):
+            raise ValueError('capacity must be at least the %d rows of the map (the result never has more), got %r' % (self._n, capacity))
+        new = AccumulatedCloud(self.voxel_size, self.device, capacity)         # checks the capacity
+        self._ensure()
+        new._ensure()
+        if self._pierced is not None:
+            new._pierced = torch.zeros((capacity,), dtype=torch.int32, device=self.device)
+            new._pierce_counters = self._pierce_counters.clone()
+        counters = torch.empty((native.SELECT_COUNTERS,), dtype=torch.int64, device=self.device)
+        native.accum_select(self._cur, self._n, self._pierced, min_count, max_moving_fraction, mask, bool(invert), new._cur, new._pierced, counters,
+                            new._state)
+        host = counters.tolist()                                   # the one read-back of a select
+        if host[native.SELECT_STATUS] == native.SELECT_BAD_MASK:
+            raise _bad_mask(host[native.SELECT_KEPT])
+        new._n = host[native.SELECT_SELECTED]
+        return new
+
+    def difference(self, other, max_distance=None, min_count=1, max_moving_fraction=None):
+        """What this map has and `other` has nothing near: select() of the rows of extract(min_count, max_moving_fraction) that compare(other,
+        max_distance, min_count, max_moving_fraction) gives neither SAME nor NEAR, as a NEW AccumulatedCloud."""
+        status = self.compare(other, max_distance, min_count, max_moving_fraction)['self']['status']
+        return self.select(~(status & (native.COMPARE_SAME | native.COMPARE_NEAR)).bool(), min_count=min_count, max_moving_fraction=max_moving_fraction)
 
     def save_ply(self, path, normals=True, min_count=1, max_moving_fraction=None, **normal_args):
         """extract(min_count, max_moving_fraction) as a binary PLY: x y z, with normals=True nx ny nz of normals(**normal_args) under the same filter

@@ -1037,6 +1037,59 @@ def accum_regrid(tables_in, m, pierced_in, pose, out_voxel_size, carry_dropped, 
                                     _dev(ws), ws.numel(), _stream()), 'accum_regrid')
 
 
+COMPARE_SAME, COMPARE_HELD, COMPARE_NEAR = 1, 2, 4
+COMPARE_COUNTERS, COMPARE_SIDE_COUNTERS = 12, 6
+COMPARE_ROWS, COMPARE_KEPT, COMPARE_N_SAME, COMPARE_N_HELD, COMPARE_N_NEAR, COMPARE_N_ONLY = 0, 1, 2, 3, 4, 5
+COMPARE_FIELDS = (('status', torch.uint8, ()), ('same_row', torch.int32, ()), ('row', torch.int32, ()), ('distance', torch.float64, ()),
+                  ('pierced', torch.int32, ()))
+SELECT_COUNTERS = 4
+SELECT_STATUS, SELECT_ROWS, SELECT_KEPT, SELECT_SELECTED = 0, 1, 2, 3
+SELECT_OK, SELECT_BAD_MASK = 0, 1
+
+
+def accum_compare(tables_a, ma, pierced_a, tables_b, mb, pierced_b, voxel_size, max_distance, min_count, max_moving_fraction, out_a=None, out_b=None,
+                  counters=None):
+    """The first ma rows of map A against the first mb rows of map B and the reverse, both on one grid of voxel_size; see include/pcacc.h (C13).
+    pierced_a / pierced_b [cap] i32 or None; one filter for both maps.  out_a / out_b: dicts of the COMPARE_FIELDS tensors (ma / mb rows each) to
+    write into (None = new ones), counters [12] i64 likewise.  -> {'a': out_a, 'b': out_b, 'counters': counters}: the caller reads the counters
+    and slices each side to its kept count.  Neither map is modified; nothing is read back."""
+    ak, aa, _, acap = _accum_tables(tables_a, 'accum_compare A')
+    bk, ba, _, bcap = _accum_tables(tables_b, 'accum_compare B')
+    dev = tables_a[0].device
+    ma, mb = int(ma), int(mb)
+    _shaped('accum_compare', 'pierced_a', pierced_a, (acap,))
+    _shaped('accum_compare', 'pierced_b', pierced_b, (bcap,))
+    out_a, counters, (a_status, a_same, a_row, a_distance, a_pierced) = _out_columns('accum_compare', COMPARE_FIELDS, max(ma, 0), out_a, counters,
+                                                                                      COMPARE_COUNTERS, dev)
+    out_b, counters, (b_status, b_same, b_row, b_distance, b_pierced) = _out_columns('accum_compare', COMPARE_FIELDS, max(mb, 0), out_b, counters,
+                                                                                      COMPARE_COUNTERS, dev)
+    use_f, f = _fraction(max_moving_fraction)
+    ws = _workspace(lib().pcacc_accum_compare_workspace_bytes, dev, ma, mb)
+    _check(lib().pcacc_accum_compare(ak, aa, _opt(pierced_a, torch.int32, 'pierced_a'), acap, ma, bk, ba, _opt(pierced_b, torch.int32, 'pierced_b'), bcap,
+                                     mb, float(voxel_size), float(max_distance), int(min_count), use_f, f, a_status, a_same, a_row, a_distance,
+                                     a_pierced, b_status, b_same, b_row, b_distance, b_pierced, _dev(counters, torch.int64, 'counters'), _dev(ws),
+                                     ws.numel(), _stream()), 'accum_compare')
+    return {'a': out_a, 'b': out_b, 'counters': counters}
+
+
+def accum_select(tables_in, m, pierced_in, min_count, max_moving_fraction, mask, invert, tables_out, pierced_out, counters, state):
+    """The rows of accum_extract on the first m rows of a map that mask [V] u8 names (with invert: the others), as a map, out of place; see
+    include/pcacc.h (C13).  pierced_in [cap] i32 or None; tables_out = (keys, acc, stamps) of at least m rows, pierced_out [cap] i32 with pierced_in;
+    state [8] i64: the new map's, every word written.  Writes counters [4] i64 (status, rows, kept, selected); with SELECT_BAD_MASK nothing else.
+    Nothing is read back."""
+    ik, ia, is_, icap = _accum_tables(tables_in, 'accum_select input')
+    _shaped('accum_select', 'pierced_in', pierced_in, (icap,))
+    _shaped('accum_select', 'mask', mask, ('V',))
+    _shaped('accum_select', 'counters', counters, (SELECT_COUNTERS,))
+    ok, oa, os_, op, ocap, st = _out_tables('accum_select', tables_out, pierced_out, state, icap)
+    m, mask_rows = int(m), mask.shape[0]
+    use_f, f = _fraction(max_moving_fraction)
+    ws = _workspace(lib().pcacc_accum_select_workspace_bytes, tables_in[0].device, m)
+    _check(lib().pcacc_accum_select(ik, ia, is_, _opt(pierced_in, torch.int32, 'pierced_in'), icap, m, int(min_count), use_f, f,
+                                    _dev(mask, torch.uint8, 'mask') if mask_rows else None, mask_rows, 1 if invert else 0, ok, oa, os_, op, ocap,
+                                    _dev(counters, torch.int64, 'counters'), st, _dev(ws), ws.numel(), _stream()), 'accum_select')
+
+
 RAYCAST_MISS, RAYCAST_HIT, RAYCAST_TRUNCATED, RAYCAST_SKIPPED, RAYCAST_DROPPED = 0, 1, 2, 3, 4
 RAYCAST_COUNTERS = 7
 RAYCAST_N_RAYS, RAYCAST_N_DROPPED, RAYCAST_N_SKIPPED, RAYCAST_N_HIT, RAYCAST_N_MISSED, RAYCAST_N_TRUNCATED, RAYCAST_N_VISITS = 0, 1, 2, 3, 4, 5, 6
