@@ -8,45 +8,14 @@
 // is written: every label row below kept and every component row below K is written exactly once, the rows behind them stay poison; the removal's
 // destinations below `kept` are written exactly once, keys ascend, and the poison behind is untouched.
 //   in : i64 m, in_capacity, out_capacity, has_pierced, has_mask, mask_rows, min_count, use_fraction, radius, min_voxels, min_points, dry_run, seed;
-//        f64 max_moving_fraction; i64 keys[m]; i64 acc[5][m]; i32 stamps[2][m]; i32 pierced[m] (has_pierced); u8 mask[mask_rows] (has_mask)
+//        f64 max_moving_fraction; a map (see accum_host.h); u8 mask[mask_rows] (has_mask)
 //   out: i64 counters[7]; i64 remove_counters[4]; i64 edges; i32 label[kept]; per component (K rows): i32 voxels; i64 points; i64 moving; i64 sum_q[K][3];
 //        f32 centroid[K][3]; i32 lo[K][3]; i32 hi[K][3]; i32 t_first; i32 t_last; i32 first_row; then, unless dry_run or a status other than OK:
-//        i64 keys[rk]; i64 acc[5][rk]; i32 stamps[2][rk]; i32 pierced[rk] (has_pierced), rk = remove_counters[0]
-#include <cassert>
-#include <cstdio>
-#include <cstring>
+//        the map of rk = remove_counters[0] rows
 #include <utility>
-#include <vector>
 
 #include "accum_components.h"
-
-typedef unsigned long long u64;
-
-#define POISON_KEY 0x5a5a5a5a5a5a5a5aull
-#define POISON_ACC 0x5b5b5b5b5b5b5b5bll
-#define POISON_I32 0x5c5c5c5c
-#define POISON_F32 -1234.5f
-
-template <class T> static std::vector<T> rd(FILE *f, size_t n)
-{
-    std::vector<T> v(n);
-    if (n) assert(fread(v.data(), sizeof(T), n, f) == n);
-    return v;
-}
-
-template <class T> static void wr(FILE *f, const std::vector<T> &v, size_t n)
-{
-    assert(n <= v.size());
-    if (n) assert(fwrite(v.data(), sizeof(T), n, f) == n);
-}
-
-// kpos[0..m] = exclusive scan of flag, kpos[m] = total
-static std::vector<int> scan(const std::vector<int> &flag)
-{
-    std::vector<int> kpos(flag.size() + 1, 0);
-    for (size_t i = 0; i < flag.size(); ++i) kpos[i + 1] = kpos[i] + flag[i];
-    return kpos;
-}
+#include "accum_host.h"
 
 static void check_descending(const std::vector<int> &parent, int64_t kept)
 {
@@ -55,50 +24,26 @@ static void check_descending(const std::vector<int> &parent, int64_t kept)
 
 int main(int argc, char **argv)
 {
-    assert(argc == 3);
-    FILE *f = fopen(argv[1], "rb"), *o = fopen(argv[2], "wb");
-    assert(f && o);
+    FILE *f, *o;
+    open_io(argc, argv, &f, &o);
     const std::vector<int64_t> h = rd<int64_t>(f, 13);
     const std::vector<double> g = rd<double>(f, 1);
     const int64_t m = h[0], cap = h[1], ocap = h[2], mask_rows = h[5], min_count = h[6], min_voxels = h[9], min_points = h[10];
     const bool has_pierced = h[3] != 0, has_mask = h[4] != 0, use_fraction = h[7] != 0, dry_run = h[11] != 0;
     const int radius = (int)h[8];
     u64 seed = (u64)h[12];
-    assert(m >= 0 && cap >= m && cap >= 1 && ocap >= m && ocap >= 1 && mask_rows >= 0 && radius >= 1 && radius <= ACCN_MAX_RADIUS);
+    assert(ocap >= m && ocap >= 1 && mask_rows >= 0 && radius >= 1 && radius <= ACCN_MAX_RADIUS);
     assert(min_voxels >= 0 && min_points >= 0);
     // rows past m: a key that would mislead any search that read it, a record that passes every filter
-    std::vector<u64> keys(cap, 0);
-    std::vector<int64_t> acc((size_t)ACC_FIELDS * cap, 1000);
-    std::vector<int32_t> stamps(2 * cap, 0x7fffffff), pierced(has_pierced ? cap : 0, 0);
-    {
-        const std::vector<int64_t> k = rd<int64_t>(f, m), a = rd<int64_t>(f, (size_t)ACC_FIELDS * m);
-        const std::vector<int32_t> s = rd<int32_t>(f, 2 * m), p = rd<int32_t>(f, has_pierced ? m : 0);
-        for (int64_t i = 0; i < m; ++i) {
-            keys[i] = (u64)k[i];
-            assert(i == 0 || keys[i - 1] < keys[i]);
-            for (int c = 0; c < ACC_FIELDS; ++c) acc[(size_t)c * cap + i] = a[(size_t)c * m + i];
-            stamps[i] = s[i];
-            stamps[cap + i] = s[m + i];
-            if (has_pierced) pierced[i] = p[i];
-        }
-    }
+    const Map in = read_map(f, m, cap, has_pierced, Fills{0, 1000, 1000, 0x7fffffff, 0});
     const std::vector<uint8_t> mask_v = rd<uint8_t>(f, has_mask ? mask_rows : 0);
     static const uint8_t no_rows = 0;
     const uint8_t *mask = has_mask ? (mask_rows ? mask_v.data() : &no_rows) : nullptr;
-    const int32_t *pin = has_pierced ? pierced.data() : nullptr;
 
     // the row table
-    std::vector<int> keepf(m);
-    for (int64_t i = 0; i < m; ++i)
-        keepf[i] = accum_keep(acc[accum_field(0, i, cap)], acc[accum_field(1, i, cap)], min_count, use_fraction, g[0]) ? 1 : 0;
-    const std::vector<int> kp = scan(keepf);
-    const int64_t kept = kp[m];
-    std::vector<int> dst(m, -1), rows(kept, -1);
-    for (int64_t i = 0; i < m; ++i) {
-        const int64_t d = keepf[i] ? accum_merge_dst(kp[i], 0, kept) : -1;
-        dst[i] = (int)d;
-        if (d >= 0) { PCACC_BOUND(d, kept); assert(rows[d] == -1); rows[d] = (int)i; }
-    }
+    const RowTable filtered = row_table(in, min_count, use_fraction, g[0]);
+    const std::vector<int> &dst = filtered.dst, &rows = filtered.rows;
+    const int64_t kept = filtered.kept;
     const bool fits = accc_mask_fits(mask, mask_rows, kept);
     std::vector<int64_t> counters(ACCC_COUNTERS, 0), rcounters(ACCC_REMOVE_COUNTERS, 0);
     counters[ACCC_C_ROWS] = m;
@@ -117,7 +62,7 @@ int main(int argc, char **argv)
             assert(i >= 0 && i < m && dst[i] == j && accc_row(dst.data(), mask, kept, i, m) == (accc_takes_part(mask, kept, j) ? j : ACCC_MASKED));
             if (!accc_takes_part(mask, kept, j)) { counters[ACCC_C_MASKED] += 1; continue; }
             counters[ACCC_C_PARTICIPATING] += 1;
-            const int n = accc_edges(keys.data(), m, dst.data(), mask, kept, i, j, radius, [&](int64_t a, int64_t b) {
+            const int n = accc_edges(in.keys.data(), m, dst.data(), mask, kept, i, j, radius, [&](int64_t a, int64_t b) {
                 assert(a == j && b >= 0 && b < j);
                 edges.push_back(std::make_pair((int)a, (int)b));
             });
@@ -163,7 +108,7 @@ int main(int argc, char **argv)
             lab = (int32_t)c;
             if (root == j) { assert(first_row[c] == POISON_I32); first_row[c] = (int32_t)j; }
             AcccStat s;
-            assert(accc_stat_row(keys.data(), acc.data(), stamps.data(), cap, m, rows[j], &s));
+            assert(accc_stat_row(in.keys.data(), in.acc.data(), in.stamps.data(), cap, m, rows[j], &s));
             accc_stat_merge(&stat[c], s);
         }
         PCACC_BOUND(j, tab);
@@ -202,51 +147,29 @@ int main(int argc, char **argv)
     const std::vector<int> kpos = scan(flag);
     const int64_t rk = kpos[m];
     const bool dry = dry_run || !ok;
-    std::vector<u64> okeys(ocap, POISON_KEY);
-    std::vector<int64_t> oacc((size_t)ACC_FIELDS * ocap, POISON_ACC);
-    std::vector<int32_t> ostamps(2 * ocap, POISON_I32), opierced(has_pierced ? ocap : 0, POISON_I32);
+    Map out = poison_map(ocap, has_pierced);
     std::vector<int> written(ocap, 0);
     for (int64_t i = 0; i < m; ++i) {
         rcounters[flag[i] ? ACCC_R_KEPT : ACCC_R_SMALL] += 1;
         if (dry || !flag[i]) continue;
         const int64_t d = accum_merge_dst(kpos[i], 0, rk);
         assert(d >= 0 && d < rk);
-        assert(accr_move_row(keys.data(), acc.data(), stamps.data(), pin, cap, m, i, okeys.data(), oacc.data(), ostamps.data(),
-                             has_pierced ? opierced.data() : nullptr, ocap, rk, d));
+        assert(accr_move_row(in.keys.data(), in.acc.data(), in.stamps.data(), in.p(), cap, m, i, out.keys.data(), out.acc.data(), out.stamps.data(), out.p(),
+                             ocap, rk, d));
         written[d] += 1;
     }
     for (int64_t c = 0; c < K; ++c) rcounters[(ok && accc_small(voxels[c], points[c], min_voxels, min_points)) ? ACCC_R_COMPONENTS_REMOVED : ACCC_R_COMPONENTS_KEPT] += 1;
     assert(rcounters[ACCC_R_KEPT] + rcounters[ACCC_R_SMALL] == m && rcounters[ACCC_R_KEPT] == rk);
     assert(rcounters[ACCC_R_COMPONENTS_REMOVED] + rcounters[ACCC_R_COMPONENTS_KEPT] == K);
-    for (int64_t d = 0; d < ocap; ++d) {
-        assert(written[d] == (!dry && d < rk ? 1 : 0));
-        if (!dry && d < rk) {
-            assert(d == 0 || okeys[d - 1] < okeys[d]);
-            continue;
-        }
-        assert(okeys[d] == POISON_KEY && ostamps[d] == POISON_I32 && ostamps[ocap + d] == POISON_I32);
-        for (int c = 0; c < ACC_FIELDS; ++c) assert(oacc[(size_t)c * ocap + d] == POISON_ACC);
-        if (has_pierced) assert(opierced[d] == POISON_I32);
-    }
+    assert_written_once(written, dry ? 0 : rk);
+    assert_poison_from(out, dry ? 0 : rk);
 
     wr(o, counters, ACCC_COUNTERS); wr(o, rcounters, ACCC_REMOVE_COUNTERS);
     const std::vector<int64_t> n_edges(1, (int64_t)edges.size());
     wr(o, n_edges, 1);
     wr(o, label, kept); wr(o, voxels, K); wr(o, points, K); wr(o, moving, K); wr(o, sum_q, 3 * K); wr(o, centroid, 3 * K); wr(o, lo, 3 * K); wr(o, hi, 3 * K);
     wr(o, t_first, K); wr(o, t_last, K); wr(o, first_row, K);
-    if (!dry) {
-        std::vector<int64_t> k64(rk), a64((size_t)ACC_FIELDS * rk);
-        std::vector<int32_t> s32(2 * rk), p32(has_pierced ? rk : 0);
-        for (int64_t d = 0; d < rk; ++d) {
-            k64[d] = (int64_t)okeys[d];
-            for (int c = 0; c < ACC_FIELDS; ++c) a64[(size_t)c * rk + d] = oacc[(size_t)c * ocap + d];
-            s32[d] = ostamps[d];
-            s32[rk + d] = ostamps[ocap + d];
-            if (has_pierced) p32[d] = opierced[d];
-        }
-        wr(o, k64, k64.size()); wr(o, a64, a64.size()); wr(o, s32, s32.size()); wr(o, p32, p32.size());
-    }
-    fclose(o);
-    fclose(f);
+    if (!dry) write_map(o, out, rk);
+    close_io(f, o);
     return 0;
 }

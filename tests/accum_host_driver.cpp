@@ -6,16 +6,12 @@
 //   out: per add and point 5 i64 (valid, key, q_x, q_y, q_z); then i64 M, dropped, growths; keys[M]; acc[5][M]; stamps[2][M] as i64;
 //        then i64 V; per kept row 12 i64: coords[3], centroid bits[3], count, moving, t_first, t_last, 0, 0
 #include <algorithm>
-#include <cassert>
-#include <cstdio>
-#include <cstring>
-#include <vector>
 
 #include "accum_grid.h"
+#include "accum_host.h"
 
-typedef unsigned long long u64;
-
-struct Map {
+// the map that grows: zeroed tables, swapped after every add
+struct Tables {
     int64_t cap = 0, m = 0;
     std::vector<u64> keys;
     std::vector<int64_t> acc;
@@ -23,26 +19,18 @@ struct Map {
     void resize(int64_t c) { cap = c; keys.assign(c, 0); acc.assign(ACC_FIELDS * c, 0); stamps.assign(2 * c, 0); }
 };
 
-template <class T> static std::vector<T> rd(FILE *f, size_t n)
-{
-    std::vector<T> v(n);
-    if (n) assert(fread(v.data(), sizeof(T), n, f) == n);
-    return v;
-}
-
-static void put(FILE *f, int64_t v) { fwrite(&v, 8, 1, f); }
+static void put(FILE *f, int64_t v) { wr1(f, v); }
 
 int main(int argc, char **argv)
 {
-    assert(argc == 3);
-    FILE *f = fopen(argv[1], "rb"), *o = fopen(argv[2], "wb");
-    assert(f && o);
+    FILE *f, *o;
+    open_io(argc, argv, &f, &o);
     const std::vector<int64_t> h = rd<int64_t>(f, 4);
     const std::vector<double> hd = rd<double>(f, 2);
     const int64_t n_adds = h[0], min_count = h[2];
     const bool use_fraction = h[3] != 0;
     const double frac = hd[0], vs = hd[1];
-    Map cur, alt;
+    Tables cur, alt;
     cur.resize(h[1]);
     int64_t dropped_total = 0, growths = 0;
     for (int64_t a = 0; a < n_adds; ++a) {
@@ -151,11 +139,10 @@ int main(int argc, char **argv)
     for (int fl = 0; fl < ACC_FIELDS; ++fl) for (int64_t i = 0; i < cur.m; ++i) put(o, cur.acc[accum_field(fl, i, cur.cap)]);
     for (int s = 0; s < 2; ++s) for (int64_t i = 0; i < cur.m; ++i) put(o, cur.stamps[s * cur.cap + i]);
     // extract
-    std::vector<int> keep(cur.m), kpos(cur.m + 1, 0);
-    for (int64_t i = 0; i < cur.m; ++i) {
+    std::vector<int> keep(cur.m);
+    for (int64_t i = 0; i < cur.m; ++i)
         keep[i] = accum_keep(cur.acc[accum_field(0, i, cur.cap)], cur.acc[accum_field(1, i, cur.cap)], min_count, use_fraction, frac);
-        kpos[i + 1] = kpos[i] + keep[i];
-    }
+    const std::vector<int> kpos = scan(keep);
     const int64_t kept = kpos[cur.m];
     put(o, kept);
     int64_t written = 0;
@@ -175,7 +162,6 @@ int main(int argc, char **argv)
         }
         put(o, count); put(o, cur.acc[accum_field(1, i, cur.cap)]); put(o, cur.stamps[i]); put(o, cur.stamps[cur.cap + i]); put(o, 0); put(o, 0);
     }
-    fclose(o);
-    fclose(f);
+    close_io(f, o);
     return 0;
 }

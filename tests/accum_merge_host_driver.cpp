@@ -8,121 +8,28 @@
 //           out: i64 counters[5]; i64 state[8] (before the call: NUM_VOXELS = ma, DROPPED = 100, the rest 7); with STATUS = 0 the map of NEEDED rows
 //   regrid  in : i64 1, m, capacity, has_pierced, out_capacity, has_pose, carry_dropped; f64 out_voxel_size, pose[16]; the map
 //           out: i64 counters[5]; i64 state[8] (poison before the call); the map of ROWS_OUT rows
-//   a map   : i64 keys[m]; i64 acc[5][m]; i32 stamps[2][m]; i32 pierced[m] (with a sidecar)
+//   a map   : see accum_host.h
 #include <algorithm>
-#include <cassert>
 #include <climits>
-#include <cstdio>
-#include <vector>
 
 #include "accum_merge.h"
-
-typedef unsigned long long u64;
-
-#define POISON_KEY 0x5a5a5a5a5a5a5a5aull
-#define POISON_ACC 0x5b5b5b5b5b5b5b5bll
-#define POISON_I32 0x5c5c5c5c
+#include "accum_host.h"
 
 // the state and counter words of include/pcacc.h (C4, C12) that the steps between the header's functions write
 enum { STATE_WORDS = 8, NUM_VOXELS = 0, DROPPED = 1, OK = 0, TOO_SMALL = 1 };
 enum { M_STATUS = 0, M_NEEDED = 1, M_SHARED = 2, M_NEW = 3, M_SATURATED = 4 };
 enum { G_ROWS_IN = 0, G_ROWS_OUT = 1, G_DROPPED_ROWS = 2, G_DROPPED_POINTS = 3, G_SATURATED = 4 };
 
-template <class T> static std::vector<T> rd(FILE *f, size_t n)
-{
-    std::vector<T> v(n);
-    if (n) assert(fread(v.data(), sizeof(T), n, f) == n);
-    return v;
-}
-
-template <class T> static void wr(FILE *f, const std::vector<T> &v)
-{
-    if (!v.empty()) assert(fwrite(v.data(), sizeof(T), v.size(), f) == v.size());
-}
-
-struct Map {
-    int64_t m, cap;
-    bool has_pierced;
-    std::vector<u64> keys;
-    std::vector<int64_t> acc;
-    std::vector<int32_t> stamps, pierced;
-    const int32_t *p() const { return has_pierced ? pierced.data() : nullptr; }
-    int32_t *p() { return has_pierced ? pierced.data() : nullptr; }
-};
-
 // rows past m: a key that would mislead any search that read it, a record that would pass for a real one
-static Map read_map(FILE *f, int64_t m, int64_t cap, bool has_pierced)
-{
-    assert(m >= 0 && cap >= m && cap >= 1);
-    Map t;
-    t.m = m; t.cap = cap; t.has_pierced = has_pierced;
-    t.keys.assign(cap, 0);
-    t.acc.assign((size_t)ACC_FIELDS * cap, 1000);
-    t.stamps.assign(2 * cap, 0x7fffffff);
-    t.pierced.assign(has_pierced ? cap : 0, 77);
-    const std::vector<int64_t> k = rd<int64_t>(f, m), a = rd<int64_t>(f, (size_t)ACC_FIELDS * m);
-    const std::vector<int32_t> s = rd<int32_t>(f, 2 * m), p = rd<int32_t>(f, has_pierced ? m : 0);
-    for (int64_t i = 0; i < m; ++i) {
-        t.keys[i] = (u64)k[i];
-        assert(i == 0 || t.keys[i - 1] < t.keys[i]);
-        for (int c = 0; c < ACC_FIELDS; ++c) t.acc[(size_t)c * cap + i] = a[(size_t)c * m + i];
-        t.stamps[i] = s[i];
-        t.stamps[cap + i] = s[m + i];
-        if (has_pierced) t.pierced[i] = p[i];
-    }
-    return t;
-}
-
-static Map poison_map(int64_t cap, bool has_pierced)
-{
-    Map t;
-    t.m = 0; t.cap = cap; t.has_pierced = has_pierced;
-    t.keys.assign(cap, POISON_KEY);
-    t.acc.assign((size_t)ACC_FIELDS * cap, POISON_ACC);
-    t.stamps.assign(2 * cap, POISON_I32);
-    t.pierced.assign(has_pierced ? cap : 0, POISON_I32);
-    return t;
-}
-
-static void assert_poison(const Map &t, int64_t from)
-{
-    for (int64_t d = from; d < t.cap; ++d) {
-        assert(t.keys[d] == POISON_KEY && t.stamps[d] == POISON_I32 && t.stamps[t.cap + d] == POISON_I32);
-        for (int c = 0; c < ACC_FIELDS; ++c) assert(t.acc[(size_t)c * t.cap + d] == POISON_ACC);
-        if (t.has_pierced) assert(t.pierced[d] == POISON_I32);
-    }
-}
-
-static void write_map(FILE *o, const Map &t, int64_t rows)
-{
-    std::vector<int64_t> k64(rows), a64((size_t)ACC_FIELDS * rows);
-    std::vector<int32_t> s32(2 * rows), p32(t.has_pierced ? rows : 0);
-    for (int64_t d = 0; d < rows; ++d) {
-        assert(d == 0 || t.keys[d - 1] < t.keys[d]);
-        k64[d] = (int64_t)t.keys[d];
-        for (int c = 0; c < ACC_FIELDS; ++c) a64[(size_t)c * rows + d] = t.acc[(size_t)c * t.cap + d];
-        s32[d] = t.stamps[d];
-        s32[rows + d] = t.stamps[t.cap + d];
-        if (t.has_pierced) p32[d] = t.pierced[d];
-    }
-    wr(o, k64); wr(o, a64); wr(o, s32); wr(o, p32);
-}
-
-// out[0..n] = exclusive scan of flag, out[n] = total
-static std::vector<int> scan(const std::vector<int> &flag)
-{
-    std::vector<int> out(flag.size() + 1, 0);
-    for (size_t i = 0; i < flag.size(); ++i) out[i + 1] = out[i] + flag[i];
-    return out;
-}
+static const Fills FILLS = {0, 1000, 1000, 0x7fffffff, 77};
 
 static void run_merge(FILE *f, FILE *o)
 {
     const std::vector<int64_t> h = rd<int64_t>(f, 9);
     const int64_t ma = h[0], mb = h[3], ocap = h[6], add_dropped = h[8];
     const bool same = h[7] != 0;
-    const Map A = read_map(f, ma, h[1], h[2] != 0);
-    const Map B = same ? A : read_map(f, mb, h[4], h[5] != 0);
+    const Map A = read_map(f, ma, h[1], h[2] != 0, FILLS);
+    const Map B = same ? A : read_map(f, mb, h[4], h[5] != 0, FILLS);
     assert(B.m == mb && ocap >= 1);
     const bool sidecar = A.has_pierced || B.has_pierced;
     Map out = poison_map(ocap, sidecar);
@@ -165,10 +72,10 @@ static void run_merge(FILE *f, FILE *o)
                                 out.acc.data(), out.stamps.data(), out.p(), ocap, total) == ACCM_WRITTEN);
             written[accum_merge_dst(pos[j], mrank[j], total)] += 1;
         }
-        for (int64_t d = 0; d < ocap; ++d) assert(written[d] == (d < total ? 1 : 0));
+        assert_written_once(written, total);
         rows = total;
     }
-    assert_poison(out, rows);
+    assert_poison_from(out, rows);
     wr(o, counters); wr(o, state);
     write_map(o, out, rows);
 }
@@ -180,7 +87,7 @@ static void run_regrid(FILE *f, FILE *o)
     const int64_t m = h[0], ocap = h[3], carry = h[5];
     const double vs = g[0];
     const double *pose = h[4] ? g.data() + 1 : nullptr;
-    const Map A = read_map(f, m, h[1], h[2] != 0);
+    const Map A = read_map(f, m, h[1], h[2] != 0, FILLS);
     assert(ocap >= m && ocap >= 1 && vs > 0.0);
     Map out = poison_map(ocap, A.has_pierced);
     std::vector<int64_t> counters(5, 0), state(STATE_WORDS, POISON_ACC);
@@ -247,20 +154,18 @@ static void run_regrid(FILE *f, FILE *o)
     counters[G_ROWS_IN] = m; counters[G_ROWS_OUT] = runs;
     for (int k = 0; k < STATE_WORDS; ++k) state[k] = 0;
     state[NUM_VOXELS] = runs; state[DROPPED] = carry + counters[G_DROPPED_POINTS];
-    assert_poison(out, runs);
+    assert_poison_from(out, runs);
     wr(o, counters); wr(o, state);
     write_map(o, out, runs);
 }
 
 int main(int argc, char **argv)
 {
-    assert(argc == 3);
-    FILE *f = fopen(argv[1], "rb"), *o = fopen(argv[2], "wb");
-    assert(f && o);
+    FILE *f, *o;
+    open_io(argc, argv, &f, &o);
     const int64_t mode = rd<int64_t>(f, 1)[0];
     assert(mode == 0 || mode == 1);
     if (mode == 0) run_merge(f, o); else run_regrid(f, o);
-    fclose(o);
-    fclose(f);
+    close_io(f, o);
     return 0;
 }

@@ -5,27 +5,8 @@
 //   in : i64 n, S, m, capacity, use_stamp, stamp, max_steps, has_moving, has_index, has_pose; f64 voxel_size, margin, max_range (< 0: none);
 //        f32 points[n][3]; u8 moving[n]; f64 origins[S][3]; i32 origin_index[n]; f64 pose[16]; i64 keys[m]; i32 stamps[2][m]
 //   out: i32 pierced[m]; i64 counters[5] (walked, dropped, skipped, truncated, hits); i64 visits
-#include <cassert>
-#include <cstdio>
-#include <vector>
-
 #include "accum_pierce.h"
-
-typedef unsigned long long u64;
-
-#define POISON_COUNT 0x5a5a5a5a
-
-template <class T> static std::vector<T> rd(FILE *f, size_t n)
-{
-    std::vector<T> v(n);
-    if (n) assert(fread(v.data(), sizeof(T), n, f) == n);
-    return v;
-}
-
-template <class T> static void wr(FILE *f, const std::vector<T> &v)
-{
-    if (!v.empty()) assert(fwrite(v.data(), sizeof(T), v.size(), f) == v.size());
-}
+#include "accum_host.h"
 
 struct Hit {
     int32_t *pierced;
@@ -35,9 +16,8 @@ struct Hit {
 
 int main(int argc, char **argv)
 {
-    assert(argc == 3);
-    FILE *f = fopen(argv[1], "rb"), *o = fopen(argv[2], "wb");
-    assert(f && o);
+    FILE *f, *o;
+    open_io(argc, argv, &f, &o);
     const std::vector<int64_t> h = rd<int64_t>(f, 10);
     const std::vector<double> g = rd<double>(f, 3);
     const int64_t n = h[0], S = h[1], m = h[2], cap = h[3];
@@ -54,18 +34,7 @@ int main(int argc, char **argv)
     double T[12];
     for (int k = 0; k < 12; ++k) T[k] = h[9] ? pose[k] : ((k % 5 == 0) ? 1.0 : 0.0);
     // rows past m: a key that would mislead any search that read it, stamps that pass every stamp rule
-    std::vector<u64> keys(cap, 0);
-    std::vector<int32_t> stamps(2 * cap, -7);
-    {
-        const std::vector<int64_t> k = rd<int64_t>(f, m);
-        const std::vector<int32_t> s = rd<int32_t>(f, 2 * m);
-        for (int64_t i = 0; i < m; ++i) {
-            keys[i] = (u64)k[i];
-            assert(i == 0 || keys[i - 1] < keys[i]);
-            stamps[i] = s[i];
-            stamps[cap + i] = s[m + i];
-        }
-    }
+    const Map map = read_map(f, m, cap, false, Fills{0, 0, 0, -7, 0}, MAP_STAMPS);
     std::vector<int32_t> pierced(cap, 0);
     std::vector<int64_t> counters(5, 0);
     int64_t visits = 0;
@@ -78,7 +47,7 @@ int main(int argc, char **argv)
         const double *origin = row >= 0 ? origins.data() + 3 * row : none;
         const bool mv = h[7] && moving[i];
         const AccpRay r = accp_ray(T, points.data() + 3 * i, origin, row >= 0, mv, voxel_size, margin, max_range >= 0.0, max_range, use_stamp, stamp, max_steps,
-                                   keys.data(), stamps.data(), cap, m, hit);
+                                   map.keys.data(), map.stamps.data(), cap, m, hit);
         assert(r.status == ACCP_WALKED || r.status == ACCP_DROPPED || r.status == ACCP_SKIPPED);
         assert(r.visits >= 0 && r.visits <= max_steps && r.hits >= 0 && r.hits <= r.visits);
         assert(r.status == ACCP_WALKED ? r.visits >= 1 : (r.visits == 0 && !r.truncated));
@@ -93,8 +62,7 @@ int main(int argc, char **argv)
     pierced.resize(m);
     wr(o, pierced);
     wr(o, counters);
-    assert(fwrite(&visits, 8, 1, o) == 1);
-    fclose(o);
-    fclose(f);
+    wr1(o, visits);
+    close_io(f, o);
     return 0;
 }

@@ -5,91 +5,37 @@
 // loop, and every row of every column is asserted written exactly once.
 //   in : i64 m, capacity, has_pierced, min_count, use_fraction, has_normals, require_normal, radius, min_neighbors, n_viewpoints, stamp_base, n, has_pose,
 //        short_rows (the normal tables are handed over this many rows short: BAD_TABLE); f64 max_moving_fraction, voxel_size, max_distance;
-//        i64 keys[m]; i64 acc[5][m]; i32 stamps[2][m]; i32 pierced[m] (has_pierced); f64 viewpoints[n_viewpoints][3]; f32 points[n][3]; f64 pose[16] (has_pose)
+//        a map (see accum_host.h); f64 viewpoints[n_viewpoints][3]; f32 points[n][3]; f64 pose[16] (has_pose)
 //   out: i64 counters[7]; i64 V (rows the filter keeps); f32 normals[V][3]; u8 flags[V] (has_normals, else nothing); u8 status[n]; i64 count[n], moving[n];
 //        i32 t_first[n], t_last[n], pierced[n], row[n]; f32 nearest[n][3]; f64 distance[n], plane_distance[n]
-#include <cassert>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
 #include "accum_query.h"
-
-typedef unsigned long long u64;
-
-#define POISON_U8 0xa5                  // every byte of every output before the loop
-
-template <class T> static std::vector<T> rd(FILE *f, size_t n)
-{
-    std::vector<T> v(n);
-    if (n) assert(fread(v.data(), sizeof(T), n, f) == n);
-    return v;
-}
-
-template <class T> static void wr(FILE *f, const std::vector<T> &v)
-{
-    if (!v.empty()) assert(fwrite(v.data(), sizeof(T), v.size(), f) == v.size());
-}
-
-template <class T> static bool is_poison(const T &v)
-{
-    unsigned char b[sizeof(T)];
-    memcpy(b, &v, sizeof(T));
-    for (size_t k = 0; k < sizeof(T); ++k)
-        if (b[k] != POISON_U8) return false;
-    return true;
-}
+#include "accum_host.h"
 
 int main(int argc, char **argv)
 {
-    assert(argc == 3);
-    FILE *f = fopen(argv[1], "rb"), *o = fopen(argv[2], "wb");
-    assert(f && o);
+    FILE *f, *o;
+    open_io(argc, argv, &f, &o);
     const std::vector<int64_t> h = rd<int64_t>(f, 14);
     const std::vector<double> g = rd<double>(f, 3);
     const int64_t m = h[0], cap = h[1], min_count = h[3], n_view = h[9], stamp_base = h[10], n = h[11], short_rows = h[13];
     const bool has_pierced = h[2] != 0, use_fraction = h[4] != 0, has_normals = h[5] != 0, require_normal = h[6] != 0, has_pose = h[12] != 0;
     const int radius = (int)h[7], min_neighbors = (int)h[8];
     const double frac = g[0], voxel_size = g[1], max_distance = g[2];
-    assert(m >= 0 && cap >= m && cap >= 1 && n >= 0 && n_view >= 0 && short_rows >= 0 && (has_normals || !require_normal));
+    assert(n >= 0 && n_view >= 0 && short_rows >= 0 && (has_normals || !require_normal));
     assert(!has_normals || (radius >= 1 && radius <= ACCN_MAX_RADIUS && min_neighbors >= ACCN_MIN_NEIGHBORS));
     assert(voxel_size > 0.0 && max_distance > 0.0 && max_distance <= voxel_size);
-    std::vector<u64> keys(cap, 0);
-    std::vector<int64_t> acc((size_t)ACC_FIELDS * cap, 1000);
-    std::vector<int32_t> stamps(2 * cap, 0x7fffffff), pierced(has_pierced ? cap : 0, 77);
-    {
-        const std::vector<int64_t> k = rd<int64_t>(f, m), a = rd<int64_t>(f, (size_t)ACC_FIELDS * m);
-        const std::vector<int32_t> s = rd<int32_t>(f, 2 * m), p = rd<int32_t>(f, has_pierced ? m : 0);
-        for (int64_t i = 0; i < m; ++i) {
-            keys[i] = (u64)k[i];
-            assert(i == 0 || keys[i - 1] < keys[i]);
-            for (int c = 0; c < ACC_FIELDS; ++c) acc[(size_t)c * cap + i] = a[(size_t)c * m + i];
-            stamps[i] = s[i];
-            stamps[cap + i] = s[m + i];
-            if (has_pierced) pierced[i] = p[i];
-        }
-    }
+    const Map map = read_map(f, m, cap, has_pierced, Fills{0, 1000, 1000, 0x7fffffff, 77});
     const std::vector<double> view = rd<double>(f, 3 * n_view);
     const std::vector<float> points = rd<float>(f, 3 * n);
     const std::vector<double> pose = rd<double>(f, has_pose ? 16 : 0);
     // the row table (pass 1 of C5) and, when asked for, the normals of the kept rows
-    std::vector<int> dst(m), kpos(m + 1, 0), rows(m, -1);
-    for (int64_t i = 0; i < m; ++i) {
-        dst[i] = accum_keep(acc[accum_field(0, i, cap)], acc[accum_field(1, i, cap)], min_count, use_fraction, frac) ? 1 : 0;
-        kpos[i + 1] = kpos[i] + dst[i];
-    }
-    const int64_t kept = kpos[m];
-    for (int64_t i = 0; i < m; ++i) {
-        const int64_t d = dst[i] ? accum_merge_dst(kpos[i], 0, kept) : -1;
-        assert(!dst[i] || d >= 0);
-        dst[i] = (int)d;
-        if (d >= 0) { PCACC_BOUND(d, m); assert(rows[d] == -1); rows[d] = (int)i; }
-    }
+    const RowTable tab = row_table(map, min_count, use_fraction, frac);
+    const int64_t kept = tab.kept;
     std::vector<float> n32(has_normals ? 3 * kept : 0);
     std::vector<uint8_t> fl(has_normals ? kept : 0);
     for (int64_t j = 0; has_normals && j < kept; ++j) {
         AccnResult r;
-        const bool ok = accum_normal_voxel(keys.data(), acc.data(), stamps.data(), cap, m, dst.data(), rows[j], radius, min_neighbors,
+        const bool ok = accum_normal_voxel(map.keys.data(), map.acc.data(), map.stamps.data(), cap, m, tab.dst.data(), tab.rows[j], radius, min_neighbors,
                                            n_view > 0 ? view.data() : nullptr, n_view, stamp_base, &r);
         assert(ok);
         for (int a = 0; a < 3; ++a) n32[3 * j + a] = (float)r.normal[a];
@@ -102,7 +48,7 @@ int main(int argc, char **argv)
     const std::vector<uint8_t> fl_given(fl.begin(), fl.begin() + (has_normals ? n_rows : 0));
     const bool given = has_normals && n_rows > 0;                                         // an empty table is a NULL table
     AccqParams P;
-    P.keys = keys.data(); P.acc = acc.data(); P.stamps = stamps.data(); P.pierced = has_pierced ? pierced.data() : nullptr; P.dst = dst.data();
+    P.keys = map.keys.data(); P.acc = map.acc.data(); P.stamps = map.stamps.data(); P.pierced = map.p(); P.dst = tab.dst.data();
     P.normals = given ? n32_given.data() : nullptr; P.flags = given ? fl_given.data() : nullptr;
     P.capacity = cap; P.m = m; P.n_rows = n_rows; P.min_count = min_count;
     P.voxel_size = voxel_size; P.max_d2 = max_distance * max_distance; P.max_moving_fraction = frac;
@@ -112,14 +58,11 @@ int main(int argc, char **argv)
     double T[16];
     pcacc_pose_seed(T, has_pose ? pose.data() : nullptr);
     // outputs: poison everywhere
-    std::vector<uint8_t> status(n, POISON_U8);
-    std::vector<int64_t> count(n), moving(n);
-    std::vector<int32_t> t_first(n), t_last(n), prc(n), row(n);
-    std::vector<float> nearest(3 * n);
-    std::vector<double> distance(n), plane(n);
-    memset(count.data(), POISON_U8, n * 8); memset(moving.data(), POISON_U8, n * 8); memset(t_first.data(), POISON_U8, n * 4);
-    memset(t_last.data(), POISON_U8, n * 4); memset(prc.data(), POISON_U8, n * 4); memset(row.data(), POISON_U8, n * 4);
-    memset(nearest.data(), POISON_U8, n * 12); memset(distance.data(), POISON_U8, n * 8); memset(plane.data(), POISON_U8, n * 8);
+    std::vector<uint8_t> status = poisoned<uint8_t>(n);
+    std::vector<int64_t> count = poisoned<int64_t>(n), moving = poisoned<int64_t>(n);
+    std::vector<int32_t> t_first = poisoned<int32_t>(n), t_last = poisoned<int32_t>(n), prc = poisoned<int32_t>(n), row = poisoned<int32_t>(n);
+    std::vector<float> nearest = poisoned<float>(3 * n);
+    std::vector<double> distance = poisoned<double>(n), plane = poisoned<double>(n);
     const AccqOut out = {status.data(), count.data(), moving.data(), t_first.data(), t_last.data(), prc.data(), row.data(), nearest.data(),
                          distance.data(), plane.data()};
     std::vector<int> written(n, 0);
@@ -151,10 +94,9 @@ int main(int argc, char **argv)
         assert(tables != ACCQ_BAD_TABLES || !(status[i] & (ACCQ_MATCHED | ACCQ_NORMAL)));
     }
     wr(o, counters);
-    assert(fwrite(&kept, 8, 1, o) == 1);
+    wr1(o, kept);
     wr(o, n32); wr(o, fl);
     wr(o, status); wr(o, count); wr(o, moving); wr(o, t_first); wr(o, t_last); wr(o, prc); wr(o, row); wr(o, nearest); wr(o, distance); wr(o, plane);
-    fclose(o);
-    fclose(f);
+    close_io(f, o);
     return 0;
 }

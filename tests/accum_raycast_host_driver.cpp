@@ -7,50 +7,13 @@
 //        max_moving_fraction; f32 targets[n][3]; f64 origins[S][3]; i32 origin_index[n] (has_index); f64 pose[16] (has_pose); i64 keys[m]; i64 acc[5][m]
 //   out: i64 counters[7]; i64 V (rows the filter keeps); u8 status[n]; i32 row[n], coords[n][3]; f32 point[n][3]; f64 range_in[n], depth[n], length[n];
 //        i32 visits[n]
-#include <cassert>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
 #include "accum_raycast.h"
-
-typedef unsigned long long u64;
-
-#define POISON_U8 0xa5                  // every byte of every output before the loop
-
-template <class T> static std::vector<T> rd(FILE *f, size_t n)
-{
-    std::vector<T> v(n);
-    if (n) assert(fread(v.data(), sizeof(T), n, f) == n);
-    return v;
-}
-
-template <class T> static void wr(FILE *f, const std::vector<T> &v)
-{
-    if (!v.empty()) assert(fwrite(v.data(), sizeof(T), v.size(), f) == v.size());
-}
-
-template <class T> static bool is_poison(const T &v)
-{
-    unsigned char b[sizeof(T)];
-    memcpy(b, &v, sizeof(T));
-    for (size_t k = 0; k < sizeof(T); ++k)
-        if (b[k] != POISON_U8) return false;
-    return true;
-}
-
-template <class T> static std::vector<T> poisoned(size_t n)
-{
-    std::vector<T> v(n);
-    if (n) memset(v.data(), POISON_U8, n * sizeof(T));
-    return v;
-}
+#include "accum_host.h"
 
 int main(int argc, char **argv)
 {
-    assert(argc == 3);
-    FILE *f = fopen(argv[1], "rb"), *o = fopen(argv[2], "wb");
-    assert(f && o);
+    FILE *f, *o;
+    open_io(argc, argv, &f, &o);
     const std::vector<int64_t> h = rd<int64_t>(f, 9);
     const std::vector<double> g = rd<double>(f, 5);
     const int64_t n = h[0], S = h[1], m = h[2], cap = h[3], min_count = h[7];
@@ -63,32 +26,13 @@ int main(int argc, char **argv)
     const std::vector<double> origins = rd<double>(f, 3 * S);
     const std::vector<int32_t> index = rd<int32_t>(f, has_index ? n : 0);
     const std::vector<double> pose = rd<double>(f, has_pose ? 16 : 0);
-    // rows past m: a key that would mislead any search that read it, a record that passes every filter
-    std::vector<u64> keys(cap, 0);
-    std::vector<int64_t> acc((size_t)ACC_FIELDS * cap, 1000);
-    for (int64_t i = m; i < cap; ++i) acc[accum_field(1, i, cap)] = 0;
-    {
-        const std::vector<int64_t> k = rd<int64_t>(f, m), a = rd<int64_t>(f, (size_t)ACC_FIELDS * m);
-        for (int64_t i = 0; i < m; ++i) {
-            keys[i] = (u64)k[i];
-            assert(i == 0 || keys[i - 1] < keys[i]);
-            for (int c = 0; c < ACC_FIELDS; ++c) acc[(size_t)c * cap + i] = a[(size_t)c * m + i];
-        }
-    }
+    // rows past m: a key that would mislead any search that read it, a record that passes every filter (none of its points moving)
+    const Map map = read_map(f, m, cap, false, Fills{0, 1000, 0, 0, 0}, MAP_ACC);
     // the row table (pass 1 of C5)
-    std::vector<int> dst(m), kpos(m + 1, 0);
-    for (int64_t i = 0; i < m; ++i) {
-        dst[i] = accum_keep(acc[accum_field(0, i, cap)], acc[accum_field(1, i, cap)], min_count, use_fraction, frac) ? 1 : 0;
-        kpos[i + 1] = kpos[i] + dst[i];
-    }
-    const int64_t kept = kpos[m];
-    for (int64_t i = 0; i < m; ++i) {
-        const int64_t d = dst[i] ? accum_merge_dst(kpos[i], 0, kept) : -1;
-        assert(!dst[i] || d >= 0);
-        dst[i] = (int)d;
-    }
+    const RowTable tab = row_table(map, min_count, use_fraction, frac);
+    const int64_t kept = tab.kept;
     AccyParams P;
-    P.keys = keys.data(); P.acc = acc.data(); P.dst = dst.data();
+    P.keys = map.keys.data(); P.acc = map.acc.data(); P.dst = tab.dst.data();
     P.capacity = cap; P.m = m;
     P.voxel_size = voxel_size; P.min_range = min_range; P.margin = margin; P.max_range = max_range;
     P.use_range = max_range >= 0.0 ? 1 : 0; P.max_steps = max_steps;
@@ -134,9 +78,8 @@ int main(int argc, char **argv)
     assert(counters[ACCY_C_RAYS] == n && counters[ACCY_C_DROPPED] + counters[ACCY_C_SKIPPED] + counters[ACCY_C_HIT] + counters[ACCY_C_MISSED] +
                                                 counters[ACCY_C_TRUNCATED] == n);
     wr(o, counters);
-    assert(fwrite(&kept, 8, 1, o) == 1);
+    wr1(o, kept);
     wr(o, status); wr(o, row); wr(o, coords); wr(o, point); wr(o, range_in); wr(o, depth); wr(o, length); wr(o, visits);
-    fclose(o);
-    fclose(f);
+    close_io(f, o);
     return 0;
 }

@@ -7,18 +7,17 @@ g++ and run stage by stage with every table index assert-checked; the header, th
 GPU leg: one add at the sizes where a stage can go wrong, merges at both ends of the map, growth, invalid input, order independence, the extract
 filters, save / load, and the model tie-in on the model_tiny_test inputs."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import accumulate_helpers as ah
 import accumulate_reference as ref
-from helpers import build_host_driver
+from accumulate_helpers import DEV
+from helpers import ROOT, build_host_driver
 from pcaccumulation_amd.config import default_config
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = 'cuda:0'
 FIELDS = ('points', 'coords', 'count', 'moving', 't_first', 't_last')
 
 
@@ -98,24 +97,19 @@ def test_restatement_unique_formulation_equals_a_per_point_loop():
 
 def _run_host_driver(exe, tmp_path, tag, voxel_size, adds, capacity=64, min_count=1, max_moving_fraction=None):
     """adds: [(points, pose or None, moving or None, stamp)] -> the driver's map against the restatement; every assert of the driver aborts it."""
-    path, out = str(tmp_path / (tag + '.bin')), str(tmp_path / (tag + '.out'))
     r = ref.ReferenceMap(voxel_size)
     per_point = []
-    with open(path, 'wb') as f:
-        f.write(np.array([len(adds), capacity, min_count, 0 if max_moving_fraction is None else 1], np.int64).tobytes())
-        f.write(np.array([0.0 if max_moving_fraction is None else max_moving_fraction, voxel_size], np.float64).tobytes())
-        for pts, pose, mv, stamp in adds:
-            pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
-            n = pts.shape[0]
-            f.write(np.array([n, stamp, 0 if pose is None else 1], np.int64).tobytes())
-            f.write(np.ascontiguousarray(np.eye(4) if pose is None else pose, np.float64).tobytes())
-            f.write(pts.tobytes())
-            f.write((np.zeros(n, np.uint8) if mv is None else (np.asarray(mv) != 0).astype(np.uint8)).tobytes())
-            r.add(pts, pose, mv, stamp)
-            valid, key, q = ref.per_point(pts, pose, voxel_size)
-            per_point.append(np.concatenate([valid[:, None].astype(np.int64), key[:, None], q], 1))
-    subprocess.check_call([exe, path, out])
-    got = np.fromfile(out, np.int64)
+    chunks = [np.array([len(adds), capacity, min_count, 0 if max_moving_fraction is None else 1], np.int64),
+              np.array([0.0 if max_moving_fraction is None else max_moving_fraction, voxel_size], np.float64)]
+    for pts, pose, mv, stamp in adds:
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        chunks += [np.array([n, stamp, 0 if pose is None else 1], np.int64), np.ascontiguousarray(np.eye(4) if pose is None else pose, np.float64), pts,
+                   np.zeros(n, np.uint8) if mv is None else (np.asarray(mv) != 0).astype(np.uint8)]
+        r.add(pts, pose, mv, stamp)
+        valid, key, q = ref.per_point(pts, pose, voxel_size)
+        per_point.append(np.concatenate([valid[:, None].astype(np.int64), key[:, None], q], 1))
+    got = np.frombuffer(ah.run_driver(exe, tmp_path, tag, *chunks, suffix='.bin'), np.int64)
     want_pp = np.concatenate(per_point).reshape(-1)
     assert np.array_equal(got[:want_pp.size], want_pp), (tag, np.flatnonzero(got[:want_pp.size] != want_pp)[:10] // 5)
     got = got[want_pp.size:]

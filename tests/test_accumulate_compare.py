@@ -9,72 +9,25 @@ Every result is an integer, a copied record or a float64 computed in one order, 
         against extract() under a filter; the counters against merge's; select against copy() + prune(), against merge() of its two halves and against
         extract() indexed by the mask; difference against select() built by hand."""
 import ctypes
-import io
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import accumulate_compare_reference as cref
+import accumulate_helpers as ah
 import accumulate_merge_reference as mref
 import accumulate_reference as ref
-from helpers import build_host_driver
+from accumulate_helpers import DEV
+from helpers import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = 'cuda:0'
-BIAS = 1 << 20
 COLUMNS = (('status', np.uint8), ('same_row', np.int32), ('row', np.int32), ('distance', np.float64), ('pierced', np.int32))
 SIDES = (('self', 'a'), ('other', 'b'))
 
 
-def _key(c):
-    return ((c[0] + BIAS) << 42) | ((c[1] + BIAS) << 21) | (c[2] + BIAS)
-
-
-def _rot(axis, angle, t):
-    a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    T = np.eye(4)
-    T[:3, :3] = np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * (K @ K)
-    T[:3, 3] = t
-    return T
-
-
 # ---- scenes (those of tests/test_accumulate_merge.py): (ReferenceMap, {key: rays} or None), built once and never modified -------------------------------
-def _rows(coords, seed, rays=False, vs=0.1):
-    """Random records on the given voxels: counts 1..6, stamps 0..15, centroids inside the voxel; rays 0..4 with rays=True."""
-    rs = np.random.RandomState(seed)
-    r, p = ref.ReferenceMap(vs), ({} if rays else None)
-    for c in coords:
-        count = int(rs.randint(1, 7))
-        t_first = int(rs.randint(0, 11))
-        q = [int(np.rint((v + rs.uniform(0.1, 0.9)) * vs * 65536.0)) * count + int(rs.randint(0, count)) for v in c]
-        r.rec[_key(c)] = [count, int(rs.randint(0, count + 1))] + q + [t_first, t_first + int(rs.randint(0, 6))]
-        if rays:
-            p[_key(c)] = int(rs.randint(0, 5))
-    r.dropped = int(rs.randint(0, 9))
-    return r, p
-
-
-CELLS = [(x, y, z) for x in range(-2, 3) for y in range(-2, 3) for z in range(-2, 3)]
 ROW_COUNTS = (0, 1, 63, 64, 65)
-
-
-def _some(m, seed):
-    return [CELLS[i] for i in np.random.RandomState(seed).permutation(len(CELLS))[:m]]
-
-
-def _wavy(shift=0.0):
-    """26 m x 26 m at 0.1 m, four points in every column, and one far voxel -- 76 661 voxels: more than one workgroup, m mod 64 != 0, more than one
-    scan chunk."""
-    g = np.arange(520) * 0.05 + 0.025 - 13.0
-    x, y = np.meshgrid(g, g, indexing='ij')
-    z = 0.4 * np.sin(0.9 * x) * np.cos(0.7 * y) + 0.013
-    pts = np.concatenate([np.stack([x, y, z], -1).reshape(-1, 3), [[40.0, 40.0, 40.0]]])
-    pts[:, 0] += shift
-    return pts.astype(np.float32)
 
 
 def _dense(seed, rays_seed=None):
@@ -106,27 +59,27 @@ _scenes = {}
 def _build_scene(name):
     if name.startswith('rows'):                                                  # rows<m>_<seed>: with a sidecar
         m, seed = (int(v) for v in name[4:].split('_'))
-        return _rows(_some(m, seed), 50 + 7 * m + seed, rays=True)
+        return ah.rows(ah.some(m, seed), 50 + 7 * m + seed, rays=True)
     line = lambda xs: [(x, 1, -1) for x in xs]
     if name == 'low':
-        return _rows(line(range(-40, -10)), 1)
+        return ah.rows(line(range(-40, -10)), 1)
     if name == 'high':
-        return _rows(line(range(10, 47)), 2)
+        return ah.rows(line(range(10, 47)), 2)
     if name == 'even':
-        return _rows(line(range(-20, 20, 2)), 3)
+        return ah.rows(line(range(-20, 20, 2)), 3)
     if name == 'odd':
-        return _rows(line(range(-19, 21, 2)), 4)
+        return ah.rows(line(range(-19, 21, 2)), 4)
     if name == 'outer':
-        return _rows(line(range(-30, 30)), 5)
+        return ah.rows(line(range(-30, 30)), 5)
     if name == 'inner':
-        return _rows(line(range(-7, 9)), 6)
+        return ah.rows(line(range(-7, 9)), 6)
     if name in ('plain_a', 'plain_b'):                                           # overlapping, no sidecar
-        return _rows(_some(70, 11 if name == 'plain_a' else 12), 13 if name == 'plain_a' else 14)
+        return ah.rows(ah.some(70, 11 if name == 'plain_a' else 12), 13 if name == 'plain_a' else 14)
     if name in ('rays_a', 'rays_b'):
-        return _rows(_some(70, 11 if name == 'rays_a' else 12), 15 if name == 'rays_a' else 16, rays=True)
+        return ah.rows(ah.some(70, 11 if name == 'rays_a' else 12), 15 if name == 'rays_a' else 16, rays=True)
     if name in ('wavy', 'wavy_near', 'wavy_half'):
         r = ref.ReferenceMap(0.1)
-        r.add(_wavy({'wavy': 0.0, 'wavy_near': 0.03, 'wavy_half': 13.0}[name]), stamp=3 if name == 'wavy' else 8)
+        r.add(ah.wavy({'wavy': 0.0, 'wavy_near': 0.03, 'wavy_half': 13.0}[name]), stamp=3 if name == 'wavy' else 8)
         return r, None
     if name == 'dense':
         return _dense(30)
@@ -183,23 +136,12 @@ def _mask(name):
 
 
 # ---- the host build ----------------------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def host_exe(tmp_path_factory):
-    return build_host_driver(tmp_path_factory.mktemp('compare_host'), 'accum_compare_host_driver')
+host_exe = ah.host_driver_fixture('accum_compare_host_driver', 'compare_host')
 
 
 def _map_bytes(r, pierced):
     keys, acc, stamps = r.records()
-    raw = keys.tobytes() + np.ascontiguousarray(acc, np.int64).tobytes() + np.ascontiguousarray(stamps, np.int32).tobytes()
-    return raw + (b'' if pierced is None else mref.aligned(pierced, keys).tobytes())
-
-
-def _run(exe, tmp_path, tag, raw):
-    src, dst = os.path.join(str(tmp_path), tag + '.in'), os.path.join(str(tmp_path), tag + '.out')
-    with open(src, 'wb') as f:
-        f.write(raw)
-    subprocess.check_call([exe, src, dst])
-    return open(dst, 'rb').read()
+    return ah.map_bytes(keys, acc, stamps, None if pierced is None else mref.aligned(pierced, keys))
 
 
 def _run_host_compare(exe, tmp_path, tag, a, b, max_distance, min_count, mmf, spare=3):
@@ -207,15 +149,12 @@ def _run_host_compare(exe, tmp_path, tag, a, b, max_distance, min_count, mmf, sp
     (ra, pa), (rb, pb) = a, (a if b is None else b)
     head = [0, ra.num_voxels, ra.num_voxels + spare, 0 if pa is None else 1, rb.num_voxels, rb.num_voxels + spare, 0 if pb is None else 1,
             1 if b is None else 0, min_count, 0 if mmf is None else 1]
-    raw = _run(exe, tmp_path, tag, np.array(head, np.int64).tobytes() + np.array([0.0 if mmf is None else mmf, max_distance], np.float64).tobytes()
-               + _map_bytes(ra, pa) + (b'' if b is None else _map_bytes(rb, pb)))
+    raw = ah.run_driver(exe, tmp_path, tag, np.array(head, np.int64), np.array([0.0 if mmf is None else mmf, max_distance], np.float64),
+                        _map_bytes(ra, pa), b'' if b is None else _map_bytes(rb, pb))
     counters = np.frombuffer(raw, np.int64, 12).tolist()
     out, off = {'counters': counters}, 96
     for side, at in (('self', 0), ('other', 6)):
-        rows, out[side] = counters[at + 1], {}
-        for name, dtype in COLUMNS:
-            out[side][name] = np.frombuffer(raw, dtype, rows, off).copy()
-            off += rows * np.dtype(dtype).itemsize
+        out[side], off = ah.unpack(raw, off, [(name, dtype, (counters[at + 1],)) for name, dtype in COLUMNS])
     assert off == len(raw)
     return out
 
@@ -224,20 +163,14 @@ def _run_host_select(exe, tmp_path, tag, a, mask, invert, min_count, mmf, spare_
     r, p = a
     m = r.num_voxels
     head = [1, m, m + spare_in, 0 if p is None else 1, m + spare_out, min_count, 0 if mmf is None else 1, mask.shape[0], 1 if invert else 0]
-    raw = _run(exe, tmp_path, tag, np.array(head, np.int64).tobytes() + np.array([0.0 if mmf is None else mmf], np.float64).tobytes() + _map_bytes(r, p)
-               + np.ascontiguousarray(mask, np.uint8).tobytes())
+    raw = ah.run_driver(exe, tmp_path, tag, np.array(head, np.int64), np.array([0.0 if mmf is None else mmf], np.float64), _map_bytes(r, p),
+                        np.ascontiguousarray(mask, np.uint8))
     counters, state = np.frombuffer(raw, np.int64, 4).tolist(), np.frombuffer(raw, np.int64, 8, 32).tolist()
-    rows, off = counters[3], 96
-    out = dict(counters=counters, state=state)
-    for name, dtype, shape in (('keys', np.int64, (rows,)), ('acc', np.int64, (5, rows)), ('stamps', np.int32, (2, rows)),
-                               ('pierced', np.int32, (rows if p is not None else 0,))):
-        n = int(np.prod(shape))
-        out[name] = np.frombuffer(raw, dtype, n, off).reshape(shape).copy()
-        off += n * np.dtype(dtype).itemsize
+    out, off = ah.unpack(raw, 96, ah.map_layout(counters[3], p is not None))
     assert off == len(raw)
     if p is None:
         out['pierced'] = None
-    return out
+    return dict(out, counters=counters, state=state)
 
 
 _hosted = {}
@@ -276,18 +209,6 @@ def _assert_columns(got, want, what):
     for name, dtype in COLUMNS:
         g, w = got[name], want[name]
         assert g.dtype == w.dtype == dtype and g.shape == w.shape and g.tobytes() == w.tobytes(), (what, name)     # float64 as bits
-
-
-def _as_tables(r, pierced):
-    keys, acc, stamps = r.records()
-    return dict(keys=keys, acc=acc.reshape(5, -1), stamps=stamps.reshape(2, -1), pierced=None if pierced is None else mref.aligned(pierced, keys))
-
-
-def _assert_tables(got, want, what):
-    for f in ('keys', 'acc', 'stamps'):
-        assert got[f].dtype == want[f].dtype and np.array_equal(got[f], want[f]), (what, f)
-    assert (got['pierced'] is None) == (want['pierced'] is None), what
-    assert got['pierced'] is None or np.array_equal(got['pierced'], want['pierced']), what
 
 
 # ---- CPU: host build == restatement ----------------------------------------------------------------------------------------------------------------------
@@ -355,9 +276,9 @@ def test_select_host_build_equals_the_restatement(host_exe, tmp_path, name):
         assert counters[0] == cref.BAD_MASK and got['state'] == [0x5b5b5b5b5b5b5b5b] * 8 and got['keys'].shape[0] == 0, name
         return
     assert counters[0] == cref.OK and got['state'] == [counters[3]] + [0] * 7, name
-    _assert_tables(got, _as_tables(want, wp), name)
+    ah.assert_tables(got, ah.as_tables(want, wp), name)
     if name == 'all':
-        _assert_tables(got, _as_tables(r, p), name)
+        ah.assert_tables(got, ah.as_tables(r, p), name)
     if name == 'none':
         assert counters[3] == 0
     if name == 'sheet':
@@ -462,30 +383,8 @@ def test_bad_arguments_return_before_anything_is_launched():
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------------------------------------------
 def _device_cloud(r, pierced):
-    """The restatement's map and ray counts as an AccumulatedCloud on the device, through load()."""
-    from pcaccumulation_amd.accumulate import AccumulatedCloud
-    keys, acc, stamps = r.records()
-    extra = {}
-    if pierced is not None:
-        extra = dict(pierced=mref.aligned(pierced, keys), pierce_counters=np.arange(5, dtype=np.int64) + r.num_voxels)
-    buf = io.BytesIO()
-    np.savez(buf, keys=keys, acc=acc.reshape(5, -1), stamps=stamps.reshape(2, -1), voxel_size=np.float64(r.voxel_size), dropped=np.int64(r.dropped), **extra)
-    buf.seek(0)
-    return AccumulatedCloud.load(buf, DEV)
-
-
-def _snapshot(m):
-    n = m.num_voxels
-    keys, acc, stamps = m._cur
-    return (n, m.capacity, m.dropped, keys[:n].clone(), acc[:, :n].clone(), stamps[:, :n].clone(), None if m._pierced is None else m._pierced[:n].clone(),
-            m._state.clone(), None if m._pierce_counters is None else m._pierce_counters.clone())
-
-
-def _assert_unchanged(m, snap, what):
-    now = _snapshot(m)
-    assert now[:3] == snap[:3], what
-    for a, b in zip(now[3:], snap[3:]):
-        assert (a is None and b is None) or torch.equal(a, b), what
+    """The restatement's map and {key: rays} dict as an AccumulatedCloud on the device."""
+    return ah.device_cloud(r, None if pierced is None else mref.aligned(pierced, r.records()[0]), np.arange(5, dtype=np.int64) + r.num_voxels)
 
 
 def _assert_same_map(a, b, what):
@@ -513,29 +412,6 @@ def _host_columns(side):
     return {name: side[name].cpu().numpy() for name, _ in COLUMNS}
 
 
-_windows = {}
-
-
-def _window(k):
-    """2049 random points in a 6 m x 6 m x 3 m box with flags, a stamp and a pose; two of them not finite."""
-    if k not in _windows:
-        rs = np.random.RandomState(70 + k)
-        pts = rs.uniform((-3, -3, -1.5), (3, 3, 1.5), (2049, 3)).astype(np.float32)
-        pts[5 + k] = np.nan
-        pts[900 + 7 * k, 1] = np.inf
-        _windows[k] = (pts, rs.uniform(0, 1, 2049) < 0.3, 10 - 3 * k if k % 2 else k, _rot((0.1 * k, 1.0, 0.3), 0.02 * k, (0.05 * k, -0.03 * k, 0.01)))
-    return _windows[k]
-
-
-def _added(ks, capacity=64, vs=0.1):
-    from pcaccumulation_amd.accumulate import AccumulatedCloud
-    m = AccumulatedCloud(vs, DEV, capacity)
-    for k in ks:
-        pts, mv, stamp, pose = _window(k)
-        m.add(torch.from_numpy(pts).to(DEV), pose, torch.from_numpy(mv).to(DEV), stamp)
-    return m
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize('name', COMPARE_NAMES)
 def test_compare_kernel_equals_the_host_build_gpu(host_exe, tmp_path, name):
@@ -544,15 +420,15 @@ def test_compare_kernel_equals_the_host_build_gpu(host_exe, tmp_path, name):
     host = _host_compare(host_exe, tmp_path, name)
     A = _device_cloud(*_scene(a))
     B = A if b is None else _device_cloud(*_scene(b))
-    snap_a, snap_b = _snapshot(A), _snapshot(B)
+    snap_a, snap_b = ah.snapshot(A), ah.snapshot(B)
     got = A.compare(B, dist, min_count, mmf)
     assert _flat(got['counters']) == host['counters'] and all(type(v) is int for c in got['counters'].values() for v in c.values()), name
     for side, m in (('self', A), ('other', B)):
         assert all(t.device == m._cur[0].device for t in got[side].values()), name
         _assert_columns(_host_columns(got[side]), host[side], (name, side))
         assert got[side]['status'].shape[0] == m.extract(min_count, mmf)['count'].shape[0] == got['counters'][side]['kept'], name
-    _assert_unchanged(A, snap_a, name)
-    _assert_unchanged(B, snap_b, name)
+    ah.assert_unchanged(A, snap_a, name)
+    ah.assert_unchanged(B, snap_b, name)
     if name == 'filter':                                                         # same_row and row index the OTHER side's extract under the filter
         s, other = got['self'], B.extract(min_count, mmf)
         same, near = (s['status'] & cref.SAME) != 0, (s['status'] & cref.NEAR) != 0
@@ -586,11 +462,11 @@ def test_compare_is_query_gpu():
 @pytest.mark.gpu
 def test_compare_agrees_with_merge_gpu():
     """Claim 5, on add-built maps at min_count = 1."""
-    A, B = _added((1, 3)), _added((2, 4))
-    snap_a, snap_b = _snapshot(A), _snapshot(B)
+    A, B = ah.added((1, 3)), ah.added((2, 4))
+    snap_a, snap_b = ah.snapshot(A), ah.snapshot(B)
     got = A.compare(B)
-    _assert_unchanged(A, snap_a, 'compare modifies nothing')
-    _assert_unchanged(B, snap_b, 'compare modifies nothing')
+    ah.assert_unchanged(A, snap_a, 'compare modifies nothing')
+    ah.assert_unchanged(B, snap_b, 'compare modifies nothing')
     res = A.copy().merge(B)
     ca, cb = got['counters']['self'], got['counters']['other']
     assert ca['same'] == cb['same'] == res['shared'] > 0 and cb['kept'] - cb['held'] == res['new'] > 0
@@ -602,8 +478,8 @@ def test_compare_agrees_with_merge_gpu():
         assert bool((s['status'] == 7).all()) and bool((s['distance'] == 0.0).all()), side
         assert torch.equal(s['same_row'], torch.arange(n, dtype=torch.int32, device=DEV)) and torch.equal(s['row'], s['same_row']), side
         assert own['counters'][side] == dict(rows=n, kept=n, same=n, held=n, near=n, only=0)
-    _assert_unchanged(A, snap_a, 'compare(self)')
-    empty = _added(())                                                           # a map that never saw an add
+    ah.assert_unchanged(A, snap_a, 'compare(self)')
+    empty = ah.added(())                                                           # a map that never saw an add
     got = A.compare(empty)
     assert got['counters']['self'] == dict(rows=n, kept=n, same=0, held=0, near=0, only=n) and got['counters']['other'] == dict.fromkeys(cref.SIDE, 0)
     assert got['other']['status'].shape[0] == 0 and bool((got['self']['row'] == -1).all()) and bool(torch.isinf(got['self']['distance']).all())
@@ -616,7 +492,7 @@ def test_select_kernel_equals_the_host_build_gpu(host_exe, tmp_path, name):
     scene, rule, invert, min_count, mmf = SELECT_CASES[name]
     host = _host_select(host_exe, tmp_path, name)
     A = _device_cloud(*_scene(scene))
-    snap = _snapshot(A)
+    snap = ah.snapshot(A)
     mask = torch.from_numpy(_mask(name)).to(DEV)
     if rule in ('short', 'long'):                                                # a mask of the wrong length: the method raises,
         with pytest.raises(ValueError, match=r'one entry per row of extract\(\) under the same filter \(%d rows\)' % host['counters'][2]):
@@ -627,10 +503,10 @@ def test_select_kernel_equals_the_host_build_gpu(host_exe, tmp_path, name):
         native.accum_select(A._cur, A.num_voxels, A._pierced, min_count, mmf, mask, invert, out, pout, counters, state)
         assert counters.tolist() == host['counters'] and counters.tolist()[0] == native.SELECT_BAD_MASK
         assert state.tolist() == [7] * 8 and all(bool((t == 7).all()) for t in out + (() if pout is None else (pout,)))
-        _assert_unchanged(A, snap, name)
+        ah.assert_unchanged(A, snap, name)
         return
     got = A.select(mask.bool() if name == 'rows65' else mask, invert, min_count, mmf)
-    _assert_unchanged(A, snap, name)
+    ah.assert_unchanged(A, snap, name)
     _assert_device_equals_host(got, host, name)
     assert got._state.tolist() == host['state'] and got.dropped == 0 and got.capacity == A.capacity and got.voxel_size == A.voxel_size, name
     assert got is not A and got._cur[0].data_ptr() != A._cur[0].data_ptr()
@@ -650,7 +526,7 @@ def test_select_kernel_equals_the_host_build_gpu(host_exe, tmp_path, name):
 def test_select_is_prune_and_its_halves_merge_back_gpu():
     for scene in ('dense_b', 'dense'):                                           # with and without a sidecar
         A = _device_cloud(*_scene(scene))
-        snap = _snapshot(A)
+        snap = ah.snapshot(A)
         kept = A.extract(2)['count'].shape[0]
         got = A.select(torch.ones(kept, dtype=torch.bool, device=DEV), min_count=2)
         want = A.copy()
@@ -662,7 +538,7 @@ def test_select_is_prune_and_its_halves_merge_back_gpu():
         assert x.num_voxels + y.num_voxels == A.num_voxels and 0 < x.num_voxels < A.num_voxels
         x.merge(y)
         _assert_same_map(x, A, scene)
-        _assert_unchanged(A, snap, scene)
+        ah.assert_unchanged(A, snap, scene)
 
 
 @pytest.mark.gpu
@@ -670,14 +546,14 @@ def test_difference_gpu():
     from pcaccumulation_amd import native
     for a, b, dist, min_count, mmf in (SHEET_CASES['sheet_half'], COMPARE_CASES['filter'], COMPARE_CASES['sidecar_both']):
         A, B = _device_cloud(*_scene(a)), _device_cloud(*_scene(b))
-        snap_a, snap_b = _snapshot(A), _snapshot(B)
+        snap_a, snap_b = ah.snapshot(A), ah.snapshot(B)
         got = A.difference(B, dist, min_count, mmf)
         c = A.compare(B, dist, min_count, mmf)
         by_hand = A.select((c['self']['status'] & (native.COMPARE_SAME | native.COMPARE_NEAR)) == 0, min_count=min_count, max_moving_fraction=mmf)
         _assert_same_map(got, by_hand, a)
         assert got.num_voxels == c['counters']['self']['only'] and 0 < got.num_voxels < A.num_voxels, a
-        _assert_unchanged(A, snap_a, a)
-        _assert_unchanged(B, snap_b, a)
+        ah.assert_unchanged(A, snap_a, a)
+        ah.assert_unchanged(B, snap_b, a)
     assert A.difference(A).num_voxels == 0
 
 
@@ -686,7 +562,7 @@ def test_bad_arguments_launch_nothing_gpu():
     from pcaccumulation_amd import native
     A, B = _device_cloud(*_scene('rays_a')), _device_cloud(*_scene('rays_b'))
     assert (A.num_voxels, A.capacity, B.num_voxels, B.capacity) == (70, 128, 70, 128)
-    snap_a, snap_b = _snapshot(A), _snapshot(B)
+    snap_a, snap_b = ah.snapshot(A), ah.snapshot(B)
     fresh = lambda rows: {name: torch.full((rows,) + shape, 7, dtype=dtype, device=DEV) for name, dtype, shape in native.COMPARE_FIELDS}
     oa, ob, cc = fresh(70), fresh(70), torch.full((12,), 7, dtype=torch.int64, device=DEV)
     good = dict(tables_a=A._cur, ma=70, pierced_a=A._pierced, tables_b=B._cur, mb=70, pierced_b=B._pierced, voxel_size=0.1, max_distance=0.1, min_count=1,
@@ -709,8 +585,8 @@ def test_bad_arguments_launch_nothing_gpu():
         with pytest.raises(native.NativeError, match='PCACC_E_ARG'):
             native.accum_select(**dict(sgood, **bad))
     torch.cuda.synchronize()
-    _assert_unchanged(A, snap_a, 'bad arguments')
-    _assert_unchanged(B, snap_b, 'bad arguments')
+    ah.assert_unchanged(A, snap_a, 'bad arguments')
+    ah.assert_unchanged(B, snap_b, 'bad arguments')
     assert all(bool((t == 7).all()) for t in out + small + (pout, cc, sc, state) + tuple(oa.values()) + tuple(ob.values()))    # nothing was written
     native.accum_compare(**dict(good, ma=0, mb=0, out_a=fresh(0), out_b=fresh(0)))           # ma = mb = 0: the zero counters, nothing else
     assert cc.tolist() == [0] * 12

@@ -8,20 +8,18 @@ float32 bits:
   GPU   the kernels against the g++ build on the same scenes, identities that tie the tables to extract(), the blob scene that prune() cannot clean,
         objects on a ground sheet, a life cycle against the restatement, the model forward and the argument checks."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import accumulate_components_reference as cref
+import accumulate_helpers as ah
 import accumulate_prune_reference as rref
 import accumulate_reference as ref
 import test_accumulate_prune as tp
-from helpers import build_host_driver
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = 'cuda:0'
+from accumulate_helpers import DEV
+from helpers import ROOT
 TABLES = (('voxels', np.int32, ()), ('points', np.int64, ()), ('moving', np.int64, ()), ('sum_q', np.int64, (3,)), ('centroid', np.float32, (3,)),
           ('lo', np.int32, (3,)), ('hi', np.int32, (3,)), ('t_first', np.int32, ()), ('t_last', np.int32, ()), ('first_row', np.int32, ()))
 FILTER = dict(min_count=2, max_moving_fraction=0.5)
@@ -50,7 +48,7 @@ def _wavy_blobs():
     rs = np.random.RandomState(5)
     corners = {(int(x), int(y), int(z)) for x, y, z in zip(rs.randint(-60, 60, 40) * 2, rs.randint(-60, 60, 40) * 2, rs.randint(12, 30, 40))}
     blobs = [(x + a, y + b, z + c) for x, y, z in sorted(corners) for a in (0, 1) for b in (0, 1) for c in (0, 1)]
-    return np.concatenate([tp._wavy(), tp._centres(blobs, 0.1)]).astype(np.float32)
+    return np.concatenate([ah.wavy(), ah.centres(blobs, 0.1)]).astype(np.float32)
 
 
 def _sizes_scene():
@@ -63,7 +61,7 @@ def _sizes_scene():
             pierced[(10 * n, k, 0)] = n + k
         rows[(10 * n, n, 0)] = (1, 0, 0, 9)
         pierced[(10 * n, n, 0)] = 50 + n
-    return tp._records(0.1, rows), pierced
+    return ah.records(0.1, rows), pierced
 
 
 def _build_scene(name):
@@ -71,30 +69,30 @@ def _build_scene(name):
     if name.startswith('rows') or name in ('ratio', 'bound', 'wavy'):
         return tp._scene(name)
     if name == 'chain_x':
-        return tp._records(0.1, {(k - 500, 3, -2): (1, 0, k % 7, k % 7 + 1) for k in range(1025)}), None
+        return ah.records(0.1, {(k - 500, 3, -2): (1, 0, k % 7, k % 7 + 1) for k in range(1025)}), None
     if name == 'chain_z':
-        return tp._records(0.1, {(3, -2, k - 500): (2, 1, 0, k % 5) for k in range(1025)}), None
+        return ah.records(0.1, {(3, -2, k - 500): (2, 1, 0, k % 5) for k in range(1025)}), None
     if name == 'serpentine':
-        return tp._records(0.1, {c: one for c in _serpentine()}), None
+        return ah.records(0.1, {c: one for c in _serpentine()}), None
     if name == 'corners':
-        return tp._records(0.1, {c: one for c in [(k, k, k) for k in range(8)] + [(-k, k, -k) for k in range(1, 8)]}), None
+        return ah.records(0.1, {c: one for c in [(k, k, k) for k in range(8)] + [(-k, k, -k) for k in range(1, 8)]}), None
     if name == 'lattice2':
-        return tp._records(0.1, {(2 * a, 2 * b, 2 * c): one for a in range(4) for b in range(4) for c in range(4)}), None
+        return ah.records(0.1, {(2 * a, 2 * b, 2 * c): one for a in range(4) for b in range(4) for c in range(4)}), None
     if name == 'lattice4':
-        return tp._records(0.1, {(4 * a, 4 * b, 4 * c): one for a in range(3) for b in range(3) for c in range(3)}), None
+        return ah.records(0.1, {(4 * a, 4 * b, 4 * c): one for a in range(3) for b in range(3) for c in range(3)}), None
     if name == 'walls':
-        return tp._records(0.1, {(x, y, z): one for x in (0, 2) for y in range(5) for z in range(5)}), None
+        return ah.records(0.1, {(x, y, z): one for x in (0, 2) for y in range(5) for z in range(5)}), None
     if name == 'dumbbell':
         rows = {(x0 + a, b, c): (3, 0, 0, 0) for x0 in (0, 4) for a in range(3) for b in range(3) for c in range(3)}
         rows[(3, 1, 1)] = one                                                        # the bridge
-        return tp._records(0.1, rows), None
+        return ah.records(0.1, rows), None
     if name == 'sizes':
         return _sizes_scene()
     if name == 'blobs':
         sheet, blobs = _blob_scene()
-        return tp._points_map(0.1, [(np.concatenate([sheet, tp._centres(blobs, 0.1)]), None, 0)]), None
+        return ah.points_map(0.1, [(np.concatenate([sheet, ah.centres(blobs, 0.1)]), None, 0)]), None
     assert name == 'wavy_blobs'
-    return tp._points_map(0.1, [(_wavy_blobs(), None, 0)]), None
+    return ah.points_map(0.1, [(_wavy_blobs(), None, 0)]), None
 
 
 _scenes = {}
@@ -171,47 +169,30 @@ def _restate(name):
         removed = cref.remove_components(r, pierced, args.get('min_voxels', 0), args.get('min_points', 0), args.get('dry_run', False), **a)
         keys, acc, stamps = r.records()
         _restated[name] = dict(comp, remove_counters=removed, keys=keys, acc=acc.reshape(5, -1), stamps=stamps.reshape(2, -1),
-                               pierced=None if pierced is None else tp._aligned(pierced, keys))
+                               pierced=None if pierced is None else ah.aligned(pierced, keys))
     return _restated[name]
 
 
 # ---- the host build -------------------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def host_exe(tmp_path_factory):
-    return build_host_driver(tmp_path_factory.mktemp('components_host'), 'accum_components_host_driver')
+host_exe = ah.host_driver_fixture('accum_components_host_driver', 'components_host')
 
 
 def _run_host(exe, tmp_path, tag, records, pierced, mask, spare_in=3, spare_out=5, radius=1, min_count=1, max_moving_fraction=None, min_voxels=0, min_points=0,
               dry_run=False, seed=1):
-    keys, acc, stamps = records
-    m = keys.shape[0]
+    m = records[0].shape[0]
     head = [m, max(m + spare_in, 1), max(m + spare_out, 1), 0 if pierced is None else 1, 0 if mask is None else 1, 0 if mask is None else len(mask), min_count,
             0 if max_moving_fraction is None else 1, radius, min_voxels, min_points, 1 if dry_run else 0, seed]
-    src, dst = os.path.join(str(tmp_path), tag + '.in'), os.path.join(str(tmp_path), tag + '.out')
-    with open(src, 'wb') as f:
-        f.write(np.array(head, np.int64).tobytes())
-        f.write(np.array([0.0 if max_moving_fraction is None else max_moving_fraction], np.float64).tobytes())
-        f.write(np.ascontiguousarray(keys, np.int64).tobytes())
-        f.write(np.ascontiguousarray(acc, np.int64).tobytes())
-        f.write(np.ascontiguousarray(stamps, np.int32).tobytes())
-        if pierced is not None:
-            f.write(np.ascontiguousarray(pierced, np.int32).tobytes())
-        if mask is not None:
-            f.write(np.ascontiguousarray(mask, np.uint8).tobytes())
-    subprocess.check_call([exe, src, dst])
-    raw = open(dst, 'rb').read()
+    raw = ah.run_driver(exe, tmp_path, tag, np.array(head, np.int64), np.array([0.0 if max_moving_fraction is None else max_moving_fraction], np.float64),
+                        ah.map_bytes(*records, pierced), b'' if mask is None else np.ascontiguousarray(mask, np.uint8))
     head = np.frombuffer(raw, np.int64, 12)
     out = dict(counters=head[:7].tolist(), remove_counters=head[7:11].tolist(), edges=int(head[11]))
-    kept, k, off = out['counters'][0] - out['counters'][2], out['counters'][4], 96
+    kept, k = out['counters'][0] - out['counters'][2], out['counters'][4]
     fields = [('label', np.int32, (kept,))] + [(n, d, (k,) + s) for n, d, s in TABLES]
     if not dry_run and out['counters'][6] == cref.OK:
-        rk = out['remove_counters'][0]
-        fields += [('keys', np.int64, (rk,)), ('acc', np.int64, (5, rk)), ('stamps', np.int32, (2, rk)), ('pierced', np.int32, (rk if pierced is not None else 0,))]
-    for name, dtype, shape in fields:
-        n = int(np.prod(shape))
-        out[name] = np.frombuffer(raw, dtype, n, off).reshape(shape).copy()
-        off += n * np.dtype(dtype).itemsize
+        fields += ah.map_layout(out['remove_counters'][0], pierced is not None)
+    tables, off = ah.unpack(raw, 96, fields)
     assert off == len(raw)
+    out.update(tables)
     if pierced is None:
         out['pierced'] = None
     return out
@@ -229,7 +210,7 @@ def _host(exe, tmp_path, name):
         scene, args = CASES[name] if name in CASES else ('wavy_blobs', BIG[name])
         r, pierced = _scene(scene)
         keys = r.records()[0]
-        _hosted[name] = _run_host(exe, tmp_path, name, r.records(), None if pierced is None else tp._aligned(pierced, keys), _mask(scene, args),
+        _hosted[name] = _run_host(exe, tmp_path, name, r.records(), None if pierced is None else ah.aligned(pierced, keys), _mask(scene, args),
                                   **_host_args(args))
     return _hosted[name]
 
@@ -269,7 +250,7 @@ def test_scenes_hold_what_they_are_for():
 
 def test_no_link_through_an_overflowed_field():
     """The index-bound scene at 0.01 m with its decoys: the components are those of a direct Chebyshev flood fill on the coordinates."""
-    vox, decoys = tp._bound_voxels()
+    vox, decoys = ah.bound_voxels()
     cells = set(vox + decoys)
     for r in (1, 2, 3):
         todo, n = set(cells), 0
@@ -294,7 +275,7 @@ def test_host_build_equals_the_restatement(host_exe, tmp_path, name):
         tp._assert_same(dict(host, counters=[]), dict(want, counters=[]), name)
     scene, args = CASES[name]
     r, pierced = _scene(scene)
-    other = _run_host(host_exe, tmp_path, name + '_seed', r.records(), None if pierced is None else tp._aligned(pierced, r.records()[0]), _mask(scene, args),
+    other = _run_host(host_exe, tmp_path, name + '_seed', r.records(), None if pierced is None else ah.aligned(pierced, r.records()[0]), _mask(scene, args),
                       spare_in=0, spare_out=0, seed=12345, **_host_args(args))   # another order of the joins, tables with no spare row
     assert all(np.array_equal(other[f], host[f]) for f in host if host[f] is not None), name
 
@@ -389,12 +370,12 @@ def _device_case(host_exe, tmp_path, name, scene, args):
     from pcaccumulation_amd import native
     host = _host(host_exe, tmp_path, name)
     m = tp._device_cloud(*_scene(scene))
-    before, state = tp._snapshot(m), m._state.tolist()
+    before, state = ah.snapshot(m), m._state.tolist()
     mask = _mask(scene, args)
     got, behind, raw = _native_components(m, mask, args['radius'], **_filter(args))
     _assert_components_equal(got, host, name)
     assert behind and got['counters'][6] != cref.GAVE_UP, name                    # rows behind kept / K are not written
-    tp._assert_unchanged(m, before, name)                                         # components() leaves keys, records, stamps, sidecar, state, num_voxels
+    ah.assert_unchanged(m, before, name)                                         # components() leaves keys, records, stamps, sidecar, state, num_voxels
     again, _, _ = _native_components(m, mask, args['radius'], **_filter(args))
     assert all(np.array_equal(again[f].view(np.uint8) if f != 'counters' else again[f], got[f].view(np.uint8) if f != 'counters' else got[f]) for f in got), name
     call = dict(min_voxels=args.get('min_voxels') or None, min_points=args.get('min_points') or None, radius=args['radius'],
@@ -405,7 +386,7 @@ def _device_case(host_exe, tmp_path, name, scene, args):
         for dry in (True, False):
             with pytest.raises(ValueError):
                 m.remove_components(dry_run=dry, **call)
-            tp._assert_unchanged(m, before, name)
+            ah.assert_unchanged(m, before, name)
         with pytest.raises(ValueError):
             m.components(radius=args['radius'], mask=call['mask'], **_filter(args))
         return
@@ -414,7 +395,7 @@ def _device_case(host_exe, tmp_path, name, scene, args):
     dry = m.remove_components(dry_run=True, **call)
     want = dict(zip(cref.REMOVE_COUNTERS + cref.COUNTERS[:6], host['remove_counters'] + host['counters'][:6]))
     assert dry == want and all(type(v) is int for v in dry.values()), name
-    tp._assert_unchanged(m, before, name)                                         # dry_run: records, sidecar, num_voxels and the state words stay
+    ah.assert_unchanged(m, before, name)                                         # dry_run: records, sidecar, num_voxels and the state words stay
     if args.get('dry_run'):
         return
     assert m.remove_components(**call) == want, name
@@ -467,10 +448,10 @@ def test_identities_gpu():
     fine, coarse = m.components(radius=1), m.components(radius=2)                 # every r = 1 component maps into exactly one r = 2 component
     pairs = torch.unique(torch.stack([fine['label'], coarse['label']], 1), dim=0)
     assert pairs.shape[0] == fine['voxels'].shape[0] and coarse['voxels'].shape[0] <= fine['voxels'].shape[0]
-    snap = tp._snapshot(m)
+    snap = ah.snapshot(m)
     res = m.remove_components(min_voxels=1)
     assert res['small'] == 0 and res['kept'] == 257
-    tp._assert_unchanged(m, snap, 'min_voxels = 1')                               # a bit-identical map
+    ah.assert_unchanged(m, snap, 'min_voxels = 1')                               # a bit-identical map
     m, k = tp._device_cloud(*_scene('sizes')), 4                                  # components of 2 .. 6 voxels: no filter, no mask
     before = m.components(radius=1)
     stay = before['voxels'] >= k
@@ -506,7 +487,7 @@ def test_objects_on_the_ground_gpu():
     rows = dict(ground)
     for lo, hi in boxes:
         rows.update({(x, y, z): (3, 1, 1, 2) for x in range(lo[0], hi[0] + 1) for y in range(lo[1], hi[1] + 1) for z in range(lo[2], hi[2] + 1)})
-    r = tp._records(0.1, rows)
+    r = ah.records(0.1, rows)
     m = tp._device_cloud(r, None)
     whole = m.components()
     assert whole['voxels'].tolist() == [len(rows)] and whole['counters'].tolist()[4:] == [1, len(rows), 0]
@@ -599,7 +580,7 @@ def test_bad_arguments_launch_nothing_gpu():
     from pcaccumulation_amd import native
     r, pierced = _scene('rows65')
     m = tp._device_cloud(r, pierced)
-    snap = tp._snapshot(m)
+    snap = ah.snapshot(m)
     out = {name: torch.full((65,) + shape, POISON, dtype=dtype, device=DEV) for name, dtype, shape in native.COMPONENTS_FIELDS}
     counters = torch.full((7,), POISON, dtype=torch.int64, device=DEV)
     good = dict(tables=m._cur, m=65, min_count=1, max_moving_fraction=None, mask=None, radius=1, out=out, counters=counters)
@@ -630,13 +611,13 @@ def test_bad_arguments_launch_nothing_gpu():
         with pytest.raises(native.NativeError, match='PCACC_E_ARG'):
             native.accum_remove_components(**dict(good, **bad))
     torch.cuda.synchronize()
-    tp._assert_unchanged(m, snap, 'bad arguments')
+    ah.assert_unchanged(m, snap, 'bad arguments')
     assert all(bool((t == POISON).all()) for t in tuple(out.values()) + tabs + (pout, counters, rcounters))
     empty = {name: torch.zeros((0,) + shape, dtype=dtype, device=DEV) for name, dtype, shape in native.COMPONENTS_FIELDS}
     zero = native.accum_components(m._cur, 0, 1, None, None, 1, out=empty, counters=counters)        # m = 0: the zero counters and nothing else
     native.accum_remove_components(**dict(good, m=0, first=zero))
     assert counters.tolist() == [0] * 7 and rcounters.tolist() == [0] * 4 and all(bool((t == POISON).all()) for t in tabs + (pout,))
-    tp._assert_unchanged(m, snap, 'm = 0')
+    ah.assert_unchanged(m, snap, 'm = 0')
     for bad in (dict(radius=4), dict(mask=torch.ones(65, dtype=torch.float32, device=DEV)), dict(mask=torch.ones(65, 1, dtype=torch.bool, device=DEV))):
         with pytest.raises(ValueError):
             m.components(**bad)
@@ -649,4 +630,4 @@ def test_bad_arguments_launch_nothing_gpu():
         m.components(mask=torch.ones(65, dtype=torch.bool))
     with pytest.raises(ValueError):
         m.components(mask=torch.ones(64, dtype=torch.bool, device=DEV))           # BAD_MASK, found on the device
-    tp._assert_unchanged(m, snap, 'ValueError')
+    ah.assert_unchanged(m, snap, 'ValueError')

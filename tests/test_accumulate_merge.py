@@ -6,74 +6,25 @@ Every result is an integer or a copied record, so every claim is an equality:
         destination written exactly once, keys ascending) against the plain-Python restatement (tests/accumulate_merge_reference.py);
   GPU   merge against add itself (the map one accumulator holds after every add of both), the kernels against the g++ build on the same scenes, regrid
         against add on points that are exact in float32 and in fixed point, and merge(other, pose) against regrid + merge."""
-import io
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import accumulate_helpers as ah
 import accumulate_merge_reference as mref
 import accumulate_reference as ref
-from helpers import build_host_driver
+from accumulate_helpers import DEV
+from helpers import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = 'cuda:0'
 BIAS = 1 << 20
 I31 = (1 << 31) - 1
-
-
-def _key(c):
-    return ((c[0] + BIAS) << 42) | ((c[1] + BIAS) << 21) | (c[2] + BIAS)
-
-
-def _rot(axis, angle, t):
-    """Rodrigues: a rotation by `angle` about `axis` and a translation, [4,4] f64."""
-    a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    T = np.eye(4)
-    T[:3, :3] = np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * (K @ K)
-    T[:3, 3] = t
-    return T
-
-
-SKEW = _rot((0.3, -0.5, 0.8), 0.7, (1.37, -2.11, 0.53))
+SKEW = ah.rot_axis((0.3, -0.5, 0.8), 0.7, (1.37, -2.11, 0.53))
 
 
 # ---- scenes: (ReferenceMap, {key: rays} or None), built once and never modified ---------------------------------------------------------------------
-def _rows(coords, seed, rays=False, vs=0.1):
-    """Random records on the given voxels: counts 1..6, stamps 0..15, centroids inside the voxel; rays 0..4 with rays=True."""
-    rs = np.random.RandomState(seed)
-    r, p = ref.ReferenceMap(vs), ({} if rays else None)
-    for c in coords:
-        count = int(rs.randint(1, 7))
-        t_first = int(rs.randint(0, 11))
-        q = [int(np.rint((v + rs.uniform(0.1, 0.9)) * vs * 65536.0)) * count + int(rs.randint(0, count)) for v in c]
-        r.rec[_key(c)] = [count, int(rs.randint(0, count + 1))] + q + [t_first, t_first + int(rs.randint(0, 6))]
-        if rays:
-            p[_key(c)] = int(rs.randint(0, 5))
-    r.dropped = int(rs.randint(0, 9))
-    return r, p
-
-
-CELLS = [(x, y, z) for x in range(-2, 3) for y in range(-2, 3) for z in range(-2, 3)]
 ROW_COUNTS = (0, 1, 63, 64, 65)
-
-
-def _some(m, seed):
-    return [CELLS[i] for i in np.random.RandomState(seed).permutation(len(CELLS))[:m]]
-
-
-def _wavy(shift=0.0):
-    """test_accumulate_prune.py's sheet: 26 m x 26 m at 0.1 m, four points in every column, and one far voxel -- 76 661 voxels, more than one workgroup,
-    m mod 64 != 0, more than one scan chunk."""
-    g = np.arange(520) * 0.05 + 0.025 - 13.0
-    x, y = np.meshgrid(g, g, indexing='ij')
-    z = 0.4 * np.sin(0.9 * x) * np.cos(0.7 * y) + 0.013
-    pts = np.concatenate([np.stack([x, y, z], -1).reshape(-1, 3), [[40.0, 40.0, 40.0]]])
-    pts[:, 0] += shift
-    return pts.astype(np.float32)
 
 
 def _cloud_points(seed, n, lo=(-1, -1, -0.5), hi=(1, 1, 0.5)):
@@ -86,33 +37,33 @@ _scenes = {}
 def _build_scene(name):
     if name.startswith('rows'):                                                  # rows<m>_<seed>: with a sidecar
         m, seed = (int(v) for v in name[4:].split('_'))
-        return _rows(_some(m, seed), 50 + 7 * m + seed, rays=True)
+        return ah.rows(ah.some(m, seed), 50 + 7 * m + seed, rays=True)
     line = lambda xs: [(x, 1, -1) for x in xs]
     if name == 'low':
-        return _rows(line(range(-40, -10)), 1)
+        return ah.rows(line(range(-40, -10)), 1)
     if name == 'high':
-        return _rows(line(range(10, 47)), 2)
+        return ah.rows(line(range(10, 47)), 2)
     if name == 'even':
-        return _rows(line(range(-20, 20, 2)), 3)
+        return ah.rows(line(range(-20, 20, 2)), 3)
     if name == 'odd':
-        return _rows(line(range(-19, 21, 2)), 4)
+        return ah.rows(line(range(-19, 21, 2)), 4)
     if name == 'outer':
-        return _rows(line(range(-30, 30)), 5)
+        return ah.rows(line(range(-30, 30)), 5)
     if name == 'inner':
-        return _rows(line(range(-7, 9)), 6)
+        return ah.rows(line(range(-7, 9)), 6)
     if name in ('plain_a', 'plain_b'):                                           # overlapping, no sidecar
-        return _rows(_some(70, 11 if name == 'plain_a' else 12), 13 if name == 'plain_a' else 14)
+        return ah.rows(ah.some(70, 11 if name == 'plain_a' else 12), 13 if name == 'plain_a' else 14)
     if name in ('rays_a', 'rays_b'):
-        return _rows(_some(70, 11 if name == 'rays_a' else 12), 15 if name == 'rays_a' else 16, rays=True)
+        return ah.rows(ah.some(70, 11 if name == 'rays_a' else 12), 15 if name == 'rays_a' else 16, rays=True)
     if name in ('sat_a', 'sat_b'):                                               # (2^31 - 2) + 5, (2^31 - 1) + 0, (2^31 - 1) + (2^31 - 1), 7 + 8, one side only
-        r, _ = _rows(line(range(5)) if name == 'sat_a' else line(range(4)) + [(9, 1, -1)], 17)
+        r, _ = ah.rows(line(range(5)) if name == 'sat_a' else line(range(4)) + [(9, 1, -1)], 17)
         rays = (I31 - 1, I31, I31, 7, I31) if name == 'sat_a' else (5, 0, I31, 8, I31)
         return r, {k: v for k, v in zip(sorted(r.rec), rays)}
     if name in ('grow_a', 'grow_b'):                                             # 1000 distinct voxels each, disjoint
-        return _rows([(x, y, 0 if name == 'grow_a' else 5) for x in range(40) for y in range(25)], 18)
+        return ah.rows([(x, y, 0 if name == 'grow_a' else 5) for x in range(40) for y in range(25)], 18)
     if name in ('wavy', 'wavy_shifted'):
         r = ref.ReferenceMap(0.1)
-        r.add(_wavy(0.0 if name == 'wavy' else 13.0), stamp=3 if name == 'wavy' else 8)
+        r.add(ah.wavy(0.0 if name == 'wavy' else 13.0), stamp=3 if name == 'wavy' else 8)
         return r, None
     if name in ('dense', 'dense_rays'):                                          # many points per voxel, three stamps, flags, dropped points
         r = ref.ReferenceMap(0.1)
@@ -123,13 +74,13 @@ def _build_scene(name):
         rs = np.random.RandomState(44)
         return r, ({k: int(rs.randint(0, 9)) for k in r.rec} if name == 'dense_rays' else None)
     if name == 'crafted':                                                        # unusable rows among usable ones: count 0, -3, 2^31 + 1; and 2^31
-        r, p = _rows(line(range(8)), 19, rays=True)
+        r, p = ah.rows(line(range(8)), 19, rays=True)
         for k, count in zip(sorted(r.rec)[1::2], (0, -3, (1 << 31) + 1, 1 << 31)):
             r.rec[k][0] = count
             r.rec[k][2:5] = [0, 0, 0]
         return r, p
     assert name == 'sat_regrid'                                                  # two rows of one 0.2 m voxel whose ray counts do not fit together
-    r, _ = _rows([(0, 0, 0), (1, 0, 0), (4, 4, 4)], 20)
+    r, _ = ah.rows([(0, 0, 0), (1, 0, 0), (4, 4, 4)], 20)
     return r, {k: v for k, v in zip(sorted(r.rec), (I31 - 1, 5, 9))}
 
 
@@ -161,30 +112,21 @@ REGRID_NAMES = sorted(REGRID_CASES)
 
 
 # ---- the host build ----------------------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def host_exe(tmp_path_factory):
-    return build_host_driver(tmp_path_factory.mktemp('merge_host'), 'accum_merge_host_driver')
+host_exe = ah.host_driver_fixture('accum_merge_host_driver', 'merge_host')
 
 
 def _map_bytes(r, pierced):
     keys, acc, stamps = r.records()
-    raw = keys.tobytes() + np.ascontiguousarray(acc, np.int64).tobytes() + np.ascontiguousarray(stamps, np.int32).tobytes()
-    return raw + (b'' if pierced is None else mref.aligned(pierced, keys).tobytes())
+    return ah.map_bytes(keys, acc, stamps, None if pierced is None else mref.aligned(pierced, keys))
 
 
 def _read_result(raw, sidecar, rows_word):
     counters, state = np.frombuffer(raw, np.int64, 5).tolist(), np.frombuffer(raw, np.int64, 8, 40).tolist()
-    rows, off = counters[rows_word], 104
-    out = dict(counters=counters, state=state)
-    for name, dtype, shape in (('keys', np.int64, (rows,)), ('acc', np.int64, (5, rows)), ('stamps', np.int32, (2, rows)),
-                               ('pierced', np.int32, (rows if sidecar else 0,))):
-        n = int(np.prod(shape))
-        out[name] = np.frombuffer(raw, dtype, n, off).reshape(shape).copy()
-        off += n * np.dtype(dtype).itemsize
+    out, off = ah.unpack(raw, 104, ah.map_layout(counters[rows_word], sidecar))
     assert off == len(raw)
     if not sidecar:
         out['pierced'] = None
-    return out
+    return dict(out, counters=counters, state=state)
 
 
 def _run_host_merge(exe, tmp_path, tag, a, b, out_capacity=None, spare=3):
@@ -195,11 +137,8 @@ def _run_host_merge(exe, tmp_path, tag, a, b, out_capacity=None, spare=3):
         out_capacity = len(set(ra.rec) | set(rb.rec)) + 5
     head = [0, ma, ma + spare, 0 if pa is None else 1, mb, mb + spare, 0 if pb is None else 1, out_capacity,
             1 if b is None else 0, rb.dropped]
-    src, dst = os.path.join(str(tmp_path), tag + '.in'), os.path.join(str(tmp_path), tag + '.out')
-    with open(src, 'wb') as f:
-        f.write(np.array(head, np.int64).tobytes() + _map_bytes(ra, pa) + (b'' if b is None else _map_bytes(rb, pb)))
-    subprocess.check_call([exe, src, dst])
-    res = _read_result(open(dst, 'rb').read(), pa is not None or pb is not None, 1)
+    raw = ah.run_driver(exe, tmp_path, tag, np.array(head, np.int64), _map_bytes(ra, pa), b'' if b is None else _map_bytes(rb, pb))
+    res = _read_result(raw, pa is not None or pb is not None, 1)
     if res['counters'][0] != 0:                                                  # TOO_SMALL: no map follows
         res = dict(res, keys=res['keys'][:0])
     return res
@@ -209,24 +148,17 @@ def _run_host_regrid(exe, tmp_path, tag, a, pose, voxel_size, spare_in=3, spare_
     r, p = a
     m = r.num_voxels
     head = [1, m, m + spare_in, 0 if p is None else 1, m + spare_out, 0 if pose is None else 1, r.dropped]
-    src, dst = os.path.join(str(tmp_path), tag + '.in'), os.path.join(str(tmp_path), tag + '.out')
-    with open(src, 'wb') as f:
-        f.write(np.array(head, np.int64).tobytes())
-        f.write(np.concatenate([[voxel_size], (np.eye(4) if pose is None else np.asarray(pose, np.float64)).reshape(-1)]).astype(np.float64).tobytes())
-        f.write(_map_bytes(r, p))
-    subprocess.check_call([exe, src, dst])
-    return _read_result(open(dst, 'rb').read(), p is not None, 1)
+    raw = ah.run_driver(exe, tmp_path, tag, np.array(head, np.int64),
+                        np.concatenate([[voxel_size], (np.eye(4) if pose is None else np.asarray(pose, np.float64)).reshape(-1)]).astype(np.float64),
+                        _map_bytes(r, p))
+    return _read_result(raw, p is not None, 1)
 
 
 def _too_small_result(exe, tmp_path, tag, a, b, out_capacity):
     (ra, pa), (rb, pb) = a, b
     head = [0, ra.num_voxels, ra.num_voxels + 3, 0 if pa is None else 1, rb.num_voxels, rb.num_voxels + 3, 0 if pb is None else 1, out_capacity, 0, rb.dropped]
-    src, dst = os.path.join(str(tmp_path), tag + '.in'), os.path.join(str(tmp_path), tag + '.out')
-    with open(src, 'wb') as f:
-        f.write(np.array(head, np.int64).tobytes() + _map_bytes(ra, pa) + _map_bytes(rb, pb))
-    subprocess.check_call([exe, src, dst])
-    raw = open(dst, 'rb').read()
-    assert len(raw) == 104                                                       # counters and state, no map
+    raw = ah.run_driver(exe, tmp_path, tag, np.array(head, np.int64), _map_bytes(ra, pa), _map_bytes(rb, pb))
+    assert len(raw) == 104                                                      # counters and state, no map
     return np.frombuffer(raw, np.int64, 5).tolist(), np.frombuffer(raw, np.int64, 8, 40).tolist()
 
 
@@ -245,18 +177,6 @@ def _host_regrid(exe, tmp_path, name):
         scene, pose, vs = REGRID_CASES[name]
         _hosted[('g', name)] = _run_host_regrid(exe, tmp_path, name, _scene(scene), pose, vs)
     return _hosted[('g', name)]
-
-
-def _as_tables(r, pierced):
-    keys, acc, stamps = r.records()
-    return dict(keys=keys, acc=acc.reshape(5, -1), stamps=stamps.reshape(2, -1), pierced=None if pierced is None else mref.aligned(pierced, keys))
-
-
-def _assert_tables(got, want, what):
-    for f in ('keys', 'acc', 'stamps'):
-        assert got[f].dtype == want[f].dtype and np.array_equal(got[f], want[f]), (what, f)
-    assert (got['pierced'] is None) == (want['pierced'] is None), what
-    assert got['pierced'] is None or np.array_equal(got['pierced'], want['pierced']), what
 
 
 # ---- CPU: host build == restatement ----------------------------------------------------------------------------------------------------------------------
@@ -280,7 +200,7 @@ def test_merge_host_build_equals_the_restatement(host_exe, tmp_path, name):
     got = _host_merge(host_exe, tmp_path, name)
     assert got['counters'] == [0, res['rows'], res['shared'], res['new'], res['saturated']], name
     assert got['state'] == [res['rows'], 100 + rb.dropped] + [7] * 6, name     # NUM_VOXELS and DROPPED, every other word left alone
-    _assert_tables(got, _as_tables(want, wp), name)
+    ah.assert_tables(got, ah.as_tables(want, wp), name)
     assert res['rows'] == ra.num_voxels + res['new'] and res['shared'] + res['new'] == rb.num_voxels
 
 
@@ -293,7 +213,7 @@ def test_merge_relations_and_saturation(host_exe, tmp_path):
     assert below['keys'][:30].tolist() == sorted(_scene('low')[0].rec) and below['keys'][30:].tolist() == sorted(_scene('high')[0].rec)
     # a.merge(a): every count and sum doubled, the stamps the same, the centroids bit-equal
     r, p = _scene('rows65_1')
-    twice, once = _host_merge(host_exe, tmp_path, 'self'), _as_tables(r, p)
+    twice, once = _host_merge(host_exe, tmp_path, 'self'), ah.as_tables(r, p)
     assert np.array_equal(twice['keys'], once['keys']) and np.array_equal(twice['acc'], 2 * once['acc']) and np.array_equal(twice['stamps'], once['stamps'])
     assert np.array_equal(twice['pierced'], 2 * once['pierced']) and twice['counters'] == [0, 65, 65, 0, 0]
     c = lambda t: ((t['acc'][2:5].astype(np.float64) / t['acc'][0].astype(np.float64)) * 2.0 ** -16).astype(np.float32)
@@ -326,13 +246,13 @@ def test_regrid_host_build_equals_the_restatement(host_exe, tmp_path, name):
     got = _host_regrid(host_exe, tmp_path, name)
     assert got['counters'] == [res['rows_in'], res['rows_out'], res['dropped_rows'], res['dropped_points'], res['saturated']], name
     assert got['state'] == [res['rows_out'], r.dropped + res['dropped_points']] + [0] * 6 and want.dropped == got['state'][1], name
-    _assert_tables(got, _as_tables(want, wp), name)
+    ah.assert_tables(got, ah.as_tables(want, wp), name)
 
 
 def test_regrid_drops_conserves_and_saturates(host_exe, tmp_path):
     dense = _scene('dense')[0]
     total = lambda t, f: int(t['acc'][f].sum())
-    src = _as_tables(dense, None)
+    src = ah.as_tables(dense, None)
     doubled = _host_regrid(host_exe, tmp_path, 'doubled')                        # identity pose, twice the voxel size: nothing is lost but resolution
     assert doubled['counters'][2:] == [0, 0, 0] and doubled['counters'][1] < doubled['counters'][0] == dense.num_voxels
     assert total(doubled, 0) == total(src, 0) == 9000 - 18 and total(doubled, 1) == total(src, 1)
@@ -353,8 +273,8 @@ def test_regrid_drops_conserves_and_saturates(host_exe, tmp_path):
         assert got['counters'][2:4] == [3, (1 << 31) + 1] and got['counters'][1] == 5, name
     same = _host_regrid(host_exe, tmp_path, 'crafted_identity')                  # the identity at the same voxel size: a usable row stays in its voxel;
     crafted = _scene('crafted')[0]                                               # the row of 2^31 points was given the sums 0: its centroid is the origin
-    assert set(same['keys'].tolist()) == set(sorted(crafted.rec)[0::2]) | {_key((0, 0, 0))}
-    assert same['acc'][:, same['keys'].tolist().index(_key((0, 0, 0)))].tolist() == [1 << 31, crafted.rec[sorted(crafted.rec)[7]][1], 0, 0, 0]
+    assert set(same['keys'].tolist()) == set(sorted(crafted.rec)[0::2]) | {ah.key((0, 0, 0))}
+    assert same['acc'][:, same['keys'].tolist().index(ah.key((0, 0, 0)))].tolist() == [1 << 31, crafted.rec[sorted(crafted.rec)[7]][1], 0, 0, 0]
     sat = _host_regrid(host_exe, tmp_path, 'saturation')
     assert sat['counters'] == [3, 2, 0, 0, 1] and sat['pierced'].tolist() == [I31, 9]
     assert _host_regrid(host_exe, tmp_path, 'empty')['counters'] == [0, 0, 0, 0, 0]
@@ -408,31 +328,9 @@ def test_header_binding_and_argument_checks():
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------------------------------------------
-def _device_cloud(r, pierced, capacity=None):
-    """The restatement's map and ray counts as an AccumulatedCloud on the device, through load()."""
-    from pcaccumulation_amd.accumulate import AccumulatedCloud
-    keys, acc, stamps = r.records()
-    extra = {}
-    if pierced is not None:
-        extra = dict(pierced=mref.aligned(pierced, keys), pierce_counters=np.arange(5, dtype=np.int64) + r.num_voxels)
-    buf = io.BytesIO()
-    np.savez(buf, keys=keys, acc=acc.reshape(5, -1), stamps=stamps.reshape(2, -1), voxel_size=np.float64(r.voxel_size), dropped=np.int64(r.dropped), **extra)
-    buf.seek(0)
-    return AccumulatedCloud.load(buf, DEV)
-
-
-def _snapshot(m):
-    n = m.num_voxels
-    keys, acc, stamps = m._cur
-    return (n, m.capacity, m.dropped, keys[:n].clone(), acc[:, :n].clone(), stamps[:, :n].clone(), None if m._pierced is None else m._pierced[:n].clone(),
-            m._state.clone(), None if m._pierce_counters is None else m._pierce_counters.clone())
-
-
-def _assert_unchanged(m, snap, what):
-    now = _snapshot(m)
-    assert now[:3] == snap[:3], what
-    for a, b in zip(now[3:], snap[3:]):
-        assert (a is None and b is None) or torch.equal(a, b), what
+def _device_cloud(r, pierced):
+    """The restatement's map and {key: rays} dict as an AccumulatedCloud on the device."""
+    return ah.device_cloud(r, None if pierced is None else mref.aligned(pierced, r.records()[0]), np.arange(5, dtype=np.int64) + r.num_voxels)
 
 
 def _assert_same_map(a, b, what):
@@ -466,37 +364,14 @@ def _saved(m, tmp_path, tag):
         return {k: (z[k].dtype.str, z[k].shape, z[k].tobytes()) for k in z.files}
 
 
-_windows = {}
-
-
-def _window(k):
-    """2049 random points in a 6 m x 6 m x 3 m box with flags, a stamp and a pose; two of them not finite."""
-    if k not in _windows:
-        rs = np.random.RandomState(70 + k)
-        pts = rs.uniform((-3, -3, -1.5), (3, 3, 1.5), (2049, 3)).astype(np.float32)
-        pts[5 + k] = np.nan
-        pts[900 + 7 * k, 1] = np.inf
-        _windows[k] = (pts, rs.uniform(0, 1, 2049) < 0.3, 10 - 3 * k if k % 2 else k, _rot((0.1 * k, 1.0, 0.3), 0.02 * k, (0.05 * k, -0.03 * k, 0.01)))
-    return _windows[k]
-
-
-def _added(ks, capacity=64, vs=0.1):
-    from pcaccumulation_amd.accumulate import AccumulatedCloud
-    m = AccumulatedCloud(vs, DEV, capacity)
-    for k in ks:
-        pts, mv, stamp, pose = _window(k)
-        m.add(torch.from_numpy(pts).to(DEV), pose, torch.from_numpy(mv).to(DEV), stamp)
-    return m
-
-
 @pytest.mark.gpu
 def test_merge_is_add_gpu(tmp_path):
-    A, B, C = _added((1, 3)), _added((2, 4)), _added((1, 2, 3, 4))
-    snap_a, snap_b = _snapshot(A), _snapshot(B)
+    A, B, C = ah.added((1, 3)), ah.added((2, 4)), ah.added((1, 2, 3, 4))
+    snap_a, snap_b = ah.snapshot(A), ah.snapshot(B)
     ab = A.copy()
     res = ab.merge(B)
-    _assert_unchanged(B, snap_b, 'other is not modified')
-    _assert_unchanged(A, snap_a, 'a copy is independent')
+    ah.assert_unchanged(B, snap_b, 'other is not modified')
+    ah.assert_unchanged(A, snap_a, 'a copy is independent')
     _assert_same_map(ab, C, 'A.merge(B)')
     assert ab.dropped == C.dropped == 8 and _saved(ab, tmp_path, 'ab') == _saved(C, tmp_path, 'c')
     assert res['rows'] == C.num_voxels == A.num_voxels + res['new'] and res['shared'] + res['new'] == B.num_voxels and res['shared'] > 0
@@ -506,7 +381,7 @@ def test_merge_is_add_gpu(tmp_path):
     ba.merge(A)
     _assert_same_map(ba, C, 'B.merge(A)')
     assert _saved(ba, tmp_path, 'ba') == _saved(C, tmp_path, 'c')
-    D = _added((5,))                                                             # grouping: (A u B) u D == A u (B u D)
+    D = ah.added((5,))                                                             # grouping: (A u B) u D == A u (B u D)
     left = ab.copy()
     left.merge(D)
     bd = B.copy()
@@ -514,15 +389,15 @@ def test_merge_is_add_gpu(tmp_path):
     right = A.copy()
     right.merge(bd)
     _assert_same_map(left, right, 'grouping')
-    _assert_same_map(left, _added((1, 2, 3, 4, 5)), 'five windows')
-    pts, mv, stamp, pose = _window(6)                                            # an add onto the merged map: the buffer swap
+    _assert_same_map(left, ah.added((1, 2, 3, 4, 5)), 'five windows')
+    pts, mv, stamp, pose = ah.window(6)                                            # an add onto the merged map: the buffer swap
     ab.add(torch.from_numpy(pts).to(DEV), pose, torch.from_numpy(mv).to(DEV), stamp)
-    _assert_same_map(ab, _added((1, 2, 3, 4, 6)), 'add after merge')
-    empty = _added(())
-    before = _snapshot(ab)
+    _assert_same_map(ab, ah.added((1, 2, 3, 4, 6)), 'add after merge')
+    empty = ah.added(())
+    before = ah.snapshot(ab)
     assert ab.merge(empty) == dict(rows=ab.num_voxels, shared=0, new=0, dropped_rows=0, dropped_points=0, saturated=0)
-    _assert_unchanged(ab, before, 'an empty other changes nothing')
-    into = _added(())                                                            # a map that never saw an add takes another whole
+    ah.assert_unchanged(ab, before, 'an empty other changes nothing')
+    into = ah.added(())                                                            # a map that never saw an add takes another whole
     into.merge(C)
     _assert_same_map(into, C, 'empty.merge(C)')
 
@@ -535,13 +410,13 @@ def test_merge_kernel_equals_the_host_build_gpu(host_exe, tmp_path, name):
     host = _host_merge(host_exe, tmp_path, name)
     A = _device_cloud(*_scene(a))
     B = A if b is None else _device_cloud(*_scene(b))
-    snap_b, state, drop_a, drop_b = _snapshot(B), A._state.tolist(), A.dropped, B.dropped
+    snap_b, state, drop_a, drop_b = ah.snapshot(B), A._state.tolist(), A.dropped, B.dropped
     counters = (None if A._pierce_counters is None else A._pierce_counters.clone(), None if B._pierce_counters is None else B._pierce_counters.clone())
     res = A.merge(B)
     assert [0, res['rows'], res['shared'], res['new'], res['saturated']] == host['counters'], name
     _assert_device_equals_host(A, host, name)
     if b is not None:
-        _assert_unchanged(B, snap_b, name)
+        ah.assert_unchanged(B, snap_b, name)
     if B.num_voxels or b is None:                                                # an empty other returns before the device is asked
         state[native.ACCUM_NUM_VOXELS], state[native.ACCUM_DROPPED] = host['counters'][1], drop_a + drop_b
     assert A._state.tolist() == state and A.dropped == state[native.ACCUM_DROPPED], name
@@ -571,18 +446,18 @@ def test_merge_grows_by_the_devices_count_gpu(host_exe, tmp_path):
     from pcaccumulation_amd import native
     A, B = _device_cloud(*_scene('grow_a')), _device_cloud(*_scene('grow_b'))
     assert (A.capacity, A.num_voxels, B.capacity, B.num_voxels) == (1024, 1000, 1024, 1000)
-    snap_a, snap_b = _snapshot(A), _snapshot(B)
+    snap_a, snap_b = ah.snapshot(A), ah.snapshot(B)
     # the refused attempt on its own: a capacity the host knows is too small, nothing overrun, nothing written
     out = tuple(torch.full_like(t, 7) for t in A._cur)
     counters = torch.full((5,), 7, dtype=torch.int64, device=DEV)
     native.accum_merge(A._cur, 1000, None, B._cur, 1000, None, B.dropped, out, None, counters, A._state)
     assert counters.tolist() == [native.ACCUM_TOO_SMALL, 2000, 0, 1000, 0] and all(bool((t == 7).all()) for t in out)
-    _assert_unchanged(A, snap_a, 'refused attempt')
-    _assert_unchanged(B, snap_b, 'refused attempt')
+    ah.assert_unchanged(A, snap_a, 'refused attempt')
+    ah.assert_unchanged(B, snap_b, 'refused attempt')
     res = A.merge(B)
     assert res == dict(rows=2000, shared=0, new=1000, dropped_rows=0, dropped_points=0, saturated=0) and (A.capacity, A.num_voxels) == (2048, 2000)
     _assert_device_equals_host(A, _run_host_merge(host_exe, tmp_path, 'grow', _scene('grow_a'), _scene('grow_b')), 'grow')
-    _assert_unchanged(B, snap_b, 'other')
+    ah.assert_unchanged(B, snap_b, 'other')
     assert A._pierced is None and A._cur[0].shape[0] == 2048
 
 
@@ -625,9 +500,9 @@ def test_regrid_is_add_gpu(name):
         src.add(p, None, f, stamp)
         want.add(p, SKEW, f, stamp)
     assert src.num_voxels == n and src.dropped == 0                              # one point per source voxel
-    snap = _snapshot(src)
+    snap = ah.snapshot(src)
     got = src.regrid(pose=SKEW, voxel_size=0.5)
-    _assert_unchanged(src, snap, name)
+    ah.assert_unchanged(src, snap, name)
     _assert_same_map(got, want, name)
     assert got._state.tolist() == [want.num_voxels, 0, 0, 0, 0, 0, 0, 0] and got.capacity == src.capacity and got.device == src.device
     assert want.num_voxels == {'scattered': want.num_voxels, 'one_voxel': 1, 'distinct': 4096}[name] and (want.num_voxels < n) == (name != 'distinct')
@@ -641,10 +516,10 @@ def test_regrid_kernel_equals_the_host_build_gpu(host_exe, tmp_path, name):
     r, p = _scene(scene)
     host = _host_regrid(host_exe, tmp_path, name)
     src = _device_cloud(r, p)                                                    # count 0 and 2^31 + 1 come in through load()
-    snap = _snapshot(src)
+    snap = ah.snapshot(src)
     got, counters = src._regrid(pose, vs, None)
     assert counters == host['counters'], name
-    _assert_unchanged(src, snap, name)
+    ah.assert_unchanged(src, snap, name)
     _assert_device_equals_host(got, host, name)
     assert got._state.tolist() == host['state'] and got.dropped == host['state'][1] and got.voxel_size == vs, name
     if p is not None:
@@ -669,10 +544,10 @@ def test_merge_with_a_pose_is_regrid_then_merge_gpu():
     for scene, pose, vs in (('dense_rays', SKEW, 0.1), ('dense', SKEW, 0.25), ('dense_rays', FAR, 0.1), ('crafted', None, 0.1)):
         other = _device_cloud(*_scene(scene))
         pose = np.eye(4) if pose is None else pose
-        snap = _snapshot(other)
-        a, b = _added((1, 2), vs=vs), _added((1, 2), vs=vs)
+        snap = ah.snapshot(other)
+        a, b = ah.added((1, 2), vs=vs), ah.added((1, 2), vs=vs)
         res = a.merge(other, pose=torch.from_numpy(pose))
-        _assert_unchanged(other, snap, scene)
+        ah.assert_unchanged(other, snap, scene)
         tmp, counters = other._regrid(pose, vs, None)
         want = b.merge(tmp)
         _assert_same_map(a, b, scene)
@@ -686,7 +561,7 @@ def test_bad_arguments_launch_nothing_gpu():
     from pcaccumulation_amd import native
     A, B = _device_cloud(*_scene('rays_a')), _device_cloud(*_scene('rays_b'))
     assert (A.num_voxels, A.capacity, B.num_voxels, B.capacity) == (70, 128, 70, 128)
-    snap_a, snap_b = _snapshot(A), _snapshot(B)
+    snap_a, snap_b = ah.snapshot(A), ah.snapshot(B)
     out = tuple(torch.full_like(t, 7) for t in A._cur)                           # 128 rows: any of them may stand in for an input's table
     pout = torch.full_like(A._pierced, 7)
     small = tuple(t[..., :69].contiguous() for t in out)
@@ -707,8 +582,8 @@ def test_bad_arguments_launch_nothing_gpu():
         with pytest.raises(native.NativeError, match='PCACC_E_ARG'):
             native.accum_regrid(**dict(rgood, **bad))
     torch.cuda.synchronize()
-    _assert_unchanged(A, snap_a, 'bad arguments')
-    _assert_unchanged(B, snap_b, 'bad arguments')
+    ah.assert_unchanged(A, snap_a, 'bad arguments')
+    ah.assert_unchanged(B, snap_b, 'bad arguments')
     assert all(bool((t == 7).all()) for t in out + small + (pout, mc, rc, state))   # nothing was written
     native.accum_merge(**dict(good, ma=0, mb=0))                                 # ma = mb = 0: the zero counters and NUM_VOXELS = 0, nothing else
     assert mc.tolist() == [0] * 5 and state.tolist() == [0] + [7] * 7 and all(bool((t == 7).all()) for t in out + (pout,))

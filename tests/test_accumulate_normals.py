@@ -7,22 +7,18 @@ the PLY writer; header, binding and argument checks.
 GPU leg: the kernel against the host build BIT FOR BIT at r = 1, 2, 3 on every scene of the CPU leg and on a sheet of more than 65 536 voxels;
 orientation by viewpoints; order independence; row alignment with extract."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import accumulate_helpers as ah
 import accumulate_normals_reference as nref
 import accumulate_reference as ref
-from helpers import build_host_driver
+from accumulate_helpers import DEV, EDGE
+from helpers import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = 'cuda:0'
 OUT = ('normals', 'eigenvalues', 'neighbors', 'flags')
-EDGE = 1 << 20
-
-
 # ---- scenes ----------------------------------------------------------------------------------------------------------------------------
 def _plane():
     rs = np.random.RandomState(7)
@@ -48,36 +44,9 @@ def _two_sheets():
     return np.concatenate([xy, z[:, None]], 1).astype(np.float32)
 
 
-def _centres(idx, vs):
-    return ((np.asarray(idx, np.float64) + 0.5) * vs).astype(np.float32)
-
-
 def _bound_voxels():
-    """Voxel indices at both ends of every axis (3 x 3 x 3 clusters that touch -2^20 and 2^20 - 1) and DECOYS exactly where a key with an overflowed
-    or borrowed y / z field would land: for (x, 2^20-1, z) the key of offset dy = +1 would be that of (x+1, -2^20, z); for (x, -2^20, z) and dy = -1
-    that of (x-1, 2^20-1, z); the same for z into y."""
-    vox = []
-    for axis in range(3):
-        for lo in (-EDGE, EDGE - 3):
-            for a in range(3):
-                for b in (-1, 0, 1):
-                    for c in (-1, 0, 1):
-                        v = [b, c]
-                        v.insert(axis, lo + a)
-                        vox.append(v)
-    cluster = np.array(vox, np.int64)
-    decoys = []
-    for x, y, z in cluster.tolist():
-        if y == EDGE - 1:
-            decoys.append((x + 1, -EDGE, z))
-        if y == -EDGE:
-            decoys.append((x - 1, EDGE - 1, z))
-        if z == EDGE - 1:
-            decoys.append((x, y + 1, -EDGE))
-        if z == -EDGE:
-            decoys.append((x, y - 1, EDGE - 1))
-    decoys = np.array([d for d in decoys if all(-EDGE <= c < EDGE for c in d)], np.int64)
-    return cluster, decoys
+    """The index-bound clusters and their decoys (accumulate_helpers.bound_voxels) as int64 arrays [N,3]."""
+    return tuple(np.array(v, np.int64) for v in ah.bound_voxels())
 
 
 def _scene(name):
@@ -90,23 +59,19 @@ def _scene(name):
         return 0.1, [(_two_sheets(), None, 0)]
     if name == 'bound':
         cluster, decoys = _bound_voxels()
-        return 0.01, [(_centres(np.concatenate([cluster, decoys]), 0.01), None, 0)]
+        return 0.01, [(ah.centres(np.concatenate([cluster, decoys]), 0.01), None, 0)]
     if name == 'single':
         return 0.1, [(np.array([[0.43, -1.21, 0.07]], np.float32), None, 0)]
     if name == 'row9':
-        return 0.1, [(_centres([(k, 4, -2) for k in range(-4, 5)], 0.1), None, 0)]
+        return 0.1, [(ah.centres([(k, 4, -2) for k in range(-4, 5)], 0.1), None, 0)]
     if name == 'block27':
-        return 0.1, [(_centres([(x, y, z) for x in range(3) for y in range(3) for z in range(3)], 0.1), None, 0)]
+        return 0.1, [(ah.centres([(x, y, z) for x in range(3) for y in range(3) for z in range(3)], 0.1), None, 0)]
     if name == 'flagged':                                                        # several points per voxel, some predicted moving, two stamps
         pts = _plane()
         mv = np.random.RandomState(8).uniform(0, 1, pts.shape[0]) < 0.08
         return 0.1, [(pts[:12000], mv[:12000], 3), (pts[12000:], mv[12000:], 1)]
     assert name == 'wavy'                                                        # 26 m x 26 m at 0.1 m: four points in every column, > 65 536 voxels
-    g = np.arange(520) * 0.05 + 0.025 - 13.0
-    x, y = np.meshgrid(g, g, indexing='ij')
-    z = 0.4 * np.sin(0.9 * x) * np.cos(0.7 * y) + 0.013
-    pts = np.stack([x, y, z], -1).reshape(-1, 3)
-    return 0.1, [(np.concatenate([pts, [[40.0, 40.0, 40.0]]]).astype(np.float32), None, 0)]
+    return 0.1, [(ah.wavy(), None, 0)]
 
 
 CPU_SCENES = ('plane', 'sphere', 'two_sheets', 'bound', 'single', 'row9', 'block27', 'flagged')
@@ -126,11 +91,7 @@ def _ref_map(name):
 
 
 # ---- the host build ----------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def host_exe(tmp_path_factory):
-    return build_host_driver(tmp_path_factory.mktemp('accn'), 'accum_normals_host_driver')
-
-
+host_exe = ah.host_driver_fixture('accum_normals_host_driver', 'accn')
 _host_cache = {}
 
 
@@ -144,22 +105,12 @@ def _host(exe, tmp_path, name, radius, min_neighbors=5, min_count=1, max_moving_
     m = keys.shape[0]
     vp = np.zeros((0, 3)) if viewpoints is None else np.ascontiguousarray(viewpoints, np.float64).reshape(-1, 3)
     tag = '%s_r%d_%d' % (name, radius, len(_host_cache))
-    path, out = str(tmp_path / (tag + '.bin')), str(tmp_path / (tag + '.out'))
-    with open(path, 'wb') as f:
-        f.write(np.array([m, max(m + spare, 1), min_count, 0 if max_moving_fraction is None else 1, radius, min_neighbors, vp.shape[0], stamp_base],
-                         np.int64).tobytes())
-        f.write(np.array([0.0 if max_moving_fraction is None else max_moving_fraction], np.float64).tobytes())
-        f.write(np.ascontiguousarray(keys, np.int64).tobytes() + np.ascontiguousarray(acc, np.int64).tobytes() + np.ascontiguousarray(stamps, np.int32).tobytes())
-        f.write(vp.tobytes())
-    subprocess.check_call([exe, path, out])
-    raw = open(out, 'rb').read()
+    head = [m, max(m + spare, 1), min_count, 0 if max_moving_fraction is None else 1, radius, min_neighbors, vp.shape[0], stamp_base]
+    raw = ah.run_driver(exe, tmp_path, tag, np.array(head, np.int64), np.array([0.0 if max_moving_fraction is None else max_moving_fraction], np.float64),
+                        ah.map_bytes(keys, acc, stamps), vp, suffix='.bin')
     v = int(np.frombuffer(raw, np.int64, 1)[0])
-    off, res = 8, {}
-    for k, dt, cols in (('normals', np.float64, 3), ('eigenvalues', np.float64, 3), ('neighbors', np.int32, 1), ('flags', np.uint8, 1),
-                        ('normals32', np.float32, 3), ('eigenvalues32', np.float32, 3)):
-        a = np.frombuffer(raw, dt, v * cols, off)
-        off += a.nbytes
-        res[k] = a.reshape(v, 3) if cols == 3 else a
+    res, off = ah.unpack(raw, 8, [('normals', np.float64, (v, 3)), ('eigenvalues', np.float64, (v, 3)), ('neighbors', np.int32, (v,)), ('flags', np.uint8, (v,)),
+                                  ('normals32', np.float32, (v, 3)), ('eigenvalues32', np.float32, (v, 3))])
     assert off == len(raw)
     if records is None:
         _host_cache[key] = res

@@ -7,74 +7,41 @@ around the wave size; the geometry of the walk checked on the restatement alone.
 GPU leg: the kernel against the host build, integer for integer, on every scene; order and split independence; the sidecar carried through add and
 growth, save / load, pierced() against extract(), the PLY column, a ghost trail that only the rays reveal, and the model tie-in."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import accumulate_helpers as ah
 import accumulate_pierce_reference as pref
 import accumulate_reference as ref
-from helpers import build_host_driver
+from accumulate_helpers import DEV, EDGE
+from helpers import ROOT
 from pcaccumulation_amd.config import default_config
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = 'cuda:0'
-EDGE = 1 << 20
 NAN, INF = float('nan'), float('inf')
 
 
 # ---- maps ------------------------------------------------------------------------------------------------------------------------------
-def _centres(idx, vs):
-    return ((np.asarray(idx, np.float64) + 0.5) * vs).astype(np.float32)
-
-
-def _block(lo, hi):
-    g = np.arange(lo, hi)
-    return np.stack(np.meshgrid(g, g, g, indexing='ij'), -1).reshape(-1, 3)
-
-
-def _bound_voxels():
-    """The last three voxels of every axis at both ends, which the bound scene's rays walk, and DECOYS where a key with an overflowed y or z field would
-    land had a walk stepped past the edge: (x, 2^20, z) aliases (x+1, -2^20, z), (x, y, 2^20) aliases (x, y+1, -2^20), and the mirror images."""
-    walked, decoys = [], []
-    for axis in range(3):
-        for lo in (-EDGE, EDGE - 3):
-            for a in range(3):
-                v = [1, -2]
-                v.insert(axis, lo + a)
-                walked.append(tuple(v))
-    for x, y, z in walked:
-        if y == EDGE - 1:
-            decoys.append((x + 1, -EDGE, z))
-        if y == -EDGE:
-            decoys.append((x - 1, EDGE - 1, z))
-        if z == EDGE - 1:
-            decoys.append((x, y + 1, -EDGE))
-        if z == -EDGE:
-            decoys.append((x, y - 1, EDGE - 1))
-    return walked, decoys
-
-
 def _map_adds(name):
     """-> (voxel_size, [(points, stamp)]): the adds that build a map."""
     if name == 'third':                                                          # a random third of the 40^3 block around the origin
         keep = np.random.RandomState(5).uniform(0, 1, 64000) < 1.0 / 3.0
-        return 0.1, [(_centres(_block(-20, 20)[keep], 0.1), 0)]
+        return 0.1, [(ah.centres(ah.block(-20, 20)[keep], 0.1), 0)]
     if name == 'block9':
-        return 0.25, [(_centres(_block(-4, 5), 0.25), 0)]
+        return 0.25, [(ah.centres(ah.block(-4, 5), 0.25), 0)]
     if name == 'slab':                                                           # x -3..12, y and z -2..2
         idx = np.array([(x, y, z) for x in range(-3, 13) for y in range(-2, 3) for z in range(-2, 3)])
-        return 0.1, [(_centres(idx, 0.1), 0)]
+        return 0.1, [(ah.centres(idx, 0.1), 0)]
     if name == 'bound':
-        walked, decoys = _bound_voxels()
-        return 0.01, [(_centres(walked + decoys, 0.01), 0)]
+        walked, decoys = ah.walked_voxels()
+        return 0.01, [(ah.centres(walked + decoys, 0.01), 0)]
     if name == 'empty':
         return 0.1, []
     assert name == 'stamped'                                                     # voxel (k, 0, 0) was filled from stamp 3 to stamp 3 + k
     adds = []
     for k in range(4):
-        adds.append((_centres([(j, 0, 0) for j in range(k, 4)], 0.1), 3 + k))
+        adds.append((ah.centres([(j, 0, 0) for j in range(k, 4)], 0.1), 3 + k))
     return 0.1, adds
 
 
@@ -93,25 +60,6 @@ def _ref_map(name):
 
 
 # ---- cases: a map and the arguments of ONE see_through call ----------------------------------------------------------------------------------
-def _random_rays():
-    """400 rays: origins within +-0.3 m (row 0 float32-representable, so that a component of d can be exactly zero), end points within +-2 m."""
-    rs = np.random.RandomState(11)
-    origins = rs.uniform(-0.3, 0.3, (3, 3))
-    origins[0] = origins[0].astype(np.float32)
-    index = rs.randint(0, 3, 400).astype(np.int32)
-    pts = rs.uniform(-2, 2, (400, 3)).astype(np.float32)
-    o0 = origins[0].astype(np.float32)
-    index[:24] = 0
-    pts[0:6, 0] = o0[0]                                                          # d_x == 0 exactly
-    pts[6:10, 1] = o0[1]                                                         # d_y == 0
-    pts[10:14, 2] = o0[2]                                                        # d_z == 0
-    for j, (axis, sign) in enumerate([(0, 1), (0, -1), (1, 1), (1, -1), (2, 1), (2, -1)]):    # along one axis: two zero components
-        pts[14 + j] = o0
-        pts[14 + j, axis] += np.float32(sign * (1.1 + 0.1 * j))
-    pts[20:22, 0], pts[20:22, 1] = o0[0], o0[1]
-    return pts, origins, index
-
-
 def _rot_z(angle, t):
     T = np.eye(4)
     T[0, 0] = T[1, 1] = np.cos(angle)
@@ -122,7 +70,7 @@ def _rot_z(angle, t):
 
 def _cases():
     c = {}
-    pts, origins, index = _random_rays()
+    pts, origins, index = ah.random_rays()
     c['random'] = dict(map='third', points=pts, origins=origins, origin_index=index, margin=0.2)
     # exact ties: every t_a equal at every step; a face start with a negative direction (t = -0.0 steps at once)
     c['ties'] = dict(map='block9', points=np.array([[1, 1, 1]], np.float32), origins=np.zeros((1, 3)), margin=0.0)
@@ -154,7 +102,7 @@ def _cases():
     c['n0'] = dict(map='slab', points=np.zeros((0, 3), np.float32), origins=o)
     c['m0'] = dict(map='empty', points=good, origins=o)
     # the index bound at 0.01 m: every ray ends in the LAST voxel of an axis, margin 0, pointing outwards; two more end outside and are dropped
-    walked, _ = _bound_voxels()
+    walked, _ = ah.walked_voxels()
     ends, starts = [], []
     for axis in range(3):
         for lo, last in ((-EDGE, -EDGE), (EDGE - 3, EDGE - 1)):
@@ -163,9 +111,9 @@ def _cases():
             e.insert(axis, last)
             starts.append(s)
             ends.append(e)
-    ends = _centres(ends, 0.01)
+    ends = ah.centres(ends, 0.01)
     outside = np.array([[10485.77, 0.015, -0.015], [0.015, 0.015, -10485.78]], np.float32)
-    c['bound'] = dict(map='bound', points=np.concatenate([ends, outside]), origins=_centres(starts, 0.01).astype(np.float64),
+    c['bound'] = dict(map='bound', points=np.concatenate([ends, outside]), origins=ah.centres(starts, 0.01).astype(np.float64),
                       origin_index=np.array([0, 1, 2, 3, 4, 5, 0, 5], np.int32), margin=0.0)
     # the stamp rule: one ray through voxels (0..3, 0, 0) whose (t_first, t_last) are (3, 3), (3, 4), (3, 5), (3, 6)
     through = dict(map='stamped', points=np.array([[0.55, 0.05, 0.05]], np.float32), origins=np.array([[-0.15, 0.05, 0.05]]), margin=0.0)
@@ -196,11 +144,7 @@ def _in_key_order(name, pierced):
 
 
 # ---- the host build ----------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def host_exe(tmp_path_factory):
-    return build_host_driver(tmp_path_factory.mktemp('accp'), 'accum_pierce_host_driver')
-
-
+host_exe = ah.host_driver_fixture('accum_pierce_host_driver', 'accp')
 _host_cache = {}
 
 
@@ -216,17 +160,12 @@ def _host(exe, tmp_path, case, tag, spare=3):
     org = np.ascontiguousarray(case['origins'], np.float64).reshape(-1, 3)
     mv, idx, pose, stamp = case.get('moving'), case.get('origin_index'), case.get('pose'), case.get('stamp')
     margin = case['margin'] if case.get('margin') is not None else 2.0 * r.voxel_size
-    path, out = str(tmp_path / (tag + '.bin')), str(tmp_path / (tag + '.out'))
-    with open(path, 'wb') as f:
-        f.write(np.array([n, org.shape[0], m, m + spare, stamp is not None, stamp or 0, case.get('max_steps', 4096), mv is not None, idx is not None,
-                          pose is not None], np.int64).tobytes())
-        f.write(np.array([r.voxel_size, margin, -1.0 if case.get('max_range') is None else case['max_range']], np.float64).tobytes())
-        f.write(pts.tobytes() + (np.zeros(n, np.uint8) if mv is None else np.asarray(mv).astype(np.uint8)).tobytes() + org.tobytes())
-        f.write((np.zeros(n, np.int32) if idx is None else np.asarray(idx, np.int32)).tobytes())
-        f.write((np.eye(4) if pose is None else np.ascontiguousarray(pose, np.float64)).tobytes())
-        f.write(np.ascontiguousarray(keys, np.int64).tobytes() + np.ascontiguousarray(stamps, np.int32).tobytes())
-    subprocess.check_call([exe, path, out])
-    raw = open(out, 'rb').read()
+    head = [n, org.shape[0], m, m + spare, stamp is not None, stamp or 0, case.get('max_steps', 4096), mv is not None, idx is not None, pose is not None]
+    raw = ah.run_driver(exe, tmp_path, tag, np.array(head, np.int64),
+                        np.array([r.voxel_size, margin, -1.0 if case.get('max_range') is None else case['max_range']], np.float64),
+                        pts, np.zeros(n, np.uint8) if mv is None else np.asarray(mv).astype(np.uint8), org,
+                        np.zeros(n, np.int32) if idx is None else np.asarray(idx, np.int32), np.eye(4) if pose is None else np.ascontiguousarray(pose, np.float64),
+                        ah.map_bytes(keys, stamps=stamps), suffix='.bin')
     assert len(raw) == 4 * m + 48
     res = (np.frombuffer(raw, np.int32, m), np.frombuffer(raw, np.int64, 5, 4 * m), int(np.frombuffer(raw, np.int64, 1, 4 * m + 40)[0]))
     _host_cache[tag] = res
@@ -242,7 +181,7 @@ def test_maps_hold_the_intended_voxels():
         for pts, _ in adds:
             want |= set(map(tuple, np.floor(pts.astype(np.float64) / vs).astype(np.int64).tolist()))
         assert set(_ref_map(name)[1]) == want and _ref_map(name)[0].dropped == 0
-    walked, decoys = _bound_voxels()
+    walked, decoys = ah.walked_voxels()
     assert set(_ref_map('bound')[1]) == set(walked) | set(decoys) and len(decoys) == 4 and not set(walked) & set(decoys)
     assert 20000 < len(_ref_map('third')[1]) < 22500
     assert sorted(_ref_map('stamped')[1].items()) == [((k, 0, 0), (3, 3 + k)) for k in range(4)]
@@ -261,7 +200,7 @@ def test_host_build_equals_the_restatement(host_exe, tmp_path, name):
 
 
 def test_random_scene_has_the_special_rays():
-    pts, origins, index = _random_rays()
+    pts, origins, index = ah.random_rays()
     d = pts[:24].astype(np.float64) - origins[0]
     assert np.all(d[0:6, 0] == 0) and np.all(d[6:10, 1] == 0) and np.all(d[10:14, 2] == 0)
     assert np.all((d[14:22] == 0).sum(1) == 2)
@@ -304,7 +243,7 @@ def test_degenerate_rays_in_the_restatement():
 
 def test_index_bound_and_decoys():
     """Rays that end in the last voxel of an axis walk its last three voxels and stop; a ray that ends outside is dropped; no decoy is touched."""
-    walked, decoys = _bound_voxels()
+    walked, decoys = ah.walked_voxels()
     pierced, counters = _restate(CASES['bound'])
     assert counters == [6, 2, 0, 0, 18]
     assert pierced == {v: 1 for v in walked}
@@ -339,7 +278,7 @@ def test_walk_geometry_on_the_restatement():
     shrunk by 1e-9 m holds a chord longer than 1e-9 m is visited; every visited voxel's box grown by 1e-9 m is hit; visited voxels that meet only the
     second condition are 'in the band', at most 0.1 % of the must-visit pairs."""
     eps = 1e-9
-    idx = _block(-20, 20)
+    idx = ah.block(-20, 20)
     lo, hi = idx * 0.1, (idx + 1) * 0.1
     row_of = {tuple(c): j for j, c in enumerate(idx.tolist())}
     walks = []
@@ -479,11 +418,11 @@ def test_add_carries_the_sidecar_gpu(tmp_path):
     the sidecar equals the restatement's dict, keyed by coordinates.  save / load mid-scene round-trips the sidecar and the counters."""
     from pcaccumulation_amd.accumulate import AccumulatedCloud
     vs = 0.1
-    first = _centres([(x, 0, 0) for x in range(0, 12, 2)] + [(x, 1, 0) for x in range(0, 12, 2)], vs)
-    window = _centres([(-3, 0, 0), (-2, 5, 1)] + [(x, 0, 0) for x in range(1, 12, 2)] + [(20, 0, 0), (5, 0, 0), (14, -1, 2)], vs)
-    big = _centres(_block(-7, 7)[::1], vs)[:2500]
+    first = ah.centres([(x, 0, 0) for x in range(0, 12, 2)] + [(x, 1, 0) for x in range(0, 12, 2)], vs)
+    window = ah.centres([(-3, 0, 0), (-2, 5, 1)] + [(x, 0, 0) for x in range(1, 12, 2)] + [(20, 0, 0), (5, 0, 0), (14, -1, 2)], vs)
+    big = ah.centres(ah.block(-7, 7)[::1], vs)[:2500]
     origins = np.array([[-0.55, 0.05, 0.05], [-0.55, 0.12, 0.03]])
-    rays = dict(points=_centres([(13, 0, 0), (13, 1, 0), (25, 0, 0), (10, 1, 0), (-1, 6, 1)], vs), origins=origins, origin_index=np.array([0, 1, 0, 1, 0], np.int32),
+    rays = dict(points=ah.centres([(13, 0, 0), (13, 1, 0), (25, 0, 0), (10, 1, 0), (-1, 6, 1)], vs), origins=origins, origin_index=np.array([0, 1, 0, 1, 0], np.int32),
                 margin=0.0)
     m, r = AccumulatedCloud(vs, DEV, 64), ref.ReferenceMap(vs)
     pierced, counters = {}, [0] * 5
@@ -583,35 +522,13 @@ def test_pierced_aligns_with_extract_and_save_ply_gpu(tmp_path):
 
 
 # ---- the capability: a ghost trail that only the rays reveal -------------------------------------------------------------------------------
-GHOST_SENSOR = np.array([[0.03, 0.02, 0.01]])
-
-
-def _ghost_scans():
-    """Six scans from a fixed sensor: a wall one voxel layer thick at x = 3.05 (end points mid-layer) and a 3 x 3 x 3 cluster of voxel centres, never
-    flagged moving, at a different y in front of the wall at each stamp.  Wall returns whose ray would have crossed the cluster of their own stamp are
-    left out (the cluster shadows them).  -> [(wall points, cluster points, cluster voxels)]."""
-    vs = 0.1
-    wall = _centres([(30, y, z) for y in range(-20, 20) for z in range(-10, 10)], vs)
-    scans = []
-    for k in range(6):
-        y0 = -8 + 3 * k
-        vox = [(15 + a, y0 + b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1)]
-        s = GHOST_SENSOR[0]
-        t = (1.55 - s[0]) / (wall[:, 0].astype(np.float64) - s[0])                # where the wall ray passes the cluster's depth
-        y = s[1] + t * (wall[:, 1] - s[1])
-        z = s[2] + t * (wall[:, 2] - s[2])
-        shadow = (np.abs(y - (y0 + 0.5) * vs) < 0.3) & (np.abs(z - 0.05) < 0.3)
-        scans.append((wall[~shadow], _centres(vox, vs), vox))
-    return scans
-
-
 def _ghost_restatement():
     vs = 0.1
     r = ref.ReferenceMap(vs)
     pierced, counters = {}, [0] * 5
-    for k, (wall, cluster, _) in enumerate(_ghost_scans()):
+    for k, (wall, cluster, _) in enumerate(ah.ghost_scans()):
         pts = np.concatenate([wall, cluster])
-        pref.pierce(pref.voxels_of(r), pts, GHOST_SENSOR, voxel_size=vs, stamp=k, pierced=pierced, counters=counters)
+        pref.pierce(pref.voxels_of(r), pts, ah.GHOST_SENSOR, voxel_size=vs, stamp=k, pierced=pierced, counters=counters)
         r.add(pts, stamp=k)
     return r, pierced, counters
 
@@ -621,7 +538,7 @@ def test_ghost_scene_in_the_restatement():
     cluster voxel of stamps 0-4 that a later wall ray geometrically crosses (slab test, a chord of more than 1e-9 m inside the box shrunk by 1e-9 m,
     the ray cut at its t_end) has a count of at least 1."""
     vs, eps = 0.1, 1e-9
-    scans = _ghost_scans()
+    scans = ah.ghost_scans()
     r, pierced, counters = _ghost_restatement()
     assert counters[1] == counters[2] == counters[3] == 0
     wall_vox = {(30, y, z) for y in range(-20, 20) for z in range(-10, 10)}
@@ -633,9 +550,9 @@ def test_ghost_scene_in_the_restatement():
         crossed = np.zeros(len(vox), bool)
         for k in range(j + 1, 6):
             for p in scans[k][0].astype(np.float64):
-                d = p - GHOST_SENSOR[0]
+                d = p - ah.GHOST_SENSOR[0]
                 L = float(np.sqrt((d * d).sum()))
-                crossed |= _slab(GHOST_SENSOR[0], d, lo, hi, 1.0 - 0.2 / L) * L > eps
+                crossed |= _slab(ah.GHOST_SENSOR[0], d, lo, hi, 1.0 - 0.2 / L) * L > eps
         assert crossed.sum() >= 9, (j, crossed.sum())
         assert all(pierced.get(tuple(v), 0) >= 1 for v in vox[crossed].tolist()), j
         crossed_total += int(crossed.sum())
@@ -649,9 +566,9 @@ def test_ghost_scene_gpu():
     from pcaccumulation_amd.accumulate import AccumulatedCloud
     r, pierced, counters = _ghost_restatement()
     m = AccumulatedCloud(0.1, DEV, 64)
-    for k, (wall, cluster, _) in enumerate(_ghost_scans()):
+    for k, (wall, cluster, _) in enumerate(ah.ghost_scans()):
         pts = torch.from_numpy(np.concatenate([wall, cluster])).to(DEV)
-        got = m.see_through(pts, GHOST_SENSOR, stamp=k)
+        got = m.see_through(pts, ah.GHOST_SENSOR, stamp=k)
         m.add(pts, stamp=k)
     assert got.tolist() == counters
     _check_sidecar(m, pierced, counters, 'ghost')

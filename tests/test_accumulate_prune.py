@@ -5,62 +5,23 @@ Every result is an integer or a copied record, so every claim is an equality:
         plain-Python restatement on a coordinate dict (tests/accumulate_prune_reference.py): counters, surviving keys, records, stamps, ray counts;
   GPU   the kernels against the g++ build on the same scenes, then identities that tie prune to extract / normals / register / pierced, a life
         cycle against the restatement, the ghost scene of section 9f and a sliding box."""
-import io
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import accumulate_helpers as ah
 import accumulate_pierce_reference as pref
 import accumulate_prune_reference as rref
 import accumulate_reference as ref
-from helpers import build_host_driver
+from accumulate_helpers import DEV, EDGE, I32_MAX, I32_MIN
+from helpers import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = 'cuda:0'
-EDGE = 1 << 20
-I32_MIN, I32_MAX = -(1 << 31), (1 << 31) - 1
 WHOLE_GRID = ((-EDGE,) * 3, (EDGE - 1,) * 3)
 
 
 # ---- scenes: a ReferenceMap and a {coord: rays} dict (None: no sidecar), built once and never modified ----------------------------------------
-def _centres(idx, vs):
-    return ((np.asarray(idx, np.float64).reshape(-1, 3) + 0.5) * vs).astype(np.float32)
-
-
-def _records(vs, rows):
-    """rows: {coord: (count, moving, t_first, t_last)} -> a ReferenceMap whose coordinate sums put every centroid in the middle of its voxel."""
-    r = ref.ReferenceMap(vs)
-    for c, (count, moving, t_first, t_last) in rows.items():
-        q = [int(np.rint((v + 0.5) * vs * 65536.0)) for v in c]
-        r.rec[rref.key_of(c)] = [count, moving, count * q[0], count * q[1], count * q[2], t_first, t_last]
-    return r
-
-
-def _points_map(vs, adds):
-    r = ref.ReferenceMap(vs)
-    for pts, mv, stamp in adds:
-        r.add(pts, None, mv, stamp)
-    return r
-
-
-def _random_rows(m, seed):
-    """m voxels of the 7^3 block around the origin with random records, stamps 0..15 and ray counts 0..4."""
-    rs = np.random.RandomState(seed)
-    cells = [(x, y, z) for x in range(-3, 4) for y in range(-3, 4) for z in range(-3, 4)]
-    rows, pierced = {}, {}
-    for i in rs.permutation(len(cells))[:m]:
-        count = int(rs.randint(1, 7))
-        t_first = int(rs.randint(0, 11))
-        rows[cells[i]] = (count, int(rs.randint(0, count + 1)), t_first, t_first + int(rs.randint(0, 6)))
-        p = int(rs.randint(0, 5))
-        if p:
-            pierced[cells[i]] = p
-    return rows, pierced
-
-
 # (voxel, points, moving) of tests/test_accumulate.py's ratio test: 1 of 4 sits exactly on 0.25; 1 of 3 and 2 of 4 above; 0 of 2 and 0 of 1 below; 4 of 4
 RATIO_SPEC = [((2, 0, 0), 4, 1), ((-1, 3, 0), 3, 1), ((0, 0, 5), 4, 2), ((0, -2, 1), 2, 0), ((-7, 0, 0), 1, 0), ((2, 0, -1), 4, 4), ((0, 0, -5), 8, 2)]
 RATIO_FILTERS = ((dict(min_count=1), 7), (dict(min_count=4), 4), (dict(min_count=5), 1), (dict(min_count=9), 0), (dict(max_moving_fraction=0.25), 4),
@@ -77,86 +38,45 @@ ORDER_ROWS = {(0, 0, 0): ((1, 0, 0, 9), 0, 'kept'), (1, 0, 0): ((1, 1, 0, 2), 9,
 ORDER_ARGS = dict(max_moving_fraction=0.5, before_stamp=5, box=((0, -1, -1), (9, 1, 1)), min_pierced=3)
 
 
-def _bound_voxels():
-    """3 x 3 columns through the last three voxels of every axis at both ends, and DECOYS where a key with an overflowed y or z field would land had
-    an offset stepped past the edge: (x, 2^20, z) aliases (x+1, -2^20, z), (x, y, 2^20) aliases (x, y+1, -2^20), and the mirror images."""
-    vox = []
-    for axis in range(3):
-        for lo in (-EDGE, EDGE - 3):
-            for a in range(3):
-                for b in (-1, 0, 1):
-                    for c in (-1, 0, 1):
-                        v = [b, c]
-                        v.insert(axis, lo + a)
-                        vox.append(tuple(v))
-    decoys = []
-    for x, y, z in vox:
-        if y == EDGE - 1:
-            decoys.append((x + 1, -EDGE, z))
-        if y == -EDGE:
-            decoys.append((x - 1, EDGE - 1, z))
-        if z == EDGE - 1:
-            decoys.append((x, y + 1, -EDGE))
-        if z == -EDGE:
-            decoys.append((x, y - 1, EDGE - 1))
-    return vox, [d for d in decoys if all(-EDGE <= c < EDGE for c in d)]
-
-
-def _noisy_plane():
-    """A 3 m x 3 m sheet with 1 cm noise and forty single points scattered above it."""
-    rs = np.random.RandomState(21)
-    sheet = np.concatenate([rs.uniform(-1.5, 1.5, (6000, 2)), rs.normal(0.02, 0.01, (6000, 1))], 1)
-    stray = np.concatenate([rs.uniform(-1.5, 1.5, (40, 2)), rs.uniform(0.4, 2.0, (40, 1))], 1)
-    return np.concatenate([sheet, stray]).astype(np.float32)
-
-
-def _wavy():
-    """26 m x 26 m at 0.1 m, four points in every column, and one far voxel: 76 661 voxels, more than one workgroup, m mod 64 != 0."""
-    g = np.arange(520) * 0.05 + 0.025 - 13.0
-    x, y = np.meshgrid(g, g, indexing='ij')
-    z = 0.4 * np.sin(0.9 * x) * np.cos(0.7 * y) + 0.013
-    return np.concatenate([np.stack([x, y, z], -1).reshape(-1, 3), [[40.0, 40.0, 40.0]]]).astype(np.float32)
-
-
 ROW_COUNTS = (0, 1, 63, 64, 65, 257)
 _scenes = {}
 
 
 def _build_scene(name):
     if name == 'rows_no_sidecar':
-        return _records(0.1, _random_rows(65, 7)[0]), None
+        return ah.records(0.1, ah.random_rows(65, 7)[0]), None
     if name.startswith('rows'):
-        rows, pierced = _random_rows(int(name[4:]), 100 + int(name[4:]))
-        return _records(0.1, rows), pierced
+        rows, pierced = ah.random_rows(int(name[4:]), 100 + int(name[4:]))
+        return ah.records(0.1, rows), pierced
     if name == 'ratio':
-        return _records(1.0, {v: (k, j, 0, 0) for v, k, j in RATIO_SPEC}), None
+        return ah.records(1.0, {v: (k, j, 0, 0) for v, k, j in RATIO_SPEC}), None
     if name == 'order':
-        return _records(0.1, {c: v[0] for c, v in ORDER_ROWS.items()}), {c: v[1] for c, v in ORDER_ROWS.items() if v[1]}
+        return ah.records(0.1, {c: v[0] for c, v in ORDER_ROWS.items()}), {c: v[1] for c, v in ORDER_ROWS.items() if v[1]}
     if name == 'stamps':                                                         # t_last = 4, 5, 6 and the ends of int32
-        return _records(0.1, {(k, 0, 0): (1, 0, t, t) for k, t in enumerate((4, 5, 6, I32_MIN, I32_MIN + 1, I32_MAX - 1, I32_MAX))}), None
+        return ah.records(0.1, {(k, 0, 0): (1, 0, t, t) for k, t in enumerate((4, 5, 6, I32_MIN, I32_MIN + 1, I32_MAX - 1, I32_MAX))}), None
     if name == 'rays':                                                           # (count, rays): p / count against 0.5 and 1/3, p against min_pierced 2
         spec = [(4, 2), (4, 3), (3, 1), (6, 2), (6, 3), (1000, 2), (2, 1), (2, 2), (1, 5)]
-        return (_records(0.1, {(k, 2, -1): (c, 0, 0, 0) for k, (c, _) in enumerate(spec)}), {(k, 2, -1): p for k, (_, p) in enumerate(spec)})
+        return (ah.records(0.1, {(k, 2, -1): (c, 0, 0, 0) for k, (c, _) in enumerate(spec)}), {(k, 2, -1): p for k, (_, p) in enumerate(spec)})
     if name == 'block7':                                                         # the full 7^3 block: every face of a box
-        return _records(0.1, {(x, y, z): (1, 0, 0, 0) for x in range(-3, 4) for y in range(-3, 4) for z in range(-3, 4)}), None
+        return ah.records(0.1, {(x, y, z): (1, 0, 0, 0) for x in range(-3, 4) for y in range(-3, 4) for z in range(-3, 4)}), None
     if name == 'bound':
-        vox, decoys = _bound_voxels()
-        return _points_map(0.01, [(_centres(vox + decoys, 0.01), None, 0)]), None
+        vox, decoys = ah.bound_voxels()
+        return ah.points_map(0.01, [(ah.centres(vox + decoys, 0.01), None, 0)]), None
     if name == 'plane':
-        return _points_map(0.1, [(_noisy_plane(), None, 0)]), None
+        return ah.points_map(0.1, [(ah.noisy_plane(), None, 0)]), None
     if name == 'block27':
-        return _records(0.1, {(x, y, z): (1, 0, 0, 0) for x in range(3) for y in range(3) for z in range(3)}), None
+        return ah.records(0.1, {(x, y, z): (1, 0, 0, 0) for x in range(3) for y in range(3) for z in range(3)}), None
     if name == 'row9':
-        return _records(0.1, {(k, 4, -2): (1, 0, 0, 0) for k in range(-4, 5)}), None
+        return ah.records(0.1, {(k, 4, -2): (1, 0, 0, 0) for k in range(-4, 5)}), None
     if name == 'single':
-        return _records(0.1, {(4, -12, 0): (1, 0, 0, 0)}), None
+        return ah.records(0.1, {(4, -12, 0): (1, 0, 0, 0)}), None
     if name == 'saved':
         # X has one neighbour, Y, which stage A removes (count 1): X is isolated although Y "would have saved" it.  P Q R in a row: Q keeps its 3
         # neighbours of stage A although P and R leave in stage B.
         rows = {(0, 0, 0): (5, 0, 0, 0), (1, 0, 0): (1, 0, 0, 0), (10, 0, 0): (5, 0, 0, 0), (11, 0, 0): (5, 0, 0, 0), (12, 0, 0): (5, 0, 0, 0)}
-        return _records(0.1, rows), None
+        return ah.records(0.1, rows), None
     assert name == 'wavy'
-    return _points_map(0.1, [(_wavy(), None, 0)]), None
+    return ah.points_map(0.1, [(ah.wavy(), None, 0)]), None
 
 
 def _scene(name):
@@ -214,10 +134,6 @@ def _copy(r, pierced):
     return c, (None if pierced is None else dict(pierced))
 
 
-def _aligned(pierced, keys):
-    return np.array([pierced.get(rref.coord_of(int(k)), 0) for k in keys.tolist()], np.int32)
-
-
 _restated = {}
 
 
@@ -230,47 +146,30 @@ def _restate(name):
         counters = rref.prune(r, pierced, **args)
         keys, acc, stamps = r.records()
         _restated[name] = dict(counters=counters, keys=keys, acc=acc.reshape(5, -1), stamps=stamps.reshape(2, -1),
-                               pierced=None if pierced is None else _aligned(pierced, keys), k=k)
+                               pierced=None if pierced is None else ah.aligned(pierced, keys), k=k)
     return _restated[name]
 
 
 # ---- the host build -------------------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def host_exe(tmp_path_factory):
-    return build_host_driver(tmp_path_factory.mktemp('prune_host'), 'accum_prune_host_driver')
+host_exe = ah.host_driver_fixture('accum_prune_host_driver', 'prune_host')
 
 
 def _run_host(exe, tmp_path, tag, records, pierced, spare_in=3, spare_out=5, min_count=1, max_moving_fraction=None, before_stamp=None, box=None, min_pierced=0,
               ratio=None, min_neighbors=0, radius=1):
-    keys, acc, stamps = records
-    m = keys.shape[0]
+    m = records[0].shape[0]
     lo, hi = ((0, 0, 0), (0, 0, 0)) if box is None else box
     head = [m, m + spare_in, m + spare_out, 0 if pierced is None else 1, min_count, 0 if max_moving_fraction is None else 1,
             0 if before_stamp is None else 1, 0 if before_stamp is None else before_stamp, 0 if box is None else 1] + list(lo) + list(hi) + [
             min_pierced, 0 if ratio is None else 1, min_neighbors, radius]
-    src, dst = os.path.join(str(tmp_path), tag + '.in'), os.path.join(str(tmp_path), tag + '.out')
-    with open(src, 'wb') as f:
-        f.write(np.array(head, np.int64).tobytes())
-        f.write(np.array([0.0 if max_moving_fraction is None else max_moving_fraction, 0.0 if ratio is None else ratio], np.float64).tobytes())
-        f.write(np.ascontiguousarray(keys, np.int64).tobytes())
-        f.write(np.ascontiguousarray(acc, np.int64).tobytes())
-        f.write(np.ascontiguousarray(stamps, np.int32).tobytes())
-        if pierced is not None:
-            f.write(np.ascontiguousarray(pierced, np.int32).tobytes())
-    subprocess.check_call([exe, src, dst])
-    raw = open(dst, 'rb').read()
-    counters = np.frombuffer(raw, np.int64, 6)
-    kept, off = int(counters[0]), 48
-    out = dict(counters=counters.tolist())
-    for name, dtype, shape in (('keys', np.int64, (kept,)), ('acc', np.int64, (5, kept)), ('stamps', np.int32, (2, kept)),
-                               ('pierced', np.int32, (kept if pierced is not None else 0,)), ('k', np.int32, (m,)), ('reason', np.uint8, (m,))):
-        n = int(np.prod(shape))
-        out[name] = np.frombuffer(raw, dtype, n, off).reshape(shape).copy()
-        off += n * np.dtype(dtype).itemsize
+    raw = ah.run_driver(exe, tmp_path, tag, np.array(head, np.int64),
+                        np.array([0.0 if max_moving_fraction is None else max_moving_fraction, 0.0 if ratio is None else ratio], np.float64),
+                        ah.map_bytes(*records, pierced))
+    counters = np.frombuffer(raw, np.int64, 6).tolist()
+    out, off = ah.unpack(raw, 48, ah.map_layout(counters[0], pierced is not None) + [('k', np.int32, (m,)), ('reason', np.uint8, (m,))])
     assert off == len(raw)
     if pierced is None:
         out['pierced'] = None
-    return out
+    return dict(out, counters=counters)
 
 
 _hosted = {}
@@ -281,7 +180,7 @@ def _host(exe, tmp_path, name):
         scene, args = CASES[name]
         r, pierced = _scene(scene)
         keys = r.records()[0]
-        _hosted[name] = _run_host(exe, tmp_path, name, r.records(), None if pierced is None else _aligned(pierced, keys), **args)
+        _hosted[name] = _run_host(exe, tmp_path, name, r.records(), None if pierced is None else ah.aligned(pierced, keys), **args)
     return _hosted[name]
 
 
@@ -298,7 +197,7 @@ def _assert_same(got, want, what, pierced=True):
 def test_scenes_hold_what_they_are_for():
     assert [_scene('rows%d' % m)[0].num_voxels for m in ROW_COUNTS] == list(ROW_COUNTS)
     assert _scene('wavy')[0].num_voxels == 76661 and 76661 % 64 != 0
-    vox, decoys = _bound_voxels()
+    vox, decoys = ah.bound_voxels()
     assert _scene('bound')[0].num_voxels == len(set(vox + decoys)) and len(decoys) >= 36
     plane = _scene('plane')[0]
     assert plane.num_voxels > 900
@@ -388,7 +287,7 @@ def test_stage_b_on_the_restatement():
     chain = _restate('saved_chain')
     assert chain['counters'] == [1, 1, 0, 0, 0, 3] and chain['k'][(11, 0, 0)] == 3 and [rref.coord_of(int(k)) for k in chain['keys']] == [(11, 0, 0)]
     # index bound: no voxel of a 3 x 3 column at an edge counts a decoy, at any radius
-    vox, decoys = _bound_voxels()
+    vox, decoys = ah.bound_voxels()
     for r in (1, 2, 3):
         k = _restate('bound_r%d' % r)['k']
         for c in vox:
@@ -426,16 +325,8 @@ def test_header_binding_and_argument_checks():
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------------------------------------
 def _device_cloud(r, pierced):
-    """The restatement's map and ray counts as an AccumulatedCloud on the device, through load()."""
-    from pcaccumulation_amd.accumulate import AccumulatedCloud
-    keys, acc, stamps = r.records()
-    extra = {}
-    if pierced is not None:
-        extra = dict(pierced=_aligned(pierced, keys), pierce_counters=np.zeros(5, np.int64))
-    buf = io.BytesIO()
-    np.savez(buf, keys=keys, acc=acc.reshape(5, -1), stamps=stamps.reshape(2, -1), voxel_size=np.float64(r.voxel_size), dropped=np.int64(r.dropped), **extra)
-    buf.seek(0)
-    return AccumulatedCloud.load(buf, DEV)
+    """The restatement's map and {coord: rays} dict as an AccumulatedCloud on the device."""
+    return ah.device_cloud(r, None if pierced is None else ah.aligned(pierced, r.records()[0]), np.zeros(5, np.int64))
 
 
 def _metres(box, vs):
@@ -448,19 +339,6 @@ def _prune(m, args, dry_run=False):
     return m.prune(min_pierced=a.get('min_pierced') or None, pierced_ratio=a.get('ratio'), before_stamp=a.get('before_stamp'),
                    min_count=a.get('min_count', 1), max_moving_fraction=a.get('max_moving_fraction'), box=_metres(a.get('box'), m.voxel_size),
                    min_neighbors=a.get('min_neighbors') or None, radius=a.get('radius', 1), dry_run=dry_run)
-
-
-def _snapshot(m):
-    n = m.num_voxels
-    keys, acc, stamps = m._cur
-    return (n, keys[:n].clone(), acc[:, :n].clone(), stamps[:, :n].clone(), None if m._pierced is None else m._pierced[:n].clone(), m._state.clone())
-
-
-def _assert_unchanged(m, snap, what):
-    now = _snapshot(m)
-    assert now[0] == snap[0], what
-    for a, b in zip(now[1:], snap[1:]):
-        assert (a is None and b is None) or torch.equal(a, b), what
 
 
 def _assert_device_equals_host(m, res, host, what):
@@ -482,17 +360,17 @@ def test_kernel_equals_the_host_build_gpu(host_exe, tmp_path, name):
     scene, args = CASES[name]
     host = _host(host_exe, tmp_path, name)
     m = _device_cloud(*_scene(scene))
-    before, state = _snapshot(m), m._state.tolist()
+    before, state = ah.snapshot(m), m._state.tolist()
     dry = _prune(m, args, dry_run=True)
     assert [dry[f] for f in rref.NAMES] == host['counters'], name
-    _assert_unchanged(m, before, name)                                            # dry_run: records, sidecar, num_voxels and the state words stay
+    ah.assert_unchanged(m, before, name)                                            # dry_run: records, sidecar, num_voxels and the state words stay
     res = _prune(m, args)
     _assert_device_equals_host(m, res, host, name)
     state[native.ACCUM_NUM_VOXELS] = host['counters'][0]
     assert m._state.tolist() == state, name                                      # the state word is set on the device, the others are left alone
     again = _device_cloud(*_scene(scene))                                         # a second run gives the same map
     assert _prune(again, args) == res
-    _assert_unchanged(again, _snapshot(m), name)
+    ah.assert_unchanged(again, ah.snapshot(m), name)
 
 
 @pytest.mark.gpu
@@ -510,40 +388,17 @@ def test_kernel_on_76661_voxels_gpu(host_exe, tmp_path, args):
 
 
 # ---- identities: prune against extract, normals, register and pierced --------------------------------------------------------------------------------------
-CORNER = np.array([0.43, -1.21, 0.27])
 FILTER = dict(min_count=2, max_moving_fraction=0.0)
 
 
-def _rot(rx, ry, rz, t):
-    T = np.eye(4)
-    for axis, a in ((0, rx), (1, ry), (2, rz)):
-        i, j = [(1, 2), (2, 0), (0, 1)][axis]
-        R = np.eye(4)
-        R[i, i], R[i, j], R[j, i], R[j, j] = np.cos(a), -np.sin(a), np.sin(a), np.cos(a)
-        T = R @ T
-    T[:3, 3] = t
-    return T
-
-
-TRUE_POSE = _rot(np.deg2rad(0.6), np.deg2rad(-0.5), np.deg2rad(0.7), (0.02, -0.015, 0.017))
-
-
-def _corner(seed, per_sheet, noise=0.01):
-    """Three mutually orthogonal noisy sheets of 2 m x 2 m that meet in CORNER (world frame, float64)."""
-    rs = np.random.RandomState(seed)
-    sheets = []
-    for axis in range(3):
-        p = rs.uniform(0.0, 2.0, (per_sheet, 3))
-        p[:, axis] = rs.normal(0, noise, per_sheet)
-        sheets.append(p + CORNER)
-    return np.concatenate(sheets)
+TRUE_POSE = ah.rot_xyz(np.deg2rad(0.6), np.deg2rad(-0.5), np.deg2rad(0.7), (0.02, -0.015, 0.017))
 
 
 def _corner_cloud():
     """The room corner with a region predicted moving, two stamps: the filter min_count=2, max_moving_fraction=0.0 removes part of it."""
     from pcaccumulation_amd.accumulate import AccumulatedCloud
-    pts = _corner(11, 9000).astype(np.float32)
-    mv = (pts[:, 0] > CORNER[0] + 1.6) & (np.random.RandomState(4).uniform(0, 1, pts.shape[0]) < 0.5)
+    pts = ah.corner(11, 9000).astype(np.float32)
+    mv = (pts[:, 0] > ah.CORNER[0] + 1.6) & (np.random.RandomState(4).uniform(0, 1, pts.shape[0]) < 0.5)
     m = AccumulatedCloud(0.1, DEV, 64)
     m.add(torch.from_numpy(pts[:15000]).to(DEV), moving=torch.from_numpy(mv[:15000]).to(DEV), stamp=3)
     m.add(torch.from_numpy(pts[15000:]).to(DEV), moving=torch.from_numpy(mv[15000:]).to(DEV), stamp=1)
@@ -552,7 +407,7 @@ def _corner_cloud():
 
 def _corner_scan():
     inv = np.linalg.inv(TRUE_POSE)
-    return torch.from_numpy((_corner(12, 1300) @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32)).to(DEV)
+    return torch.from_numpy((ah.corner(12, 1300) @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32)).to(DEV)
 
 
 def _equal_dicts(a, b):
@@ -582,28 +437,6 @@ def test_prune_then_read_equals_the_filtered_read_gpu(host_exe, tmp_path):
 
 
 # ---- the ghost scene of section 9f, rebuilt here --------------------------------------------------------------------------------------------------------------
-GHOST_SENSOR = np.array([[0.03, 0.02, 0.01]])
-
-
-def _ghost_scans():
-    """Six scans from a fixed sensor: a wall one voxel layer thick at x = 3.05 (end points mid-layer) and a 3 x 3 x 3 cluster of voxel centres, never
-    flagged moving, at a different y in front of the wall at each stamp.  Wall returns whose ray would have crossed the cluster of their own stamp are
-    left out (the cluster shadows them).  -> [(wall points, cluster points, cluster voxels)]."""
-    vs = 0.1
-    wall = _centres([(30, y, z) for y in range(-20, 20) for z in range(-10, 10)], vs)
-    scans = []
-    for k in range(6):
-        y0 = -8 + 3 * k
-        vox = [(15 + a, y0 + b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1)]
-        s = GHOST_SENSOR[0]
-        t = (1.55 - s[0]) / (wall[:, 0].astype(np.float64) - s[0])                # where the wall ray passes the cluster's depth
-        y = s[1] + t * (wall[:, 1] - s[1])
-        z = s[2] + t * (wall[:, 2] - s[2])
-        shadow = (np.abs(y - (y0 + 0.5) * vs) < 0.3) & (np.abs(z - 0.05) < 0.3)
-        scans.append((wall[~shadow], _centres(vox, vs), vox))
-    return scans
-
-
 _ghost = {}
 
 
@@ -612,9 +445,9 @@ def _ghost_restatement():
     if not _ghost:
         r = ref.ReferenceMap(0.1)
         pierced, counters = {}, [0] * 5
-        for k, (wall, cluster, _) in enumerate(_ghost_scans()):
+        for k, (wall, cluster, _) in enumerate(ah.ghost_scans()):
             pts = np.concatenate([wall, cluster])
-            pref.pierce(pref.voxels_of(r), pts, GHOST_SENSOR, voxel_size=0.1, stamp=k, pierced=pierced, counters=counters)
+            pref.pierce(pref.voxels_of(r), pts, ah.GHOST_SENSOR, voxel_size=0.1, stamp=k, pierced=pierced, counters=counters)
             r.add(pts, stamp=k)
         _ghost['r'] = (r, pierced)
     return _copy(*_ghost['r'])
@@ -623,9 +456,9 @@ def _ghost_restatement():
 def _ghost_cloud():
     from pcaccumulation_amd.accumulate import AccumulatedCloud
     m = AccumulatedCloud(0.1, DEV, 64)
-    for k, (wall, cluster, _) in enumerate(_ghost_scans()):
+    for k, (wall, cluster, _) in enumerate(ah.ghost_scans()):
         pts = torch.from_numpy(np.concatenate([wall, cluster])).to(DEV)
-        m.see_through(pts, GHOST_SENSOR, stamp=k)
+        m.see_through(pts, ah.GHOST_SENSOR, stamp=k)
         m.add(pts, stamp=k)
     return m
 
@@ -636,7 +469,7 @@ def _assert_equals_restatement(m, r, pierced, what):
     assert m.num_voxels == r.num_voxels, what
     assert np.array_equal(got[0], keys) and np.array_equal(got[1], acc.reshape(5, -1)) and np.array_equal(got[2], stamps.reshape(2, -1)), what
     if pierced is not None:
-        assert np.array_equal(m._pierced[:m.num_voxels].cpu().numpy(), _aligned(pierced, keys)), what
+        assert np.array_equal(m._pierced[:m.num_voxels].cpu().numpy(), ah.aligned(pierced, keys)), what
 
 
 @pytest.mark.gpu
@@ -656,7 +489,7 @@ def test_ghost_trail_is_removed_from_the_map_gpu():
     assert int(m.pierced().sum()) == 0
     coords = after['coords'].cpu().numpy()
     assert (coords[:, 0] == 30).sum() == 800                                     # every wall voxel survives
-    scans = _ghost_scans()
+    scans = ah.ghost_scans()
     early = {v for k in range(5) for v in scans[k][2]}
     left = {tuple(c) for c in coords.tolist()}
     assert len(early) == 135 and len(early - left) >= 100                        # section 9f's figures, now gone from the map itself
@@ -667,13 +500,13 @@ def test_ghost_trail_is_removed_from_the_map_gpu():
 
 # ---- life cycle against the restatement --------------------------------------------------------------------------------------------------------------------
 def _both_add(m, r, idx, stamp):
-    pts = _centres(idx, r.voxel_size)
+    pts = ah.centres(idx, r.voxel_size)
     m.add(torch.from_numpy(pts).to(DEV), stamp=stamp)
     r.add(pts, stamp=stamp)
 
 
 def _both_see(m, r, pierced, targets, stamp):
-    pts = _centres(targets, r.voxel_size)
+    pts = ah.centres(targets, r.voxel_size)
     m.see_through(torch.from_numpy(pts).to(DEV), np.array([[0.05, 0.05, 0.05]]), stamp=stamp)
     pref.pierce(pref.voxels_of(r), pts, np.array([[0.05, 0.05, 0.05]]), voxel_size=r.voxel_size, stamp=stamp, pierced=pierced)
 
@@ -712,11 +545,11 @@ def test_life_cycle_gpu(tmp_path):
     assert m.capacity == 64 and m.num_voxels < 64
     big = [(x, y, z) for x in range(-8, 8) for y in range(-8, 8) for z in range(40, 56)]        # 4096 new voxels: 64 -> 8192 rows
     for cloud in (m, loaded):
-        cloud.add(torch.from_numpy(_centres(big + [(6, 0, 0)], 0.1)).to(DEV), stamp=4)
+        cloud.add(torch.from_numpy(ah.centres(big + [(6, 0, 0)], 0.1)).to(DEV), stamp=4)
         assert cloud.capacity >= 4096
-        cloud.see_through(torch.from_numpy(_centres([(0, 0, 70)], 0.1)).to(DEV), np.array([[0.05, 0.05, 0.05]]), stamp=5)
-    r.add(_centres(big + [(6, 0, 0)], 0.1), stamp=4)
-    pref.pierce(pref.voxels_of(r), _centres([(0, 0, 70)], 0.1), np.array([[0.05, 0.05, 0.05]]), voxel_size=0.1, stamp=5, pierced=pierced)
+        cloud.see_through(torch.from_numpy(ah.centres([(0, 0, 70)], 0.1)).to(DEV), np.array([[0.05, 0.05, 0.05]]), stamp=5)
+    r.add(ah.centres(big + [(6, 0, 0)], 0.1), stamp=4)
+    pref.pierce(pref.voxels_of(r), ah.centres([(0, 0, 70)], 0.1), np.array([[0.05, 0.05, 0.05]]), voxel_size=0.1, stamp=5, pierced=pierced)
     want = rref.prune(r, pierced, min_pierced=1, box=rref.box_indices(((-0.45, -0.8, 0.0), (0.75, 0.8, 9.0)), 0.1))
     for cloud in (m, loaded):
         res = cloud.prune(min_pierced=1, box=((-0.45, -0.8, 0.0), (0.75, 0.8, 9.0)))
@@ -749,7 +582,7 @@ def test_bad_arguments_launch_nothing_gpu():
     from pcaccumulation_amd import native
     r, pierced = _scene('rows65')
     m = _device_cloud(r, pierced)
-    snap = _snapshot(m)
+    snap = ah.snapshot(m)
     out = tuple(torch.full_like(t, 7) for t in m._cur)
     pout = torch.full_like(m._pierced, 7)
     counters = torch.full((6,), 7, dtype=torch.int64, device=DEV)
@@ -764,14 +597,14 @@ def test_bad_arguments_launch_nothing_gpu():
         with pytest.raises(native.NativeError, match='PCACC_E_ARG'):
             native.accum_prune(**dict(good, **bad))
     torch.cuda.synchronize()
-    _assert_unchanged(m, snap, 'bad arguments')
+    ah.assert_unchanged(m, snap, 'bad arguments')
     assert all(bool((t == 7).all()) for t in out + (pout, counters))
     native.accum_prune(**dict(good, m=0))                                        # m = 0: the zero counters and nothing else
     assert counters.tolist() == [0] * 6 and all(bool((t == 7).all()) for t in out + (pout,))
-    _assert_unchanged(m, snap, 'm = 0')
+    ah.assert_unchanged(m, snap, 'm = 0')
     for bad in (dict(radius=4, min_neighbors=2), dict(min_neighbors=344), dict(pierced_ratio=1.0), dict(box=((0, 0, 0), (float('nan'), 1, 1))),
                 dict(box=((1, 0, 0), (0, 1, 1)))):
         with pytest.raises(ValueError):
             m.prune(**bad)
-    _assert_unchanged(m, snap, 'ValueError')
+    ah.assert_unchanged(m, snap, 'ValueError')
     assert m.prune(dry_run=True) == dict(kept=65, filter=0, stale=0, box=0, pierced=0, isolated=0)

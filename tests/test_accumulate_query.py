@@ -7,63 +7,25 @@ Every result is an integer, a copied record or a float64 computed by + - * / and
   GPU   the kernel against the g++ build on the same scenes, then identities that tie query to extract / pierced / register, a life cycle against the
         restatement, the ghost scene of section 9f and the novelty of drifting windows.
 The one tolerance (1e-9 relative) is the rmse of register, whose sum runs in another order."""
-import io
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import accumulate_helpers as ah
 import accumulate_pierce_reference as pref
 import accumulate_prune_reference as rref
 import accumulate_query_reference as qref
 import accumulate_reference as ref
-from helpers import build_host_driver
+from accumulate_helpers import DEV, EDGE
+from helpers import ROOT
 from pcaccumulation_amd.config import default_config
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = 'cuda:0'
-EDGE = 1 << 20
 I, O, K, M, N = qref.INVALID, qref.OCCUPIED, qref.KEPT, qref.MATCHED, qref.NORMAL
 
 
 # ---- scenes: a ReferenceMap and a {coord: rays} dict (None: no sidecar), built once and never modified --------------------------------------------
-def _centres(idx, vs):
-    return ((np.asarray(idx, np.float64).reshape(-1, 3) + 0.5) * vs).astype(np.float32)
-
-
-def _records(vs, rows):
-    """rows: {coord: (count, moving, t_first, t_last)} -> a ReferenceMap whose coordinate sums put every centroid in the middle of its voxel."""
-    r = ref.ReferenceMap(vs)
-    for c, (count, moving, t_first, t_last) in rows.items():
-        q = [int(np.rint((v + 0.5) * vs * 65536.0)) for v in c]
-        r.rec[rref.key_of(c)] = [count, moving, count * q[0], count * q[1], count * q[2], t_first, t_last]
-    return r
-
-
-def _points_map(vs, adds):
-    r = ref.ReferenceMap(vs)
-    for pts, mv, stamp in adds:
-        r.add(pts, None, mv, stamp)
-    return r
-
-
-def _random_rows(m, seed):
-    """m voxels of the 7^3 block around the origin with random records, stamps 0..15 and ray counts 0..4 (the random block of the C8 tests)."""
-    rs = np.random.RandomState(seed)
-    cells = [(x, y, z) for x in range(-3, 4) for y in range(-3, 4) for z in range(-3, 4)]
-    rows, pierced = {}, {}
-    for i in rs.permutation(len(cells))[:m]:
-        count = int(rs.randint(1, 7))
-        t_first = int(rs.randint(0, 11))
-        rows[cells[i]] = (count, int(rs.randint(0, count + 1)), t_first, t_first + int(rs.randint(0, 6)))
-        p = int(rs.randint(0, 5))
-        if p:
-            pierced[cells[i]] = p
-    return rows, pierced
-
-
 # (voxel, points, moving): 1 of 4 sits exactly on 0.25; 1 of 3 and 2 of 4 above; 0 of 2 and 0 of 1 below; 4 of 4
 RATIO_SPEC = [((2, 0, 0), 4, 1), ((-1, 3, 0), 3, 1), ((0, 0, 5), 4, 2), ((0, -2, 1), 2, 0), ((-7, 0, 0), 1, 0), ((2, 0, -1), 4, 4), ((0, 0, -5), 8, 2)]
 RATIO_FILTERS = ((dict(min_count=1), 7), (dict(min_count=4), 4), (dict(min_count=5), 1), (dict(min_count=9), 0), (dict(max_moving_fraction=0.25), 4),
@@ -72,84 +34,21 @@ RATIO_FILTERS = ((dict(min_count=1), 7), (dict(min_count=4), 4), (dict(min_count
                  (dict(max_moving_fraction=1.0), 7))
 
 
-def _bound_voxels():
-    """3 x 3 columns through the last three voxels of every axis at both ends, and DECOYS where a key with an overflowed y or z field would land had
-    an offset stepped past the edge: (x, 2^20, z) aliases (x+1, -2^20, z), (x, y, 2^20) aliases (x, y+1, -2^20), and the mirror images."""
-    vox = []
-    for axis in range(3):
-        for lo in (-EDGE, EDGE - 3):
-            for a in range(3):
-                for b in (-1, 0, 1):
-                    for c in (-1, 0, 1):
-                        v = [b, c]
-                        v.insert(axis, lo + a)
-                        vox.append(tuple(v))
-    decoys = []
-    for x, y, z in vox:
-        if y == EDGE - 1:
-            decoys.append((x + 1, -EDGE, z))
-        if y == -EDGE:
-            decoys.append((x - 1, EDGE - 1, z))
-        if z == EDGE - 1:
-            decoys.append((x, y + 1, -EDGE))
-        if z == -EDGE:
-            decoys.append((x, y - 1, EDGE - 1))
-    return vox, [d for d in decoys if all(-EDGE <= c < EDGE for c in d)]
-
-
-def _noisy_plane():
-    rs = np.random.RandomState(21)
-    sheet = np.concatenate([rs.uniform(-1.5, 1.5, (6000, 2)), rs.normal(0.02, 0.01, (6000, 1))], 1)
-    stray = np.concatenate([rs.uniform(-1.5, 1.5, (40, 2)), rs.uniform(0.4, 2.0, (40, 1))], 1)
-    return np.concatenate([sheet, stray]).astype(np.float32)
-
-
-def _wavy():
-    """26 m x 26 m at 0.1 m, four points in every column, and one far voxel: 76 661 voxels (the sheet of section 9d)."""
-    g = np.arange(520) * 0.05 + 0.025 - 13.0
-    x, y = np.meshgrid(g, g, indexing='ij')
-    z = 0.4 * np.sin(0.9 * x) * np.cos(0.7 * y) + 0.013
-    return np.concatenate([np.stack([x, y, z], -1).reshape(-1, 3), [[40.0, 40.0, 40.0]]]).astype(np.float32)
-
-
-CORNER = np.array([0.43, -1.21, 0.27])
 FILTER = dict(min_count=2, max_moving_fraction=0.0)
 
 
-def _rot(rx, ry, rz, t):
-    T = np.eye(4)
-    for axis, a in ((0, rx), (1, ry), (2, rz)):
-        i, j = [(1, 2), (2, 0), (0, 1)][axis]
-        R = np.eye(4)
-        R[i, i], R[i, j], R[j, i], R[j, j] = np.cos(a), -np.sin(a), np.sin(a), np.cos(a)
-        T = R @ T
-    T[:3, 3] = t
-    return T
-
-
-POSE = _rot(np.deg2rad(0.6), np.deg2rad(-0.5), np.deg2rad(0.7), (0.02, -0.015, 0.017))      # about 1 degree and 0.3 voxel of 0.1 m
-
-
-def _corner(seed, per_sheet, noise=0.01):
-    """Three mutually orthogonal noisy sheets of 2 m x 2 m that meet in CORNER (the room corner of section 9e)."""
-    rs = np.random.RandomState(seed)
-    sheets = []
-    for axis in range(3):
-        p = rs.uniform(0.0, 2.0, (per_sheet, 3))
-        p[:, axis] = rs.normal(0, noise, per_sheet)
-        sheets.append(p + CORNER)
-    return np.concatenate(sheets)
+POSE = ah.rot_xyz(np.deg2rad(0.6), np.deg2rad(-0.5), np.deg2rad(0.7), (0.02, -0.015, 0.017))      # about 1 degree and 0.3 voxel of 0.1 m
 
 
 def _corner_adds():
-    pts = _corner(11, 3000).astype(np.float32)
-    mv = (pts[:, 0] > CORNER[0] + 1.6) & (np.random.RandomState(4).uniform(0, 1, pts.shape[0]) < 0.5)
+    pts = ah.corner(11, 3000).astype(np.float32)
+    mv = (pts[:, 0] > ah.CORNER[0] + 1.6) & (np.random.RandomState(4).uniform(0, 1, pts.shape[0]) < 0.5)
     return [(pts[:5000], mv[:5000], 3), (pts[5000:], mv[5000:], 1)]
 
 
 def _corner_scan(n=300):
     inv = np.linalg.inv(POSE)
-    return (_corner(12, n) @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32)
+    return (ah.corner(12, n) @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32)
 
 
 _scenes = {}
@@ -157,29 +56,29 @@ _scenes = {}
 
 def _build_scene(name):
     if name == 'rows65_no_sidecar':
-        return _records(0.1, _random_rows(65, 7)[0]), None
+        return ah.records(0.1, ah.random_rows(65, 7)[0]), None
     if name == 'rows343_no_sidecar':
-        return _records(0.1, _random_rows(343, 8)[0]), None
+        return ah.records(0.1, ah.random_rows(343, 8)[0]), None
     if name.startswith('rows'):
-        rows, pierced = _random_rows(int(name[4:]), 100 + int(name[4:]))
-        return _records(0.1, rows), pierced
+        rows, pierced = ah.random_rows(int(name[4:]), 100 + int(name[4:]))
+        return ah.records(0.1, rows), pierced
     if name == 'ratio':
-        return _records(1.0, {v: (k, j, 0, 0) for v, k, j in RATIO_SPEC}), None
+        return ah.records(1.0, {v: (k, j, 0, 0) for v, k, j in RATIO_SPEC}), None
     if name == 'bound':
-        vox, decoys = _bound_voxels()
-        return _points_map(0.01, [(_centres(vox + decoys, 0.01), None, 0)]), None
+        vox, decoys = ah.bound_voxels()
+        return ah.points_map(0.01, [(ah.centres(vox + decoys, 0.01), None, 0)]), None
     if name == 'tie':                                                              # 0.25 is exact: every centroid exactly at its voxel centre
-        return _records(0.25, {(x, y, z): (1, 0, 0, 0) for x in (0, 1) for y in (0, 1) for z in (0, 1)}), None
+        return ah.records(0.25, {(x, y, z): (1, 0, 0, 0) for x in (0, 1) for y in (0, 1) for z in (0, 1)}), None
     if name == 'filter':                                                           # (0,0,0) fails max_moving_fraction=0, (1,0,0) and (3,0,0) pass, (2,0,0) is empty
-        return _records(0.1, {(0, 0, 0): (3, 1, 0, 2), (1, 0, 0): (2, 0, 1, 1), (3, 0, 0): (5, 0, 0, 4), (20, 20, 20): (1, 0, 0, 0)}), {(0, 0, 0): 3}
+        return ah.records(0.1, {(0, 0, 0): (3, 1, 0, 2), (1, 0, 0): (2, 0, 1, 1), (3, 0, 0): (5, 0, 0, 4), (20, 20, 20): (1, 0, 0, 0)}), {(0, 0, 0): 3}
     if name == 'plane':
-        return _points_map(0.1, [(_noisy_plane(), None, 0)]), None
+        return ah.points_map(0.1, [(ah.noisy_plane(), None, 0)]), None
     if name == 'corner':
-        return _points_map(0.1, _corner_adds()), None
+        return ah.points_map(0.1, _corner_adds()), None
     if name == 'uniform':
-        return _points_map(0.1, [(np.random.RandomState(5).uniform(-0.6, 0.6, (2500, 3)).astype(np.float32), None, 0)]), None
+        return ah.points_map(0.1, [(np.random.RandomState(5).uniform(-0.6, 0.6, (2500, 3)).astype(np.float32), None, 0)]), None
     assert name == 'wavy'
-    return _points_map(0.1, [(_wavy(), None, 0)]), None
+    return ah.points_map(0.1, [(ah.wavy(), None, 0)]), None
 
 
 def _scene(name):
@@ -200,10 +99,10 @@ def _block_points(n, seed):
 
 
 def _bound_points():
-    vox, _ = _bound_voxels()
+    vox, _ = ah.bound_voxels()
     last = [v for v in vox if any(c in (-EDGE, EDGE - 1) for c in v)]                # the last voxel of each axis at both ends
     rs = np.random.RandomState(3)
-    return np.concatenate([_centres(last, 0.01), _centres(last, 0.01) + rs.uniform(-0.002, 0.002, (len(last), 3)).astype(np.float32)]), last
+    return np.concatenate([ah.centres(last, 0.01), ah.centres(last, 0.01) + rs.uniform(-0.002, 0.002, (len(last), 3)).astype(np.float32)]), last
 
 
 def _cases():
@@ -226,7 +125,7 @@ def _cases():
     fpts = np.array([[0.09, 0.05, 0.05], [0.22, 0.05, 0.05], [1.0, 1.0, 1.0], [2.05, 2.05, 2.05]], np.float32)
     cases['filter'] = ('filter', fpts, dict(max_moving_fraction=0.0))
     cases['filter_none'] = ('filter', fpts, dict())
-    rpts = np.concatenate([_centres([v for v, _, _ in RATIO_SPEC], 1.0), _centres([v for v, _, _ in RATIO_SPEC], 1.0) + np.float32(0.3)])
+    rpts = np.concatenate([ah.centres([v for v, _, _ in RATIO_SPEC], 1.0), ah.centres([v for v, _, _ in RATIO_SPEC], 1.0) + np.float32(0.3)])
     for k, (f, _) in enumerate(RATIO_FILTERS):
         cases['ratio_filter%d' % k] = ('ratio', rpts, dict(f))
     cases['pose'] = ('corner', _corner_scan(), dict(pose=POSE))
@@ -241,7 +140,7 @@ def _cases():
     cases['corner_few_require'] = ('corner', _corner_scan(), dict(pose=POSE, normals=True, require_normal=True, min_neighbors=9))
     cases['bad_table'] = ('corner', _corner_scan(), dict(pose=POSE, normals=True, short_rows=1))
     cases['bad_table_require'] = ('corner', _corner_scan(), dict(pose=POSE, normals=True, require_normal=True, short_rows=1, **FILTER))
-    cases['plane_normals'] = ('plane', _noisy_plane()[::20] + np.float32(0.013), dict(normals=True, max_distance=0.09))
+    cases['plane_normals'] = ('plane', ah.noisy_plane()[::20] + np.float32(0.013), dict(normals=True, max_distance=0.09))
     return cases
 
 
@@ -249,50 +148,27 @@ CASES = _cases()
 CASE_NAMES = sorted(CASES)
 
 
-def _aligned(pierced, keys):
-    return np.array([pierced.get(rref.coord_of(int(k)), 0) for k in keys.tolist()], np.int32)
-
-
 # ---- the host build ------------------------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def host_exe(tmp_path_factory):
-    return build_host_driver(tmp_path_factory.mktemp('query_host'), 'accum_query_host_driver')
+host_exe = ah.host_driver_fixture('accum_query_host_driver', 'query_host')
 
 
 def _run_host(exe, tmp_path, tag, records, pierced, points, spare=3, pose=None, max_distance=None, voxel_size=0.1, min_count=1, max_moving_fraction=None,
               normals=False, require_normal=False, radius=1, min_neighbors=5, viewpoints=None, stamp_base=0, short_rows=0):
-    keys, acc, stamps = records
-    m, n = keys.shape[0], points.shape[0]
+    m, n = records[0].shape[0], points.shape[0]
     view = np.zeros((0, 3)) if viewpoints is None else np.asarray(viewpoints, np.float64).reshape(-1, 3)
     head = [m, m + spare, 0 if pierced is None else 1, min_count, 0 if max_moving_fraction is None else 1, 1 if normals else 0, 1 if require_normal else 0,
             radius, min_neighbors, view.shape[0], stamp_base, n, 0 if pose is None else 1, short_rows]
-    src, dst = os.path.join(str(tmp_path), tag + '.in'), os.path.join(str(tmp_path), tag + '.out')
-    with open(src, 'wb') as f:
-        f.write(np.array(head, np.int64).tobytes())
-        f.write(np.array([0.0 if max_moving_fraction is None else max_moving_fraction, voxel_size, voxel_size if max_distance is None else max_distance],
-                         np.float64).tobytes())
-        f.write(np.ascontiguousarray(keys, np.int64).tobytes())
-        f.write(np.ascontiguousarray(acc, np.int64).tobytes())
-        f.write(np.ascontiguousarray(stamps, np.int32).tobytes())
-        if pierced is not None:
-            f.write(np.ascontiguousarray(pierced, np.int32).tobytes())
-        f.write(view.tobytes())
-        f.write(np.ascontiguousarray(points, np.float32).tobytes())
-        if pose is not None:
-            f.write(np.ascontiguousarray(pose, np.float64).tobytes())
-    subprocess.check_call([exe, src, dst])
-    raw = open(dst, 'rb').read()
-    out = dict(counters=np.frombuffer(raw, np.int64, 7).tolist())
-    kept, off = int(np.frombuffer(raw, np.int64, 1, 56)[0]), 64
+    raw = ah.run_driver(exe, tmp_path, tag, np.array(head, np.int64),
+                        np.array([0.0 if max_moving_fraction is None else max_moving_fraction, voxel_size, voxel_size if max_distance is None else max_distance],
+                                 np.float64),
+                        ah.map_bytes(*records, pierced), view, np.ascontiguousarray(points, np.float32),
+                        b'' if pose is None else np.ascontiguousarray(pose, np.float64))
+    kept = int(np.frombuffer(raw, np.int64, 1, 56)[0])
     v = kept if normals else 0
     layout = [('normals32', np.float32, (v, 3)), ('flags', np.uint8, (v,))] + [(f, qref.DTYPES[f], (n, 3) if f == 'nearest' else (n,)) for f in qref.FIELDS]
-    for name, dtype, shape in layout:
-        k = int(np.prod(shape))
-        out[name] = np.frombuffer(raw, dtype, k, off).reshape(shape).copy()
-        off += k * np.dtype(dtype).itemsize
+    out, off = ah.unpack(raw, 64, layout)
     assert off == len(raw)
-    out['kept'] = kept
-    return out
+    return dict(out, counters=np.frombuffer(raw, np.int64, 7).tolist(), kept=kept)
 
 
 _hosted, _restated = {}, {}
@@ -303,7 +179,7 @@ def _host(exe, tmp_path, name):
         scene, points, args = CASES[name]
         r, pierced = _scene(scene)
         keys = r.records()[0]
-        _hosted[name] = _run_host(exe, tmp_path, name, r.records(), None if pierced is None else _aligned(pierced, keys), points,
+        _hosted[name] = _run_host(exe, tmp_path, name, r.records(), None if pierced is None else ah.aligned(pierced, keys), points,
                                   voxel_size=r.voxel_size, **args)
     return _hosted[name]
 
@@ -321,23 +197,18 @@ def _restate(exe, tmp_path, name):
     return _restated[name]
 
 
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.int32, 8: np.int64}[a.dtype.itemsize]) if a.dtype.kind == 'f' else a
-
-
 def _assert_same(got, want, what):
     assert list(got['counters']) == list(want['counters']), (what, got['counters'], want['counters'])
     for f in qref.FIELDS:
         assert got[f].dtype == want[f].dtype and got[f].shape == want[f].shape, (what, f)
-        assert np.array_equal(_bits(got[f]), _bits(want[f])), (what, f, np.flatnonzero(_bits(got[f]).reshape(got[f].shape[0], -1) !=
-                                                                                         _bits(want[f]).reshape(got[f].shape[0], -1))[:5])
+        assert np.array_equal(ah.bits(got[f]), ah.bits(want[f])), (what, f, np.flatnonzero(ah.bits(got[f]).reshape(got[f].shape[0], -1) !=
+                                                                                         ah.bits(want[f]).reshape(got[f].shape[0], -1))[:5])
 
 
 # ---- CPU: host build == restatement -------------------------------------------------------------------------------------------------------------------------
 def test_scenes_hold_what_they_are_for():
     assert [_scene('rows%d' % m)[0].num_voxels for m in (0, 1, 65, 343)] == [0, 1, 65, 343]
-    vox, decoys = _bound_voxels()
+    vox, decoys = ah.bound_voxels()
     assert _scene('bound')[0].num_voxels == len(set(vox + decoys)) and len(decoys) >= 36
     corner = _scene('corner')[0]
     assert 1000 < len(qref.kept_voxels(corner, **FILTER)) < corner.num_voxels
@@ -369,7 +240,7 @@ def test_sizes_and_validity(host_exe, tmp_path):
     assert (first['status'][:k] == I).all() and (first['status'][k:] & (I | O | M) == (O | M)).all() and first['counters'][1] == k
     assert (last['status'][-k:] == I).all() and (last['status'][:-k] & (I | O | M) == (O | M)).all()
     for f in qref.FIELDS[1:]:
-        assert np.array_equal(_bits(first[f][:k]), _bits(last[f][-k:])) and np.array_equal(_bits(first[f][k:]), _bits(last[f][:-k])), f
+        assert np.array_equal(ah.bits(first[f][:k]), ah.bits(last[f][-k:])) and np.array_equal(ah.bits(first[f][k:]), ah.bits(last[f][:-k])), f
     for j in range(k):
         assert _host(host_exe, tmp_path, 'invalid_alone%d' % j)['counters'] == [1, 1, 0, 0, 0, 0, 0]
 
@@ -420,7 +291,7 @@ def test_normals_and_bad_table(host_exe, tmp_path):
     assert (need['distance'][flagged] >= plain['distance'][flagged]).all() and (need['row'][flagged] != plain['row'][flagged]).all()
     assert need['counters'][4] == need['counters'][5] <= plain['counters'][4] and plain['counters'][5] < plain['counters'][4]
     same = ~flagged & ((plain['status'] & N) != 0)
-    assert np.array_equal(plain['row'][same], need['row'][same]) and np.array_equal(_bits(plain['plane_distance'][same]), _bits(need['plane_distance'][same]))
+    assert np.array_equal(plain['row'][same], need['row'][same]) and np.array_equal(ah.bits(plain['plane_distance'][same]), ah.bits(need['plane_distance'][same]))
     ok = _host(host_exe, tmp_path, 'corner_normals')
     on = (ok['status'] & N) != 0
     assert on.sum() > 700 and (np.abs(ok['plane_distance'][on]) <= ok['distance'][on] * (1 + 1e-6)).all()
@@ -438,13 +309,13 @@ def test_the_match_is_the_global_nearest_kept_centroid(scene, fraction):
     """The theorem of the contract: for max_distance <= 0.9 voxel_size the 27-voxel search returns the nearest kept centroid of the WHOLE map."""
     r, _ = _scene(scene)
     rs = np.random.RandomState(int(fraction * 10))
-    base = {'plane': _noisy_plane()[::40], 'corner': _corner(13, 60).astype(np.float32), 'uniform': rs.uniform(-0.7, 0.7, (150, 3)).astype(np.float32)}[scene]
+    base = {'plane': ah.noisy_plane()[::40], 'corner': ah.corner(13, 60).astype(np.float32), 'uniform': rs.uniform(-0.7, 0.7, (150, 3)).astype(np.float32)}[scene]
     pts = np.concatenate([base + rs.normal(0, 0.04, base.shape).astype(np.float32), [[np.inf, 0, 0]]]).astype(np.float32)
     f = FILTER if scene == 'corner' else dict()
     got = qref.query(r, None, pts, max_distance=fraction * 0.1, **f)
     valid, row, dist = qref.brute_force(r, pts, max_distance=fraction * 0.1, **f)
     assert np.array_equal(valid, got['status'] != I) and valid.sum() == len(pts) - 1
-    assert np.array_equal(row[valid], got['row'][valid]) and np.array_equal(_bits(dist[valid]), _bits(got['distance'][valid]))
+    assert np.array_equal(row[valid], got['row'][valid]) and np.array_equal(ah.bits(dist[valid]), ah.bits(got['distance'][valid]))
     assert (fraction < 0.2 or (row >= 0).sum() > 0) and (fraction > 0.2 or (row < 0).sum() > 0)
 
 
@@ -469,16 +340,8 @@ def test_header_binding_and_argument_checks():
 
 # ---- GPU ----------------------------------------------------------------------------------------------------------------------------------------------------
 def _device_cloud(r, pierced):
-    """The restatement's map and ray counts as an AccumulatedCloud on the device, through load()."""
-    from pcaccumulation_amd.accumulate import AccumulatedCloud
-    keys, acc, stamps = r.records()
-    extra = {}
-    if pierced is not None:
-        extra = dict(pierced=_aligned(pierced, keys), pierce_counters=np.zeros(5, np.int64))
-    buf = io.BytesIO()
-    np.savez(buf, keys=keys, acc=acc.reshape(5, -1), stamps=stamps.reshape(2, -1), voxel_size=np.float64(r.voxel_size), dropped=np.int64(r.dropped), **extra)
-    buf.seek(0)
-    return AccumulatedCloud.load(buf, DEV)
+    """The restatement's map and {coord: rays} dict as an AccumulatedCloud on the device."""
+    return ah.device_cloud(r, None if pierced is None else ah.aligned(pierced, r.records()[0]), np.zeros(5, np.int64))
 
 
 _clouds = {}
@@ -489,19 +352,6 @@ def _cloud(scene):
     if scene not in _clouds:
         _clouds[scene] = _device_cloud(*_scene(scene))
     return _clouds[scene]
-
-
-def _snapshot(m):
-    n = m.num_voxels
-    keys, acc, stamps = m._cur
-    return (n, keys[:n].clone(), acc[:, :n].clone(), stamps[:, :n].clone(), None if m._pierced is None else m._pierced.clone(), m._state.clone())
-
-
-def _assert_unchanged(m, snap, what):
-    now = _snapshot(m)
-    assert now[0] == snap[0], what
-    for a, b in zip(now[1:], snap[1:]):
-        assert (a is None and b is None) or torch.equal(a, b), what
 
 
 def _query(m, points, args):
@@ -525,7 +375,7 @@ def _assert_device_equals_host(res, host, what):
         want = torch.from_numpy(host[f]).to(DEV)
         assert res[f].is_cuda and res[f].dtype == want.dtype and res[f].shape == want.shape, (what, f)
         if want.dtype.is_floating_point:                                            # torch.equal on the bits: +inf, -0.0 and every last bit
-            assert torch.equal(res[f].view(torch.int64 if want.dtype == torch.float64 else torch.int32), torch.from_numpy(_bits(host[f])).to(DEV)), (what, f)
+            assert torch.equal(res[f].view(torch.int64 if want.dtype == torch.float64 else torch.int32), torch.from_numpy(ah.bits(host[f])).to(DEV)), (what, f)
         assert torch.equal(res[f], want), (what, f)
 
 
@@ -535,21 +385,21 @@ def test_kernel_equals_the_host_build_gpu(host_exe, tmp_path, name):
     scene, points, args = CASES[name]
     host = _host(host_exe, tmp_path, name)
     m = _cloud(scene)
-    snap = _snapshot(m)
+    snap = ah.snapshot(m, whole_sidecar=True)
     res = _query(m, points, args)
     _assert_device_equals_host(res, host, name)
     again = _query(m, points, args)                                               # a second run gives the same bits
     assert all(torch.equal(res[f], again[f]) for f in res)
-    _assert_unchanged(m, snap, name)                                              # read-only: keys, records, stamps, sidecar, state words, num_voxels
+    ah.assert_unchanged(m, snap, name)                                              # read-only: keys, records, stamps, sidecar, state words, num_voxels
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('args', [dict(max_distance=0.07), dict(normals=True, require_normal=True, pose=_rot(0.002, -0.001, 0.003, (0.01, 0.02, -0.01)))],
+@pytest.mark.parametrize('args', [dict(max_distance=0.07), dict(normals=True, require_normal=True, pose=ah.rot_xyz(0.002, -0.001, 0.003, (0.01, 0.02, -0.01)))],
                          ids=['plain', 'normals_pose'])
 def test_kernel_on_76661_voxels_and_100003_points_gpu(host_exe, tmp_path, args):
     r, _ = _scene('wavy')
     rs = np.random.RandomState(77)
-    pts = _wavy()[rs.randint(0, 270400, 100003)] + rs.uniform(-0.03, 0.03, (100003, 3)).astype(np.float32)
+    pts = ah.wavy()[rs.randint(0, 270400, 100003)] + rs.uniform(-0.03, 0.03, (100003, 3)).astype(np.float32)
     pts[::3, 2] += rs.uniform(0.0, 0.2, pts[::3].shape[0]).astype(np.float32)      # a third lifted off the sheet by up to two voxels
     assert r.num_voxels == 76661 and pts.shape[0] % 64 != 0 and pts.shape[0] % 256 != 0
     host = _run_host(host_exe, tmp_path, 'wavy', r.records(), None, pts, **args)
@@ -634,17 +484,17 @@ def test_life_cycle_gpu(tmp_path):
     from pcaccumulation_amd.accumulate import AccumulatedCloud
     m, r, pierced = AccumulatedCloud(0.1, DEV, 64), ref.ReferenceMap(0.1), {}
     origin = np.array([[0.05, 0.05, 0.05]])
-    slab = _centres([(x, y, z) for x in (5, 6, 7) for y in range(-2, 3) for z in (-1, 0, 1)], 0.1)
-    probe = np.concatenate([slab + np.float32(0.03), _centres([(9, 0, 0), (6, 9, 9), (-9, 0, 0)], 0.1), [[np.nan, 0, 0]]]).astype(np.float32)
+    slab = ah.centres([(x, y, z) for x in (5, 6, 7) for y in range(-2, 3) for z in (-1, 0, 1)], 0.1)
+    probe = np.concatenate([slab + np.float32(0.03), ah.centres([(9, 0, 0), (6, 9, 9), (-9, 0, 0)], 0.1), [[np.nan, 0, 0]]]).astype(np.float32)
     _both_add(m, r, np.concatenate([slab, slab[::2]]), 0)
     a = _assert_query_equals_restatement(m, r, None, probe, 'after add', min_count=2)
-    _both_see(m, r, pierced, _centres([(20, y, 0) for y in (-2, 0, 3)], 0.1), origin, 1)
+    _both_see(m, r, pierced, ah.centres([(20, y, 0) for y in (-2, 0, 3)], 0.1), origin, 1)
     b = _assert_query_equals_restatement(m, r, pierced, probe, 'after see_through', min_count=2)
     assert int(a['pierced'].sum()) == 0 < int(b['pierced'].sum()) and torch.equal(a['row'], b['row'])
     assert m.prune(min_pierced=1)['pierced'] == rref.prune(r, pierced, min_pierced=1)[4] > 0
     c = _assert_query_equals_restatement(m, r, pierced, probe, 'after prune', min_count=2)
     assert int(c['counters'][2]) < int(b['counters'][2]) and int(c['pierced'].sum()) == 0
-    _both_add(m, r, _centres([(-9, 0, 0), (6, 0, 0), (6, 0, 0), (6, 9, 9)], 0.1), 2)
+    _both_add(m, r, ah.centres([(-9, 0, 0), (6, 0, 0), (6, 0, 0), (6, 9, 9)], 0.1), 2)
     d = _assert_query_equals_restatement(m, r, pierced, probe, 'add after prune')
     assert int(d['counters'][2]) > int(c['counters'][2])
     path = os.path.join(str(tmp_path), 'map.npz')
@@ -655,42 +505,21 @@ def test_life_cycle_gpu(tmp_path):
 
 
 # ---- the ghost scene of section 9f, rebuilt here --------------------------------------------------------------------------------------------------------------
-GHOST_SENSOR = np.array([[0.03, 0.02, 0.01]])
-
-
-def _ghost_scans():
-    """Six scans from a fixed sensor: a wall one voxel layer thick at x = 3.05 and a 3 x 3 x 3 cluster of voxel centres, never flagged moving, at a
-    different y in front of the wall at each stamp.  Wall returns whose ray would have crossed the cluster of their own stamp are left out."""
-    vs = 0.1
-    wall = _centres([(30, y, z) for y in range(-20, 20) for z in range(-10, 10)], vs)
-    scans = []
-    for k in range(6):
-        y0 = -8 + 3 * k
-        vox = [(15 + a, y0 + b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1)]
-        s = GHOST_SENSOR[0]
-        t = (1.55 - s[0]) / (wall[:, 0].astype(np.float64) - s[0])
-        y = s[1] + t * (wall[:, 1] - s[1])
-        z = s[2] + t * (wall[:, 2] - s[2])
-        shadow = (np.abs(y - (y0 + 0.5) * vs) < 0.3) & (np.abs(z - 0.05) < 0.3)
-        scans.append((wall[~shadow], _centres(vox, vs), vox))
-    return scans
-
-
 @pytest.mark.gpu
 def test_ghost_trail_seen_from_a_fresh_scan_gpu():
     from pcaccumulation_amd.accumulate import AccumulatedCloud
     m, r, pierced = AccumulatedCloud(0.1, DEV, 64), ref.ReferenceMap(0.1), {}
-    scans = _ghost_scans()
+    scans = ah.ghost_scans()
     for k, (wall, cluster, _) in enumerate(scans):
         pts = np.concatenate([wall, cluster])
-        _both_see(m, r, pierced, pts, GHOST_SENSOR, k)
+        _both_see(m, r, pierced, pts, ah.GHOST_SENSOR, k)
         _both_add(m, r, pts, k)
     rs = np.random.RandomState(8)
     wall_vox = [(30, int(y), int(z)) for y, z in zip(rs.randint(-20, 20, 400), rs.randint(-10, 10, 400))]
     early = sorted({v for k in range(5) for v in scans[k][2]})
     ghost_vox = [early[i] for i in rs.permutation(len(early))[:100]]
     free_vox = [(8, int(y), int(z)) for y, z in zip(rs.randint(-20, 20, 100), rs.randint(-10, 10, 100))]
-    fresh = (_centres(wall_vox + ghost_vox + free_vox, 0.1) + rs.uniform(-0.04, 0.04, (600, 3)).astype(np.float32)).astype(np.float32)
+    fresh = (ah.centres(wall_vox + ghost_vox + free_vox, 0.1) + rs.uniform(-0.04, 0.04, (600, 3)).astype(np.float32)).astype(np.float32)
     got = _assert_query_equals_restatement(m, r, pierced, fresh, 'ghost before')
     s, p = got['status'].cpu().numpy(), got['pierced'].cpu().numpy()
     assert ((s[:400] & K) != 0).all() and (p[:400] == 0).all()                   # the wall: kept, no ray went through it
@@ -714,9 +543,9 @@ def test_novelty_of_drifting_windows_gpu():
     m, r = AccumulatedCloud(0.1, DEV, 64), ref.ReferenceMap(0.1)
     occupied = []
     for k in range(8):
-        truth = _rot(0.002 * k, -0.001 * k, 0.003 * k, (0.05 * k, -0.03 * k, 0.01 * k))
+        truth = ah.rot_xyz(0.002 * k, -0.001 * k, 0.003 * k, (0.05 * k, -0.03 * k, 0.01 * k))
         inv = np.linalg.inv(truth)
-        pts = (_corner(40 + k, 250) @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32)
+        pts = (ah.corner(40 + k, 250) @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32)
         if k:
             got = m.query(torch.from_numpy(pts).to(DEV), pose=truth)
             want = qref.query(r, None, pts, pose=truth)
@@ -725,10 +554,10 @@ def test_novelty_of_drifting_windows_gpu():
         _both_add(m, r, pts, k, truth)
     assert all(o > 300 for o in occupied)
     # the same window, added once with a drifted pose (1.5 voxels off) and once with the pose a registration returns
-    truth = _rot(0.016, -0.008, 0.024, (0.4, -0.24, 0.08))
+    truth = ah.rot_xyz(0.016, -0.008, 0.024, (0.4, -0.24, 0.08))
     inv = np.linalg.inv(truth)
-    window = torch.from_numpy((_corner(48, 250) @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32)).to(DEV)
-    again = torch.from_numpy((_corner(49, 250) @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32)).to(DEV)
+    window = torch.from_numpy((ah.corner(48, 250) @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32)).to(DEV)
+    again = torch.from_numpy((ah.corner(49, 250) @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32)).to(DEV)
     drifted = truth.copy()
     drifted[:3, 3] += (0.15, -0.15, 0.15)
     started = truth.copy()
@@ -765,8 +594,8 @@ def test_query_results_on_the_model_forward_gpu(golden):
     with torch.no_grad():
         out = model(inp)
     m = AccumulatedCloud(0.2, dev, 64).add_results(out, inp, stamp=0)
-    res = m.query_results(out, inp, pose=_rot(0, 0, 0.01, (0.02, -0.01, 0.0)), normals=True)
-    same = m.query(out['rec_est'], _rot(0, 0, 0.01, (0.02, -0.01, 0.0)), normals=True)
+    res = m.query_results(out, inp, pose=ah.rot_xyz(0, 0, 0.01, (0.02, -0.01, 0.0)), normals=True)
+    same = m.query(out['rec_est'], ah.rot_xyz(0, 0, 0.01, (0.02, -0.01, 0.0)), normals=True)
     assert all(torch.equal(res[k], same[k]) for k in res)
     s = res['status']
     n = out['rec_est'].shape[0]
@@ -781,7 +610,7 @@ def test_bad_arguments_launch_nothing_gpu():
     from pcaccumulation_amd import native
     r, pierced = _scene('rows65')
     m = _device_cloud(r, pierced)
-    snap = _snapshot(m)
+    snap = ah.snapshot(m, whole_sidecar=True)
     n = 10
     pts = torch.from_numpy(_block_points(n, 1)).to(DEV)
     out = {name: torch.full((n,) + shape, 7, dtype=dtype, device=DEV) for name, dtype, shape in native.QUERY_FIELDS}
@@ -810,7 +639,7 @@ def test_bad_arguments_launch_nothing_gpu():
         assert call(ptr=ptr[:k] + [None] + ptr[k + 1:]) == -1, k                  # a NULL output of non-zero size
     torch.cuda.synchronize()
     assert all(bool((t == 7).all()) for t in list(out.values()) + [counters])     # nothing was launched: outputs and counters keep their poison
-    _assert_unchanged(m, snap, 'bad arguments')
+    ah.assert_unchanged(m, snap, 'bad arguments')
     for bad in (dict(max_distance=0.0), dict(max_distance=0.1000001), dict(max_distance=float('nan')), dict(radius=0), dict(radius=4), dict(min_neighbors=2),
                 dict(require_normal=True), dict(pose=np.eye(3))):
         with pytest.raises(ValueError):
@@ -822,4 +651,4 @@ def test_bad_arguments_launch_nothing_gpu():
     zero = native.accum_query(**dict(good, points=pts[:0], out={k: t[:0] for k, t in out.items()}))      # n = 0: the zero counters and nothing else
     assert zero['counters'].tolist() == [0] * 7 and all(bool((t == 7).all()) for t in out.values())
     assert call() == 0 and counters.tolist()[0] == n and not bool((out['status'] == 7).any())
-    _assert_unchanged(m, snap, 'after all')
+    ah.assert_unchanged(m, snap, 'after all')

@@ -8,26 +8,23 @@ Every result is an integer, a copied value or a float64 computed by + - * / and 
   GPU   the kernel against the g++ build on the same scenes, then identities that tie raycast to extract and see_through, occlusion and the
         new-object / seen-through / consistent classes on a wall scene, the range image, a life cycle and the model forward.
 No test asserts a time."""
-import io
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import accumulate_helpers as ah
 import accumulate_pierce_reference as pref
 import accumulate_prune_reference as rref
 import accumulate_query_reference as qref
 import accumulate_raycast_reference as yref
 import accumulate_reference as ref
-from helpers import build_host_driver
+from accumulate_helpers import DEV, EDGE
+from helpers import ROOT
 from pcaccumulation_amd.config import default_config
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = 'cuda:0'
-EDGE = 1 << 20
 NAN, INF = float('nan'), float('inf')
 MISS, HIT, TRUNCATED, SKIPPED, DROPPED = yref.MISS, yref.HIT, yref.TRUNCATED, yref.SKIPPED, yref.DROPPED
 EPS = 1e-9                                                                        # C7's band, and the slack of the depth bound
@@ -38,31 +35,6 @@ def _bound_on_depth(vs):
 
 
 # ---- scenes: a ReferenceMap, built once and never modified -----------------------------------------------------------------------------------------
-def _centres(idx, vs):
-    return ((np.asarray(idx, np.float64).reshape(-1, 3) + 0.5) * vs).astype(np.float32)
-
-
-def _block(lo, hi):
-    g = np.arange(lo, hi)
-    return np.stack(np.meshgrid(g, g, g, indexing='ij'), -1).reshape(-1, 3)
-
-
-def _records(vs, rows):
-    """rows: {coord: (count, moving)} -> a ReferenceMap whose coordinate sums put every centroid in the middle of its voxel."""
-    r = ref.ReferenceMap(vs)
-    for c, (count, moving) in rows.items():
-        q = [int(np.rint((v + 0.5) * vs * 65536.0)) for v in c]
-        r.rec[rref.key_of(c)] = [count, moving, count * q[0], count * q[1], count * q[2], 0, 0]
-    return r
-
-
-def _points_map(vs, adds):
-    r = ref.ReferenceMap(vs)
-    for pts, mv, stamp in adds:
-        r.add(pts, None, mv, stamp)
-    return r
-
-
 def _random_rows(m, seed):
     """m voxels of the 7^3 block around the origin with random records (the random block of the C8 / C9 tests)."""
     rs = np.random.RandomState(seed)
@@ -82,48 +54,7 @@ RATIO_FILTERS = ((dict(min_count=1), 7), (dict(min_count=4), 4), (dict(min_count
                  (dict(max_moving_fraction=1.0), 7))
 
 
-def _bound_voxels():
-    """The last three voxels of every axis at both ends, which the bound scene's rays walk, and DECOYS where a key with an overflowed y or z field would
-    land had a walk stepped past the edge: (x, 2^20, z) aliases (x+1, -2^20, z), (x, y, 2^20) aliases (x, y+1, -2^20), and the mirror images."""
-    walked, decoys = [], []
-    for axis in range(3):
-        for lo in (-EDGE, EDGE - 3):
-            for a in range(3):
-                v = [1, -2]
-                v.insert(axis, lo + a)
-                walked.append(tuple(v))
-    for x, y, z in walked:
-        if y == EDGE - 1:
-            decoys.append((x + 1, -EDGE, z))
-        if y == -EDGE:
-            decoys.append((x - 1, EDGE - 1, z))
-        if z == EDGE - 1:
-            decoys.append((x, y + 1, -EDGE))
-        if z == -EDGE:
-            decoys.append((x, y - 1, EDGE - 1))
-    return walked, decoys
-
-
-def _wavy():
-    """26 m x 26 m at 0.1 m, four points in every column, and one far voxel: 76 661 voxels (the sheet of section 9d)."""
-    g = np.arange(520) * 0.05 + 0.025 - 13.0
-    x, y = np.meshgrid(g, g, indexing='ij')
-    z = 0.4 * np.sin(0.9 * x) * np.cos(0.7 * y) + 0.013
-    return np.concatenate([np.stack([x, y, z], -1).reshape(-1, 3), [[40.0, 40.0, 40.0]]]).astype(np.float32)
-
-
-def _rot(rx, ry, rz, t):
-    T = np.eye(4)
-    for axis, a in ((0, rx), (1, ry), (2, rz)):
-        i, j = [(1, 2), (2, 0), (0, 1)][axis]
-        R = np.eye(4)
-        R[i, i], R[i, j], R[j, i], R[j, j] = np.cos(a), -np.sin(a), np.sin(a), np.cos(a)
-        T = R @ T
-    T[:3, 3] = t
-    return T
-
-
-POSE = _rot(np.deg2rad(4.0), np.deg2rad(-3.0), np.deg2rad(17.0), (0.02, -0.015, 0.017))
+POSE = ah.rot_xyz(np.deg2rad(4.0), np.deg2rad(-3.0), np.deg2rad(17.0), (0.02, -0.015, 0.017))
 SENSOR = np.array([[0.03, 0.02, 0.01]])                                             # the fixed sensor of section 9f
 WALL_YZ = [(y, z) for y in range(-20, 20) for z in range(-10, 10)]
 GHOST = [(10 + a, 6 + b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1)]       # held by the map, 2 m in front of the wall
@@ -134,38 +65,38 @@ _scenes = {}
 
 def _build_scene(name):
     if name.startswith('rows'):
-        return _records(0.1, _random_rows(int(name[4:]), 100 + int(name[4:])))
+        return ah.records(0.1, _random_rows(int(name[4:]), 100 + int(name[4:])))
     if name == 'third':                                                            # a random third of the 40^3 block around the origin (C7's)
         keep = np.random.RandomState(5).uniform(0, 1, 64000) < 1.0 / 3.0
-        return _points_map(0.1, [(_centres(_block(-20, 20)[keep], 0.1), None, 0)])
+        return ah.points_map(0.1, [(ah.centres(ah.block(-20, 20)[keep], 0.1), None, 0)])
     if name == 'sparse':                                                           # 2 % of a 40^3 block at 0.25 m
         keep = np.random.RandomState(6).uniform(0, 1, 64000) < 0.02
-        return _records(0.25, {tuple(c): (1, 0) for c in _block(-20, 20)[keep].tolist()})
+        return ah.records(0.25, {tuple(c): (1, 0) for c in ah.block(-20, 20)[keep].tolist()})
     if name == 'tie':                                                              # 0.25 is exact; only the last voxel of the written-down walk
-        return _records(0.25, {(3, 3, 3): (1, 0)})
+        return ah.records(0.25, {(3, 3, 3): (1, 0)})
     if name == 'face':
-        return _records(0.25, {(-1, 1, 1): (1, 0), (-3, 1, 1): (1, 0)})
+        return ah.records(0.25, {(-1, 1, 1): (1, 0), (-3, 1, 1): (1, 0)})
     if name == 'face_next':                                                        # the voxel the ray enters at t = -0.0
-        return _records(0.25, {(1, 1, 1): (1, 0)})
+        return ah.records(0.25, {(1, 1, 1): (1, 0)})
     if name == 'posts':                                                            # three voxels on the x axis at 0.25 m: every number of the ray is exact
-        return _records(0.25, {(2, 0, 0): (1, 0), (4, 0, 0): (1, 0), (6, 0, 0): (1, 0)})
+        return ah.records(0.25, {(2, 0, 0): (1, 0), (4, 0, 0): (1, 0), (6, 0, 0): (1, 0)})
     if name == 'ratio':
-        return _records(1.0, {v: (k, j) for v, k, j in RATIO_SPEC})
+        return ah.records(1.0, {v: (k, j) for v, k, j in RATIO_SPEC})
     if name == 'filter':                                                           # along +x: (0,0,0) 1 of 3 moving, (1,0,0) 2 points, (3,0,0) 5 points
-        return _records(0.1, {(0, 0, 0): (3, 1), (1, 0, 0): (2, 0), (3, 0, 0): (5, 0), (20, 20, 20): (1, 0)})
+        return ah.records(0.1, {(0, 0, 0): (3, 1), (1, 0, 0): (2, 0), (3, 0, 0): (5, 0), (20, 20, 20): (1, 0)})
     if name == 'bound':
-        walked, decoys = _bound_voxels()
-        return _points_map(0.01, [(_centres(walked + decoys, 0.01), None, 0)])
+        walked, decoys = ah.walked_voxels()
+        return ah.points_map(0.01, [(ah.centres(walked + decoys, 0.01), None, 0)])
     if name == 'walls':                                                            # section 9f's wall, built once (count 1), a second wall 1 m behind it
         rows = {(30, y, z): (1, 0) for y, z in WALL_YZ}
         rows.update({(40, y, z): (2, 0) for y, z in WALL_YZ})
-        return _records(0.1, rows)
+        return ah.records(0.1, rows)
     if name == 'ghost':                                                            # the wall and a cluster the map still holds in front of it
         rows = {(30, y, z): (1, 0) for y, z in WALL_YZ}
         rows.update({v: (1, 0) for v in GHOST})
-        return _records(0.1, rows)
+        return ah.records(0.1, rows)
     assert name == 'wavy'
-    return _points_map(0.1, [(_wavy(), None, 0)])
+    return ah.points_map(0.1, [(ah.wavy(), None, 0)])
 
 
 def _scene(name):
@@ -184,25 +115,6 @@ def _block_rays(n, seed):
     return rs.uniform(-0.6, 0.7, (n, 3)).astype(np.float32), rs.uniform(-0.45, 0.55, (3, 3)), rs.randint(0, 3, n).astype(np.int32)
 
 
-def _random_rays():
-    """C7's 400 rays: origins within +-0.3 m (row 0 float32-representable, so that a component of d can be exactly zero), end points within +-2 m."""
-    rs = np.random.RandomState(11)
-    origins = rs.uniform(-0.3, 0.3, (3, 3))
-    origins[0] = origins[0].astype(np.float32)
-    index = rs.randint(0, 3, 400).astype(np.int32)
-    pts = rs.uniform(-2, 2, (400, 3)).astype(np.float32)
-    o0 = origins[0].astype(np.float32)
-    index[:24] = 0
-    pts[0:6, 0] = o0[0]                                                          # d_x == 0 exactly
-    pts[6:10, 1] = o0[1]                                                         # d_y == 0
-    pts[10:14, 2] = o0[2]                                                        # d_z == 0
-    for j, (axis, sign) in enumerate([(0, 1), (0, -1), (1, 1), (1, -1), (2, 1), (2, -1)]):    # along one axis: two zero components
-        pts[14 + j] = o0
-        pts[14 + j, axis] += np.float32(sign * (1.1 + 0.1 * j))
-    pts[20:22, 0], pts[20:22, 1] = o0[0], o0[1]
-    return pts, origins, index
-
-
 def _bound_rays():
     """Rays that start two voxels inside and point outwards through the LAST voxel of each axis at both ends; two more targets lie outside the grid."""
     ends, starts = [], []
@@ -214,14 +126,14 @@ def _bound_rays():
             starts.append(s)
             ends.append(e)
     outside = np.array([[10485.77, 0.015, -0.015], [0.015, 0.015, -10485.78]], np.float32)
-    return (np.concatenate([_centres(ends, 0.01), outside]), _centres(starts, 0.01).astype(np.float64), np.array([0, 1, 2, 3, 4, 5, 0, 5], np.int32), ends)
+    return (np.concatenate([ah.centres(ends, 0.01), outside]), ah.centres(starts, 0.01).astype(np.float64), np.array([0, 1, 2, 3, 4, 5, 0, 5], np.int32), ends)
 
 
 def _scan_of_the_ghost_scene():
     """A new scan from SENSOR: every wall voxel's centre (jittered by 0.03 m), then the 27 centres of FRESH."""
     rs = np.random.RandomState(8)
-    wall = _centres([(30, y, z) for y, z in WALL_YZ], 0.1) + rs.uniform(-0.03, 0.03, (len(WALL_YZ), 3)).astype(np.float32)
-    return np.concatenate([wall, _centres(FRESH, 0.1)]).astype(np.float32)
+    wall = ah.centres([(30, y, z) for y, z in WALL_YZ], 0.1) + rs.uniform(-0.03, 0.03, (len(WALL_YZ), 3)).astype(np.float32)
+    return np.concatenate([wall, ah.centres(FRESH, 0.1)]).astype(np.float32)
 
 
 POST_O = np.array([[0.125, 0.125, 0.125]])
@@ -238,7 +150,7 @@ def _cases():
     pts, org, idx = _block_rays(257, 5)
     c['rows343_to_target'] = ('rows343', pts, org, dict(origin_index=idx, pose=POSE))
     c['rows343_filtered'] = ('rows343', pts, org, dict(origin_index=idx, max_range=1.2, min_range=0.15, min_count=2, max_moving_fraction=0.5))
-    pts, org, idx = _random_rays()
+    pts, org, idx = ah.random_rays()
     c['random'] = ('third', pts, org, dict(origin_index=idx, margin=0.2))
     c['random_range'] = ('third', pts, org, dict(origin_index=idx, max_range=1.5, min_range=0.35))
     # exact ties: every t_a equal at every step; a face start with a negative direction (t = -0.0 steps at once)
@@ -289,7 +201,7 @@ def _cases():
     c['bound_last'] = ('bound', ends, starts, dict(origin_index=index, max_range=0.1, min_range=0.012))
     c['bound_through'] = ('bound', ends, starts, dict(origin_index=index, max_range=0.1, min_range=0.03))
     # accum_keep's ratio boundaries: one ray to the centre of every voxel of RATIO_SPEC
-    rays = _centres([v for v, _, _ in RATIO_SPEC], 1.0)
+    rays = ah.centres([v for v, _, _ in RATIO_SPEC], 1.0)
     for k, (flt, _) in enumerate(RATIO_FILTERS):
         c['ratio_filter%d' % k] = ('ratio', rays, np.array([[0.5, 0.5, 0.5]]), dict(flt))
     # a filtered-out voxel in front of a kept one is transparent
@@ -298,7 +210,7 @@ def _cases():
                      ('count6', dict(min_count=6))):
         c['transparent_' + tag] = ('filter',) + along + (flt,)
     # occlusion: a second wall behind the first
-    far = _centres([(40, y, z) for y, z in WALL_YZ[::7]], 0.1)
+    far = ah.centres([(40, y, z) for y, z in WALL_YZ[::7]], 0.1)
     c['walls_near'] = ('walls', far, SENSOR, dict())
     c['walls_min_range'] = ('walls', far, SENSOR, dict(min_range=3.75))
     c['walls_min_count'] = ('walls', far, SENSOR, dict(min_count=2))
@@ -311,9 +223,7 @@ CASE_NAMES = sorted(CASES)
 
 
 # ---- the host build and the restatement, each computed once per case ------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def host_exe(tmp_path_factory):
-    return build_host_driver(tmp_path_factory.mktemp('raycast_host'), 'accum_raycast_host_driver')
+host_exe = ah.host_driver_fixture('accum_raycast_host_driver', 'raycast_host')
 
 
 def _run_host(exe, tmp_path, tag, records, targets, origins, voxel_size, spare=3, origin_index=None, pose=None, max_range=None, min_range=0.0, margin=0.0,
@@ -323,30 +233,14 @@ def _run_host(exe, tmp_path, tag, records, targets, origins, voxel_size, spare=3
     origins = np.asarray(origins, np.float64).reshape(-1, 3)
     head = [n, origins.shape[0], m, m + spare, max_steps, 0 if origin_index is None else 1, 0 if pose is None else 1, min_count,
             0 if max_moving_fraction is None else 1]
-    src, dst = os.path.join(str(tmp_path), tag + '.in'), os.path.join(str(tmp_path), tag + '.out')
-    with open(src, 'wb') as f:
-        f.write(np.array(head, np.int64).tobytes())
-        f.write(np.array([voxel_size, min_range, -1.0 if max_range is None else max_range, margin,
-                          0.0 if max_moving_fraction is None else max_moving_fraction], np.float64).tobytes())
-        f.write(np.ascontiguousarray(targets, np.float32).tobytes())
-        f.write(np.ascontiguousarray(origins).tobytes())
-        if origin_index is not None:
-            f.write(np.ascontiguousarray(origin_index, np.int32).tobytes())
-        if pose is not None:
-            f.write(np.ascontiguousarray(pose, np.float64).tobytes())
-        f.write(np.ascontiguousarray(keys, np.int64).tobytes())
-        f.write(np.ascontiguousarray(acc, np.int64).tobytes())
-    subprocess.check_call([exe, src, dst])
-    raw = open(dst, 'rb').read()
-    out = dict(counters=np.frombuffer(raw, np.int64, 7).tolist(), kept=int(np.frombuffer(raw, np.int64, 1, 56)[0]))
-    off = 64
-    for name in yref.FIELDS:
-        shape = (n, 3) if name in yref.WIDE else (n,)
-        k = int(np.prod(shape))
-        out[name] = np.frombuffer(raw, yref.DTYPES[name], k, off).reshape(shape).copy()
-        off += k * np.dtype(yref.DTYPES[name]).itemsize
+    raw = ah.run_driver(exe, tmp_path, tag, np.array(head, np.int64),
+                        np.array([voxel_size, min_range, -1.0 if max_range is None else max_range, margin,
+                                  0.0 if max_moving_fraction is None else max_moving_fraction], np.float64),
+                        np.ascontiguousarray(targets, np.float32), origins, b'' if origin_index is None else np.ascontiguousarray(origin_index, np.int32),
+                        b'' if pose is None else np.ascontiguousarray(pose, np.float64), ah.map_bytes(keys, acc))
+    out, off = ah.unpack(raw, 64, [(f, yref.DTYPES[f], (n, 3) if f in yref.WIDE else (n,)) for f in yref.FIELDS])
     assert off == len(raw)
-    return out
+    return dict(out, counters=np.frombuffer(raw, np.int64, 7).tolist(), kept=int(np.frombuffer(raw, np.int64, 1, 56)[0]))
 
 
 _hosted, _restated = {}, {}
@@ -369,17 +263,12 @@ def _restate(name):
     return _restated[name]
 
 
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.int32, 8: np.int64}[a.dtype.itemsize]) if a.dtype.kind == 'f' else a
-
-
 def _assert_same(got, want, what):
     assert list(got['counters']) == list(want['counters']), (what, got['counters'], want['counters'])
     for f in yref.FIELDS:
         assert got[f].dtype == want[f].dtype and got[f].shape == want[f].shape, (what, f)
-        assert np.array_equal(_bits(got[f]), _bits(want[f])), (what, f, np.flatnonzero(_bits(got[f]).reshape(got[f].shape[0], -1) !=
-                                                                                         _bits(want[f]).reshape(got[f].shape[0], -1))[:5])
+        assert np.array_equal(ah.bits(got[f]), ah.bits(want[f])), (what, f, np.flatnonzero(ah.bits(got[f]).reshape(got[f].shape[0], -1) !=
+                                                                                         ah.bits(want[f]).reshape(got[f].shape[0], -1))[:5])
 
 
 def _assert_well_formed(res, voxel_size, what):
@@ -397,7 +286,7 @@ def _assert_well_formed(res, voxel_size, what):
 # ---- CPU: host build == restatement -------------------------------------------------------------------------------------------------------------------------
 def test_scenes_hold_what_they_are_for():
     assert [_scene('rows%d' % m).num_voxels for m in (0, 1, 65, 343)] == [0, 1, 65, 343]
-    walked, decoys = _bound_voxels()
+    walked, decoys = ah.walked_voxels()
     assert _scene('bound').num_voxels == len(set(walked + decoys)) and len(decoys) == 4
     assert 20000 < _scene('third').num_voxels < 22500 and 1100 < _scene('sparse').num_voxels < 1500
     assert np.rad2deg(np.arccos((np.trace(POSE[:3, :3]) - 1) / 2)) > 10.0                    # no pose near the identity
@@ -421,7 +310,7 @@ def test_sizes_and_validity():
     first, last = _restate('bad_first')[0], _restate('bad_last')[0]
     assert (first['status'][:5] == DROPPED).all() and (first['status'][5:] != DROPPED).all() and first['counters'][1] == 5
     for f in yref.FIELDS:
-        assert np.array_equal(_bits(first[f][:5]), _bits(last[f][-5:])) and np.array_equal(_bits(first[f][5:]), _bits(last[f][:-5])), f
+        assert np.array_equal(ah.bits(first[f][:5]), ah.bits(last[f][-5:])) and np.array_equal(ah.bits(first[f][5:]), ah.bits(last[f][:-5])), f
     first, last = _restate('bad_origins_first')[0], _restate('bad_origins_last')[0]
     assert (first['status'][:5] == DROPPED).all() and (first['status'][5:] != DROPPED).all() and (last['status'][-5:] == DROPPED).all()
     assert np.array_equal(first['status'][5:], last['status'][:6]) and (first['status'][5:] == HIT).sum() >= 1
@@ -466,7 +355,7 @@ def test_exact_boundaries_of_the_extent():
 
 def test_index_bound_and_decoys():
     """Rays that leave the grid through the last voxel of an axis stop there: MISS, and no decoy is ever the hit."""
-    walked, decoys = _bound_voxels()
+    walked, decoys = ah.walked_voxels()
     ends = _bound_rays()[3]
     first, last, through = (_restate(n)[0] for n in ('bound_first', 'bound_last', 'bound_through'))
     for res in (first, last, through):
@@ -548,8 +437,8 @@ def test_depth_bound_on_random_centroids():
     middle): the 'third' block filled with random points."""
     rs = np.random.RandomState(23)
     pts = rs.uniform(-1.0, 1.0, (6000, 3)).astype(np.float32)
-    r = _points_map(0.1, [(pts, None, 0)])
-    targets, origins, index = _random_rays()
+    r = ah.points_map(0.1, [(pts, None, 0)])
+    targets, origins, index = ah.random_rays()
     res = yref.raycast(r, targets, origins, origin_index=index, max_range=3.0)
     _assert_well_formed(res, 0.1, 'random centroids')
     hit = res['status'] == HIT
@@ -640,37 +529,14 @@ def test_header_binding_and_argument_checks():
 
 
 # ---- GPU ----------------------------------------------------------------------------------------------------------------------------------------------------
-def _device_cloud(r):
-    """The restatement's map as an AccumulatedCloud on the device, through load()."""
-    from pcaccumulation_amd.accumulate import AccumulatedCloud
-    keys, acc, stamps = r.records()
-    buf = io.BytesIO()
-    np.savez(buf, keys=keys, acc=acc.reshape(5, -1), stamps=stamps.reshape(2, -1), voxel_size=np.float64(r.voxel_size), dropped=np.int64(r.dropped))
-    buf.seek(0)
-    return AccumulatedCloud.load(buf, DEV)
-
-
 _clouds = {}
 
 
 def _cloud(scene):
     """A device map per scene, shared: raycast does not modify it (a test below says so)."""
     if scene not in _clouds:
-        _clouds[scene] = _device_cloud(_scene(scene))
+        _clouds[scene] = ah.device_cloud(_scene(scene))
     return _clouds[scene]
-
-
-def _snapshot(m):
-    n = m.num_voxels
-    keys, acc, stamps = m._cur
-    return (n, keys[:n].clone(), acc[:, :n].clone(), stamps[:, :n].clone(), None if m._pierced is None else m._pierced.clone(), m._state.clone())
-
-
-def _assert_unchanged(m, snap, what):
-    now = _snapshot(m)
-    assert now[0] == snap[0], what
-    for a, b in zip(now[1:], snap[1:]):
-        assert (a is None and b is None) or torch.equal(a, b), what
 
 
 def _cast(m, targets, origins, args):
@@ -688,7 +554,7 @@ def _assert_device_equals(res, want, what):
         w = torch.from_numpy(want[f]).to(DEV)
         assert res[f].is_cuda and res[f].dtype == w.dtype and res[f].shape == w.shape, (what, f)
         if w.dtype.is_floating_point:
-            assert torch.equal(res[f].view(torch.int64 if w.dtype == torch.float64 else torch.int32), torch.from_numpy(_bits(want[f])).to(DEV)), (what, f)
+            assert torch.equal(res[f].view(torch.int64 if w.dtype == torch.float64 else torch.int32), torch.from_numpy(ah.bits(want[f])).to(DEV)), (what, f)
         assert torch.equal(res[f], w), (what, f)
 
 
@@ -698,18 +564,18 @@ def test_kernel_equals_the_host_build_gpu(host_exe, tmp_path, name):
     scene, targets, origins, args = CASES[name]
     host = _host(host_exe, tmp_path, name)
     m = _cloud(scene)
-    snap = _snapshot(m)
+    snap = ah.snapshot(m, whole_sidecar=True)
     res = _cast(m, targets, origins, args)
     _assert_device_equals(res, host, name)
     again = _cast(m, targets, origins, args)                                      # a second run gives the same bits
     assert all(torch.equal(res[f], again[f]) for f in res)
-    _assert_unchanged(m, snap, name)                                              # read-only: keys, records, stamps, sidecar, state words, num_voxels
+    ah.assert_unchanged(m, snap, name)                                              # read-only: keys, records, stamps, sidecar, state words, num_voxels
 
 
 def _short_rays(n=70001):
     """n rays of 0.3 - 1.5 m that end on the wavy sheet (jittered), each from its own origin, mostly from above."""
     rs = np.random.RandomState(77)
-    targets = _wavy()[rs.randint(0, 270400, n)] + rs.uniform(-0.03, 0.03, (n, 3)).astype(np.float32)
+    targets = ah.wavy()[rs.randint(0, 270400, n)] + rs.uniform(-0.03, 0.03, (n, 3)).astype(np.float32)
     direction = rs.normal(0, 1, (n, 3))
     direction[:, 2] = np.abs(direction[:, 2]) + 0.3
     direction /= np.linalg.norm(direction, axis=1, keepdims=True)
@@ -718,7 +584,7 @@ def _short_rays(n=70001):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('args', [dict(), dict(max_range=2.0, min_range=0.1, min_count=4, pose=_rot(0.002, -0.001, 0.003, (0.01, 0.02, -0.01)))],
+@pytest.mark.parametrize('args', [dict(), dict(max_range=2.0, min_range=0.1, min_count=4, pose=ah.rot_xyz(0.002, -0.001, 0.003, (0.01, 0.02, -0.01)))],
                          ids=['to_target', 'range_filtered_pose'])
 def test_kernel_on_76661_voxels_and_70001_rays_gpu(host_exe, tmp_path, args):
     r = _scene('wavy')
@@ -727,22 +593,22 @@ def test_kernel_on_76661_voxels_and_70001_rays_gpu(host_exe, tmp_path, args):
     assert r.num_voxels == 76661 and n == 70001 and n % 64 != 0 and n % 256 != 0
     host = _run_host(host_exe, tmp_path, 'wavy', r.records(), targets, origins, r.voxel_size, origin_index=index, **args)
     m = _cloud('wavy')
-    snap = _snapshot(m)
+    snap = ah.snapshot(m, whole_sidecar=True)
     res = _cast(m, targets, origins, dict(args, origin_index=index))
     _assert_device_equals(res, host, 'wavy')
     _assert_well_formed(host, r.voxel_size, 'wavy')
     assert host['counters'][3] > 20000 and host['counters'][4] > 100 and host['counters'][1] == host['counters'][2] == 0
     assert all(torch.equal(res[f], v) for f, v in _cast(m, targets, origins, dict(args, origin_index=index)).items())
-    _assert_unchanged(m, snap, 'wavy')
+    ah.assert_unchanged(m, snap, 'wavy')
 
 
 @pytest.mark.gpu
 def test_identities_with_extract_gpu():
     from pcaccumulation_amd import native
-    r = _points_map(0.1, [(np.random.RandomState(23).uniform(-1.0, 1.0, (6000, 3)).astype(np.float32), None, 0),
+    r = ah.points_map(0.1, [(np.random.RandomState(23).uniform(-1.0, 1.0, (6000, 3)).astype(np.float32), None, 0),
                           (np.random.RandomState(24).uniform(-1.0, 1.0, (3000, 3)).astype(np.float32), np.arange(3000) % 5 == 0, 1)])
-    m = _device_cloud(r)
-    targets, origins, index = _random_rays()
+    m = ah.device_cloud(r)
+    targets, origins, index = ah.random_rays()
     for f in (dict(), dict(min_count=2, max_moving_fraction=0.0)):
         e = m.extract(**f)
         res = _cast(m, targets, origins, dict(f, origin_index=index, max_range=3.0))
@@ -765,16 +631,16 @@ def test_tie_to_see_through_gpu():
     """On a fresh sidecar, after see_through of the same rays with the same margin and no stamp, every voxel raycast(max_range=None, min_count=1) hits
     has pierced >= 1: the two walk the same voxels.  When see_through's hit counter stays 0, no ray hits."""
     from pcaccumulation_amd import native
-    targets, origins, index = _random_rays()
+    targets, origins, index = ah.random_rays()
     pts, idx = torch.from_numpy(targets).to(DEV), torch.from_numpy(index).to(DEV)
-    m = _device_cloud(_scene('third'))
+    m = ah.device_cloud(_scene('third'))
     counters = m.see_through(pts, origins, idx, margin=0.2)
     res = m.raycast(pts, origins, idx, max_range=None, margin=0.2, min_count=1)
     hit = res['status'] == HIT
     assert int(hit.sum()) > 300 and int(counters[native.PIERCE_HITS]) >= int(hit.sum())
     assert bool((m.pierced()[res['row'][hit].long()] >= 1).all())
     assert int(counters[native.PIERCE_WALKED]) == 400 - int((res['status'] == SKIPPED).sum()) - int((res['status'] == DROPPED).sum())
-    away = _device_cloud(_records(0.1, {(25, 25, 25): (1, 0), (-25, 25, 25): (1, 0)}))
+    away = ah.device_cloud(ah.records(0.1, {(25, 25, 25): (1, 0), (-25, 25, 25): (1, 0)}))
     counters = away.see_through(pts, origins, idx, margin=0.2)
     res = away.raycast(pts, origins, idx, max_range=None, margin=0.2, min_count=1)
     assert int(counters[native.PIERCE_HITS]) == 0 and int(counters[native.PIERCE_WALKED]) > 380 and not bool((res['status'] == HIT).any())
@@ -784,7 +650,7 @@ def test_tie_to_see_through_gpu():
 def test_new_objects_and_ghosts_gpu():
     """The restatement's classes on the device, and after see_through of the scan and prune(min_pierced=1) no beam goes through anything the map holds."""
     r = _scene('ghost')
-    m = _device_cloud(r)
+    m = ah.device_cloud(r)
     scan = _assert_ghost_classes(*(_restate('ghost')[0][f] for f in ('depth', 'length')))
     res = _cast(m, scan, SENSOR, dict(max_range=30.0))
     _assert_device_equals(res, _restate('ghost')[0], 'ghost')
@@ -858,9 +724,9 @@ def test_life_cycle_gpu(tmp_path):
     from pcaccumulation_amd.accumulate import AccumulatedCloud
     m, r, pierced = AccumulatedCloud(0.1, DEV, 64), ref.ReferenceMap(0.1), {}
     origin = np.array([[0.05, 0.05, 0.05]])
-    slab = _centres([(x, y, z) for x in (5, 6, 7) for y in range(-2, 3) for z in (-1, 0, 1)], 0.1)
-    behind = _centres([(20, y, z) for y in (-4, -2, 0, 3, 5) for z in (-2, 0, 2)], 0.1)
-    rays = np.concatenate([behind, slab[::3] + np.float32(0.03), _centres([(-9, 0, 0), (6, 9, 9)], 0.1), [[NAN, 0, 0]]]).astype(np.float32)
+    slab = ah.centres([(x, y, z) for x in (5, 6, 7) for y in range(-2, 3) for z in (-1, 0, 1)], 0.1)
+    behind = ah.centres([(20, y, z) for y in (-4, -2, 0, 3, 5) for z in (-2, 0, 2)], 0.1)
+    rays = np.concatenate([behind, slab[::3] + np.float32(0.03), ah.centres([(-9, 0, 0), (6, 9, 9)], 0.1), [[NAN, 0, 0]]]).astype(np.float32)
     _both_add(m, r, np.concatenate([slab, slab[::2]]), 0)
     a = _assert_raycast_equals_restatement(m, r, rays, origin, 'after add', max_range=3.0, min_count=2)
     every = _assert_raycast_equals_restatement(m, r, rays, origin, 'after add, all', max_range=3.0)
@@ -872,7 +738,7 @@ def test_life_cycle_gpu(tmp_path):
     assert m.prune(min_pierced=1)['pierced'] == rref.prune(r, pierced, min_pierced=1)[4] > 0
     c = _assert_raycast_equals_restatement(m, r, rays, origin, 'after prune', max_range=3.0)
     assert int(c['counters'][3]) < int(every['counters'][3])                       # the rays that went through the slab now find nothing
-    _both_add(m, r, _centres([(-9, 0, 0), (6, 0, 0), (6, 0, 0), (6, 9, 9), (20, 0, 0)], 0.1), 2)
+    _both_add(m, r, ah.centres([(-9, 0, 0), (6, 0, 0), (6, 0, 0), (6, 9, 9), (20, 0, 0)], 0.1), 2)
     d = _assert_raycast_equals_restatement(m, r, rays, origin, 'add after prune', max_range=3.0)
     assert int(d['counters'][3]) > int(c['counters'][3])
     path = os.path.join(str(tmp_path), 'map.npz')
@@ -907,7 +773,7 @@ def test_raycast_results_on_the_model_forward_gpu(golden):
     with torch.no_grad():
         out = model(inp)
     m = AccumulatedCloud(0.2, dev, 64).add_results(out, inp, stamp=0)
-    pose, offset = _rot(0, 0, 0.01, (0.02, -0.01, 0.0)), (0.1, -0.2, 1.8)
+    pose, offset = ah.rot_xyz(0, 0, 0.01, (0.02, -0.01, 0.0)), (0.1, -0.2, 1.8)
     res = m.raycast_results(out, inp, pose=pose, sensor_offset=offset, max_range=30.0)
     ego = out['ego_motion_est'][0].detach().double()
     origins = torch.stack([((ego[t, :3, 0] * offset[0] + ego[t, :3, 1] * offset[1]) + ego[t, :3, 2] * offset[2]) + ego[t, :3, 3] for t in range(ego.shape[0])])
@@ -922,8 +788,8 @@ def test_raycast_results_on_the_model_forward_gpu(golden):
 @pytest.mark.gpu
 def test_bad_arguments_launch_nothing_gpu():
     from pcaccumulation_amd import native
-    m = _device_cloud(_scene('rows65'))
-    snap = _snapshot(m)
+    m = ah.device_cloud(_scene('rows65'))
+    snap = ah.snapshot(m, whole_sidecar=True)
     n = 10
     targets, origins, index = _block_rays(n, 1)
     pts, org, idx = torch.from_numpy(targets).to(DEV), torch.from_numpy(origins).to(DEV), torch.from_numpy(index).to(DEV)
@@ -951,7 +817,7 @@ def test_bad_arguments_launch_nothing_gpu():
         assert call(ptr=ptr[:k] + [None] + ptr[k + 1:]) == -1, k                  # a NULL output of non-zero size
     torch.cuda.synchronize()
     assert all(bool((t == 7).all()) for t in list(out.values()) + [counters])     # nothing was launched: outputs and counters keep their poison
-    _assert_unchanged(m, snap, 'bad arguments')
+    ah.assert_unchanged(m, snap, 'bad arguments')
     for bad in (dict(min_range=-0.1), dict(min_range=INF), dict(margin=-1.0), dict(margin=NAN), dict(max_range=-1.0), dict(max_range=NAN), dict(max_steps=0),
                 dict(max_steps=(1 << 16) + 1), dict(max_range=1.0, margin=0.1), dict(pose=np.eye(3)), dict(origin_index=idx[:5])):
         with pytest.raises(ValueError):
@@ -966,4 +832,4 @@ def test_bad_arguments_launch_nothing_gpu():
     zero = native.accum_raycast(**dict(good, targets=pts[:0], origin_index=idx[:0], out={k: t[:0] for k, t in out.items()}))   # n = 0: the zero counters only
     assert zero['counters'].tolist() == [0] * 7 and all(bool((t == 7).all()) for t in out.values())
     assert call() == 0 and counters.tolist()[0] == n and not bool((out['status'] == 7).any())
-    _assert_unchanged(m, snap, 'after all')
+    ah.assert_unchanged(m, snap, 'after all')

@@ -6,20 +6,18 @@ np.linalg.solve): correspondence rows, counts, status and iterations equal; pose
 GPU leg: the kernels against the host build BIT FOR BIT at max_iter = 1 and at convergence on every scene of the CPU leg; reproducibility; the map
 untouched; drifted windows registered before their add; argument errors; the model tie-in."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import accumulate_helpers as ah
 import accumulate_reference as ref
 import accumulate_register_reference as rref
-from helpers import build_host_driver
+from accumulate_helpers import DEV
+from helpers import ROOT
 from pcaccumulation_amd.config import default_config
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = 'cuda:0'
-EDGE = 1 << 20
 MAX_ITER = 20
 # Pose (largest entry of the 3 x 4 difference), fitness and rmse of the host build against the restatement: ten times the largest difference measured
 # on the CPU over every scene below, floored at 1e-9.  Measured (profiles/accum_register_parity.txt): 4.9e-15 after one update, 3.1e-16 at convergence
@@ -29,31 +27,7 @@ SPHERE_CENTRE = np.array([0.3, -0.2, 0.1])
 
 
 # ---- scenes ----------------------------------------------------------------------------------------------------------------------------
-def _rot(rx, ry, rz, t):
-    """Rotations about x, y, z (radians, composed z y x) and a translation, float64 [4,4]."""
-    T = np.eye(4)
-    for axis, a in ((0, rx), (1, ry), (2, rz)):
-        i, j = [(1, 2), (2, 0), (0, 1)][axis]
-        R = np.eye(4)
-        R[i, i], R[i, j], R[j, i], R[j, j] = np.cos(a), -np.sin(a), np.sin(a), np.cos(a)
-        T = R @ T
-    T[:3, 3] = t
-    return T
-
-
-CORNER = np.array([0.43, -1.21, 0.27])
-TRUE_POSE = _rot(np.deg2rad(0.6), np.deg2rad(-0.5), np.deg2rad(0.7), (0.02, -0.015, 0.017))      # about 1 degree and 0.3 voxel of 0.1
-
-
-def _corner(seed, per_sheet, noise=0.01):
-    """Three mutually orthogonal noisy sheets of 2 m x 2 m that meet in CORNER (world frame, float64)."""
-    rs = np.random.RandomState(seed)
-    sheets = []
-    for axis in range(3):
-        p = rs.uniform(0.0, 2.0, (per_sheet, 3))
-        p[:, axis] = rs.normal(0, noise, per_sheet)
-        sheets.append(p + CORNER)
-    return np.concatenate(sheets)
+TRUE_POSE = ah.rot_xyz(np.deg2rad(0.6), np.deg2rad(-0.5), np.deg2rad(0.7), (0.02, -0.015, 0.017))      # about 1 degree and 0.3 voxel of 0.1
 
 
 def _into_scan_frame(world, pose):
@@ -69,40 +43,14 @@ def _sphere(seed, n):
     return SPHERE_CENTRE + d * (1.5 + rs.normal(0, 0.005, n))[:, None]
 
 
-def _centres(idx, vs):
-    return ((np.asarray(idx, np.float64) + 0.5) * vs).astype(np.float32)
-
-
 def _bound_voxels():
-    """Section 9d's index-bound scene: 3 x 3 x 3 clusters that touch -2^20 and 2^20 - 1 on every axis, and DECOYS exactly where a key with an
-    overflowed or borrowed y / z field would land."""
-    vox = []
-    for axis in range(3):
-        for lo in (-EDGE, EDGE - 3):
-            for a in range(3):
-                for b in (-1, 0, 1):
-                    for c in (-1, 0, 1):
-                        v = [b, c]
-                        v.insert(axis, lo + a)
-                        vox.append(v)
-    cluster = np.array(vox, np.int64)
-    decoys = []
-    for x, y, z in cluster.tolist():
-        if y == EDGE - 1:
-            decoys.append((x + 1, -EDGE, z))
-        if y == -EDGE:
-            decoys.append((x - 1, EDGE - 1, z))
-        if z == EDGE - 1:
-            decoys.append((x, y + 1, -EDGE))
-        if z == -EDGE:
-            decoys.append((x, y - 1, EDGE - 1))
-    decoys = np.array([d for d in decoys if all(-EDGE <= c < EDGE for c in d)], np.int64)
-    return cluster, decoys
+    """Section 9d's index-bound clusters and their decoys (accumulate_helpers.bound_voxels) as int64 arrays [N,3]."""
+    return tuple(np.array(v, np.int64) for v in ah.bound_voxels())
 
 
 def _tie_sheet():
     """Voxel size 2^-3: a 6 x 6 sheet of voxel centres, every number exact.  Interior voxels get the normal (0, 0, 1)."""
-    return _centres([(x, y, 0) for x in range(6) for y in range(6)], 0.125)
+    return ah.centres([(x, y, 0) for x in range(6) for y in range(6)], 0.125)
 
 
 _BAD_ROWS = np.array([[np.nan, 0, 0], [0, np.inf, 0], [0, 0, -np.inf], [32768.0, 0, 0], [0, -32768.0, 0]], np.float32)
@@ -111,7 +59,7 @@ _BAD_ROWS = np.array([[np.nan, 0, 0], [0, np.inf, 0], [0, 0, -np.inf], [32768.0,
 def _map_adds(name):
     """-> (voxel_size, [(points, moving or None, stamp)]) of the map a case registers against."""
     if name == 'corner':
-        return 0.1, [(_corner(11, 9000).astype(np.float32), None, 0)]
+        return 0.1, [(ah.corner(11, 9000).astype(np.float32), None, 0)]
     if name == 'plane':                                                          # z is one float32 for every point: every valid normal is exactly (0, 0, 1)
         rs = np.random.RandomState(5)
         xy = rs.uniform(-1.0, 1.0, (6000, 2))
@@ -120,11 +68,11 @@ def _map_adds(name):
         return 0.1, [(_sphere(7, 40000).astype(np.float32), None, 0)]
     if name == 'bound':
         cluster, decoys = _bound_voxels()
-        return 0.01, [(_centres(np.concatenate([cluster, decoys]), 0.01), None, 0)]
+        return 0.01, [(ah.centres(np.concatenate([cluster, decoys]), 0.01), None, 0)]
     if name == 'tie':
         return 0.125, [(_tie_sheet(), None, 0)]
     if name == 'flagged':                                                        # the corner with points predicted moving, two stamps
-        pts = _corner(11, 9000).astype(np.float32)
+        pts = ah.corner(11, 9000).astype(np.float32)
         mv = np.random.RandomState(8).uniform(0, 1, pts.shape[0]) < 0.01
         perm = np.random.RandomState(9).permutation(pts.shape[0])
         a, b = perm[:14000], perm[14000:]
@@ -134,7 +82,7 @@ def _map_adds(name):
 
 
 def _corner_scan(n_per_sheet=1300, seed=12):
-    return _into_scan_frame(_corner(seed, n_per_sheet), TRUE_POSE)
+    return _into_scan_frame(ah.corner(seed, n_per_sheet), TRUE_POSE)
 
 
 def _case(name):
@@ -143,12 +91,12 @@ def _case(name):
     if name == 'corner':
         return dict(map='corner', points=scan)
     if name == 'corner_init':                                                    # a start that is not the identity, and a tighter gate
-        init = _rot(0, 0, np.deg2rad(0.3), (0.01, 0.0, 0.0))
+        init = ah.rot_xyz(0, 0, np.deg2rad(0.3), (0.01, 0.0, 0.0))
         return dict(map='corner', points=scan, init_pose=init, max_distance=0.08)
     if name == 'plane':
         rs = np.random.RandomState(6)
         pts = np.concatenate([rs.uniform(-0.8, 0.8, (2000, 2)), 0.05 + rs.normal(0, 0.01, (2000, 1))], 1)
-        return dict(map='plane', points=_into_scan_frame(pts, _rot(0.004, -0.003, 0, (0, 0, 0.01))), init_pose=_rot(0, 0, 0.002, (0.001, 0.002, 0)))
+        return dict(map='plane', points=_into_scan_frame(pts, ah.rot_xyz(0.004, -0.003, 0, (0, 0, 0.01))), init_pose=ah.rot_xyz(0, 0, 0.002, (0.001, 0.002, 0)))
     if name == 'sphere':
         vp = SPHERE_CENTRE[None]
         return dict(map='sphere', points=_into_scan_frame(_sphere(17, 4000), TRUE_POSE), viewpoints=vp)
@@ -211,9 +159,7 @@ def _args(case, max_iter):
 
 
 # ---- the host build ----------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def host_exe(tmp_path_factory):
-    return build_host_driver(tmp_path_factory.mktemp('accr'), 'accum_register_host_driver')
+host_exe = ah.host_driver_fixture('accum_register_host_driver', 'accr')
 
 
 def _run_host(exe, tmp_path, records, voxel_size, points, a, spare=3):
@@ -222,31 +168,21 @@ def _run_host(exe, tmp_path, records, voxel_size, points, a, spare=3):
     m, n = keys.shape[0], points.shape[0]
     vp = np.zeros((0, 3)) if a['viewpoints'] is None else np.ascontiguousarray(a['viewpoints'], np.float64).reshape(-1, 3)
     frac = a['max_moving_fraction']
-    path, out = str(tmp_path / ('r%d.bin' % len(os.listdir(str(tmp_path))))), str(tmp_path / ('r%d.out' % len(os.listdir(str(tmp_path)))))
-    with open(path, 'wb') as f:
-        f.write(np.array([m, max(m + spare, 1), a['min_count'], 0 if frac is None else 1, a['radius'], a['min_neighbors'], vp.shape[0], a['stamp_base'], n,
-                          0 if a['moving'] is None else 1, a['max_iter'], 0 if a['init_pose'] is None else 1], np.int64).tobytes())
-        f.write(np.array([0.0 if frac is None else frac, voxel_size, voxel_size if a['max_distance'] is None else a['max_distance']], np.float64).tobytes())
-        f.write(np.ascontiguousarray(keys, np.int64).tobytes() + np.ascontiguousarray(acc, np.int64).tobytes() + np.ascontiguousarray(stamps, np.int32).tobytes())
-        f.write(vp.tobytes() + np.ascontiguousarray(points, np.float32).tobytes())
-        if a['moving'] is not None:
-            f.write((np.asarray(a['moving']) != 0).astype(np.uint8).tobytes())
-        if a['init_pose'] is not None:
-            f.write(np.ascontiguousarray(a['init_pose'], np.float64).tobytes())
-    subprocess.check_call([exe, path, out])
-    raw = open(out, 'rb').read()
+    head = [m, max(m + spare, 1), a['min_count'], 0 if frac is None else 1, a['radius'], a['min_neighbors'], vp.shape[0], a['stamp_base'], n,
+            0 if a['moving'] is None else 1, a['max_iter'], 0 if a['init_pose'] is None else 1]
+    raw = ah.run_driver(exe, tmp_path, 'r%d' % len(os.listdir(str(tmp_path))), np.array(head, np.int64),
+                        np.array([0.0 if frac is None else frac, voxel_size, voxel_size if a['max_distance'] is None else a['max_distance']], np.float64),
+                        ah.map_bytes(keys, acc, stamps), vp, np.ascontiguousarray(points, np.float32),
+                        b'' if a['moving'] is None else (np.asarray(a['moving']) != 0).astype(np.uint8),
+                        b'' if a['init_pose'] is None else np.ascontiguousarray(a['init_pose'], np.float64), suffix='.bin')
     res = {'pose': np.frombuffer(raw, np.float64, 16).reshape(4, 4), 'fitness': np.frombuffer(raw, np.float64, 1, 128)[0],
            'rmse': np.frombuffer(raw, np.float64, 1, 136)[0]}
     res['iterations'], res['status'], res['correspondences'] = (int(x) for x in np.frombuffer(raw, np.int32, 3, 144))
     v = int(np.frombuffer(raw, np.int64, 1, 156)[0])
-    off = 164
-    for k, dt, count, shape in (('normals32', np.float32, 3 * v, (v, 3)), ('flags', np.uint8, v, (v,)), ('first', np.int64, n, (n,)), ('last', np.int64, n, (n,)),
-                                ('evaluations', np.int64, 1, ())):
-        x = np.frombuffer(raw, dt, count, off)
-        off += x.nbytes
-        res[k] = x.reshape(shape)
+    tables, off = ah.unpack(raw, 164, [('normals32', np.float32, (v, 3)), ('flags', np.uint8, (v,)), ('first', np.int64, (n,)), ('last', np.int64, (n,)),
+                                       ('evaluations', np.int64, ())])
     assert off == len(raw)
-    return res
+    return dict(res, **tables)
 
 
 def _host(exe, tmp_path, name, max_iter):
@@ -471,8 +407,8 @@ def test_registering_drifted_windows_before_their_add_gpu(host_exe, tmp_path):
     about a degree and a third of a voxel).  Adding with the drifted poses puts every wall into neighbouring voxels; registering each window against
     the map so far before its add gives strictly fewer voxels -- at most what the restatement, run the same way, gets."""
     from pcaccumulation_amd.accumulate import AccumulatedCloud
-    truth = [np.eye(4), TRUE_POSE, _rot(np.deg2rad(-0.7), np.deg2rad(0.4), np.deg2rad(-0.6), (-0.02, 0.02, -0.015))]
-    windows = [_into_scan_frame(_corner(20 + k, 1500), truth[k]) for k in range(3)]
+    truth = [np.eye(4), TRUE_POSE, ah.rot_xyz(np.deg2rad(-0.7), np.deg2rad(0.4), np.deg2rad(-0.6), (-0.02, 0.02, -0.015))]
+    windows = [_into_scan_frame(ah.corner(20 + k, 1500), truth[k]) for k in range(3)]
     drifted = [np.eye(4)] * 3                                                    # the pose each window comes with ignores its motion
     plain, reg, rmap = AccumulatedCloud(0.1, DEV, 64), AccumulatedCloud(0.1, DEV, 64), ref.ReferenceMap(0.1)
     for k, pts in enumerate(windows):
@@ -514,7 +450,7 @@ def test_argument_errors_and_tables_of_another_filter_gpu():
     # normal tables of another filter: values the host knows -- the call says BAD_TABLE, returns init_pose and runs no round
     nrm = m.normals(min_count=3)
     assert 0 < nrm['flags'].shape[0] < m.num_voxels
-    init = torch.from_numpy(_rot(0, 0, 0.01, (0.1, 0.2, 0.3))).to(DEV)
+    init = torch.from_numpy(ah.rot_xyz(0, 0, 0.01, (0.1, 0.2, 0.3))).to(DEV)
     out = native.accum_register(pts, None, init, m.voxel_size, m.voxel_size, 5, m._cur, m.num_voxels, 1, None, nrm['normals'], nrm['flags'])
     assert int(out[4]) == native.REGISTER_BAD_TABLE and torch.equal(out[0], init) and int(out[3]) == 0 and int(out[5]) == 0
     assert float(out[1]) == 0.0 and float(out[2]) == 0.0
@@ -550,7 +486,7 @@ def test_register_results_on_the_model_forward_gpu(golden):
         out = model(inp)
     flag = out['mos_est'].argmax(1) == 1
     m = AccumulatedCloud(0.2, dev, 64).add_results(out, inp, stamp=0)
-    init = _rot(0, 0, 0.01, (0.02, -0.01, 0.0))
+    init = ah.rot_xyz(0, 0, 0.01, (0.02, -0.01, 0.0))
     res = m.register_results(out, inp, init_pose=init, max_iter=5)
     same = m.register(out['rec_est'], init, flag, max_iter=5)
     assert all(torch.equal(res[k], same[k]) for k in res)
