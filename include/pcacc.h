@@ -1063,6 +1063,80 @@ int pcacc_accum_select(const int64_t *in_keys, const int64_t *in_acc, const int3
                        int64_t *counters, int64_t *state, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C14. Observed space: a second sorted voxel table, on C4's grid and key, of the voxels that measured laser rays crossed -- where the sensor looked
+ * and found nothing.  With it a voxel has three states: occupied (a cloud holds it), free (rays crossed it), unknown (neither).  Replaces the copy
+ * of every scan to the host and a ray walk into a dict there.  Counts no ray ends, keeps no hit / miss ratio or probability, decays nothing, merges
+ * no two tables and regrids none.
+ * The table: `capacity` rows, of which the first state[PCACC_OBSERVE_NUM_VOXELS] are in use, ascending and duplicate-free in `keys`:
+ *   keys   [capacity] i64          C4's key
+ *   rays   [capacity] i64          walked rays, over all calls, whose walk visited the voxel
+ *   stamps [2][capacity] i32       smallest and largest stamp of the calls in which some ray visited the voxel
+ *   state  [PCACC_OBSERVE_STATE_WORDS] i64 device words, all 0 for an empty table (indices below)
+ * pcacc_accum_observe.  Inputs
+ *   points, n, moving, origins, n_origins, origin_index, pose     the scan and origin arguments of pcacc_accum_pierce
+ *   stamp; voxel_size; margin >= 0, finite; use_range, max_range >= 0 (read when use_range != 0); max_steps in [1, 2^16]
+ *   visit_capacity in [1, 2^31)                                   the visits one call may make: the workspace is sized by it
+ * A ray is C7's ray, bit for bit, up to the visit (csrc/accum_observe.h restates the loop of csrc/accum_pierce.h; the host build asserts the two
+ * visit sequences equal): end points, the drop rule, "moving is SKIPPED", t_end with margin and max_range, the walk, max_steps and TRUNCATED.
+ * Every visited voxel contributes its key -- the start voxel included, whether or not any cloud keeps the voxel.  The walk is monotone: one ray
+ * visits a voxel at most once.  After the call rays[v] has grown by the walked rays of this call that visited v, and the stamps of those voxels
+ * have taken `stamp` into their minimum and maximum.  All integers: the table is a function of the SET of (ray, stamp) pairs -- not of the order
+ * of the rays, of how they were split over calls, or of the run.
+ * Route: count the visits of every ray; scan; V = their total.  V > visit_capacity: state[STATUS] = PCACC_OBSERVE_TOO_MANY, state[NEEDED_VISITS]
+ * = V and nothing else happens (the caller splits the rays).  Otherwise the walk runs again and writes its keys; radix sort; the length of a run
+ * of equal keys is a voxel's ray count in this call (no atomics); every run is searched in the table; m + misses against out_capacity:
+ * PCACC_ACCUM_TOO_SMALL and state[NEEDED] exactly as in pcacc_accum_add; otherwise the merge, OUT OF PLACE, into out_*.  Up to that decision no
+ * table is touched.  On any status other than PCACC_ACCUM_OK, NUM_VOXELS and the cumulative counters stay: a retry counts nothing twice.  On OK
+ * state[NUM_VOXELS] = rows of out_* and the five cumulative counters grow by this call's rays walked, dropped, skipped, truncated and by V.
+ * A state[NUM_VOXELS] outside [0, in_capacity] addresses nothing: PCACC_ACCUM_BAD_STATE.
+ * Return value: PCACC_E_ARG, and nothing is launched, for n outside [0, 2^30], n * max_steps >= 2^31 (the offsets are an int32 scan), S < 1, a
+ * visit_capacity outside [1, 2^31), a margin that is negative or not finite, use_range with a max_range that is not >= 0, max_steps outside
+ * [1, 2^16], a voxel size that is not positive and finite, a capacity above 2^30, out_capacity < 1, a NULL table of non-zero size or an output
+ * table that shares memory with an input table; PCACC_E_WORKSPACE for a workspace that is too small.  n = 0 launches nothing (the state is not
+ * touched); in_capacity = 0 or state[NUM_VOXELS] = 0 is a plain build of the table.
+ * pcacc_accum_observed_lookup: what the first m rows of a table know about n rows.  Exactly one of points [n,3] f32 (through pose, C4's transform
+ * and validity rule) and coords [n,3] i32 (voxel indices; valid iff every index lies in [-2^20, 2^20)) is non-NULL.
+ *   out_status [n] u8 = a sum of PCACC_OBSERVED_VALID, _SEEN (the table holds the key), _ENOUGH (SEEN and rays >= min_rays)
+ *   out_rays [n] i64, out_stamps [2][n] i32 (t_first, t_last): the row's record; 0 where unseen or invalid.  Every output of every row is written.
+ *   counters [PCACC_OBSERVED_COUNTERS] i64 (written, not added to): rows, valid, seen, enough.
+ * One launch, one lane per row, nothing read back.  Every table index comes out of a binary search and is checked against m.
+ * Return value: PCACC_E_ARG, and nothing is launched, for n outside [0, 2^30], m outside [0, capacity] (a table that does not fit addresses
+ * nothing), a capacity above 2^30, a voxel size that is not positive and finite, both or neither of points and coords with n > 0, or a NULL
+ * table or output of non-zero size.  n = 0 writes the zero counters and launches nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_OBSERVE_STATE_WORDS 16
+#define PCACC_OBSERVE_NUM_VOXELS 0     /* rows in use */
+#define PCACC_OBSERVE_STATUS 1         /* of the last call: PCACC_ACCUM_OK, _TOO_SMALL, _BAD_STATE or PCACC_OBSERVE_TOO_MANY */
+#define PCACC_OBSERVE_NEEDED 2         /* rows the last call's merged table takes */
+#define PCACC_OBSERVE_NEEDED_VISITS 3  /* V of the last call that was TOO_MANY */
+#define PCACC_OBSERVE_CALL_VISITS 4    /* V of the last call */
+#define PCACC_OBSERVE_CALL_VOXELS 5    /* distinct voxels the last call's rays visited */
+#define PCACC_OBSERVE_WALKED 6         /* cumulative, of all calls that ended OK: rays walked, ... */
+#define PCACC_OBSERVE_DROPPED 7
+#define PCACC_OBSERVE_SKIPPED 8
+#define PCACC_OBSERVE_TRUNCATED 9
+#define PCACC_OBSERVE_VISITS 10        /* ... and voxels visited */
+#define PCACC_OBSERVE_TOO_MANY 3
+#define PCACC_OBSERVED_VALID 1
+#define PCACC_OBSERVED_SEEN 2
+#define PCACC_OBSERVED_ENOUGH 4
+#define PCACC_OBSERVED_COUNTERS 4
+#define PCACC_OBSERVED_ROWS 0
+#define PCACC_OBSERVED_N_VALID 1
+#define PCACC_OBSERVED_N_SEEN 2
+#define PCACC_OBSERVED_N_ENOUGH 3
+int pcacc_accum_observe_workspace_bytes(int64_t n, int64_t visit_capacity, int64_t in_m, size_t *bytes /*host*/);
+int pcacc_accum_observe(const float *points, int64_t n, const uint8_t *moving, const double *origins, int64_t n_origins,
+                        const int32_t *origin_index, const double *pose, int32_t stamp, double voxel_size, double margin, int32_t use_range,
+                        double max_range, int32_t max_steps, int64_t visit_capacity, const int64_t *in_keys, const int64_t *in_rays,
+                        const int32_t *in_stamps, int64_t in_capacity, int64_t *out_keys, int64_t *out_rays, int32_t *out_stamps,
+                        int64_t out_capacity, int64_t *state, void *workspace, size_t workspace_bytes, void *stream);
+int pcacc_accum_observed_lookup_workspace_bytes(int64_t n, int64_t m, size_t *bytes /*host*/);
+int pcacc_accum_observed_lookup(const float *points, const int32_t *coords, int64_t n, const double *pose, double voxel_size, const int64_t *keys,
+                                const int64_t *rays, const int32_t *stamps, int64_t capacity, int64_t m, int64_t min_rays, int64_t *out_rays,
+                                int32_t *out_stamps, uint8_t *out_status, int64_t *counters, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

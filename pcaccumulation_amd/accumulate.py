@@ -30,6 +30,13 @@ coordinate sums), so the map does not depend on the order of the points, on the 
     gone = last_week.difference(m, max_distance=0.05)            # nearest centroid within a voxel; what one map has and the other has nothing near, as
     ground = m.select(static['points'][:, 2] < ground_z, min_count=2, max_moving_fraction=0.0)   # a map; any rows of extract() as a map: C13, section 9m
 
+ObservedSpace records, beside a cloud, the voxels the measured rays crossed -- where the sensor looked and found nothing (C14, section 9n).  Filled with
+space_now.observe_results(results, input_dict, pose=pose, stamp=k) next to m.add_results(...), it tells what is gone from what was never looked at:
+
+    gone = last_week.difference(m, max_distance=0.05)
+    seen = space_now.lookup_voxels(gone.extract()['coords'])
+    really_gone = seen['status'] & native.OBSERVED_ENOUGH != 0
+
 There is no CPU path: a CPU tensor raises native.NativeError."""
 import numpy as np
 import torch
@@ -857,6 +864,293 @@ class AccumulatedCloud(object):
             self._pierced = torch.zeros((capacity,), dtype=torch.int32, device=self.device)
             self._pierced[:m] = torch.from_numpy(pierced).to(self.device)
             self._pierce_counters = torch.from_numpy(counters).to(self.device)
+        return self
+
+
+def _observe_chunks(n, max_steps):
+    """[(lo, hi)]: the rays 0..n cut into runs with (hi - lo) * max_steps < 2^31, the most visits the int32 offsets of one call hold."""
+    per_call = (native.OBSERVE_MAX_VISITS - 1) // int(max_steps)
+    return [(lo, min(lo + per_call, n)) for lo in range(0, n, per_call)]
+
+
+def _observed_tables(capacity, device):
+    return (torch.empty((capacity,), dtype=torch.int64, device=device), torch.empty((capacity,), dtype=torch.int64, device=device),
+            torch.empty((2, capacity), dtype=torch.int32, device=device))
+
+
+def _voxel_keys(coords):
+    """coords [V,3] integers, every index in [-2^20, 2^20) -> C4's keys [V] i64."""
+    c = coords.to(torch.int64)
+    return ((c[:, 0] + native.ACCUM_IDX_BIAS) << 42) | ((c[:, 1] + native.ACCUM_IDX_BIAS) << 21) | (c[:, 2] + native.ACCUM_IDX_BIAS)
+
+
+_OBSERVE_COUNTERS = ('walked', 'dropped', 'skipped', 'truncated', 'visits')
+UNKNOWN, FREE, OCCUPIED = 0, 1, 2                                  # occupancy()'s three states
+
+
+class ObservedSpace(object):
+    """Where the sensor looked and found nothing: the voxels that measured rays crossed, as a second sorted table on the device (include/pcacc.h C14,
+    DESIGN.md section 9n).  Per voxel the number of rays that crossed it and the first / last stamp of the calls in which one did.  With an
+    AccumulatedCloud on the same grid a voxel is OCCUPIED, FREE or UNKNOWN (occupancy()); its own lookup() works at any voxel size, so free space may
+    be kept coarser than the cloud.  All integers: the table is a function of the set of (ray, stamp) pairs it was given.  No CPU path."""
+
+    def __init__(self, voxel_size, device='cuda', capacity=1 << 20, visit_budget=1 << 26):
+        voxel_size = float(voxel_size)
+        if not (voxel_size > 0.0 and np.isfinite(voxel_size)):
+            raise ValueError('voxel_size must be a positive finite number, got %r' % voxel_size)
+        if not 1 <= int(capacity) <= native.ACCUM_MAX_CAPACITY:
+            raise ValueError('capacity must lie in [1, 2^30], got %r' % capacity)
+        if not 1 <= int(visit_budget) < native.OBSERVE_MAX_VISITS:
+            raise ValueError('visit_budget must lie in [1, 2^31), got %r' % visit_budget)
+        self.voxel_size = voxel_size
+        self.device = torch.device(device)
+        self.capacity = int(capacity)
+        self.visit_budget = int(visit_budget)
+        self._cur = self._alt = self._state = None           # device memory is taken at the first observe
+        self._n = 0
+        self._counters = [0] * len(_OBSERVE_COUNTERS)
+        self.splits = 0                                      # times a call's rays had to be cut for the visit budget, since clear()
+
+    # ---- state -------------------------------------------------------------------------------------------------------------------------
+    @property
+    def num_voxels(self):
+        return self._n
+
+    @property
+    def counters(self):
+        """{'walked', 'dropped', 'skipped', 'truncated', 'visits'}: rays and visited voxels of every observe since clear(), Python integers."""
+        return dict(zip(_OBSERVE_COUNTERS, self._counters))
+
+    def _ensure(self):
+        if self.device.type != 'cuda':
+            raise native.NativeError('ObservedSpace lives on the GPU (got device %s); the HIP path has no CPU fallback' % self.device)
+        if self._cur is None:
+            self._cur = _observed_tables(self.capacity, self.device)
+            self._state = torch.zeros((native.OBSERVE_STATE_WORDS,), dtype=torch.int64, device=self.device)
+
+    def _write_state(self):
+        host = [0] * native.OBSERVE_STATE_WORDS
+        host[native.OBSERVE_NUM_VOXELS] = self._n
+        host[native.OBSERVE_WALKED:native.OBSERVE_WALKED + len(_OBSERVE_COUNTERS)] = self._counters
+        self._state.copy_(torch.tensor(host, dtype=torch.int64))
+
+    def clear(self):
+        self._n = 0
+        self._counters = [0] * len(_OBSERVE_COUNTERS)
+        self.splits = 0
+        if self._state is not None:
+            self._state.zero_()
+
+    _pose = AccumulatedCloud._pose
+
+    # ---- observe -----------------------------------------------------------------------------------------------------------------------
+    def observe(self, points, origins, origin_index=None, pose=None, moving=None, stamp=0, margin=None, max_range=None, max_steps=4096):
+        """Record the voxels the measured rays of a scan cross (include/pcacc.h C14).  The arguments are see_through()'s and a ray is its ray, bit for
+        bit: points [n,3] f32 (device, scan frame); origins [3] or [S,3]; origin_index [n] integers (device; None = row 0); pose [4,4] scan-to-world;
+        moving [n] (non-zero: the ray is skipped); margin (None = 2 voxel_size): the ray stops this far in front of the point it measured; max_range;
+        max_steps in [1, 2^16].  stamp: one integer for the call.  Every voxel a walked ray visits, its start voxel included, gains one ray and takes
+        the stamp into its first / last.
+        The rays are cut into calls of fewer than 2^31 possible visits; a call whose rays make more than visit_budget visits is cut again.  The table
+        grows by doubling as add() does.  One read-back of the state words per attempt.  -> self."""
+        n = _scan_points('observe', 'points', points, native.ACCUM_MAX_POINTS)
+        _scan_rows('observe', 'moving', moving, n)
+        _scan_rows('observe', 'origin_index', origin_index, n)
+        origins = _origins(origins)
+        margin = 2.0 * self.voxel_size if margin is None else float(margin)
+        if not (margin >= 0.0 and np.isfinite(margin)):
+            raise ValueError('margin must be a finite number >= 0, got %r' % margin)
+        if max_range is not None and not float(max_range) >= 0.0:
+            raise ValueError('max_range must be >= 0 or None, got %r' % max_range)
+        max_steps = int(max_steps)
+        if not 1 <= max_steps <= native.PIERCE_MAX_STEPS:
+            raise ValueError('max_steps must lie in [1, 2^16], got %r' % max_steps)
+        if self.visit_budget < max_steps:
+            raise ValueError('visit_budget %d is below max_steps %d: a single ray must fit' % (self.visit_budget, max_steps))
+        if not -0x80000000 <= int(stamp) <= 0x7fffffff:
+            raise ValueError('stamp must fit 32 bits, got %r' % stamp)
+        pose = self._pose(pose)
+        if n == 0:
+            return self
+        self._ensure()
+        pts = points.detach().float().contiguous()
+        mv = (moving != 0).to(torch.uint8).contiguous() if moving is not None else None
+        idx = _origin_rows(origin_index, origins.shape[0])
+        org = origins.to(device=self.device, dtype=torch.float64).contiguous()
+        work = _observe_chunks(n, max_steps)[::-1]                 # a stack: the next rays on top
+        while work:
+            lo, hi = work.pop()
+            needed = self._observe_rows(pts[lo:hi], None if mv is None else mv[lo:hi], org, None if idx is None else idx[lo:hi], pose, int(stamp), margin,
+                                        max_range, max_steps)
+            if needed:                                             # more visits than the budget: cut these rays and go on
+                pieces = min(-(-needed // self.visit_budget), hi - lo)
+                if pieces < 2:
+                    raise native.NativeError('accum_observe: %d rays make %d visits, which a budget of %d must hold' % (hi - lo, needed, self.visit_budget))
+                self.splits += 1
+                cuts = [lo + (hi - lo) * k // pieces for k in range(pieces + 1)]
+                work.extend((a, b) for a, b in list(zip(cuts[:-1], cuts[1:]))[::-1] if b > a)
+        return self
+
+    def _observe_rows(self, pts, mv, org, idx, pose, stamp, margin, max_range, max_steps):
+        """One run of rays through the double-the-tables loop of add().  -> 0, or the visits of a run that exceeds the budget (nothing has changed)."""
+        visit_capacity = min(self.visit_budget, pts.shape[0] * max_steps)
+        out_cap = self.capacity
+        while True:
+            if self._alt is None or self._alt[0].shape[0] != out_cap:
+                self._alt = None                                   # release before taking the larger tables
+                self._alt = _observed_tables(out_cap, self.device)
+            native.accum_observe(pts, mv, org, idx, pose, stamp, self.voxel_size, margin, max_range, max_steps, visit_capacity, self._cur, self._n, self._alt,
+                                 self._state)
+            state = self._state.tolist()                           # the one read-back of an attempt
+            status = state[native.OBSERVE_STATUS]
+            if status == native.ACCUM_OK:
+                break
+            if status == native.OBSERVE_TOO_MANY:
+                return state[native.OBSERVE_NEEDED_VISITS]
+            if status != native.ACCUM_TOO_SMALL:
+                raise native.NativeError('accum_observe: the state words do not describe the table (status %d)' % status)
+            need = state[native.OBSERVE_NEEDED]
+            if need > native.ACCUM_MAX_CAPACITY:
+                raise native.NativeError('accum_observe: the table would take %d voxels, more than 2^30' % need)
+            while out_cap < need:                                  # growth by doubling; the table so far is untouched
+                out_cap = min(2 * out_cap, native.ACCUM_MAX_CAPACITY)
+        self._cur, self._alt = self._alt, self._cur
+        self.capacity = out_cap
+        self._n = state[native.OBSERVE_NUM_VOXELS]
+        self._counters = state[native.OBSERVE_WALKED:native.OBSERVE_WALKED + len(_OBSERVE_COUNTERS)]
+        return 0
+
+    def observe_results(self, results, input_dict, pose=None, sensor_offset=(0, 0, 0), stamp=0, **kw):
+        """observe() of a test / val-mode forward, with the rays see_through_results builds: the points are results['rec_est'] with
+        results['mos_est'].argmax(1) == 1 as `moving`, the origin of a point is the sensor position of its frame in the anchor frame.  One sample per
+        batch."""
+        _one_sample(results, input_dict, 'observe_results')
+        return self.observe(results['rec_est'], _sensor_origins(results, sensor_offset), input_dict['time_indice'][:, 1], pose,
+                            results['mos_est'].argmax(1) == 1, stamp, **kw)
+
+    # ---- read --------------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _min_rays(min_rays):
+        min_rays = int(min_rays)
+        if min_rays < 1:
+            raise ValueError('min_rays must be at least 1, got %r' % min_rays)
+        return min_rays
+
+    def extract(self, min_rays=1):
+        """One row per voxel that at least min_rays rays crossed, in ascending (x, y, z) voxel order: coords [V,3] i32, centers [V,3] f32 (the middle
+        of the voxel), rays [V] i64, t_first, t_last [V] i32."""
+        min_rays = self._min_rays(min_rays)
+        self._ensure()
+        keys, rays, stamps = (t[..., :self._n] for t in self._cur)
+        keep = rays >= min_rays
+        keys = keys[keep]
+        coords = torch.stack([(keys >> 42) & 0x1fffff, (keys >> 21) & 0x1fffff, keys & 0x1fffff], 1) - native.ACCUM_IDX_BIAS
+        centers = ((coords.to(torch.float64) + 0.5) * self.voxel_size).to(torch.float32)
+        return {'coords': coords.to(torch.int32), 'centers': centers, 'rays': rays[keep], 't_first': stamps[0][keep], 't_last': stamps[1][keep]}
+
+    def lookup(self, points, pose=None, min_rays=1):
+        """What the table knows at every point of a scan: points [n,3] f32 (device), pose [4,4] scan-to-world (None = identity).
+        -> dict of device tensors, one row per point: status [n] u8, a sum of native.OBSERVED_VALID (the point is finite and inside the grid),
+        OBSERVED_SEEN (a ray crossed its voxel), OBSERVED_ENOUGH (at least min_rays did); rays [n] i64, t_first, t_last [n] i32 (0 where unseen);
+        counters [4] i64: rows, valid, seen, enough.  Nothing is read back."""
+        _scan_points('lookup', 'points', points, native.ACCUM_MAX_POINTS)
+        min_rays = self._min_rays(min_rays)
+        pose = self._pose(pose)
+        self._ensure()
+        return native.accum_observed_lookup(points.detach().float().contiguous(), None, pose, self.voxel_size, self._cur, self._n, min_rays)
+
+    def lookup_voxels(self, coords, min_rays=1):
+        """lookup() of voxel index rows: coords [n,3] integers (device), e.g. extract()['coords'] of a cloud on the same grid.  A row with an index
+        outside [-2^20, 2^20) is not VALID."""
+        _scan_points('lookup_voxels', 'coords', coords, native.ACCUM_MAX_POINTS, 'rows')
+        if coords.dtype not in (torch.int32, torch.int64):
+            raise ValueError('coords must be int32 or int64 voxel indices, got %s' % coords.dtype)
+        min_rays = self._min_rays(min_rays)
+        self._ensure()
+        if coords.dtype == torch.int64:                            # an index outside the grid stays outside after the cast
+            coords = coords.clamp(-native.ACCUM_IDX_BIAS - 1, native.ACCUM_IDX_BIAS)
+        return native.accum_observed_lookup(None, coords.to(torch.int32).contiguous(), None, self.voxel_size, self._cur, self._n, min_rays)
+
+    def occupancy(self, cloud, coords, min_count=1, max_moving_fraction=None, min_rays=1):
+        """The state of every voxel index row of coords [n,3] -> [n] uint8: OCCUPIED (2) where cloud.extract(min_count, max_moving_fraction) holds the
+        voxel, else FREE (1) where at least min_rays rays crossed it, else UNKNOWN (0).  A key join, as AccumulatedCloud.pierced() is; cloud and
+        table on one grid and one device."""
+        if not isinstance(cloud, AccumulatedCloud):
+            raise TypeError('occupancy takes an AccumulatedCloud, got %s' % type(cloud).__name__)
+        if cloud.voxel_size != self.voxel_size:
+            raise ValueError('occupancy: voxel sizes %r and %r differ' % (self.voxel_size, cloud.voxel_size))
+        if _device_key(cloud.device) != _device_key(self.device):
+            raise ValueError('occupancy: the cloud lives on %s and the table on %s' % (cloud.device, self.device))
+        seen = self.lookup_voxels(coords, min_rays)['status']
+        out = ((seen & native.OBSERVED_ENOUGH) != 0).to(torch.uint8) * FREE
+        held = _voxel_keys(cloud.extract(min_count, max_moving_fraction)['coords'])       # ascending: extract is in key order
+        valid = (seen & native.OBSERVED_VALID) != 0
+        if held.shape[0] and coords.shape[0]:
+            keys = torch.where(valid, _voxel_keys(coords.clamp(-native.ACCUM_IDX_BIAS, native.ACCUM_IDX_BIAS - 1)), torch.full_like(held[:1], -1))
+            at = torch.searchsorted(held, keys).clamp(max=held.shape[0] - 1)
+            out[(held[at] == keys) & valid] = OCCUPIED
+        return out
+
+    # ---- forget ------------------------------------------------------------------------------------------------------------------------
+    def forget(self, before_stamp=None, box=None):
+        """Rows leave the table: those whose last stamp is below before_stamp and those whose voxel lies outside box = (lo [3], hi [3]), metres, both
+        faces' voxels included (prune()'s rule).  The order of the rows that stay is preserved.  -> the number kept."""
+        if before_stamp is not None and not -0x80000000 <= int(before_stamp) <= 0x7fffffff:
+            raise ValueError('before_stamp must fit 32 bits, got %r' % before_stamp)
+        if box is not None:
+            box = AccumulatedCloud._box_indices(self, box)
+        self._ensure()
+        n = self._n
+        keys, rays, stamps = self._cur
+        keep = torch.ones((n,), dtype=torch.bool, device=self.device)
+        if before_stamp is not None:
+            keep &= stamps[1, :n] >= int(before_stamp)
+        if box is not None:
+            k = keys[:n]
+            for shift, lo, hi in zip((42, 21, 0), box[0], box[1]):
+                c = ((k >> shift) & 0x1fffff) - native.ACCUM_IDX_BIAS
+                keep &= (c >= lo) & (c <= hi)
+        kept = int(keep.sum())                                     # the one read-back
+        if kept != n:
+            keys[:kept], rays[:kept] = keys[:n][keep], rays[:n][keep]
+            stamps[:, :kept] = stamps[:, :n][:, keep]
+            self._n = kept
+            self._write_state()
+        return kept
+
+    # ---- persistence -------------------------------------------------------------------------------------------------------------------
+    def records(self):
+        """The integer columns as host arrays: keys [M] i64, rays [M] i64, stamps [2,M] i32."""
+        if self._cur is None or self._n == 0:
+            return np.zeros((0,), np.int64), np.zeros((0,), np.int64), np.zeros((2, 0), np.int32)
+        keys, rays, stamps = self._cur
+        return keys[:self._n].cpu().numpy(), rays[:self._n].cpu().numpy(), stamps[:, :self._n].cpu().numpy()
+
+    def save(self, path):
+        keys, rays, stamps = self.records()
+        with open(path, 'wb') as f:
+            np.savez(f, keys=keys, rays=rays, stamps=stamps, counters=np.array(self._counters, np.int64), voxel_size=np.float64(self.voxel_size))
+
+    @classmethod
+    def load(cls, path, device='cuda'):
+        with np.load(path, allow_pickle=False) as z:
+            keys, rays, stamps, counters, voxel_size = z['keys'], z['rays'], z['stamps'], z['counters'], float(z['voxel_size'])
+        m = keys.shape[0]
+        if keys.dtype != np.int64 or rays.dtype != np.int64 or stamps.dtype != np.int32 or counters.dtype != np.int64 or keys.ndim != 1 \
+                or rays.shape != (m,) or stamps.shape != (2, m) or counters.shape != (len(_OBSERVE_COUNTERS),):
+            raise ValueError('%s does not hold the columns of an ObservedSpace' % path)
+        if m and (np.any(keys[1:] <= keys[:-1]) or keys[0] < 0):
+            raise ValueError('%s: the keys are not ascending' % path)
+        capacity = 64
+        while capacity < m:
+            capacity *= 2
+        self = cls(voxel_size, device, capacity)
+        self._ensure()
+        if m:
+            self._cur[0][:m] = torch.from_numpy(keys).to(self.device)
+            self._cur[1][:m] = torch.from_numpy(rays).to(self.device)
+            self._cur[2][:, :m] = torch.from_numpy(stamps).to(self.device)
+        self._n, self._counters = m, [int(v) for v in counters]
+        self._write_state()
         return self
 
 

@@ -42,21 +42,23 @@ static __global__ __launch_bounds__(ACCUM_KEEP_BLOCK) void accum_keep_kernel(con
         keep[i] = accum_keep(acc[accum_field(0, i, capacity)], acc[accum_field(1, i, capacity)], min_count, use_fraction != 0, max_moving_fraction) ? 1 : 0;
 }
 
+// [a, a + na) and [b, b + nb) share a byte; a NULL table shares nothing.
+static inline bool accum_bytes_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    if (!a || !b || !na || !nb) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
 // An out-of-place launch (prune, remove_components): some input table shares a byte with some output table.
 static inline bool accum_tables_overlap(const void *in_keys, const void *in_acc, const void *in_stamps, const void *in_pierced, int64_t in_capacity,
                                         const void *out_keys, const void *out_acc, const void *out_stamps, const void *out_pierced, int64_t out_capacity)
 {
-    // [a, a + na) and [b, b + nb) share a byte; a NULL table shares nothing.
-    auto overlap = [](const void *a, size_t na, const void *b, size_t nb) {
-        if (!a || !b || !na || !nb) return false;
-        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-        return x < y + nb && y < x + na;
-    };
     const void *in_tab[4] = {in_keys, in_acc, in_stamps, in_pierced};
     const void *out_tab[4] = {out_keys, out_acc, out_stamps, out_pierced};
     const size_t row_bytes[4] = {8, 8 * ACC_FIELDS, 4 * 2, 4};
     for (int a = 0; a < 4; ++a)
         for (int b = 0; b < 4; ++b)
-            if (overlap(in_tab[a], row_bytes[a] * (size_t)in_capacity, out_tab[b], row_bytes[b] * (size_t)out_capacity)) return true;
+            if (accum_bytes_overlap(in_tab[a], row_bytes[a] * (size_t)in_capacity, out_tab[b], row_bytes[b] * (size_t)out_capacity)) return true;
     return false;
 }

@@ -1090,6 +1090,87 @@ def accum_select(tables_in, m, pierced_in, min_count, max_moving_fraction, mask,
                                     _dev(counters, torch.int64, 'counters'), st, _dev(ws), ws.numel(), _stream()), 'accum_select')
 
 
+OBSERVE_STATE_WORDS = 16
+OBSERVE_NUM_VOXELS, OBSERVE_STATUS, OBSERVE_NEEDED, OBSERVE_NEEDED_VISITS, OBSERVE_CALL_VISITS, OBSERVE_CALL_VOXELS = 0, 1, 2, 3, 4, 5
+OBSERVE_WALKED, OBSERVE_DROPPED, OBSERVE_SKIPPED, OBSERVE_TRUNCATED, OBSERVE_VISITS = 6, 7, 8, 9, 10
+OBSERVE_TOO_MANY = 3                        # beside ACCUM_OK, ACCUM_TOO_SMALL, ACCUM_BAD_STATE
+OBSERVE_MAX_VISITS = 1 << 31                # n * max_steps of one call stays below it
+OBSERVED_VALID, OBSERVED_SEEN, OBSERVED_ENOUGH = 1, 2, 4
+OBSERVED_COUNTERS = 4
+OBSERVED_ROWS, OBSERVED_N_VALID, OBSERVED_N_SEEN, OBSERVED_N_ENOUGH = 0, 1, 2, 3
+
+
+def _observed_tables(tables, what):
+    """(keys [cap] i64, rays [cap] i64, stamps [2,cap] i32) -> their pointers and cap; see include/pcacc.h (C14)."""
+    keys, rays, stamps = tables
+    cap = keys.shape[0]
+    if keys.dim() != 1 or tuple(rays.shape) != (cap,) or tuple(stamps.shape) != (2, cap):
+        raise NativeError('%s: keys [cap], rays [cap], stamps [2,cap] expected, got %s %s %s' % (what, tuple(keys.shape), tuple(rays.shape), tuple(stamps.shape)))
+    return _dev(keys, torch.int64, what + ' keys'), _dev(rays, torch.int64, what + ' rays'), _dev(stamps, torch.int32, what + ' stamps'), cap
+
+
+def accum_observe_workspace_bytes(n, visit_capacity, m=0):
+    """The bytes one accum_observe call of n rays and visit_capacity visits takes (a host query, no GPU)."""
+    need = ctypes.c_size_t(0)
+    _check(lib().pcacc_accum_observe_workspace_bytes(int(n), int(visit_capacity), int(m), ctypes.byref(need)), 'accum_observe_workspace')
+    return need.value
+
+
+def accum_observe(points, moving, origins, origin_index, pose, stamp, voxel_size, margin, max_range, max_steps, visit_capacity, tables_in, m, tables_out,
+                  state):
+    """The voxels the rays origin -> point cross, into a table of observed space, out of place; see include/pcacc.h (C14).  points [n,3] f32 (n >= 1),
+    moving [n] u8 or None, origins [S,3] f64, origin_index [n] i32 or None (all 0), pose [4,4] f64 or None, max_range None = none; tables_in /
+    tables_out = (keys, rays, stamps) of the table before and after (m: the rows the caller believes in use, which sizes nothing the device
+    trusts), state [16] i64.  Nothing is read back: the caller looks at `state`."""
+    n = points.shape[0]
+    if points.dim() != 2 or points.shape[1] != 3 or n < 1:
+        raise NativeError('accum_observe: points must be [n,3] with n >= 1, got %s' % (tuple(points.shape),))
+    _shaped('accum_observe', 'moving', moving, (n,))
+    _shaped('accum_observe', 'origins', origins, ('S', 3))
+    _shaped('accum_observe', 'origin_index', origin_index, (n,))
+    _shaped('accum_observe', 'pose', pose, (4, 4))
+    _shaped('accum_observe', 'state', state, (OBSERVE_STATE_WORDS,))
+    pts = _dev(points, torch.float32, 'points')
+    ik, ir, is_, icap = _observed_tables(tables_in, 'accum_observe input')
+    ok, or_, os_, ocap = _observed_tables(tables_out, 'accum_observe output')
+    use_range, reach = _given(max_range, float)
+    ws = _workspace(lib().pcacc_accum_observe_workspace_bytes, points.device, n, int(visit_capacity), int(m))
+    _check(lib().pcacc_accum_observe(pts, n, _opt(moving, torch.uint8, 'moving'), _dev(origins, torch.float64, 'origins') if origins.shape[0] else None,
+                                     origins.shape[0], _opt(origin_index, torch.int32, 'origin_index'), _opt(pose, torch.float64, 'pose'), int(stamp),
+                                     float(voxel_size), float(margin), use_range, reach, int(max_steps), int(visit_capacity), ik, ir, is_, icap, ok, or_, os_,
+                                     ocap, _dev(state, torch.int64, 'state'), _dev(ws), ws.numel(), _stream()), 'accum_observe')
+
+
+def accum_observed_lookup(points, coords, pose, voxel_size, tables, m, min_rays, out=None, counters=None):
+    """What the first m rows of a table of observed space know about n rows; see include/pcacc.h (C14).  Exactly one of points [n,3] f32 (through pose
+    [4,4] f64 or None) and coords [n,3] i32 is given.  out: a dict of 'status' [n] u8, 'rays' [n] i64, 'stamps' [2,n] i32 to write into (None = new
+    ones), counters [4] i64 likewise.  -> {'status', 'rays', 't_first', 't_last', 'counters'} on the device; nothing is read back."""
+    if (points is None) == (coords is None):
+        raise NativeError('accum_observed_lookup: exactly one of points and coords')
+    rows = points if points is not None else coords
+    keys, rays, stamps, cap = _observed_tables(tables, 'accum_observed_lookup')
+    _shaped('accum_observed_lookup', 'points' if points is not None else 'coords', rows, ('n', 3))
+    _shaped('accum_observed_lookup', 'pose', pose, (4, 4))
+    n, m, dev = rows.shape[0], int(m), tables[0].device
+    src = _dev(rows, torch.float32 if points is not None else torch.int32, 'points' if points is not None else 'coords')
+    if out is None:
+        out = {'status': torch.empty((n,), dtype=torch.uint8, device=dev), 'rays': torch.empty((n,), dtype=torch.int64, device=dev),
+               'stamps': torch.empty((2, n), dtype=torch.int32, device=dev)}
+    _shaped('accum_observed_lookup', "out['status']", out['status'], (n,))
+    _shaped('accum_observed_lookup', "out['rays']", out['rays'], (n,))
+    _shaped('accum_observed_lookup', "out['stamps']", out['stamps'], (2, n))
+    if counters is None:
+        counters = torch.empty((OBSERVED_COUNTERS,), dtype=torch.int64, device=dev)
+    _shaped('accum_observed_lookup', 'counters', counters, (OBSERVED_COUNTERS,))
+    o_rays, o_stamps, o_status = _dev(out['rays'], torch.int64, 'rays'), _dev(out['stamps'], torch.int32, 'stamps'), _dev(out['status'], torch.uint8, 'status')
+    ws = _workspace(lib().pcacc_accum_observed_lookup_workspace_bytes, dev, n, m)
+    _check(lib().pcacc_accum_observed_lookup(src if n and points is not None else None, src if n and coords is not None else None, n,
+                                             _opt(pose, torch.float64, 'pose'), float(voxel_size), keys, rays, stamps, cap, m, int(min_rays),
+                                             o_rays if n else None, o_stamps if n else None, o_status if n else None, _dev(counters, torch.int64, 'counters'),
+                                             _dev(ws), ws.numel(), _stream()), 'accum_observed_lookup')
+    return {'status': out['status'], 'rays': out['rays'], 't_first': out['stamps'][0], 't_last': out['stamps'][1], 'counters': counters}
+
+
 RAYCAST_MISS, RAYCAST_HIT, RAYCAST_TRUNCATED, RAYCAST_SKIPPED, RAYCAST_DROPPED = 0, 1, 2, 3, 4
 RAYCAST_COUNTERS = 7
 RAYCAST_N_RAYS, RAYCAST_N_DROPPED, RAYCAST_N_SKIPPED, RAYCAST_N_HIT, RAYCAST_N_MISSED, RAYCAST_N_TRUNCATED, RAYCAST_N_VISITS = 0, 1, 2, 3, 4, 5, 6
