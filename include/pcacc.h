@@ -1137,6 +1137,70 @@ int pcacc_accum_observed_lookup(const float *points, const int32_t *coords, int6
                                 int32_t *out_stamps, uint8_t *out_status, int64_t *counters, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C15. Two tables of observed space (C14) into one, and a table under a rigid pose and / or a new voxel size.  Replaces the copy of both tables'
+ * records to the host, a numpy join there and a load.  Keeps no hit / miss ratio, re-observes nothing under a pose (that needs the rays), keeps no
+ * upper-bound column beside the maximum and no pyramid, takes two tables per call, merges out of place and filters no row.
+ * pcacc_accum_observed_merge: two tables on ONE grid, exact.  Inputs
+ *   a_keys, a_rays, a_stamps, a_capacity, ma          the first ma rows of table A;  b_*, b_capacity, mb: the first mb rows of table B
+ *   b_state [16] (read), state [16] (read and written) the state words of B and of A
+ * Both tables are ascending and duplicate-free.  A and B may be the same tables and the same state words: B's words are read before any word of
+ * `state` is written.  The result goes OUT OF PLACE to out_keys, out_rays, out_stamps (out_capacity rows): the keys are the ascending duplicate-free
+ * union.  A key in both tables gets rays = a + b (int64, not clamped: a ray count is at most the WALKED word of its table, which grows by at most
+ * 2^30 per observe call, so 2^63 is out of reach), t_first = the minimum, t_last = the maximum; a key in one table only is copied bit for bit.
+ * The tables and the five cumulative counters are, integer for integer, what ONE table would hold had it been given every observe of both.
+ *   counters [PCACC_OBSERVED_MERGE_COUNTERS] i64 (written, not added to): status, rows of the union, keys in both tables, keys of B that A lacks.
+ * Route: one lane per row of B searches A; the misses are scanned; one thread decides; old row p goes to p + (misses below it) with B's row added
+ * where it hit, missed row j to position + rank.  No atomic.  Up to the decision no table is touched.
+ * state[NUM_VOXELS] != ma or b_state[NUM_VOXELS] != mb: counters[STATUS] = PCACC_ACCUM_BAD_STATE, the other counters 0, and no table is addressed.
+ * NEEDED > out_capacity: counters[STATUS] = PCACC_ACCUM_TOO_SMALL, counters[NEEDED] says what it takes and NOTHING is written to out_* or state.
+ * Otherwise counters[STATUS] = 0 and state[NUM_VOXELS] = NEEDED, state[STATUS] = 0, state[NEEDED] = NEEDED, state[NEEDED_VISITS] =
+ * state[CALL_VISITS] = state[CALL_VOXELS] = 0 (a merge walks nothing), the five cumulative counters become A's plus B's; words 11 - 15 are left alone.
+ * Return value: PCACC_E_ARG, and nothing is launched, for ma or mb outside [0, capacity], a capacity above 2^30, a NULL table of non-zero size or
+ * an output table that shares a byte with an input table; PCACC_E_WORKSPACE for a workspace that is too small.  ma = mb = 0 writes the zero
+ * counters and launches nothing else.
+ * pcacc_accum_observed_regrid: a table under a pose and / or on a grid of out_voxel_size.  A row is treated as the CENTRE of its voxel: LOSSY by
+ * declared contract.  Per input row i < m, all float64 with no FMA contraction:
+ *   c = the voxel indices of the key;  p_a = (float64(c_a) + 0.5) * in_voxel_size
+ *   w_a, validity, i_a = floor(w_a / out_voxel_size) and the key exactly as pcacc_accum_regrid (C12) has them for a centroid: rows 0-2 of pose (NULL =
+ *   identity, through the same arithmetic), C4's validity rule (|w_a| < 32768 included)
+ * A row whose centre is invalid is never clamped and forms no address: it adds 1 to DROPPED_ROWS.  Rows that land on one key become one row: rays =
+ * the MAXIMUM over the sources, t_first = the minimum, t_last = the maximum.  The maximum and not C12's sum: a ray that crossed k source voxels of one
+ * destination voxel is one ray, and overstating the evidence for "free" is the unsafe direction.  For a nested coarsening the maximum is a lower
+ * bound on the rays that crossed the coarse voxel; under a rotation it is an estimate, and at an unchanged voxel size some destination voxels
+ * receive no centre at all (they read unknown): give a coarser out_voxel_size with a rotation.
+ * Two properties are part of the contract: (a) NULL or identity pose and out_voxel_size == in_voxel_size returns the input table bit for bit (for
+ * rows whose centre is valid, which every row that pcacc_accum_observe wrote is); (b) identity pose and out_voxel_size = f * in_voxel_size for an
+ * integer f gives floor(i / f) per axis.
+ * Output: a new sorted table in out_keys, out_rays, out_stamps (out_capacity >= m rows: the result never has more rows than the input, there is no
+ * "too small" path).  All sixteen words of out_state are written: NUM_VOXELS = rows out, the five cumulative counters copied from in_state, the
+ * rest 0.  The counters describe the RAYS the input was given, which are not walked again: VISITS no longer equals the sum of `rays`.
+ *   counters [PCACC_OBSERVED_REGRID_COUNTERS] i64 (written): rows in, rows out, rows dropped.
+ * in_state[NUM_VOXELS] != m: out_state[STATUS] = PCACC_ACCUM_BAD_STATE, the counters are zero (ROWS_IN != m tells the caller) and nothing else is
+ * written.  Integer max and min commute: the result is bit-identical from run to run.
+ * Return value: PCACC_E_ARG, and nothing is launched, for m outside [0, in_capacity], out_capacity < m, a capacity above 2^30, a voxel size on either
+ * side that is not positive and finite, a NULL table of non-zero size or an output table that shares a byte with an input table.
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_OBSERVED_MERGE_COUNTERS 4
+#define PCACC_OBSERVED_MERGE_STATUS 0  /* PCACC_ACCUM_OK, _TOO_SMALL or _BAD_STATE */
+#define PCACC_OBSERVED_MERGE_NEEDED 1  /* rows of the union */
+#define PCACC_OBSERVED_MERGE_SHARED 2  /* keys in both tables */
+#define PCACC_OBSERVED_MERGE_NEW 3     /* keys of B that A lacks */
+#define PCACC_OBSERVED_REGRID_COUNTERS 3
+#define PCACC_OBSERVED_REGRID_ROWS_IN 0
+#define PCACC_OBSERVED_REGRID_ROWS_OUT 1
+#define PCACC_OBSERVED_REGRID_DROPPED_ROWS 2
+int pcacc_accum_observed_merge_workspace_bytes(int64_t ma, int64_t mb, size_t *bytes /*host*/);
+int pcacc_accum_observed_merge(const int64_t *a_keys, const int64_t *a_rays, const int32_t *a_stamps, int64_t a_capacity, int64_t ma,
+                               const int64_t *b_keys, const int64_t *b_rays, const int32_t *b_stamps, int64_t b_capacity, int64_t mb,
+                               const int64_t *b_state, int64_t *out_keys, int64_t *out_rays, int32_t *out_stamps, int64_t out_capacity,
+                               int64_t *counters, int64_t *state, void *workspace, size_t workspace_bytes, void *stream);
+int pcacc_accum_observed_regrid_workspace_bytes(int64_t m, size_t *bytes /*host*/);
+int pcacc_accum_observed_regrid(const int64_t *in_keys, const int64_t *in_rays, const int32_t *in_stamps, int64_t in_capacity, int64_t m,
+                                const int64_t *in_state, const double *pose, double in_voxel_size, double out_voxel_size, int64_t *out_keys,
+                                int64_t *out_rays, int32_t *out_stamps, int64_t out_capacity, int64_t *counters, int64_t *out_state,
+                                void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

@@ -37,6 +37,9 @@ space_now.observe_results(results, input_dict, pose=pose, stamp=k) next to m.add
     seen = space_now.lookup_voxels(gone.extract()['coords'])
     really_gone = seen['status'] & native.OBSERVED_ENOUGH != 0
 
+Two sessions close the same way on both sides (C15, section 9o): m.merge(other_session) joins the clouds, space_now.merge(other_space) joins the observed
+spaces (with pose= when the other session kept its own frame), and space_now.occupancy(m, coords) still answers for the merged map.
+
 There is no CPU path: a CPU tensor raises native.NativeError."""
 import numpy as np
 import torch
@@ -910,6 +913,7 @@ class ObservedSpace(object):
         self._n = 0
         self._counters = [0] * len(_OBSERVE_COUNTERS)
         self.splits = 0                                      # times a call's rays had to be cut for the visit budget, since clear()
+        self.dropped_rows = 0                                # of a table that regrid() made: the rows that left the grid under the pose
 
     # ---- state -------------------------------------------------------------------------------------------------------------------------
     @property
@@ -1116,6 +1120,103 @@ class ObservedSpace(object):
             self._n = kept
             self._write_state()
         return kept
+
+    # ---- copy, regrid, merge -----------------------------------------------------------------------------------------------------------
+    def copy(self):
+        """An independent clone: device copies of the rows in use and of the state words, the counters and visit_budget; its `splits` start at 0.
+        merge() mutates its space, so `c = a.copy(); c.merge(b)` keeps a."""
+        c = ObservedSpace(self.voxel_size, self.device, self.capacity, self.visit_budget)
+        c._n, c._counters = self._n, list(self._counters)
+        if self._cur is not None:
+            c._ensure()
+            n = self._n
+            for dst, src in zip(c._cur, self._cur):
+                dst[..., :n].copy_(src[..., :n])
+            c._state.copy_(self._state)
+        return c
+
+    def _regrid(self, pose, voxel_size, capacity):
+        if pose is None and voxel_size is None:
+            raise ValueError('regrid needs a pose, a voxel_size or both')
+        voxel_size = self.voxel_size if voxel_size is None else float(voxel_size)
+        capacity = self.capacity if capacity is None else int(capacity)
+        if capacity < max(self._n, 1):
+            raise ValueError('capacity must be at least the %d rows of the table (the result never has more), got %r' % (self._n, capacity))
+        new = ObservedSpace(voxel_size, self.device, capacity, self.visit_budget)      # checks voxel_size and capacity
+        pose = self._pose(pose)
+        self._ensure()
+        new._ensure()
+        counters = torch.empty((native.OBSERVED_REGRID_COUNTERS,), dtype=torch.int64, device=self.device)
+        native.accum_observed_regrid(self._cur, self._n, self._state, pose, self.voxel_size, voxel_size, new._cur, counters, new._state)
+        host = counters.tolist()                                   # the one read-back of a regrid
+        if host[native.OBSERVED_REGRID_ROWS_IN] != self._n:
+            raise native.NativeError('accum_observed_regrid: the state words do not describe the table')
+        new._n = host[native.OBSERVED_REGRID_ROWS_OUT]
+        new._counters = list(self._counters)
+        new.dropped_rows = host[native.OBSERVED_REGRID_DROPPED_ROWS]
+        return new
+
+    def regrid(self, pose=None, voxel_size=None, capacity=None):
+        """This table under a rigid pose ([4,4] table-to-new-frame, tensor or array) and / or at another voxel size, as a NEW ObservedSpace on the same
+        device (include/pcacc.h C15); this one is not modified.  LOSSY by declared contract: a row is treated as the centre of its voxel.  Rows that
+        land in one new voxel become one row with the MAXIMUM of their ray counts (a ray that crossed several of them is one ray: the sum would
+        overstate the evidence for "free"), the minimum first and the maximum last stamp.  A row whose centre leaves the grid (or is not finite
+        under the pose) is dropped, never clamped; the result's attribute `dropped_rows` says how many.  The counters are carried over: they
+        describe the rays, and `visits` no longer equals the sum of `rays`.  Identity and the same voxel size return the same table; an integer
+        multiple of the voxel size is an exact coarsening.  With a rotation pick a COARSER voxel_size (twice this one): at the same size a
+        rotated grid leaves holes -- in one sample of a 30 degree turn about z, 13.4 % of the destination voxels received no centre, at twice the
+        size none -- and a hole reads UNKNOWN.  capacity (None = this one's) must hold this table's rows.  Only the three counters are read back."""
+        return self._regrid(pose, voxel_size, capacity)
+
+    def merge(self, other, pose=None):
+        """Take another table's voxels into this one, on the device (include/pcacc.h C15); `other` is not modified.
+        pose=None is the exact path: both tables on one grid (other.voxel_size == self.voxel_size, the same device), and the result is, integer for
+        integer, the table and the counters one ObservedSpace would hold had it been given every observe of both: ray counts added, first stamp the
+        minimum, last stamp the maximum.  With a pose ([4,4] other-to-world, tensor or array) `other` is first regridded under it onto this table's
+        voxel size (regrid: lossy by declared contract) and the result merged.
+        The capacity grows as in observe().  -> {'rows', 'shared', 'new', 'dropped_rows'}: rows of this table after the call, voxels both held,
+        voxels only `other` held, rows the regrid dropped -- Python integers, one read-back of the counters per attempt.  An empty `other` changes
+        nothing."""
+        if not isinstance(other, ObservedSpace):
+            raise TypeError('merge takes an ObservedSpace, got %s' % type(other).__name__)
+        if _device_key(other.device) != _device_key(self.device):
+            raise ValueError('merge: the maps live on %s and %s; save() / load() carries a map across' % (self.device, other.device))
+        if pose is None and other.voxel_size != self.voxel_size:
+            raise ValueError('merge: voxel sizes %r and %r differ; give pose= (np.eye(4) keeps the frame) or regrid() the other map first'
+                             % (self.voxel_size, other.voxel_size))
+        pose = self._pose(pose)
+        self._ensure()
+        other._ensure()
+        res = dict(rows=self._n, shared=0, new=0, dropped_rows=0)
+        if other._n == 0:
+            return res
+        if pose is not None:
+            other = other._regrid(pose, self.voxel_size, None)
+            res['dropped_rows'] = other.dropped_rows
+        counters = torch.empty((native.OBSERVED_MERGE_COUNTERS,), dtype=torch.int64, device=self.device)
+        out_cap = self.capacity
+        while True:
+            if self._alt is None or self._alt[0].shape[0] != out_cap:
+                self._alt = None                                   # release before taking the larger tables
+                self._alt = _observed_tables(out_cap, self.device)
+            native.accum_observed_merge(self._cur, self._n, other._cur, other._n, other._state, self._alt, counters, self._state)
+            host = counters.tolist()                               # the one read-back of an attempt
+            status = host[native.OBSERVED_MERGE_STATUS]
+            if status == native.ACCUM_OK:
+                break
+            if status != native.ACCUM_TOO_SMALL:
+                raise native.NativeError('accum_observed_merge: the state words do not describe the tables (status %d)' % status)
+            need = host[native.OBSERVED_MERGE_NEEDED]
+            if need > native.ACCUM_MAX_CAPACITY:
+                raise native.NativeError('accum_observed_merge: the table would take %d voxels, more than 2^30' % need)
+            while out_cap < need:                                  # growth by doubling; both tables are untouched
+                out_cap = min(2 * out_cap, native.ACCUM_MAX_CAPACITY)
+        self._cur, self._alt = self._alt, self._cur                # the table before the merge stays in self._alt, which the next observe overwrites
+        self.capacity = out_cap
+        self._n = host[native.OBSERVED_MERGE_NEEDED]
+        self._counters = [a + b for a, b in zip(self._counters, other._counters)]
+        res.update(rows=self._n, shared=host[native.OBSERVED_MERGE_SHARED], new=host[native.OBSERVED_MERGE_NEW])
+        return res
 
     # ---- persistence -------------------------------------------------------------------------------------------------------------------
     def records(self):

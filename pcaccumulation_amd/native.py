@@ -1171,6 +1171,46 @@ def accum_observed_lookup(points, coords, pose, voxel_size, tables, m, min_rays,
     return {'status': out['status'], 'rays': out['rays'], 't_first': out['stamps'][0], 't_last': out['stamps'][1], 'counters': counters}
 
 
+OBSERVED_MERGE_COUNTERS, OBSERVED_REGRID_COUNTERS = 4, 3
+OBSERVED_MERGE_STATUS, OBSERVED_MERGE_NEEDED, OBSERVED_MERGE_SHARED, OBSERVED_MERGE_NEW = 0, 1, 2, 3
+OBSERVED_REGRID_ROWS_IN, OBSERVED_REGRID_ROWS_OUT, OBSERVED_REGRID_DROPPED_ROWS = 0, 1, 2
+
+
+def accum_observed_merge(tables_a, ma, tables_b, mb, b_state, tables_out, counters, state):
+    """The first ma rows of table A and the first mb rows of table B of observed space, on one grid, as one table, out of place; see include/pcacc.h
+    (C15).  tables_* = (keys, rays, stamps); b_state [16] i64: B's state words (read), state [16] i64: A's (read and written).  A and B may be the
+    same.  Writes counters [4] i64 (status, needed, shared, new) and, when the status is ACCUM_OK, the tables and the state words; nothing is read
+    back."""
+    ak, ar, as_, acap = _observed_tables(tables_a, 'accum_observed_merge A')
+    bk, br, bs_, bcap = _observed_tables(tables_b, 'accum_observed_merge B')
+    ok, or_, os_, ocap = _observed_tables(tables_out, 'accum_observed_merge output')
+    _shaped('accum_observed_merge', 'counters', counters, (OBSERVED_MERGE_COUNTERS,))
+    _shaped('accum_observed_merge', 'b_state', b_state, (OBSERVE_STATE_WORDS,))
+    _shaped('accum_observed_merge', 'state', state, (OBSERVE_STATE_WORDS,))
+    ma, mb = int(ma), int(mb)
+    ws = _workspace(lib().pcacc_accum_observed_merge_workspace_bytes, tables_a[0].device, ma, mb)
+    _check(lib().pcacc_accum_observed_merge(ak, ar, as_, acap, ma, bk, br, bs_, bcap, mb, _dev(b_state, torch.int64, 'b_state'), ok, or_, os_, ocap,
+                                            _dev(counters, torch.int64, 'counters'), _dev(state, torch.int64, 'state'), _dev(ws), ws.numel(),
+                                            _stream()), 'accum_observed_merge')
+
+
+def accum_observed_regrid(tables_in, m, in_state, pose, in_voxel_size, out_voxel_size, tables_out, counters, out_state):
+    """The first m rows of a table of observed space under a pose ([4,4] f64 or None) on a grid of out_voxel_size, every row as the centre of its
+    voxel, out of place; see include/pcacc.h (C15).  tables_out = (keys, rays, stamps) of at least m rows; in_state [16] i64 (read), out_state
+    [16] i64: the new table's, every word written.  Writes counters [3] i64 (rows in, rows out, rows dropped); nothing is read back."""
+    ik, ir, is_, icap = _observed_tables(tables_in, 'accum_observed_regrid input')
+    ok, or_, os_, ocap = _observed_tables(tables_out, 'accum_observed_regrid output')
+    _shaped('accum_observed_regrid', 'pose', pose, (4, 4))
+    _shaped('accum_observed_regrid', 'counters', counters, (OBSERVED_REGRID_COUNTERS,))
+    _shaped('accum_observed_regrid', 'in_state', in_state, (OBSERVE_STATE_WORDS,))
+    _shaped('accum_observed_regrid', 'out_state', out_state, (OBSERVE_STATE_WORDS,))
+    m = int(m)
+    ws = _workspace(lib().pcacc_accum_observed_regrid_workspace_bytes, tables_in[0].device, m)
+    _check(lib().pcacc_accum_observed_regrid(ik, ir, is_, icap, m, _dev(in_state, torch.int64, 'in_state'), _opt(pose, torch.float64, 'pose'),
+                                             float(in_voxel_size), float(out_voxel_size), ok, or_, os_, ocap, _dev(counters, torch.int64, 'counters'),
+                                             _dev(out_state, torch.int64, 'out_state'), _dev(ws), ws.numel(), _stream()), 'accum_observed_regrid')
+
+
 RAYCAST_MISS, RAYCAST_HIT, RAYCAST_TRUNCATED, RAYCAST_SKIPPED, RAYCAST_DROPPED = 0, 1, 2, 3, 4
 RAYCAST_COUNTERS = 7
 RAYCAST_N_RAYS, RAYCAST_N_DROPPED, RAYCAST_N_SKIPPED, RAYCAST_N_HIT, RAYCAST_N_MISSED, RAYCAST_N_TRUNCATED, RAYCAST_N_VISITS = 0, 1, 2, 3, 4, 5, 6
