@@ -348,7 +348,7 @@ int pcacc_sample_subsets(const int32_t *counts, int32_t n_draws, int32_t k, uint
 /* Sinkhorn normalisation as a differentiable op (training) -- models/egomotion.py:100-137 with add_slack: the [P,k,k]
  * log-affinity is padded with a zero slack row / column, n_iters x (row, column) log-sum-exp normalisations that leave the
  * slack row / column themselves un-normalised, result = the un-padded block.  forward records the subtracted
- * log-sum-exps (lse_rows, lse_cols [n_iters][P][k]); backward replays the half-steps in reverse from log_alpha and those
+ * log-sum-exps (lse_rows, lse_cols [n_iters][P][k], may be NULL when n_iters = 0); backward replays the half-steps in reverse from log_alpha and those
  * vectors.  workspace: one padded [P,k+1,k+1] f32 matrix (pcacc_sinkhorn_train_workspace_bytes). */
 int pcacc_sinkhorn_train_workspace_bytes(int n_pairs, int k, size_t *bytes /*host*/);
 int pcacc_sinkhorn_forward(const float *log_alpha, int n_pairs, int k, int n_iters, float *log_perm, float *lse_rows,

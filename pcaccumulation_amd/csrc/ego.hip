@@ -13,6 +13,11 @@
 
 #define EGO_TILE 64
 
+// the affinity of one (clamped) feature distance, models/egomotion.py:180.  ONE copy: the training backward recognises a clamped entry by
+// comparing the stored value with ego_affinity_of(EGO_DIST_MIN, ...), which holds only while both sides round the same way
+#define EGO_DIST_MIN 1e-12f
+__device__ __forceinline__ float ego_affinity_of(float dist, float softplus_alpha, float denom) { return -(dist - softplus_alpha) / denom; }
+
 // ---- 1. affinity = -(max(2 - 2 <fs_i, ft_j>, 1e-12) - softplus(alpha)) * inv_temp, written into the padded matrix ----------
 __global__ __launch_bounds__(256) void ego_affinity_kernel(const float *__restrict__ fs, const float *__restrict__ ft, int k, int c,
                                                            const float *__restrict__ params, float *__restrict__ la, int kp)
@@ -51,8 +56,8 @@ __global__ __launch_bounds__(256) void ego_affinity_kernel(const float *__restri
         for (int v = 0; v < 4; ++v) {
             const int i = i0 + ty * 4 + u, j = j0 + tx * 4 + v;
             if (i < k && j < k) {
-                const float dist = fmaxf(-2.0f * acc[u][v] + 2.0f, 1e-12f);          // toolbox/utils.py:137-143
-                la[(int64_t)i * kp + j] = -(dist - softplus_alpha) / denom;          // models/egomotion.py:180
+                const float dist = fmaxf(-2.0f * acc[u][v] + 2.0f, EGO_DIST_MIN);    // toolbox/utils.py:137-143
+                la[(int64_t)i * kp + j] = ego_affinity_of(dist, softplus_alpha, denom);
             }
         }
 }
@@ -375,8 +380,38 @@ __global__ __launch_bounds__(64 * EGO_CG) void ego_sinkhorn_cols_bwd_kernel(cons
 // backward above replays.  Normalising row i replaces U[i] by  log( sum_j exp(x0[i][j] - V[j]) + 1 )  whatever it was, and likewise
 // for a column.  So the forward never has to rewrite the matrix: a half-step reads x0 once and writes one vector (the kernels
 // above read and write the padded matrix 2-3 times per half-step; 16 x 1024^2: 0.45 ms against 8 us per pass).  k % 4 == 0.
-__global__ __launch_bounds__(256) void ego_sinkhorn_rows_ro_kernel(const float *__restrict__ x0, const float *__restrict__ V, int k,
-                                                                   int n_pairs, float *__restrict__ U, float *__restrict__ lse_out)
+//
+//
+// Precision.  The in-place form subtracts a little at a time, so an entry that ends near 0 (a match: the entries that carry the weight) is
+// rounded at its own size; here it is the difference of three numbers, and float32 arithmetic loses ulp(max(|U|, |V|)) of it.  0 <= V <=
+// log(k + 1) always (the slack row holds e^0 and the rows were just normalised) and 0 <= U <= max(x0, 0) + log(k + 1), so everything hangs on
+// the largest U of the first row step.  Up to EGO_WIDE (the head: x0 <= softplus(alpha) / (exp(beta) + 0.02), 0.25 at its initial values) that
+// loss is ulp(8) / 2 at most and the arithmetic is float32.  Above it (`wide`; randn * 40: exp(log_perm) was 6 - 17 x the float32 formulation's
+// own error) U and V are float64 sums of the recorded float32 differences and every x0 - U - V is formed in float64 before it is rounded;
+// exponentials and logarithms stay float32, their arguments shifted by the running maximum first.  The first row step (V = 0) is the same
+// arithmetic either way and leaves the switch behind; the backward reads it from the first record.
+#define EGO_WIDE 8.0f
+__device__ __forceinline__ float ego_shifted(float x, double uv, double shift, bool wide)
+{
+    return wide ? (float)((double)x - uv - shift) : (x - (float)uv) - (float)shift;
+}
+// U[p][i] / V[p][j] as the read-only forward held them after `steps` steps: the sum of the recorded differences, float64 if wide
+__device__ __forceinline__ double ego_cum_ro(const float *__restrict__ lse, int steps, int64_t stride, int64_t idx, bool wide)
+{
+    if (wide) {
+        double a = 0.0;
+        for (int t = 0; t < steps; ++t) a += (double)lse[t * stride + idx];
+        return a;
+    }
+    float a = 0.f;
+    for (int t = 0; t < steps; ++t) a += lse[t * stride + idx];
+    return a;
+}
+
+// switch = the bits of some U of the first row step that is above EGO_WIDE, 0 if none is: `first` leaves it there
+template <bool wide> __device__ __forceinline__ void ego_sinkhorn_rows_ro_body(const float *__restrict__ x0, const double *__restrict__ V, int k,
+                                                                   int n_pairs, double *__restrict__ U, float *__restrict__ lse_out,
+                                                                   int *__restrict__ wide_bits, int first)
 {
     const int lane = threadIdx.x & 63;
     const int64_t n_rows = (int64_t)n_pairs * k;
@@ -384,60 +419,81 @@ __global__ __launch_bounds__(256) void ego_sinkhorn_rows_ro_kernel(const float *
     for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n_rows; row += (int64_t)gridDim.x * 4) {
         const int64_t p = row / k;
         const float4 *xr = reinterpret_cast<const float4 *>(x0 + row * k);
-        const float4 *vr = reinterpret_cast<const float4 *>(V + p * k);
+        const double4 *vr = reinterpret_cast<const double4 *>(V + p * k);
         float mx = 0.f;                                                      // the slack column: y = 0 - U[i], i.e. t = 0
         for (int j = lane; j < k4; j += 64) {
-            const float4 a = xr[j], b = vr[j];
-            mx = fmaxf(fmaxf(mx, fmaxf(a.x - b.x, a.y - b.y)), fmaxf(a.z - b.z, a.w - b.w));
+            const float4 a = xr[j];
+            const double4 b = vr[j];
+            mx = fmaxf(fmaxf(mx, fmaxf(ego_shifted(a.x, b.x, 0.0, wide), ego_shifted(a.y, b.y, 0.0, wide))),
+                       fmaxf(ego_shifted(a.z, b.z, 0.0, wide), ego_shifted(a.w, b.w, 0.0, wide)));
         }
-        mx = wave_max(mx);
+        mx = wave_max(mx);                                                   // a float32 value: the shift, not a result
+        const double m = mx;
         float sm = 0.f;
         for (int j = lane; j < k4; j += 64) {                                // second read of the row comes from L1 / L2
-            const float4 a = xr[j], b = vr[j];
-            sm += (expf(a.x - b.x - mx) + expf(a.y - b.y - mx)) + (expf(a.z - b.z - mx) + expf(a.w - b.w - mx));
+            const float4 a = xr[j];
+            const double4 b = vr[j];
+            sm += (expf(ego_shifted(a.x, b.x, m, wide)) + expf(ego_shifted(a.y, b.y, m, wide))) +
+                  (expf(ego_shifted(a.z, b.z, m, wide)) + expf(ego_shifted(a.w, b.w, m, wide)));
         }
-        const float u_new = mx + logf(wave_sum(sm) + expf(-mx));
+        const double u_new = m + (double)logf(wave_sum(sm) + expf(-mx));     // the sum of two floats: exact; rounded to float = their float sum
         if (lane == 0) {
-            lse_out[row] = u_new - U[row];                                   // what this half-step subtracted (the backward's record)
-            U[row] = u_new;
+            const double u_old = U[row];
+            // what this half-step subtracted (the backward's record), and U as the sum of the records so far: what ego_cum_ro rebuilds, bit for bit
+            const float rec = wide ? (float)(u_new - u_old) : (float)u_new - (float)u_old;
+            lse_out[row] = rec;
+            U[row] = wide ? u_old + (double)rec : (double)(float)u_new;
+            // only "above EGO_WIDE" is read: any of the racing stores says the same, and the head's inputs store nothing
+            if (first && (float)u_new > EGO_WIDE) *wide_bits = __float_as_int((float)u_new);
         }
     }
 }
+__global__ __launch_bounds__(256) void ego_sinkhorn_rows_ro_kernel(const float *__restrict__ x0, const double *__restrict__ V, int k,
+                                                                   int n_pairs, double *__restrict__ U, float *__restrict__ lse_out,
+                                                                   int *__restrict__ wide_bits, int first)
+{
+    if (!first && __int_as_float(*wide_bits) > EGO_WIDE) ego_sinkhorn_rows_ro_body<true>(x0, V, k, n_pairs, U, lse_out, wide_bits, first);
+    else ego_sinkhorn_rows_ro_body<false>(x0, V, k, n_pairs, U, lse_out, wide_bits, first);
+}
 
 // 64 columns x 16 row groups per workgroup; partial (max, sum) per column combined through LDS
-__global__ __launch_bounds__(256) void ego_sinkhorn_cols_ro_kernel(const float *__restrict__ x0, const float *__restrict__ U, int k,
-                                                                   float *__restrict__ V, float *__restrict__ lse_out)
+template <bool wide> __device__ __forceinline__ void ego_sinkhorn_cols_ro_body(const float *__restrict__ x0, const double *__restrict__ U, int k,
+                                                                   double *__restrict__ V, float *__restrict__ lse_out,
+                                                                   const int *__restrict__ wide_bits)
 {
     __shared__ float smax[16][64], ssum[16][64];
     const int p = blockIdx.y;
     const int c4 = threadIdx.x & 15, rg = threadIdx.x >> 4;                  // 16 column quads, 16 row groups
     const int col = blockIdx.x * 64 + c4 * 4;
     const float *m = x0 + (int64_t)p * k * k;
-    const float *u = U + (int64_t)p * k;
+    const double *u = U + (int64_t)p * k;
     float mx[4] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff()}, sm[4] = {0.f, 0.f, 0.f, 0.f};
     if (col < k) {
         for (int i0 = rg; i0 < k; i0 += 16 * 8) {                            // 8 rows per round: one rescale per round and column
-            float4 t[8];
+            float4 a[8];
+            double ui[8];
             float cm[4] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
                 const int i = i0 + r * 16;
                 if (i < k) {
-                    const float4 a = *reinterpret_cast<const float4 *>(m + (int64_t)i * k + col);
-                    const float ui = u[i];
-                    t[r] = make_float4(a.x - ui, a.y - ui, a.z - ui, a.w - ui);
-                    cm[0] = fmaxf(cm[0], t[r].x); cm[1] = fmaxf(cm[1], t[r].y); cm[2] = fmaxf(cm[2], t[r].z); cm[3] = fmaxf(cm[3], t[r].w);
-                } else {
-                    t[r] = make_float4(-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff());
+                    a[r] = *reinterpret_cast<const float4 *>(m + (int64_t)i * k + col);
+                    ui[r] = u[i];
+                    cm[0] = fmaxf(cm[0], ego_shifted(a[r].x, ui[r], 0.0, wide)); cm[1] = fmaxf(cm[1], ego_shifted(a[r].y, ui[r], 0.0, wide));
+                    cm[2] = fmaxf(cm[2], ego_shifted(a[r].z, ui[r], 0.0, wide)); cm[3] = fmaxf(cm[3], ego_shifted(a[r].w, ui[r], 0.0, wide));
+                } else {                                                     // past the last row: exp(-inf) = 0 below
+                    a[r] = make_float4(-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff());
+                    ui[r] = 0.0;
                 }
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float nm = fmaxf(mx[q], cm[q]);
+                const float nm = fmaxf(mx[q], cm[q]);                        // a float32 value: the shift, not a result
                 if (nm > -__builtin_inff()) {
+                    const double shift = nm;
                     float acc = sm[q] * expf(mx[q] - nm);                    // exp(-inf) = 0 on the first round
 #pragma unroll
-                    for (int r = 0; r < 8; ++r) acc += expf((q == 0 ? t[r].x : q == 1 ? t[r].y : q == 2 ? t[r].z : t[r].w) - nm);
+                    for (int r = 0; r < 8; ++r) acc += expf(ego_shifted(q == 0 ? a[r].x : q == 1 ? a[r].y : q == 2 ? a[r].z : a[r].w, ui[r], shift, wide));
                     sm[q] = acc;
                     mx[q] = nm;
                 }
@@ -459,17 +515,26 @@ __global__ __launch_bounds__(256) void ego_sinkhorn_cols_ro_kernel(const float *
                 const float pm = smax[g][threadIdx.x];
                 gs += (pm == -__builtin_inff()) ? 0.f : ssum[g][threadIdx.x] * expf(pm - gm);
             }
-            const float v_new = gm + logf(gs);
+            const double v_new = (double)gm + (double)logf(gs);
             const int64_t o = (int64_t)p * k + c;
-            lse_out[o] = v_new - V[o];
-            V[o] = v_new;
+            const double v_old = V[o];
+            const float rec = wide ? (float)(v_new - v_old) : (float)v_new - (float)v_old;
+            lse_out[o] = rec;
+            V[o] = wide ? v_old + (double)rec : (double)(float)v_new;
         }
     }
 }
+__global__ __launch_bounds__(256) void ego_sinkhorn_cols_ro_kernel(const float *__restrict__ x0, const double *__restrict__ U, int k,
+                                                                   double *__restrict__ V, float *__restrict__ lse_out,
+                                                                   const int *__restrict__ wide_bits)
+{
+    if (__int_as_float(*wide_bits) > EGO_WIDE) ego_sinkhorn_cols_ro_body<true>(x0, U, k, V, lse_out, wide_bits);
+    else ego_sinkhorn_cols_ro_body<false>(x0, U, k, V, lse_out, wide_bits);
+}
 
-__global__ __launch_bounds__(256) void ego_sinkhorn_finish_ro_kernel(const float4 *__restrict__ x0, const float *__restrict__ U,
-                                                                     const float *__restrict__ V, int k, int64_t total4,
-                                                                     float4 *__restrict__ out)
+template <bool wide> __device__ __forceinline__ void ego_sinkhorn_finish_ro_body(const float4 *__restrict__ x0, const double *__restrict__ U,
+                                                                     const double *__restrict__ V, int k, int64_t total4,
+                                                                     float4 *__restrict__ out, const int *__restrict__ wide_bits)
 {
     const int k4 = k >> 2;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total4; e += (int64_t)gridDim.x * 256) {
@@ -477,10 +542,17 @@ __global__ __launch_bounds__(256) void ego_sinkhorn_finish_ro_kernel(const float
         const int j4 = (int)(e % k4);
         const int64_t p = row / k;
         const float4 a = x0[e];
-        const float4 v = reinterpret_cast<const float4 *>(V + p * k)[j4];
-        const float ui = U[row];
-        out[e] = make_float4(a.x - ui - v.x, a.y - ui - v.y, a.z - ui - v.z, a.w - ui - v.w);
+        const double4 v = reinterpret_cast<const double4 *>(V + p * k)[j4];
+        const double ui = U[row];
+        out[e] = make_float4(ego_shifted(a.x, ui, v.x, wide), ego_shifted(a.y, ui, v.y, wide), ego_shifted(a.z, ui, v.z, wide), ego_shifted(a.w, ui, v.w, wide));
     }
+}
+__global__ __launch_bounds__(256) void ego_sinkhorn_finish_ro_kernel(const float4 *__restrict__ x0, const double *__restrict__ U,
+                                                                     const double *__restrict__ V, int k, int64_t total4,
+                                                                     float4 *__restrict__ out, const int *__restrict__ wide_bits)
+{
+    if (__int_as_float(*wide_bits) > EGO_WIDE) ego_sinkhorn_finish_ro_body<true>(x0, U, V, k, total4, out, wide_bits);
+    else ego_sinkhorn_finish_ro_body<false>(x0, U, V, k, total4, out, wide_bits);
 }
 
 // ---- backward in vector form --------------------------------------------------------------------------------------------------------
@@ -491,6 +563,15 @@ __global__ __launch_bounds__(256) void ego_sinkhorn_finish_ro_kernel(const float
 // -sum_j P_s[i][j] c_s[j]; a row step zeroes the row sums and changes the column sums by -sum_i P_s[i][j] r_s[i]: ONE read-only pass
 // over x0 per half-step (a matrix-vector product), two passes for the sums of G, one final pass (read G and x0, write dx0) -- 10
 // passes of 64 MB at 16 x 1024^2 instead of 26 read-modify-write passes over the padded gradient matrix.  k % 4 == 0.
+// The recurrences take "a column of P_s sums to 1" for granted instead of re-summing, so P_s must be the forward's own matrix to float32
+// accuracy: U_s, V_s are rebuilt as the forward held them (ego_cum_ro) and on a wide input (see the read-only forward; the switch is the
+// largest entry of the first row record) x0 - U_s - V_s is formed in float64 -- with float32 differences at U ~ 150 P_s was 1e-5 off and
+// d log_alpha 7 - 72 x the float32 formulation's own error.
+__global__ __launch_bounds__(256) void sk_wide_kernel(const float *__restrict__ lse_r0, int64_t n, int *__restrict__ wide_bits /* zeroed */)
+{
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256)
+        if (lse_r0[e] > EGO_WIDE) *wide_bits = __float_as_int(lse_r0[e]);
+}
 __global__ __launch_bounds__(256) void sk_rowsum_kernel(const float *__restrict__ G, int k, int n_pairs, float *__restrict__ R)
 {
     const int lane = threadIdx.x & 63, k4 = k >> 2;
@@ -507,8 +588,9 @@ __global__ __launch_bounds__(256) void sk_rowsum_kernel(const float *__restrict_
 // column sums of G (W == NULL) or the column-side matrix-vector product of a row step:
 //   out[j] = sum_i G[i][j]                                         |  out[j] = -exp(-V[j]) sum_i exp(x0[i][j] - U[i]) W[i]
 // 64 columns x 16 row groups per workgroup, partial sums combined through LDS (the tiling of ego_sinkhorn_cols_ro_kernel)
-__global__ __launch_bounds__(256) void sk_cols_kernel(const float *__restrict__ M, const float *__restrict__ lse_r, const float *__restrict__ lse_c,
-                                                      int nu, int nv, const float *__restrict__ W, int k, int n_pairs, float *__restrict__ out)
+template <bool wide> __device__ __forceinline__ void sk_cols_body(const float *__restrict__ M, const float *__restrict__ lse_r, const float *__restrict__ lse_c,
+                                                      int nu, int nv, const float *__restrict__ W, int k, int n_pairs, float *__restrict__ out,
+                                                      const int *__restrict__ wide_bits)
 {
     __shared__ float ssum[16][64];
     const int p = blockIdx.y;
@@ -518,17 +600,18 @@ __global__ __launch_bounds__(256) void sk_cols_kernel(const float *__restrict__ 
     const int64_t stride = (int64_t)n_pairs * k;
     float sm[4] = {0.f, 0.f, 0.f, 0.f};
     if (col < k) {
-        float4 vj = make_float4(0.f, 0.f, 0.f, 0.f);
+        double vj[4] = {0.0, 0.0, 0.0, 0.0};
         if (W) {
-            vj.x = ego_cum(lse_c, nv, stride, (int64_t)p * k + col);     vj.y = ego_cum(lse_c, nv, stride, (int64_t)p * k + col + 1);
-            vj.z = ego_cum(lse_c, nv, stride, (int64_t)p * k + col + 2); vj.w = ego_cum(lse_c, nv, stride, (int64_t)p * k + col + 3);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) vj[q] = ego_cum_ro(lse_c, nv, stride, (int64_t)p * k + col + q, wide);
         }
         for (int i = rg; i < k; i += 16) {
             const float4 a = *reinterpret_cast<const float4 *>(m + (int64_t)i * k + col);
             if (W) {
-                const float ui = ego_cum(lse_r, nu, stride, (int64_t)p * k + i), wi = W[(int64_t)p * k + i];
-                sm[0] += wi * expf(a.x - ui - vj.x); sm[1] += wi * expf(a.y - ui - vj.y);
-                sm[2] += wi * expf(a.z - ui - vj.z); sm[3] += wi * expf(a.w - ui - vj.w);
+                const double ui = ego_cum_ro(lse_r, nu, stride, (int64_t)p * k + i, wide);
+                const float wi = W[(int64_t)p * k + i];
+                sm[0] += wi * expf(ego_shifted(a.x, ui, vj[0], wide)); sm[1] += wi * expf(ego_shifted(a.y, ui, vj[1], wide));
+                sm[2] += wi * expf(ego_shifted(a.z, ui, vj[2], wide)); sm[3] += wi * expf(ego_shifted(a.w, ui, vj[3], wide));
             } else {
                 sm[0] += a.x; sm[1] += a.y; sm[2] += a.z; sm[3] += a.w;
             }
@@ -547,29 +630,44 @@ __global__ __launch_bounds__(256) void sk_cols_kernel(const float *__restrict__ 
         }
     }
 }
+__global__ __launch_bounds__(256) void sk_cols_kernel(const float *__restrict__ M, const float *__restrict__ lse_r, const float *__restrict__ lse_c,
+                                                      int nu, int nv, const float *__restrict__ W, int k, int n_pairs, float *__restrict__ out,
+                                                      const int *__restrict__ wide_bits)
+{
+    if (W && __int_as_float(*wide_bits) > EGO_WIDE) sk_cols_body<true>(M, lse_r, lse_c, nu, nv, W, k, n_pairs, out, wide_bits);
+    else sk_cols_body<false>(M, lse_r, lse_c, nu, nv, W, k, n_pairs, out, wide_bits);
+}
 
 // row-side matrix-vector product of a column step: out[i] = Rin[i] - exp(-U[i]) sum_j exp(x0[i][j] - V[j]) C[j]   (Rin == NULL: 0)
-__global__ __launch_bounds__(256) void sk_rows_kernel(const float *__restrict__ x0, const float *__restrict__ lse_r, const float *__restrict__ lse_c,
+template <bool wide> __device__ __forceinline__ void sk_rows_body(const float *__restrict__ x0, const float *__restrict__ lse_r, const float *__restrict__ lse_c,
                                                       int nu, int nv, const float *__restrict__ C, const float *__restrict__ Rin, int k, int n_pairs,
-                                                      float *__restrict__ out)
+                                                      float *__restrict__ out, const int *__restrict__ wide_bits)
 {
     const int lane = threadIdx.x & 63;
     const int64_t n_rows = (int64_t)n_pairs * k, stride = n_rows;
     for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n_rows; row += (int64_t)gridDim.x * 4) {
         const int64_t p = row / k;
         const float *xr = x0 + row * k;
-        const float u = ego_cum(lse_r, nu, stride, row);
+        const double u = ego_cum_ro(lse_r, nu, stride, row, wide);
         float sm = 0.f;
-        for (int j = lane; j < k; j += 64) sm += C[p * k + j] * expf(xr[j] - u - ego_cum(lse_c, nv, stride, p * k + j));
+        for (int j = lane; j < k; j += 64) sm += C[p * k + j] * expf(ego_shifted(xr[j], u, ego_cum_ro(lse_c, nv, stride, p * k + j, wide), wide));
         sm = wave_sum(sm);
         if (lane == 0) out[row] = (Rin ? Rin[row] : 0.f) - sm;
     }
 }
+__global__ __launch_bounds__(256) void sk_rows_kernel(const float *__restrict__ x0, const float *__restrict__ lse_r, const float *__restrict__ lse_c,
+                                                      int nu, int nv, const float *__restrict__ C, const float *__restrict__ Rin, int k, int n_pairs,
+                                                      float *__restrict__ out, const int *__restrict__ wide_bits)
+{
+    if (__int_as_float(*wide_bits) > EGO_WIDE) sk_rows_body<true>(x0, lse_r, lse_c, nu, nv, C, Rin, k, n_pairs, out, wide_bits);
+    else sk_rows_body<false>(x0, lse_r, lse_c, nu, nv, C, Rin, k, n_pairs, out, wide_bits);
+}
 
 // dx0[i][j] = G[i][j] - sum_it ( Wc[it][j] exp(x0 - U_{it+1}[i] - V_{it+1}[j]) + Wr[it][i] exp(x0 - U_{it+1}[i] - V_it[j]) )
-__global__ __launch_bounds__(256) void sk_final_kernel(const float4 *__restrict__ G, const float4 *__restrict__ x0, const float *__restrict__ lse_r,
+template <bool wide> __device__ __forceinline__ void sk_final_body(const float4 *__restrict__ G, const float4 *__restrict__ x0, const float *__restrict__ lse_r,
                                                        const float *__restrict__ lse_c, const float *__restrict__ Wc, const float *__restrict__ Wr,
-                                                       int n_iters, int k, int n_pairs, int64_t total4, float4 *__restrict__ out)
+                                                       int n_iters, int k, int n_pairs, int64_t total4, float4 *__restrict__ out,
+                                                       const int *__restrict__ wide_bits)
 {
     const int k4 = k >> 2;
     const int64_t stride = (int64_t)n_pairs * k;
@@ -579,19 +677,30 @@ __global__ __launch_bounds__(256) void sk_final_kernel(const float4 *__restrict_
         const int64_t col0 = (row / k) * k + (int64_t)j4 * 4;               // p * k + j
         const float4 a = x0[e];
         float4 acc = G[e];
-        float u = 0.f;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);                          // V_it
+        double u = 0.0;
+        double vx = 0.0, vy = 0.0, vz = 0.0, vw = 0.0;                       // V_it
         for (int it = 0; it < n_iters; ++it) {
-            u += lse_r[it * stride + row];                                   // U_{it+1}
+            u = wide ? u + (double)lse_r[it * stride + row] : (double)((float)u + lse_r[it * stride + row]);       // U_{it+1}
             const float wr = Wr[it * stride + row];
-            acc.x -= wr * expf(a.x - u - v.x); acc.y -= wr * expf(a.y - u - v.y); acc.z -= wr * expf(a.z - u - v.z); acc.w -= wr * expf(a.w - u - v.w);
+            acc.x -= wr * expf(ego_shifted(a.x, u, vx, wide)); acc.y -= wr * expf(ego_shifted(a.y, u, vy, wide));
+            acc.z -= wr * expf(ego_shifted(a.z, u, vz, wide)); acc.w -= wr * expf(ego_shifted(a.w, u, vw, wide));
             const float4 l = *reinterpret_cast<const float4 *>(lse_c + it * stride + col0);
-            v = make_float4(v.x + l.x, v.y + l.y, v.z + l.z, v.w + l.w);    // V_{it+1}
+            if (wide) { vx += (double)l.x; vy += (double)l.y; vz += (double)l.z; vw += (double)l.w; }      // V_{it+1}
+            else { vx = (float)vx + l.x; vy = (float)vy + l.y; vz = (float)vz + l.z; vw = (float)vw + l.w; }
             const float4 wc = *reinterpret_cast<const float4 *>(Wc + it * stride + col0);
-            acc.x -= wc.x * expf(a.x - u - v.x); acc.y -= wc.y * expf(a.y - u - v.y); acc.z -= wc.z * expf(a.z - u - v.z); acc.w -= wc.w * expf(a.w - u - v.w);
+            acc.x -= wc.x * expf(ego_shifted(a.x, u, vx, wide)); acc.y -= wc.y * expf(ego_shifted(a.y, u, vy, wide));
+            acc.z -= wc.z * expf(ego_shifted(a.z, u, vz, wide)); acc.w -= wc.w * expf(ego_shifted(a.w, u, vw, wide));
         }
         out[e] = acc;
     }
+}
+__global__ __launch_bounds__(256) void sk_final_kernel(const float4 *__restrict__ G, const float4 *__restrict__ x0, const float *__restrict__ lse_r,
+                                                       const float *__restrict__ lse_c, const float *__restrict__ Wc, const float *__restrict__ Wr,
+                                                       int n_iters, int k, int n_pairs, int64_t total4, float4 *__restrict__ out,
+                                                       const int *__restrict__ wide_bits)
+{
+    if (__int_as_float(*wide_bits) > EGO_WIDE) sk_final_body<true>(G, x0, lse_r, lse_c, Wc, Wr, n_iters, k, n_pairs, total4, out, wide_bits);
+    else sk_final_body<false>(G, x0, lse_r, lse_c, Wc, Wr, n_iters, k, n_pairs, total4, out, wide_bits);
 }
 
 extern "C" int pcacc_sinkhorn_train_workspace_bytes(int n_pairs, int k, size_t *bytes)
@@ -605,22 +714,25 @@ extern "C" int pcacc_sinkhorn_train_workspace_bytes(int n_pairs, int k, size_t *
 extern "C" int pcacc_sinkhorn_forward(const float *log_alpha, int n_pairs, int k, int n_iters, float *log_perm, float *lse_rows,
                                       float *lse_cols, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!log_alpha || !log_perm || !lse_rows || !lse_cols || !workspace || n_pairs < 1 || k < 1 || n_iters < 0) return PCACC_E_ARG;
+    if (!log_alpha || !log_perm || !workspace || n_pairs < 1 || k < 1 || n_iters < 0) return PCACC_E_ARG;
+    if (n_iters > 0 && (!lse_rows || !lse_cols)) return PCACC_E_ARG;          // n_iters = 0 records nothing: the [0][P][k] vectors may be NULL
     if (workspace_bytes < (size_t)n_pairs * (k + 1) * (k + 1) * sizeof(float)) return PCACC_E_WORKSPACE;
     hipStream_t s = pcacc_stream(stream);
     const int row_grid = pcacc_grid((int64_t)n_pairs * k * 64, 256);
     const int64_t stride = (int64_t)n_pairs * k;
     if (k % 4 == 0) {
-        // read-only passes over log_alpha; the workspace (sized for the padded matrix) holds the two vectors U, V
-        float *U = reinterpret_cast<float *>(workspace), *V = U + stride;
-        if (hipMemsetAsync(U, 0, (size_t)2 * stride * sizeof(float), s) != hipSuccess) return PCACC_E_LAUNCH;
+        // read-only passes over log_alpha; the workspace (sized for the padded matrix: 4 (k + 1)^2 >= 16 k bytes per pair) holds the two
+        // float64 vectors U, V and, behind them (4 (k + 1)^2 - 16 k = 4 (k - 1)^2 bytes are left), the float32 / float64 switch
+        double *U = reinterpret_cast<double *>(workspace), *V = U + stride;
+        int *wide_bits = reinterpret_cast<int *>(V + stride);
+        if (hipMemsetAsync(U, 0, (size_t)2 * stride * sizeof(double) + sizeof(int), s) != hipSuccess) return PCACC_E_LAUNCH;
         for (int it = 0; it < n_iters; ++it) {
-            ego_sinkhorn_rows_ro_kernel<<<row_grid, 256, 0, s>>>(log_alpha, V, k, n_pairs, U, lse_rows + it * stride);
-            ego_sinkhorn_cols_ro_kernel<<<dim3((k + 63) / 64, n_pairs), 256, 0, s>>>(log_alpha, U, k, V, lse_cols + it * stride);
+            ego_sinkhorn_rows_ro_kernel<<<row_grid, 256, 0, s>>>(log_alpha, V, k, n_pairs, U, lse_rows + it * stride, wide_bits, it == 0);
+            ego_sinkhorn_cols_ro_kernel<<<dim3((k + 63) / 64, n_pairs), 256, 0, s>>>(log_alpha, U, k, V, lse_cols + it * stride, wide_bits);
         }
         const int64_t total4 = stride * (k / 4);
         ego_sinkhorn_finish_ro_kernel<<<pcacc_grid(total4, 256), 256, 0, s>>>(reinterpret_cast<const float4 *>(log_alpha), U, V, k, total4,
-                                                                              reinterpret_cast<float4 *>(log_perm));
+                                                                              reinterpret_cast<float4 *>(log_perm), wide_bits);
         PCACC_CHECK_LAUNCH();
         return PCACC_OK;
     }
@@ -641,8 +753,8 @@ extern "C" int pcacc_sinkhorn_backward(const float *grad_log_perm, const float *
                                        int n_pairs, int k, int n_iters, float *grad_log_alpha, void *workspace, size_t workspace_bytes,
                                        void *stream)
 {
-    if (!grad_log_perm || !log_alpha || !lse_rows || !lse_cols || !grad_log_alpha || !workspace || n_pairs < 1 || k < 1 || n_iters < 0)
-        return PCACC_E_ARG;
+    if (!grad_log_perm || !log_alpha || !grad_log_alpha || !workspace || n_pairs < 1 || k < 1 || n_iters < 0) return PCACC_E_ARG;
+    if (n_iters > 0 && (!lse_rows || !lse_cols)) return PCACC_E_ARG;
     if (workspace_bytes < (size_t)n_pairs * (k + 1) * (k + 1) * sizeof(float)) return PCACC_E_WORKSPACE;
     hipStream_t s = pcacc_stream(stream);
     float *g = reinterpret_cast<float *>(workspace);
@@ -652,22 +764,26 @@ extern "C" int pcacc_sinkhorn_backward(const float *grad_log_perm, const float *
     if (k % 4 == 0 && n_iters >= 1 && (int64_t)(2 * n_iters + 1) * stride <= padded) {
         // vector form (see above): Wc[it] / Wr[it] = the column / row sums each half-step subtracts with, R0 = row sums of G
         float *Wc = g, *Wr = g + (int64_t)n_iters * stride, *R0 = g + (int64_t)2 * n_iters * stride;
+        // the switch of the forward, behind them: (2 n_iters + 1) k < (k + 1)^2 strictly (k does not divide (k + 1)^2), so a float is left
+        int *wide_bits = reinterpret_cast<int *>(g + (int64_t)(2 * n_iters + 1) * stride);
         const dim3 cgrid((k + 63) / 64, n_pairs);
+        if (hipMemsetAsync(wide_bits, 0, sizeof(int), s) != hipSuccess) return PCACC_E_LAUNCH;
+        sk_wide_kernel<<<pcacc_grid(stride, 256), 256, 0, s>>>(lse_rows, stride, wide_bits);
         sk_rowsum_kernel<<<row_grid, 256, 0, s>>>(grad_log_perm, k, n_pairs, R0);
-        sk_cols_kernel<<<cgrid, 256, 0, s>>>(grad_log_perm, nullptr, nullptr, 0, 0, nullptr, k, n_pairs, Wc + (int64_t)(n_iters - 1) * stride);
+        sk_cols_kernel<<<cgrid, 256, 0, s>>>(grad_log_perm, nullptr, nullptr, 0, 0, nullptr, k, n_pairs, Wc + (int64_t)(n_iters - 1) * stride, wide_bits);
         for (int it = n_iters - 1; it >= 0; --it) {
             // column step `it` (P = exp(x0 - U_{it+1} - V_{it+1})): the row sums it leaves = what row step `it` subtracts with
             sk_rows_kernel<<<row_grid, 256, 0, s>>>(log_alpha, lse_rows, lse_cols, it + 1, it + 1, Wc + (int64_t)it * stride,
-                                                    it == n_iters - 1 ? R0 : nullptr, k, n_pairs, Wr + (int64_t)it * stride);
+                                                    it == n_iters - 1 ? R0 : nullptr, k, n_pairs, Wr + (int64_t)it * stride, wide_bits);
             // row step `it` (P = exp(x0 - U_{it+1} - V_it)): the column sums it leaves = what column step `it - 1` subtracts with
             if (it > 0)
                 sk_cols_kernel<<<cgrid, 256, 0, s>>>(log_alpha, lse_rows, lse_cols, it + 1, it, Wr + (int64_t)it * stride, k, n_pairs,
-                                                     Wc + (int64_t)(it - 1) * stride);
+                                                     Wc + (int64_t)(it - 1) * stride, wide_bits);
         }
         const int64_t total4 = stride * (k / 4);
         sk_final_kernel<<<pcacc_grid(total4, 256), 256, 0, s>>>(reinterpret_cast<const float4 *>(grad_log_perm), reinterpret_cast<const float4 *>(log_alpha),
                                                                 lse_rows, lse_cols, Wc, Wr, n_iters, k, n_pairs, total4,
-                                                                reinterpret_cast<float4 *>(grad_log_alpha));
+                                                                reinterpret_cast<float4 *>(grad_log_alpha), wide_bits);
         PCACC_CHECK_LAUNCH();
         return PCACC_OK;
     }
@@ -837,15 +953,19 @@ __global__ __launch_bounds__(256) void ego_affinity_bwd_kernel(const float4 *__r
 {
     const float a = params[0], b = params[1];
     const float two_over_b = 2.0f / b;
+    // torch.clamp passes no gradient where the clamp was active.  The forward stored exactly ego_affinity_of(EGO_DIST_MIN, a, b) there and a
+    // strictly smaller value for every larger distance that a - dist still tells apart from a (the least positive one is 2^-23: softplus(alpha)
+    // below ~4).  Rebuilding the distance as a - aff * b does NOT work: for a clamped entry that is a's rounding noise, ~ulp(a) >> 1e-12, of
+    // either sign.
+    const float at_clamp = ego_affinity_of(EGO_DIST_MIN, a, b);
     double s1 = 0.0, s2 = 0.0;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n4; e += (int64_t)gridDim.x * 256) {
         const float4 g = g_aff[e], v = aff[e];
-        // aff = -(dist - a) / b  =>  dist = a - aff * b; the clamp at 1e-12 passes the gradient where the un-clamped distance was >= 1e-12
         float4 o;
-        o.x = (a - v.x * b > 1e-12f) ? g.x * two_over_b : 0.f;
-        o.y = (a - v.y * b > 1e-12f) ? g.y * two_over_b : 0.f;
-        o.z = (a - v.z * b > 1e-12f) ? g.z * two_over_b : 0.f;
-        o.w = (a - v.w * b > 1e-12f) ? g.w * two_over_b : 0.f;
+        o.x = (v.x < at_clamp) ? g.x * two_over_b : 0.f;
+        o.y = (v.y < at_clamp) ? g.y * two_over_b : 0.f;
+        o.z = (v.z < at_clamp) ? g.z * two_over_b : 0.f;
+        o.w = (v.w < at_clamp) ? g.w * two_over_b : 0.f;
         g_dot[e] = o;
         s1 += (double)g.x + (double)g.y + (double)g.z + (double)g.w;
         s2 += (double)g.x * v.x + (double)g.y * v.y + (double)g.z * v.z + (double)g.w * v.w;
@@ -853,7 +973,7 @@ __global__ __launch_bounds__(256) void ego_affinity_bwd_kernel(const float4 *__r
     if (blockIdx.x == 0 && (int)threadIdx.x < tail) {            // the last n % 4 elements
         const int64_t e = n4 * 4 + threadIdx.x;
         const float g = reinterpret_cast<const float *>(g_aff)[e], v = reinterpret_cast<const float *>(aff)[e];
-        reinterpret_cast<float *>(g_dot)[e] = (a - v * b > 1e-12f) ? g * two_over_b : 0.f;
+        reinterpret_cast<float *>(g_dot)[e] = (v < at_clamp) ? g * two_over_b : 0.f;
         s1 += (double)g;
         s2 += (double)g * v;
     }
