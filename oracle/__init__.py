@@ -659,7 +659,9 @@ def seg_loss(logits, labels, n_classes=2, ignore_index=-1):
     over the classes that are present (libs/lovasz_softmax.py:71-94, rows with the ignore label count as background of every
     class, as in the reference which passes no ignore value), the IoU counters of compute_iou, and the gradients of the two loss
     terms w.r.t. the logits (the Lovasz gradient vector is a constant, lovasz_softmax.py:92).  Ties between equal errors are
-    ordered by row index (stable sort); the loss value does not depend on that choice, the (sub)gradient does."""
+    ordered by row index (stable sort); the loss value does not depend on that choice, the (sub)gradient does.  'jaccard' [n,2] is
+    that constant per row and class (0 for an absent class).  When every row carries the ignore label the cross entropy is NaN and
+    its gradient 0, as torch.nn.functional.cross_entropy gives them."""
     z = np.asarray(logits, np.float32)
     y = np.asarray(labels).astype(np.int64)
     n = z.shape[0]
@@ -672,11 +674,12 @@ def seg_loss(logits, labels, n_classes=2, ignore_index=-1):
     safe = np.where(keep, y, 0)
     wi = w[safe] * keep
     wsum = wi.sum(dtype=np.float64)
-    bce = -(wi * logp[np.arange(n), safe]).sum(dtype=np.float64) / wsum
+    with np.errstate(invalid='ignore'):
+        bce = -(wi * logp[np.arange(n), safe]).sum(dtype=np.float64) / wsum      # 0 / 0 = NaN when nothing is labelled
     onehot = np.zeros_like(p)
     onehot[np.arange(n), safe] = 1
-    grad_bce = (wi[:, None] * (p - onehot) / wsum).astype(np.float32)
-    losses, dprob = [], np.zeros_like(p, dtype=np.float64)
+    grad_bce = (wi[:, None] * (p - onehot) / (wsum if wsum > 0 else 1.0)).astype(np.float32)   # wi = 0 throughout when wsum = 0
+    losses, dprob, jaccard = [], np.zeros_like(p, dtype=np.float64), np.zeros_like(p)
     present = [c for c in range(n_classes) if (y == c).any()]
     for c in present:
         fg = (y == c).astype(np.float32)
@@ -686,12 +689,13 @@ def seg_loss(logits, labels, n_classes=2, ignore_index=-1):
         losses.append(np.dot(err[perm].astype(np.float64), g.astype(np.float64)))
         by_row = np.empty(n, np.float32)
         by_row[perm] = g
+        jaccard[:, c] = by_row
         dprob[:, c] = by_row * -np.sign(fg - p[:, c]) / len(present)
     lovasz = float(np.mean(losses)) if losses else 0.0
     grad_lov = (p * (dprob - (dprob * p).sum(1, keepdims=True))).astype(np.float32)
     pred = (z[:, 1] > z[:, 0]).astype(np.int64) if n_classes == 2 else z.argmax(1)
     return {'bce_loss': float(bce), 'lovasz_loss': lovasz, 'metric': compute_iou(pred, y, n_classes, ignore_index),
-            'grad_bce': grad_bce, 'grad_lovasz': grad_lov}
+            'grad_bce': grad_bce, 'grad_lovasz': grad_lov, 'jaccard': jaccard}
 
 
 def offset_loss(input_points, time_indice, inst_labels, fb_labels, ego_motion_gt, inst_motion_gt, transformed_points, offset_est):
