@@ -1201,6 +1201,59 @@ int pcacc_accum_observed_regrid(const int64_t *in_keys, const int64_t *in_rays, 
                                 void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C16. The k nearest kept centroids of the accumulated scene cloud within a few voxels: of every point of a scan (pcacc_accum_knn), or of
+ * every kept centroid of the map itself (pcacc_accum_knn_self: the base of a statistical outlier removal).  Replaces the copy of the map to
+ * the host and a KD-tree there.  Does not modify the map.  C9 answers one neighbour within one voxel; this answers k within `radius` voxels.
+ * Inputs
+ *   k in [1, PCACC_KNN_MAX_K], radius in [1, PCACC_KNN_MAX_RADIUS] voxels, max_distance in (0, radius * voxel_size]
+ *   points [n,3] f32, 0 <= n <= 2^30;  pose [4,4] f64 scan-to-world, rows 0-2 are read; NULL = identity            (pcacc_accum_knn only)
+ *   keys, acc, capacity, m; min_count, use_fraction, max_moving_fraction      the map and extract's filter, as for pcacc_accum_normals
+ * Per query, all float64 with no FMA contraction, only + - * / and sqrt, in the order csrc/accum_knn.h writes down and no other:
+ *   Query: a scan point under the pose with C4's transform and validity rule (an invalid point gets PCACC_KNN_INVALID, found 0 and padding:
+ *   never clamped, no key, no address), or kept row j of the map: its float64 centroid in the voxel of its KEY, the row itself excluded.
+ *   Candidates: the rows the filter keeps in the (2 radius + 1)^3 voxels around the query's voxel; offsets that leave [-2^20, 2^20) are
+ *   skipped before a key is formed.  d2 = (e_x e_x + e_y e_y) + e_z e_z against the float64 centroid (C9's arithmetic); accepted iff
+ *   d2 <= max_distance^2.
+ *   Result: the up-to-k accepted candidates with the smallest (d2, key) -- a total order: the answer does not depend on the order the voxels
+ *   are visited in, ties go to the lower key = the lower row of pcacc_accum_extract -- in that ascending order: out_rows [.,k] = extract's row
+ *   (valid until the map changes), out_distance [.,k] = sqrt(d2); padded with -1 / +inf; out_found in [0, k]; out_status = PCACC_KNN_INVALID,
+ *   or PCACC_KNN_FOUND (found >= 1) plus PCACC_KNN_FULL (found == k).  Self mode adds out_mean_distance = (((d_0 + d_1) + d_2) + ...) / found
+ *   in that order, +inf for found = 0.
+ *   A centroid lies within 2^-17 m of its voxel.  A scan point lies in its voxel, so a centroid outside the block is farther than
+ *   radius * voxel_size - 2^-17; a self query may itself lie 2^-17 outside its voxel: radius * voxel_size - 2^-16.  For max_distance <=
+ *   (radius - 0.1) voxel_size and voxel sizes of 1 mm and up the result is the k nearest kept centroids of the WHOLE map within
+ *   max_distance.  At max_distance = radius * voxel_size the block search itself is the contract.
+ * Outputs (device; pcacc_accum_knn: n rows, every row written once; pcacc_accum_knn_self: room for m rows, the first *out_n -- the rows of
+ * pcacc_accum_extract under this filter, row for row -- written once each): out_rows i32 [.,k], out_distance f64 [.,k], out_found i32,
+ * out_status u8, out_mean_distance f64; counters [PCACC_KNN_COUNTERS] i64 (written, not added to): queries, invalid, with at least one
+ * neighbour, with k neighbours, neighbours in total.  Every table index is range-checked against m and capacity.
+ * Return value: PCACC_E_ARG, and nothing is launched, for k, radius or n outside their ranges, m outside [0, capacity], a capacity above 2^30,
+ * a voxel size that is not positive and finite, a max_distance that is NaN or outside (0, radius * voxel_size], a NULL table or output of
+ * non-zero size, or a workspace that is too small.  n = 0 writes the zero counters and launches nothing else; m = 0 gives padding everywhere
+ * (pcacc_accum_knn) / *out_n = 0 and the zero counters (pcacc_accum_knn_self).
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_KNN_MAX_K 16
+#define PCACC_KNN_MAX_RADIUS 4
+#define PCACC_KNN_INVALID 1
+#define PCACC_KNN_FOUND 2
+#define PCACC_KNN_FULL 4
+#define PCACC_KNN_COUNTERS 5
+#define PCACC_KNN_N_QUERIES 0
+#define PCACC_KNN_N_INVALID 1
+#define PCACC_KNN_N_FOUND 2
+#define PCACC_KNN_N_FULL 3
+#define PCACC_KNN_N_NEIGHBORS 4
+int pcacc_accum_knn_workspace_bytes(int64_t m, size_t *bytes /*host*/);
+int pcacc_accum_knn(const float *points, int64_t n, const double *pose, double voxel_size, double max_distance, int32_t k, int32_t radius,
+                    const int64_t *keys, const int64_t *acc, int64_t capacity, int64_t m, int64_t min_count, int32_t use_fraction,
+                    double max_moving_fraction, int32_t *out_rows, double *out_distance, int32_t *out_found, uint8_t *out_status,
+                    int64_t *counters, void *workspace, size_t workspace_bytes, void *stream);
+int pcacc_accum_knn_self(double voxel_size, double max_distance, int32_t k, int32_t radius, const int64_t *keys, const int64_t *acc,
+                         int64_t capacity, int64_t m, int64_t min_count, int32_t use_fraction, double max_moving_fraction, int32_t *out_rows,
+                         double *out_distance, int32_t *out_found, uint8_t *out_status, double *out_mean_distance, int64_t *out_n,
+                         int64_t *counters, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

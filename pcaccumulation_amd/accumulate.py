@@ -29,6 +29,9 @@ coordinate sums), so the map does not depend on the order of the points, on the 
     changed = m.compare(last_week, max_distance=0.05)            # per row of extract(), both ways: does the other map hold the voxel, which row, the
     gone = last_week.difference(m, max_distance=0.05)            # nearest centroid within a voxel; what one map has and the other has nothing near, as
     ground = m.select(static['points'][:, 2] < ground_z, min_count=2, max_moving_fraction=0.0)   # a map; any rows of extract() as a map: C13, section 9m
+    near = m.knn(scan, k=8, pose=pose, radius=2, min_count=2)    # per point: the rows of extract() and distances of its 8 nearest centroids within
+    density = m.neighbors(k=8, radius=2, min_count=2)['mean_distance']   # 2 voxels; the same of every centroid of the map itself: C16, section 9p
+    clean = m.select(m.outliers(k=8, std_ratio=2.0, min_count=2)['mask'], invert=True, min_count=2)   # statistical outlier removal, as a new map
 
 ObservedSpace records, beside a cloud, the voxels the measured rays crossed -- where the sensor looked and found nothing (C14, section 9n).  Filled with
 space_now.observe_results(results, input_dict, pose=pose, stamp=k) next to m.add_results(...), it tells what is gone from what was never looked at:
@@ -369,6 +372,70 @@ class AccumulatedCloud(object):
         """query() of a test / val-mode forward: results['rec_est'].  One sample per batch."""
         _one_sample(results, input_dict, 'query_results')
         return self.query(results['rec_est'], pose, **kw)
+
+    # ---- k nearest ---------------------------------------------------------------------------------------------------------------------
+    def _knn_args(self, k, radius, max_distance):
+        """k, radius and max_distance (None = radius * voxel_size) as the entry points of C16 take them."""
+        k, radius = int(k), int(radius)
+        if not 1 <= k <= native.KNN_MAX_K:
+            raise ValueError('k must lie in [1, %d], got %r' % (native.KNN_MAX_K, k))
+        if not 1 <= radius <= native.KNN_MAX_RADIUS:
+            raise ValueError('radius must lie in [1, %d] voxels, got %r' % (native.KNN_MAX_RADIUS, radius))
+        reach = radius * self.voxel_size
+        max_distance = reach if max_distance is None else float(max_distance)
+        if not 0.0 < max_distance <= reach:
+            raise ValueError('max_distance must lie in (0, radius * voxel_size = %r], got %r' % (reach, max_distance))
+        return k, radius, max_distance
+
+    def knn(self, points, k, pose=None, radius=2, max_distance=None, min_count=1, max_moving_fraction=None):
+        """The k nearest centroids of the map for every point of a scan, within `radius` voxels (include/pcacc.h C16).  The map is not modified.
+        points [n,3] f32 (device), k in [1, 16], pose [4,4] scan-to-world (tensor or array; None = identity), radius in [1, 4] voxels, max_distance in
+        (0, radius * voxel_size] (None = radius * voxel_size).  The candidates are the centroids extract(min_count, max_moving_fraction) returns in the
+        (2 radius + 1)^3 voxels around the point's voxel.
+        -> dict of device tensors, one row per point in the caller's order: rows [n,k] i32 (the neighbours' rows of that extract(), nearest first, ties
+        to the lower row; valid until the next add or prune; -1 = none), distance [n,k] f64 (to the float64 centroid; +inf = none), found [n] i32,
+        status [n] u8 (native.KNN_INVALID: the point is not finite or lies outside the grid; else KNN_FOUND with a neighbour, KNN_FULL with k),
+        counters [5] i64: queries, invalid, with a neighbour, with k neighbours, neighbours in total.
+        For max_distance <= (radius - 0.1) voxel_size these are the k nearest kept centroids of the whole map within max_distance.
+        Nothing is read back."""
+        _scan_points('knn', 'points', points, native.KNN_MAX_POINTS)
+        k, radius, max_distance = self._knn_args(k, radius, max_distance)
+        pose = self._pose(pose)
+        self._ensure()
+        return native.accum_knn(points.detach().float().contiguous(), pose, self.voxel_size, max_distance, k, radius, self._cur, self._n, min_count,
+                                max_moving_fraction)
+
+    def knn_results(self, results, input_dict, pose=None, **kw):
+        """knn() of a test / val-mode forward: results['rec_est'].  One sample per batch; k goes by keyword."""
+        _one_sample(results, input_dict, 'knn_results')
+        return self.knn(results['rec_est'], pose=pose, **kw)
+
+    def neighbors(self, k, radius=2, max_distance=None, min_count=1, max_moving_fraction=None):
+        """The k nearest other centroids of every centroid extract(min_count, max_moving_fraction) returns, row for row (include/pcacc.h C16, self
+        mode): knn()'s rows, distance, found, status and counters with the centroid itself left out, and mean_distance [V] f64, the mean of the found
+        distances (+inf without a neighbour): a local density.  Only the kept count is read back."""
+        k, radius, max_distance = self._knn_args(k, radius, max_distance)
+        self._ensure()
+        out = native.accum_knn_self(self.voxel_size, max_distance, k, radius, self._cur, self._n, min_count, max_moving_fraction)
+        kept = int(out.pop('kept')) if self._n else 0
+        return {name: (t if name == 'counters' else t[:kept]) for name, t in out.items()}
+
+    def outliers(self, k=8, std_ratio=2.0, radius=2, max_distance=None, min_count=1, max_moving_fraction=None):
+        """Statistical outlier test of the map itself, rows aligned with extract(min_count, max_moving_fraction): mean_distance [V] f64 of neighbors(k,
+        ...), threshold = mean + std_ratio * population standard deviation of its finite entries (float64, on the device; NaN when there is none) and
+        mask [V] bool = mean_distance > threshold; a row without a neighbour has +inf and is always an outlier.  Removal is
+        select(mask, invert=True, min_count=..., max_moving_fraction=...).  Read back: the kept count and the one scalar."""
+        std_ratio = float(std_ratio)
+        if not np.isfinite(std_ratio):
+            raise ValueError('std_ratio must be finite, got %r' % std_ratio)
+        mean = self.neighbors(k, radius, max_distance, min_count, max_moving_fraction)['mean_distance']
+        finite = torch.isfinite(mean)
+        count = finite.sum()
+        total = torch.where(finite, mean, torch.zeros_like(mean)).sum()
+        mu = total / count
+        var = (torch.where(finite, mean - mu, torch.zeros_like(mean)) ** 2).sum() / count
+        threshold = float(mu + std_ratio * torch.sqrt(var))                      # the one scalar; NaN (0 / 0) without a finite entry
+        return dict(mean_distance=mean, threshold=threshold, mask=(mean > threshold) | ~finite)
 
     # ---- see through -------------------------------------------------------------------------------------------------------------------
     def see_through(self, points, origins, origin_index=None, pose=None, moving=None, stamp=None, margin=None, max_range=None, max_steps=4096):

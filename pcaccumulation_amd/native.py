@@ -940,6 +940,59 @@ def accum_query(points, pose, voxel_size, max_distance, tables, m, pierced, min_
     return res
 
 
+KNN_MAX_K, KNN_MAX_RADIUS = 16, 4
+KNN_INVALID, KNN_FOUND, KNN_FULL = 1, 2, 4
+KNN_COUNTERS = 5
+KNN_N_QUERIES, KNN_N_INVALID, KNN_N_FOUND, KNN_N_FULL, KNN_N_NEIGHBORS = 0, 1, 2, 3, 4
+KNN_MAX_POINTS = 1 << 30
+
+
+def knn_fields(k, self_mode=False):
+    """The output columns of accum_knn (accum_knn_self with self_mode) for k neighbours, as _out_columns takes them."""
+    fields = (('rows', torch.int32, (int(k),)), ('distance', torch.float64, (int(k),)), ('found', torch.int32, ()), ('status', torch.uint8, ()))
+    return fields + ((('mean_distance', torch.float64, ()),) if self_mode else ())
+
+
+def accum_knn(points, pose, voxel_size, max_distance, k, radius, tables, m, min_count, max_moving_fraction, out=None, counters=None):
+    """The k nearest kept centroids of the first m rows of a map within `radius` voxels of every point of a scan; see include/pcacc.h (C16).  points
+    [n,3] f32, pose [4,4] f64 or None.  out: a dict of the knn_fields(k) tensors to write into (None = new ones), counters [5] i64 likewise.
+    -> out with 'counters' added; nothing is read back."""
+    keys, acc, _, cap = _accum_tables(tables, 'accum_knn')
+    dev = tables[0].device
+    n, m = points.shape[0], int(m)
+    _shaped('accum_knn', 'points', points, ('n', 3))
+    _shaped('accum_knn', 'pose', pose, (4, 4))
+    pts = _dev(points, torch.float32, 'points')
+    out, counters, (o_rows, o_distance, o_found, o_status) = _out_columns('accum_knn', knn_fields(k), n, out, counters, KNN_COUNTERS, dev)
+    use_f, f = _fraction(max_moving_fraction)
+    ws = _workspace(lib().pcacc_accum_knn_workspace_bytes, dev, m)
+    _check(lib().pcacc_accum_knn(pts if n else None, n, _opt(pose, torch.float64, 'pose'), float(voxel_size), float(max_distance), int(k), int(radius),
+                                 keys, acc, cap, m, int(min_count), use_f, f, o_rows, o_distance, o_found, o_status,
+                                 _dev(counters, torch.int64, 'counters'), _dev(ws), ws.numel(), _stream()), 'accum_knn')
+    res = dict(out)
+    res['counters'] = counters
+    return res
+
+
+def accum_knn_self(voxel_size, max_distance, k, radius, tables, m, min_count, max_moving_fraction, out=None, counters=None):
+    """The k nearest kept centroids of every kept centroid of the first m rows of a map, itself excluded, rows as accum_extract's under the same filter;
+    see include/pcacc.h (C16).  out: a dict of the knn_fields(k, True) tensors of m rows to write into (None = new ones), counters [5] i64 likewise.
+    -> out with 'counters' and 'kept' [1] i64 added: the caller reads `kept` and slices."""
+    keys, acc, _, cap = _accum_tables(tables, 'accum_knn_self')
+    dev = tables[0].device
+    m = int(m)
+    out, counters, (o_rows, o_distance, o_found, o_status, o_mean) = _out_columns('accum_knn_self', knn_fields(k, True), m, out, counters, KNN_COUNTERS, dev)
+    kept = torch.empty((1,), dtype=torch.int64, device=dev)
+    use_f, f = _fraction(max_moving_fraction)
+    ws = _workspace(lib().pcacc_accum_knn_workspace_bytes, dev, m)
+    _check(lib().pcacc_accum_knn_self(float(voxel_size), float(max_distance), int(k), int(radius), keys, acc, cap, m, int(min_count), use_f, f,
+                                      o_rows, o_distance, o_found, o_status, o_mean, _dev(kept), _dev(counters, torch.int64, 'counters'), _dev(ws),
+                                      ws.numel(), _stream()), 'accum_knn_self')
+    res = dict(out)
+    res.update(counters=counters, kept=kept)
+    return res
+
+
 COMPONENTS_COUNTERS, COMPONENTS_REMOVE_COUNTERS = 7, 4
 COMPONENTS_ROWS, COMPONENTS_PARTICIPATING, COMPONENTS_OUTSIDE, COMPONENTS_MASKED, COMPONENTS_K, COMPONENTS_LARGEST, COMPONENTS_STATUS = 0, 1, 2, 3, 4, 5, 6
 COMPONENTS_OK, COMPONENTS_BAD_MASK, COMPONENTS_GAVE_UP = 0, 1, 2
