@@ -186,6 +186,23 @@ int pcacc_pfn_features_ordered(const float *points, const int32_t *p2v, const fl
  *   in_mask [rows,k] or NULL: x is zeroed where in_mask <= 0;  out_mask [rows,n] or NULL: y is zeroed where out_mask <= 0
  * The backward-data pass is the same entry point with w transposed, the forward output as in_mask (post-ReLU layers)
  * and the forward input as out_mask (pre-ReLU layers).
+ *
+ * The mask rule of EVERY row entry point, in all three compute modes -- in_mask, out_mask, out_mask_a / out_mask_b and dy_mask of
+ * pcacc_rows_linear, _few_dual, _mixed, _bf16, _cat_bf16, _split, _split_dual, _cat_split and of pcacc_rows_wgrad, _mixed, _few, _bf16,
+ * _cat_bf16, _split, _cat_split: an element is KEPT where its mask element is > 0 and zeroed everywhere else.  -1, -0.0, +0.0 and NaN
+ * (either sign) drop; the smallest positive normal keeps.  "<= 0" above and below is shorthand for "not > 0".
+ *   Where this differs from the library: aten::threshold_backward(grad, y, 0) keeps grad where y is NaN (NaN <= 0 is false); these
+ *   kernels zero it.  A NaN mask element is a NaN forward activation: the step's loss is NaN already and the step is skipped by the
+ *   non-finite check of the gradient norm (toolbox/utils.py:147-157), so no training step's gradient depends on the choice; one rule for all of them is what the kernels implement
+ *   (mm_mask2, x3_mask4, `!(m > 0)` in mlp.hip) and what tests/test_rows_exact.py holds them to.  The convolution kernels keep on NaN
+ *   (conv_mask2, x3_outmask4): a separate contract.
+ *   ReLU on load / before the store (flags, x_relu) is max(v, 0) with -0.0 -> +0.0; the PFN blocks' x > 0 / h > 0 decisions follow the
+ *   same "> 0" rule (xmask / hmask bits, and the bf16 block's tests of x and relu_h in its backward).
+ * Where a bf16 value is held (tests/test_rows_exact.py checks each as "the exact value rounded once, to nearest even"):
+ *   y of pcacc_rows_linear_bf16 / _cat_bf16 (and y2), y of _mixed with dtypes bit 16, y16 of _few_dual / _split_dual;
+ *   with a residual the bf16 kernels round TWICE, y = bf16(bf16(x w^T + bias) + residual): the result tile is staged as bf16 before the
+ *   coalesced store phase adds the residual -- the sequence of an unfused bf16 chain (linear, then add).  Weights are rounded to bf16
+ *   once per launch, to nearest even.  fp32 outputs (every _split entry point, dw_aug) carry no rounding of this kind.
  * pcacc_rows_wgrad: dw_aug [n, k+1] f32 = dYeff^T @ [Xeff | 1] (column k is the bias gradient), fp32 MFMA;
  *   dy [rows,n], dy_mask [rows,n] or NULL (dY zeroed where dy_mask <= 0), x [rows,k], x_relu: ReLU on x at load.
  * ---------------------------------------------------------------------------------------------- */
@@ -1553,7 +1570,10 @@ int pcacc_bn_rows_backward_m(const void *grad_y, const void *x, int dtype, int64
  * x [rows,64] = `xa` when pooled == NULL, else cat(xa[row] [32], pooled[p2v[row]] [32]) (models/pillar_encoder.py:116-118).
  * forward: out [rows,32], relu_h [rows,32] (kept for the backward; may be NULL).
  * backward: grad_xa [rows,64] (pooled == NULL) or grad_xa [rows,32] + grad_xb [rows,32] (per point: the caller sums it over each
- * pillar's points); grad_params [5184] f32 = d w1 [32,32] | d b1 [32] | d ws [32,64] | d w0 [32,64] | d b0 [32]. */
+ * pillar's points); grad_params [5184] f32 = d w1 [32,32] | d b1 [32] | d ws [32,64] | d w0 [32,64] | d b0 [32].
+ * bf16 values: relu_h = bf16(relu(h)) is what the second product reads (and what the backward gets); out is rounded once; the backward holds
+ * d(h) = (grad_out w1) where relu_h > 0 as bf16 between its two products and in d w0 / d b0; grad_xa / grad_xb are rounded once; the weights
+ * are rounded to bf16 once per launch; grad_params is fp32.  "> 0" as in the mask rule of the row layers above (NaN counts as not > 0). */
 int pcacc_pfn_block_forward(const uint16_t *xa, const uint16_t *pooled, const int32_t *p2v, const float *w0, const float *b0,
                             const float *ws, const float *w1, const float *b1, uint16_t *out, uint16_t *relu_h, int64_t rows, void *stream);
 int pcacc_pfn_block_backward_workspace_bytes(int64_t rows, size_t *bytes /*host*/);
