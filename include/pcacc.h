@@ -1271,6 +1271,63 @@ int pcacc_accum_knn_self(double voxel_size, double max_distance, int32_t k, int3
                          int64_t *counters, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C17. The (x, y) columns of the accumulated scene cloud: the local ground under every column, the height of every voxel above it, what stands
+ * in a height band, and bird's-eye-view rasters of a window of columns.  Replaces the copy of extract() to the host, an np.unique over (x, y) and
+ * a minimum filter there.  Does not modify the map.  The contract is csrc/accum_columns.h, the same code in the kernels and in a g++ build.
+ * Inputs
+ *   keys, acc, stamps, capacity, m; min_count, use_fraction, max_moving_fraction     the map and extract's filter, as for pcacc_accum_normals
+ *   ground_radius R in [0, PCACC_COLUMNS_MAX_RADIUS] columns; thickness in [0, PCACC_COLUMNS_MAX_HEIGHT] voxels;
+ *   0 <= band_lo <= band_hi <= PCACC_COLUMNS_MAX_HEIGHT voxels above the ground
+ * Everything is over the rows the filter keeps; j is a row of pcacc_accum_extract under the same filter.  Keys ascend in (x, y, z), so a column
+ * is a run of consecutive rows, ascending in z.
+ *   Columns: column key = key >> 21; row j is a head iff j == 0 or its column key differs from that of row j - 1; columns are numbered in key
+ *   order, C of them.  Per column (C rows): col_key i64 (x + 2^20) << 21 | (y + 2^20); col_xy i32 [.,2]; col_first_row, col_voxels i32 (the column
+ *   is rows [first_row, first_row + voxels)); col_points, col_moving i64 (sums of count and moving); col_z_low, col_z_high i32 (voxel index z of
+ *   the first and the last row); col_t_first = min, col_t_last = max of the stamps.
+ *   Ground: col_ground_z = min col_z_low over the columns that exist within R of the column on both axes, itself included; the supplier minimises
+ *   (z_low, column key), a total order: ties go to the lower key; col_ground_row = the supplier's first_row, col_ground_column = its index.  A
+ *   neighbour outside [-2^20, 2^20) contributes nothing and forms no key.
+ *   Band: col_band_voxels = rows of the column with band_lo <= z - ground_z <= band_hi; col_band_top = the largest such z - ground_z, or -1.
+ *   Per row j: row_column i32; row_height i32 = z - ground_z(column) >= 0; row_is_ground u8 = height <= thickness; row_height_m f64 = the float64
+ *   z centroid ((sum q_z / count) * 2^-16) of row j minus that of ground_row(column), one subtraction; it may be slightly negative (a centroid
+ *   can lie 2^-17 m outside its voxel).
+ * Outputs (device): every column table and every row table has room for m rows; the first out_n[1] = C rows of the column tables and the first
+ * out_n[0] = kept rows of the row tables are written, once each; out_n [2] i64; counters [PCACC_COLUMNS_COUNTERS] i64 (written, not added to):
+ * kept rows, columns, ground rows, rows in the band, columns whose ground came from another column.
+ * pcacc_accum_bev: a width x height window of columns at the integer origin (x0, y0), |x0|, |y0| <= 2^31, width, height >= 1, width * height <=
+ * PCACC_BEV_MAX_PIXELS; pixel (r, c) = element r * width + c is column (x0 + c, y0 + r).  It takes the column tables of pcacc_accum_columns
+ * (n_columns = C, from the host) and the map under the SAME filter.  A pixel whose column lies outside the grid or is not in the list is empty:
+ * out_column -1, out_elevation and out_ground NaN, out_band_top -1, out_voxels 0.  Otherwise out_column i32 = its index, out_elevation f32 =
+ * pcacc_accum_extract's z of the column's top row (first_row + voxels - 1), out_ground f32 = that of ground_row, out_band_top, out_voxels i32.
+ * Every pixel is written once.  n_columns = 0 gives an all-empty image.
+ * Return value: PCACC_E_ARG, and nothing is launched, for a NULL table or output of non-zero size, NULL out_n, counters or workspace, m outside
+ * [0, capacity], a capacity above 2^30, n_columns outside [0, m], a radius, thickness, band or window outside its range, a workspace below
+ * pcacc_accum_columns_workspace_bytes(m) (both entries), or an output that shares a byte with a table of the map.  m = 0: zero counts.
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_COLUMNS_MAX_RADIUS 8
+#define PCACC_COLUMNS_MAX_HEIGHT 2097151
+#define PCACC_BEV_MAX_PIXELS ((int64_t)1 << 28)
+#define PCACC_COLUMNS_COUNTERS 5
+#define PCACC_COLUMNS_N_ROWS 0
+#define PCACC_COLUMNS_N_COLUMNS 1
+#define PCACC_COLUMNS_N_GROUND 2
+#define PCACC_COLUMNS_N_BAND 3
+#define PCACC_COLUMNS_N_BORROWED 4
+int pcacc_accum_columns_workspace_bytes(int64_t m, size_t *bytes /*host*/);
+int pcacc_accum_columns(const int64_t *keys, const int64_t *acc, const int32_t *stamps, int64_t capacity, int64_t m, int64_t min_count,
+                        int32_t use_fraction, double max_moving_fraction, int32_t ground_radius, int32_t thickness, int32_t band_lo,
+                        int32_t band_hi, int64_t *col_key, int32_t *col_xy, int32_t *col_first_row, int32_t *col_voxels, int64_t *col_points,
+                        int64_t *col_moving, int32_t *col_z_low, int32_t *col_z_high, int32_t *col_t_first, int32_t *col_t_last,
+                        int32_t *col_ground_z, int32_t *col_ground_row, int32_t *col_ground_column, int32_t *col_band_voxels,
+                        int32_t *col_band_top, int32_t *row_column, int32_t *row_height, uint8_t *row_is_ground, double *row_height_m,
+                        int64_t *out_n, int64_t *counters, void *workspace, size_t workspace_bytes, void *stream);
+int pcacc_accum_bev(const int64_t *keys, const int64_t *acc, int64_t capacity, int64_t m, int64_t min_count, int32_t use_fraction,
+                    double max_moving_fraction, const int64_t *col_key, const int32_t *col_first_row, const int32_t *col_voxels,
+                    const int32_t *col_ground_row, const int32_t *col_band_top, int64_t n_columns, int64_t x0, int64_t y0, int64_t width,
+                    int64_t height, int32_t *out_column, float *out_elevation, float *out_ground, int32_t *out_band_top, int32_t *out_voxels,
+                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

@@ -32,6 +32,8 @@ coordinate sums), so the map does not depend on the order of the points, on the 
     near = m.knn(scan, k=8, pose=pose, radius=2, min_count=2)    # per point: the rows of extract() and distances of its 8 nearest centroids within
     density = m.neighbors(k=8, radius=2, min_count=2)['mean_distance']   # 2 voxels; the same of every centroid of the map itself: C16, section 9p
     clean = m.select(m.outliers(k=8, std_ratio=2.0, min_count=2)['mask'], invert=True, min_count=2)   # statistical outlier removal, as a new map
+    road, objects = clean.split_ground(ground_radius=2, thickness=1)   # what the vehicle stands on and what stands on it, by the local ground under
+    image = clean.bev(band=(2, 20))['band_top']                  # every (x, y) column; elevation / ground / obstacle-height images: C17, section 9q
 
 ObservedSpace records, beside a cloud, the voxels the measured rays crossed -- where the sensor looked and found nothing (C14, section 9n).  Filled with
 space_now.observe_results(results, input_dict, pose=pose, stamp=k) next to m.add_results(...), it tells what is gone from what was never looked at:
@@ -436,6 +438,81 @@ class AccumulatedCloud(object):
         var = (torch.where(finite, mean - mu, torch.zeros_like(mean)) ** 2).sum() / count
         threshold = float(mu + std_ratio * torch.sqrt(var))                      # the one scalar; NaN (0 / 0) without a finite entry
         return dict(mean_distance=mean, threshold=threshold, mask=(mean > threshold) | ~finite)
+
+    # ---- columns, ground, bird's-eye view ----------------------------------------------------------------------------------------------
+    def _column_args(self, ground_radius, thickness, band, min_count, max_moving_fraction):
+        """ground_radius, thickness and band = (lo, hi) as the entry points of C17 take them, and the filter."""
+        ground_radius, thickness = int(ground_radius), int(thickness)
+        if not 0 <= ground_radius <= native.COLUMNS_MAX_RADIUS:
+            raise ValueError('ground_radius must lie in [0, %d] columns, got %r' % (native.COLUMNS_MAX_RADIUS, ground_radius))
+        if not 0 <= thickness <= native.COLUMNS_MAX_HEIGHT:
+            raise ValueError('thickness must lie in [0, 2^21) voxels, got %r' % thickness)
+        if band is None or len(band) != 2:
+            raise ValueError('band must be (lo, hi) in voxels above the ground, got %r' % (band,))
+        lo, hi = int(band[0]), int(band[1])
+        if not 0 <= lo <= hi <= native.COLUMNS_MAX_HEIGHT:
+            raise ValueError('band must hold 0 <= lo <= hi < 2^21, got %r' % (band,))
+        return ground_radius, thickness, lo, hi, self._filter_args(min_count, max_moving_fraction)
+
+    def columns(self, ground_radius=2, thickness=1, band=(2, 20), min_count=1, max_moving_fraction=None):
+        """The (x, y) columns of the voxels extract(min_count, max_moving_fraction) returns, the local ground under each and the height of every
+        voxel above it (include/pcacc.h C17).  The map is not modified.  A column is a run of consecutive rows of that extract(), ascending in z.
+        ground_radius in [0, 8] columns: the ground of a column is the lowest voxel of the columns within that many columns of it on both axes
+        (a minimum filter: it bridges what stands on the ground up to 2 ground_radius columns wide, and undershoots a slope by up to slope x
+        ground_radius); thickness in voxels: a voxel is ground when it lies at most that far above the local ground; band = (lo, hi) voxels above it.
+        -> dict of device tensors.  Per column, C rows in (x, y) order: key [C] i64 ((x + 2^20) << 21 | (y + 2^20)), xy [C,2] i32, first_row, voxels
+        [C] i32 (rows [first_row, first_row + voxels) of extract()), points, moving [C] i64, z_low, z_high [C] i32 (voxel indices), t_first, t_last,
+        ground_z [C] i32 (voxel index of the local ground), ground_row (the row of extract() that is it), ground_column (its column; ties go to
+        the lower (x, y)), band_voxels (voxels of the column with lo <= z - ground_z <= hi), band_top (the largest such z - ground_z, -1 = none).
+        Per row of extract(): row_column [V] i32, row_height [V] i32 = z - ground_z, row_is_ground [V] u8, row_height_m [V] f64 = the float64 z
+        centroid minus that of ground_row (slightly negative at most by 2^-16 m).  counters [5] i64: rows, columns, ground rows, rows in the band,
+        columns whose ground came from another column.  Clean floaters first (outliers, remove_components, prune): one voxel below the road pulls
+        the ground of its neighbourhood down.  Read back: the two counts."""
+        ground_radius, thickness, lo, hi, min_count = self._column_args(ground_radius, thickness, band, min_count, max_moving_fraction)
+        self._ensure()
+        out = native.accum_columns(self._cur, self._n, min_count, max_moving_fraction, ground_radius, thickness, lo, hi)
+        n = out.pop('n')
+        kept, n_col = n.tolist() if self._n else (0, 0)             # the one read-back
+        return {name: (t if name == 'counters' else t[:kept] if name.startswith('row_') else t[:n_col]) for name, t in out.items()}
+
+    def ground_mask(self, **kw):
+        """mask [V] bool over the rows of extract() under the same filter: columns(**kw)['row_is_ground'] != 0."""
+        return self.columns(**kw)['row_is_ground'] != 0
+
+    def split_ground(self, **kw):
+        """(ground, rest): the voxels ground_mask(**kw) names and the others as two NEW maps, through select(); this map is not modified."""
+        f = {a: kw[a] for a in ('min_count', 'max_moving_fraction') if a in kw}
+        mask = self.ground_mask(**kw)
+        return self.select(mask, **f), self.select(mask, invert=True, **f)
+
+    def bev(self, origin=None, shape=None, **column_kw):
+        """Bird's-eye-view images of a window of columns (include/pcacc.h C17): origin = (x0, y0) and shape = (H, W) in voxel indices, pixel (r, c) is
+        column (x0 + c, y0 + r); None = the bounding box of the columns (a min / max on the device and one more read-back; (0, 0) and (1, 1) for an
+        empty map).  column_kw: the arguments of columns().
+        -> column [H,W] i32 (the row of the columns() tables, -1 = empty), elevation [H,W] f32 (extract()'s z of the column's top voxel), ground
+        [H,W] f32 (that of its ground_row), both NaN where empty, band_top [H,W] i32 (-1), voxels [H,W] i32 (0); origin (x0, y0), voxel_size, and
+        columns: the columns() dict the images were made from."""
+        if origin is not None and (len(origin) != 2 or not all(abs(int(v)) <= 1 << 31 for v in origin)):
+            raise ValueError('origin must be (x0, y0) in voxel indices, got %r' % (origin,))
+        if shape is not None and (len(shape) != 2 or int(shape[0]) < 1 or int(shape[1]) < 1 or int(shape[0]) * int(shape[1]) > native.BEV_MAX_PIXELS):
+            raise ValueError('shape must be (H, W) with H, W >= 1 and at most 2^28 pixels, got %r' % (shape,))
+        cols = self.columns(**column_kw)
+        f = {a: column_kw[a] for a in ('min_count', 'max_moving_fraction') if a in column_kw}
+        if origin is None or shape is None:
+            if cols['xy'].shape[0]:
+                lo, hi = torch.stack([cols['xy'].min(0).values, cols['xy'].max(0).values]).tolist()       # the one more read-back
+            else:
+                lo, hi = [0, 0], [0, 0]
+            origin = tuple(lo) if origin is None else origin
+            if shape is None:
+                shape = (hi[1] - int(origin[1]) + 1, hi[0] - int(origin[0]) + 1)
+                if shape[0] < 1 or shape[1] < 1 or shape[0] * shape[1] > native.BEV_MAX_PIXELS:
+                    raise ValueError('the columns from origin %r on span %r pixels: give a shape of at most 2^28 pixels' % (tuple(origin), shape))
+        x0, y0, height, width = int(origin[0]), int(origin[1]), int(shape[0]), int(shape[1])
+        out = native.accum_bev(self._cur, self._n, self._filter_args(f.get('min_count', 1), f.get('max_moving_fraction')), f.get('max_moving_fraction'),
+                               cols, x0, y0, width, height)
+        out.update(origin=(x0, y0), voxel_size=self.voxel_size, columns=cols)
+        return out
 
     # ---- see through -------------------------------------------------------------------------------------------------------------------
     def see_through(self, points, origins, origin_index=None, pose=None, moving=None, stamp=None, margin=None, max_range=None, max_steps=4096):

@@ -993,6 +993,68 @@ def accum_knn_self(voxel_size, max_distance, k, radius, tables, m, min_count, ma
     return res
 
 
+COLUMNS_MAX_RADIUS, COLUMNS_MAX_HEIGHT, BEV_MAX_PIXELS = 8, (1 << 21) - 1, 1 << 28
+COLUMNS_COUNTERS = 5
+COLUMNS_N_ROWS, COLUMNS_N_COLUMNS, COLUMNS_N_GROUND, COLUMNS_N_BAND, COLUMNS_N_BORROWED = 0, 1, 2, 3, 4
+COLUMN_FIELDS = (('key', torch.int64, ()), ('xy', torch.int32, (2,)), ('first_row', torch.int32, ()), ('voxels', torch.int32, ()),
+                 ('points', torch.int64, ()), ('moving', torch.int64, ()), ('z_low', torch.int32, ()), ('z_high', torch.int32, ()),
+                 ('t_first', torch.int32, ()), ('t_last', torch.int32, ()), ('ground_z', torch.int32, ()), ('ground_row', torch.int32, ()),
+                 ('ground_column', torch.int32, ()), ('band_voxels', torch.int32, ()), ('band_top', torch.int32, ()))
+COLUMN_ROW_FIELDS = (('row_column', torch.int32, ()), ('row_height', torch.int32, ()), ('row_is_ground', torch.uint8, ()),
+                     ('row_height_m', torch.float64, ()))
+BEV_FIELDS = (('column', torch.int32, ()), ('elevation', torch.float32, ()), ('ground', torch.float32, ()), ('band_top', torch.int32, ()),
+              ('voxels', torch.int32, ()))
+
+
+def accum_columns(tables, m, min_count, max_moving_fraction, ground_radius, thickness, band_lo, band_hi, out=None, counters=None, n=None):
+    """The (x, y) columns of the kept voxels of the first m rows of a map, their local ground and the height of every kept row above it; see
+    include/pcacc.h (C17).  out: a dict of the COLUMN_FIELDS + COLUMN_ROW_FIELDS tensors of m rows to write into (None = new ones), counters [5] i64
+    and n [2] i64 likewise.  -> out with 'counters' and 'n' = (kept rows, columns) added: the caller reads `n` and slices."""
+    keys, acc, stamps, cap = _accum_tables(tables, 'accum_columns')
+    dev = tables[0].device
+    m = int(m)
+    out, counters, (c_key, c_xy, c_first, c_voxels, c_points, c_moving, c_zlo, c_zhi, c_tfirst, c_tlast, c_gz, c_grow, c_gcol, c_bvox, c_btop,
+                    r_column, r_height, r_ground, r_height_m) = _out_columns('accum_columns', COLUMN_FIELDS + COLUMN_ROW_FIELDS, m, out, counters,
+                                                                             COLUMNS_COUNTERS, dev)
+    if n is None:
+        n = torch.empty((2,), dtype=torch.int64, device=dev)
+    _shaped('accum_columns', 'n', n, (2,))
+    use_f, f = _fraction(max_moving_fraction)
+    ws = _workspace(lib().pcacc_accum_columns_workspace_bytes, dev, m)
+    _check(lib().pcacc_accum_columns(keys, acc, stamps, cap, m, int(min_count), use_f, f, int(ground_radius), int(thickness), int(band_lo), int(band_hi),
+                                     c_key, c_xy, c_first, c_voxels, c_points, c_moving, c_zlo, c_zhi, c_tfirst, c_tlast, c_gz, c_grow, c_gcol, c_bvox,
+                                     c_btop, r_column, r_height, r_ground, r_height_m, _dev(n, torch.int64, 'n'), _dev(counters, torch.int64, 'counters'),
+                                     _dev(ws), ws.numel(), _stream()), 'accum_columns')
+    res = dict(out)
+    res.update(counters=counters, n=n)
+    return res
+
+
+def accum_bev(tables, m, min_count, max_moving_fraction, columns, x0, y0, width, height, out=None):
+    """A width x height window of the columns of a map at the integer origin (x0, y0) as images; see include/pcacc.h (C17).  columns: the 'key',
+    'first_row', 'voxels', 'ground_row' and 'band_top' tensors of accum_columns on this map under the same filter, sliced to the C columns.  out: a
+    dict of the BEV_FIELDS tensors [height, width] to write into (None = new ones).  -> out; nothing is read back."""
+    keys, acc, _, cap = _accum_tables(tables, 'accum_bev')
+    dev = tables[0].device
+    m, width, height = int(m), int(width), int(height)
+    n_col = columns['key'].shape[0]
+    for name in ('key', 'first_row', 'voxels', 'ground_row', 'band_top'):
+        _shaped('accum_bev', 'columns[%r]' % name, columns[name], (n_col,))
+    if out is None:
+        out = {name: torch.empty((max(height, 0), max(width, 0)), dtype=dtype, device=dev) for name, dtype, _ in BEV_FIELDS}
+    for name, _, _ in BEV_FIELDS:
+        _shaped('accum_bev', 'out[%r]' % name, out[name], (max(height, 0), max(width, 0)))
+    o_column, o_elevation, o_ground, o_top, o_voxels = [_dev(out[name], dtype, name) for name, dtype, _ in BEV_FIELDS]
+    c_key, c_first, c_voxels, c_grow, c_btop = [_dev(columns[name], dtype, name) if n_col else None
+                                                for name, dtype in (('key', torch.int64), ('first_row', torch.int32), ('voxels', torch.int32),
+                                                                    ('ground_row', torch.int32), ('band_top', torch.int32))]
+    use_f, f = _fraction(max_moving_fraction)
+    ws = _workspace(lib().pcacc_accum_columns_workspace_bytes, dev, m)
+    _check(lib().pcacc_accum_bev(keys, acc, cap, m, int(min_count), use_f, f, c_key, c_first, c_voxels, c_grow, c_btop, n_col, int(x0), int(y0), width,
+                                 height, o_column, o_elevation, o_ground, o_top, o_voxels, _dev(ws), ws.numel(), _stream()), 'accum_bev')
+    return dict(out)
+
+
 COMPONENTS_COUNTERS, COMPONENTS_REMOVE_COUNTERS = 7, 4
 COMPONENTS_ROWS, COMPONENTS_PARTICIPATING, COMPONENTS_OUTSIDE, COMPONENTS_MASKED, COMPONENTS_K, COMPONENTS_LARGEST, COMPONENTS_STATUS = 0, 1, 2, 3, 4, 5, 6
 COMPONENTS_OK, COMPONENTS_BAD_MASK, COMPONENTS_GAVE_UP = 0, 1, 2
