@@ -1328,6 +1328,70 @@ int pcacc_accum_bev(const int64_t *keys, const int64_t *acc, int64_t capacity, i
                     void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C18. Planar segments of the accumulated scene cloud by normal-gated region growing: which voxels lie on one surface, with the size, box, stamps
+ * and least-squares plane of every segment and every voxel's distance to its plane.  C11 joins every voxel within `radius` of another, so a floor
+ * and the walls on it are one component; here an edge also needs the two normals of C5 to agree and each centroid to lie near the other's tangent
+ * plane.  Replaces the copy of extract() and normals() to the host and a region growing there.  The contract is csrc/accum_planes.h, the same code
+ * in the kernels and in a g++ build.  No RANSAC or growth against a running plane (order-dependent), no merging of coplanar segments across gaps,
+ * no cylinders, no label column stored in the map, no incremental relabelling, no planes across two maps, no viewpoint-oriented segment normals.
+ * Inputs
+ *   keys, acc, stamps, capacity, m; min_count, use_fraction, max_moving_fraction     the map and extract's filter, as for pcacc_accum_normals
+ *   normals, eigenvalues [n_rows,3] f32, flags [n_rows] u8     the outputs of pcacc_accum_normals on this map under this filter, on the device
+ *   mask [mask_rows] u8 or NULL      over the rows of pcacc_accum_extract under the same filter
+ *   radius 1, 2 or 3 voxels; cos_angle in [0, 1]; max_offset >= 0 metres; max_variation in [0, 1]
+ * Extract row j takes part iff the filter keeps it, mask[j] != 0 (with a mask), flags[j] has neither FEW_NEIGHBORS nor DEGENERATE, and
+ * (double)e2 <= max_variation * (((double)e0 + (double)e1) + (double)e2) with e = eigenvalues[j]; the first test that fails names the counter.
+ * Two rows i, p that take part with |delta|_inf <= radius (found as C11 finds them) are joined iff, in float64 with no FMA contraction,
+ *   |(n_ix n_px + n_iy n_py) + n_iz n_pz| >= cos_angle, and with d = c_p - c_i (c: ((double)sum q_a / (double)count) * 2^-16)
+ *   |(n_ix d_x + n_iy d_y) + n_iz d_z| <= max_offset and |(n_px d_x + n_py d_y) + n_pz d_z| <= max_offset.
+ * The rule is symmetric bit for bit, so the segments -- the connected components of that graph, numbered 0 .. K-1 by their smallest extract row --
+ * are a function of the records and the given normals alone.
+ * Outputs (device; every table has room for m rows)
+ *   out_label [kept] i32             the segment of the row, -1 where it does not take part
+ *   out_distance [kept] f64          ((n_x c_x + n_y c_y) + n_z c_z) - offset against the row's own segment; 0.0 for label -1 or a degenerate one
+ *   per segment, K rows: out_voxels i32; out_points i64; out_lo, out_hi [K,3] i32; out_first_row, out_t_first, out_t_last i32 as in C11;
+ *   out_anchor [K,3] i32 = A, the integer centroid u_a = floor(sum q_a / count) of first_row; out_spread i64 = D = max over members and axes of
+ *   |u_a - A_a|; out_shift i32 = s, the smallest s >= 0 with t = (D >> s) + 1 <= 2^31 and t t <= 2^62 / voxels; with e_a = (u_a - A_a) >> s:
+ *   out_s1 [K,3] i64 = sum e_a, out_s2 [K,6] i64 = sum e_a e_b (xx, xy, xz, yy, yz, zz), each voxel once: integers, so any order gives these bits.
+ *   The fit, a fixed float64 sequence per segment: mu_a = S1_a / voxels; C_ab = S2_ab / voxels - mu_a mu_b; the 3x3 SVD of svd3.h gives
+ *   s0 >= s1 >= s2 and u; scale = 2^(s - 16); out_normal [K,3] f64 = u[:,2], flipped iff the first non-zero of (n_z, n_y, n_x) is negative;
+ *   out_eigenvalues [K,3] f64 = s_k (scale scale); out_centroid [K,3] f64 = (A_a + mu_a 2^s) 2^-16; out_offset f64 = (n_x c_x + n_y c_y) + n_z c_z;
+ *   out_mse f64 = s2 (scale scale); out_flags u8: PCACC_PLANE_DEGENERATE when s1 <= 64 * 2^-52 * s0 (fewer than three voxels that are not
+ *   collinear): normal, offset and mse are then 0.0.
+ *   counters [PCACC_PLANES_COUNTERS] i64 (written, not added to): map rows = rows that take part + outside the filter + masked out + without a
+ *   valid normal + not flat; K; voxels of the largest segment; status.
+ * Status PCACC_PLANES_BAD_ROWS: n_rows, or mask_rows with a mask, differs from the rows the filter keeps (decided on the device): no row takes
+ * part, every label is -1, K = 0, every kept row counts as masked out.  PCACC_PLANES_GAVE_UP: as PCACC_COMPONENTS_GAVE_UP.  Rows of a table
+ * behind K (behind kept for out_label and out_distance) are not written.  The map is not modified.
+ * Return value: PCACC_E_ARG, and nothing is launched, for m outside [0, capacity], radius outside 1..3, cos_angle or max_variation outside [0, 1]
+ * or NaN, a negative or NaN max_offset, a negative row count, a NULL table or output of non-zero size, a workspace that is too small, or an output
+ * that shares a byte with a table of the map or with an input.  m = 0 writes the zero counters and launches nothing else.
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_PLANES_COUNTERS 9
+#define PCACC_PLANES_ROWS 0
+#define PCACC_PLANES_PARTICIPATING 1
+#define PCACC_PLANES_OUTSIDE 2
+#define PCACC_PLANES_MASKED 3
+#define PCACC_PLANES_INVALID 4
+#define PCACC_PLANES_NOT_FLAT 5
+#define PCACC_PLANES_K 6
+#define PCACC_PLANES_LARGEST 7
+#define PCACC_PLANES_STATUS 8
+#define PCACC_PLANES_OK 0
+#define PCACC_PLANES_BAD_ROWS 1
+#define PCACC_PLANES_GAVE_UP 2
+#define PCACC_PLANE_DEGENERATE 1
+int pcacc_accum_planes_workspace_bytes(int64_t m, size_t *bytes /*host*/);
+int pcacc_accum_planes(const int64_t *keys, const int64_t *acc, const int32_t *stamps, int64_t capacity, int64_t m, int64_t min_count,
+                       int32_t use_fraction, double max_moving_fraction, const float *normals, const float *eigenvalues, const uint8_t *flags,
+                       int64_t n_rows, const uint8_t *mask, int64_t mask_rows, int32_t radius, double cos_angle, double max_offset,
+                       double max_variation, int32_t *out_label, double *out_distance, int32_t *out_voxels, int64_t *out_points,
+                       int32_t *out_lo, int32_t *out_hi, int32_t *out_first_row, int32_t *out_t_first, int32_t *out_t_last,
+                       int32_t *out_anchor, int64_t *out_spread, int32_t *out_shift, int64_t *out_s1, int64_t *out_s2, double *out_normal,
+                       double *out_eigenvalues, double *out_centroid, double *out_offset, double *out_mse, uint8_t *out_flags,
+                       int64_t *counters, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

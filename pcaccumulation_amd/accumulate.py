@@ -34,6 +34,8 @@ coordinate sums), so the map does not depend on the order of the points, on the 
     clean = m.select(m.outliers(k=8, std_ratio=2.0, min_count=2)['mask'], invert=True, min_count=2)   # statistical outlier removal, as a new map
     road, objects = clean.split_ground(ground_radius=2, thickness=1)   # what the vehicle stands on and what stands on it, by the local ground under
     image = clean.bev(band=(2, 20))['band_top']                  # every (x, y) column; elevation / ground / obstacle-height images: C17, section 9q
+    surfaces = clean.planes(angle=15.0, min_count=2)             # a segment label per row of extract() where neighbouring normals agree, the plane and
+    flat, things = clean.split_planes(min_voxels=500, max_rms=0.03, min_count=2)   # rms of every segment; the large flat surfaces and the rest: C18, section 9r
 
 ObservedSpace records, beside a cloud, the voxels the measured rays crossed -- where the sensor looked and found nothing (C14, section 9n).  Filled with
 space_now.observe_results(results, input_dict, pose=pose, stamp=k) next to m.add_results(...), it tells what is gone from what was never looked at:
@@ -46,6 +48,8 @@ Two sessions close the same way on both sides (C15, section 9o): m.merge(other_s
 spaces (with pose= when the other session kept its own frame), and space_now.occupancy(m, coords) still answers for the merged map.
 
 There is no CPU path: a CPU tensor raises native.NativeError."""
+import math
+
 import numpy as np
 import torch
 
@@ -770,6 +774,69 @@ class AccumulatedCloud(object):
                 self._pierced = pierced_out
             self._n = res['kept']
         return res
+
+    # ---- planar segments ---------------------------------------------------------------------------------------------------------------
+    def planes(self, angle=15.0, max_offset=None, max_variation=0.01, radius=1, normal_radius=2, min_neighbors=5, min_count=1,
+               max_moving_fraction=None, mask=None, normals=None):
+        """Which voxels lie on one surface (include/pcacc.h C18): region growing over the voxels extract(min_count, max_moving_fraction) keeps.  A
+        voxel takes part when the mask (as for components) names it, its normal is valid and its neighbourhood is flat: the smallest eigenvalue
+        of normals() is at most max_variation (in [0, 1]) times the sum of the three.  Two such voxels within `radius` voxels (1, 2 or 3) are
+        joined when their normals are within `angle` degrees (in [0, 90], up to sign) and each centroid lies within max_offset metres (None = half
+        a voxel) of the other's tangent plane.  The connected sets are numbered 0 .. K-1 by their smallest (x, y, z) voxel.
+        normals: an earlier normals() result under the same filter, to be reused; otherwise normals(radius=normal_radius, min_neighbors=...) runs.
+        -> label [V] i32 aligned with extract (-1 where the row does not take part), distance [V] f64 (signed, to the plane of the row's own
+        segment); per segment voxels [K] i32, points [K] i64, lo, hi [K,3] i32, first_row, t_first, t_last [K] i32, anchor [K,3] i32, spread [K]
+        i64, shift [K] i32, s1 [K,3], s2 [K,6] i64 (the integer moments the plane is fitted to), normal, eigenvalues, centroid [K,3] f64, offset,
+        mse, rms = sqrt(mse) [K] f64, flags [K] u8 (native.PLANE_DEGENERATE: fewer than three voxels that are not collinear; normal, offset, mse
+        and every distance are then 0); counters [9] i64: native.PLANES_*.  Device tensors; only the counters are read back.  The map is not
+        modified.  Region growing is single linkage: without the flatness gate (max_variation=1) a chain of slowly turning normals joins two
+        surfaces; with it the voxels along creases and edges take no part."""
+        radius, min_count, mask = self._components_args('planes', radius, min_count, max_moving_fraction, mask)
+        angle, max_variation = float(angle), float(max_variation)
+        max_offset = 0.5 * self.voxel_size if max_offset is None else float(max_offset)
+        if not 0.0 <= angle <= 90.0:
+            raise ValueError('angle must lie in [0, 90] degrees, got %r' % angle)
+        if not max_offset >= 0.0:
+            raise ValueError('max_offset must be a distance in metres, not negative, got %r' % max_offset)
+        if not 0.0 <= max_variation <= 1.0:
+            raise ValueError('max_variation must lie in [0, 1], got %r' % max_variation)
+        if normals is not None and not (isinstance(normals, dict) and all(torch.is_tensor(normals.get(k)) for k in ('normals', 'eigenvalues', 'flags'))):
+            raise ValueError('normals must be a result of normals(): a dict with normals, eigenvalues and flags')
+        cos_angle = math.cos(math.radians(angle))                  # formed here and passed as the double: 90 degrees is 6.1e-17, not 0
+        self._ensure()
+        if normals is None:
+            normals = self.normals(radius=normal_radius, min_neighbors=min_neighbors, min_count=min_count, max_moving_fraction=max_moving_fraction)
+        res = native.accum_planes(self._cur, self._n, min_count, max_moving_fraction, normals['normals'], normals['eigenvalues'], normals['flags'],
+                                  mask, radius, cos_angle, max_offset, max_variation)
+        counters = res['counters'].tolist()                        # the one read-back
+        status = counters[native.PLANES_STATUS]
+        kept, k = counters[native.PLANES_ROWS] - counters[native.PLANES_OUTSIDE], counters[native.PLANES_K]
+        if status == native.PLANES_BAD_ROWS:
+            raise ValueError('normals and mask must have one row per row of extract() under the same filter (%d rows)' % kept)
+        if status != native.PLANES_OK:
+            raise native.NativeError('accum_planes: a join was abandoned under contention (status %d); the labels are not valid' % status)
+        out = {name: res[name][:k] for name, _, _ in native.PLANES_FIELDS}
+        out.update({name: res[name][:kept] for name, _, _ in native.PLANES_ROW_FIELDS})
+        out['rms'] = out['mse'].sqrt()
+        out['counters'] = res['counters']
+        return out
+
+    def plane_mask(self, min_voxels, max_rms=None, **kw):
+        """mask [V] bool over the rows of extract() under the same filter: the rows of the segments of planes(**kw) that have a plane, at least
+        min_voxels voxels and, with max_rms (metres), rms <= max_rms."""
+        res = self.planes(**kw)
+        good = ((res['flags'] & native.PLANE_DEGENERATE) == 0) & (res['voxels'] >= int(min_voxels))
+        if max_rms is not None:
+            good = good & (res['rms'] <= float(max_rms))
+        label = res['label'].long()
+        return (label >= 0) & good[label.clamp(min=0)] if good.shape[0] else torch.zeros_like(label, dtype=torch.bool)
+
+    def split_planes(self, min_voxels, max_rms=None, **kw):
+        """(planar, rest): the voxels plane_mask(min_voxels, max_rms, **kw) names and the others as two NEW maps, through select(); this map is
+        not modified."""
+        f = {a: kw[a] for a in ('min_count', 'max_moving_fraction') if a in kw}
+        mask = self.plane_mask(min_voxels, max_rms, **kw)
+        return self.select(mask, **f), self.select(mask, invert=True, **f)
 
     # ---- merge, regrid, copy -----------------------------------------------------------------------------------------------------------
     def copy(self):

@@ -1112,6 +1112,50 @@ def accum_remove_components(tables_in, m, pierced_in, min_count, max_moving_frac
                                                ws.numel(), _stream()), 'accum_remove_components')
 
 
+PLANES_COUNTERS = 9
+(PLANES_ROWS, PLANES_PARTICIPATING, PLANES_OUTSIDE, PLANES_MASKED, PLANES_INVALID, PLANES_NOT_FLAT, PLANES_K, PLANES_LARGEST,
+ PLANES_STATUS) = 0, 1, 2, 3, 4, 5, 6, 7, 8
+PLANES_OK, PLANES_BAD_ROWS, PLANES_GAVE_UP = 0, 1, 2
+PLANE_DEGENERATE = 1
+PLANES_ROW_FIELDS = (('label', torch.int32, ()), ('distance', torch.float64, ()))
+PLANES_FIELDS = (('voxels', torch.int32, ()), ('points', torch.int64, ()), ('lo', torch.int32, (3,)), ('hi', torch.int32, (3,)),
+                 ('first_row', torch.int32, ()), ('t_first', torch.int32, ()), ('t_last', torch.int32, ()), ('anchor', torch.int32, (3,)),
+                 ('spread', torch.int64, ()), ('shift', torch.int32, ()), ('s1', torch.int64, (3,)), ('s2', torch.int64, (6,)),
+                 ('normal', torch.float64, (3,)), ('eigenvalues', torch.float64, (3,)), ('centroid', torch.float64, (3,)),
+                 ('offset', torch.float64, ()), ('mse', torch.float64, ()), ('flags', torch.uint8, ()))
+
+
+def accum_planes(tables, m, min_count, max_moving_fraction, normals, eigenvalues, flags, mask, radius, cos_angle, max_offset, max_variation, out=None,
+                 counters=None):
+    """The planar segments of the first m rows of a map; see include/pcacc.h (C18).  normals, eigenvalues [V,3] f32, flags [V] u8: accum_normals' rows
+    on this map under the same filter (sliced to its kept count); mask [V] u8 over accum_extract's rows, or None.  out: a dict of the
+    PLANES_ROW_FIELDS + PLANES_FIELDS tensors (m rows each) to write into (None = new ones), counters [9] i64 likewise.
+    -> out with 'counters' added: the caller reads the counters and slices the row tables to the kept count, the others to K.  Nothing is read back."""
+    keys, acc, stamps, cap = _accum_tables(tables, 'accum_planes')
+    dev = tables[0].device
+    m = int(m)
+    v = normals.shape[0]
+    _shaped('accum_planes', 'normals', normals, ('V', 3))
+    _shaped('accum_planes', 'eigenvalues', eigenvalues, (v, 3))
+    _shaped('accum_planes', 'flags', flags, (v,))
+    _shaped('accum_planes', 'mask', mask, ('V',))
+    nrm, eig, flg = _dev(normals, torch.float32, 'normals'), _dev(eigenvalues, torch.float32, 'eigenvalues'), _dev(flags, torch.uint8, 'flags')
+    out, counters, (o_label, o_distance, o_voxels, o_points, o_lo, o_hi, o_row, o_first, o_last, o_anchor, o_spread, o_shift, o_s1, o_s2, o_normal,
+                    o_eig, o_centroid, o_offset, o_mse, o_flags) = _out_columns('accum_planes', PLANES_ROW_FIELDS + PLANES_FIELDS, m, out, counters,
+                                                                                PLANES_COUNTERS, dev)
+    mask_rows = 0 if mask is None else mask.shape[0]
+    use_f, f = _fraction(max_moving_fraction)
+    ws = _workspace(lib().pcacc_accum_planes_workspace_bytes, dev, m)
+    _check(lib().pcacc_accum_planes(keys, acc, stamps, cap, m, int(min_count), use_f, f, nrm if v else None, eig if v else None, flg if v else None, v,
+                                    _opt(mask, torch.uint8, 'mask'), mask_rows, int(radius), float(cos_angle), float(max_offset), float(max_variation),
+                                    o_label, o_distance, o_voxels, o_points, o_lo, o_hi, o_row, o_first, o_last, o_anchor, o_spread, o_shift, o_s1, o_s2,
+                                    o_normal, o_eig, o_centroid, o_offset, o_mse, o_flags, _dev(counters, torch.int64, 'counters'), _dev(ws),
+                                    ws.numel(), _stream()), 'accum_planes')
+    res = dict(out)
+    res['counters'] = counters
+    return res
+
+
 MERGE_COUNTERS, REGRID_COUNTERS = 5, 5
 MERGE_STATUS, MERGE_NEEDED, MERGE_SHARED, MERGE_NEW, MERGE_SATURATED = 0, 1, 2, 3, 4
 REGRID_ROWS_IN, REGRID_ROWS_OUT, REGRID_DROPPED_ROWS, REGRID_DROPPED_POINTS, REGRID_SATURATED = 0, 1, 2, 3, 4
