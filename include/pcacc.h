@@ -1392,6 +1392,62 @@ int pcacc_accum_planes(const int64_t *keys, const int64_t *acc, const int32_t *s
                        int64_t *counters, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * C19. The exact, truncated Euclidean distance field of a box of voxels of the accumulated scene cloud, with the nearest row (a feature transform):
+ * how far is every voxel of the box from the nearest voxel of the map, and which one is it.  Its planar (x, y) form is a bird's-eye-view clearance
+ * map.  Replaces the copy of extract() to the host and scipy.ndimage.distance_transform_edt there.  Does not modify the map.  The contract is
+ * csrc/accum_field.h, the same code in the kernels and in a g++ build.  No lower-envelope transform, no radius above 128 voxels and no untruncated
+ * field, no signed distance, no distance to centroids (gather extract's points by out_nearest), no incremental update, no gradient.
+ * Inputs
+ *   keys, acc, capacity, m; min_count, use_fraction, max_moving_fraction     the map and extract's filter, as for pcacc_accum_columns
+ *   x0, y0, z0, each |.| <= 2^31; nx, ny, nz >= 1: a box of voxels; max_radius R in [1, PCACC_FIELD_MAX_RADIUS] voxels; planar 0 or not
+ * Cells: nx ny nz_out with nz_out = planar ? 1 : nz, at most PCACC_FIELD_MAX_CELLS.  Cell (i, j, k) is element (i ny + j) nz_out + k (x slowest, as
+ * in the key) and stands for voxel (x0 + i, y0 + j, z0 + k).
+ * Sites: the rows of pcacc_accum_extract under the same filter whose voxel index lies inside the box (indices are subtracted in int64; a cell outside
+ * [-2^20, 2^20) never holds a site and no key is formed for it).  Row numbers are extract's: they ascend in key order.
+ * Result, planar = 0: for a cell c the lexicographic minimum over the sites s of (|c - s|^2, row(s)), |.|^2 the integer squared Euclidean distance of
+ * the indices.  If that d2 <= R^2: out_dist2[c] = d2, out_nearest[c] = row (i32 both), otherwise both are -1.  dist2 is exact wherever something
+ * lies within R voxels, and ties go to the lowest row, always.
+ * Result, planar = 1: the same in (x, y) only, d2 = dx^2 + dy^2; a site is any kept voxel of the box whatever its z inside [z0, z0 + nz), and the
+ * row reported for a column is the lowest row among the sites at the minimum: rows ascend in z within a column, so the lowest such voxel of the
+ * nearest column.  One plane is written.
+ * counters [PCACC_FIELD_COUNTERS] i64 (written, not added to): kept rows, sites, cells with a result, cells without one; the last two sum to the
+ * cells whenever m > 0.  m = 0 writes -1 to every cell and zero counters.  Every cell is written once.
+ * pcacc_accum_field_lookup: n rows, exactly one of points [n,3] f32 (through pose, rows 0-2 of a row-major 4x4 f64 or NULL = identity, by
+ * pcacc_accumulate's per-point arithmetic and validity rule at voxel_size) and coords [n,3] i32 (voxel rows, valid iff inside [-2^20, 2^20)),
+ * against the box, planar and the two grids dist2, nearest of a field call.  Per row: out_status u8 with PCACC_FIELD_VALID, PCACC_FIELD_INSIDE (the
+ * voxel lies in the box; planar: z is ignored for the cell but must lie in [z0, z0 + nz)) and PCACC_FIELD_NEAR (the cell has a result); out_dist2,
+ * out_row i32, both -1 unless NEAR.  Every output of every row is written.  counters [PCACC_FIELD_LOOKUP_COUNTERS] i64 (written): rows, valid,
+ * inside, near.  One launch, nothing is read back.
+ * Return value: PCACC_E_ARG, and nothing is launched, for a NULL table or output of non-zero size, NULL counters or workspace, m outside
+ * [0, capacity], a capacity above 2^30, a radius, origin, shape or cell count outside its range, a workspace below
+ * pcacc_accum_field_workspace_bytes(m, cells), or an output that shares a byte with a table of the map or with another output; for the lookup: n
+ * outside [0, 2^30], a voxel_size that is not positive and finite, both or neither of points and coords, a NULL grid, a box out of range.
+ * ---------------------------------------------------------------------------------------------- */
+#define PCACC_FIELD_MAX_RADIUS 128
+#define PCACC_FIELD_MAX_CELLS ((int64_t)1 << 28)
+#define PCACC_FIELD_COUNTERS 4
+#define PCACC_FIELD_N_ROWS 0
+#define PCACC_FIELD_N_SITES 1
+#define PCACC_FIELD_N_NEAR 2
+#define PCACC_FIELD_N_FAR 3
+#define PCACC_FIELD_VALID 1
+#define PCACC_FIELD_INSIDE 2
+#define PCACC_FIELD_NEAR 4
+#define PCACC_FIELD_LOOKUP_COUNTERS 4
+#define PCACC_FIELD_LOOKUP_ROWS 0
+#define PCACC_FIELD_LOOKUP_N_VALID 1
+#define PCACC_FIELD_LOOKUP_N_INSIDE 2
+#define PCACC_FIELD_LOOKUP_N_NEAR 3
+int pcacc_accum_field_workspace_bytes(int64_t m, int64_t cells, size_t *bytes /*host*/);
+int pcacc_accum_field(const int64_t *keys, const int64_t *acc, int64_t capacity, int64_t m, int64_t min_count, int32_t use_fraction,
+                      double max_moving_fraction, int64_t x0, int64_t y0, int64_t z0, int64_t nx, int64_t ny, int64_t nz, int32_t max_radius,
+                      int32_t planar, int32_t *out_dist2, int32_t *out_nearest, int64_t *counters, void *workspace, size_t workspace_bytes,
+                      void *stream);
+int pcacc_accum_field_lookup(const float *points, const int32_t *coords, int64_t n, const double *pose, double voxel_size, int64_t x0, int64_t y0,
+                             int64_t z0, int64_t nx, int64_t ny, int64_t nz, int32_t planar, const int32_t *dist2, const int32_t *nearest,
+                             uint8_t *out_status, int32_t *out_dist2, int32_t *out_row, int64_t *counters, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A6/A9. 3x3 convolution + bias + ReLU on the bf16 matrix cores -- the nn.Conv2d(3x3, stride 1, padding 1)
  * layers of models/unet.py:15-27 (conv3x3), :45-71 (DownConv), :74-113 (UpConv), :196-199 (conv_final),
  * the STPN backbone models/stpn.py:24-43, and with kt = 3 the Conv3d(3x3x3, padding 1) + ReLU stack of

@@ -36,6 +36,9 @@ coordinate sums), so the map does not depend on the order of the points, on the 
     image = clean.bev(band=(2, 20))['band_top']                  # every (x, y) column; elevation / ground / obstacle-height images: C17, section 9q
     surfaces = clean.planes(angle=15.0, min_count=2)             # a segment label per row of extract() where neighbouring normals agree, the plane and
     flat, things = clean.split_planes(min_voxels=500, max_rms=0.03, min_count=2)   # rms of every segment; the large flat surfaces and the rest: C18, section 9r
+    ground, rest = m.split_ground()                              # the clearance map of a ground robot: the exact (x, y) distance of every column of
+    f = rest.distance_field(planar=True, origin=(x0, y0, z_lo), shape=(W, H, band))   # a window to the nearest thing that stands in the robot's height
+    free = ~rest.inflate(0.6, field=f)                           # band, and where a robot of radius 0.6 m may be: C19, section 9s
 
 ObservedSpace records, beside a cloud, the voxels the measured rays crossed -- where the sensor looked and found nothing (C14, section 9n).  Filled with
 space_now.observe_results(results, input_dict, pose=pose, stamp=k) next to m.add_results(...), it tells what is gone from what was never looked at:
@@ -517,6 +520,128 @@ class AccumulatedCloud(object):
                                cols, x0, y0, width, height)
         out.update(origin=(x0, y0), voxel_size=self.voxel_size, columns=cols)
         return out
+
+    # ---- distance field, clearance, inflation ------------------------------------------------------------------------------------------
+    def _field_args(self, origin, shape, max_radius, planar, pad, min_count, max_moving_fraction):
+        """The arguments of distance_field() checked, before anything is allocated -> (max_radius, min_count)."""
+        max_radius = int(max_radius)
+        if not 1 <= max_radius <= native.FIELD_MAX_RADIUS:
+            raise ValueError('max_radius must lie in [1, %d] voxels, got %r' % (native.FIELD_MAX_RADIUS, max_radius))
+        if origin is not None and (len(origin) != 3 or not all(abs(int(v)) <= native.FIELD_MAX_ORIGIN for v in origin)):
+            raise ValueError('origin must be (x0, y0, z0) in voxel indices, each at most 2^31 in size, got %r' % (origin,))
+        if shape is not None and (len(shape) != 3 or not all(int(v) >= 1 for v in shape)):
+            raise ValueError('shape must be (nx, ny, nz) with every side >= 1, got %r' % (shape,))
+        if origin is not None and shape is not None:
+            self._field_box(origin, shape, max_radius, planar, pad)
+        return max_radius, self._filter_args(min_count, max_moving_fraction)
+
+    @staticmethod
+    def _field_box(origin, shape, max_radius, planar, pad):
+        """The box a call runs on: (origin, shape) grown by max_radius on every side (x and y only when planar) with pad -> (origin, shape, grow)."""
+        grow = (max_radius, max_radius, 0 if planar else max_radius) if pad else (0, 0, 0)
+        origin = tuple(int(v) - g for v, g in zip(origin, grow))
+        shape = tuple(int(v) + 2 * g for v, g in zip(shape, grow))
+        if not all(abs(v) <= native.FIELD_MAX_ORIGIN for v in origin):
+            raise ValueError('the box%s starts at %r: beyond 2^31' % (' grown by max_radius' if pad else '', origin))
+        if shape[0] * shape[1] * (1 if planar else shape[2]) > native.FIELD_MAX_CELLS:
+            raise ValueError('the box%s has %r cells: at most 2^28; give a smaller box, a smaller max_radius or pad=False'
+                             % (' grown by max_radius' if pad else '', shape))
+        return origin, shape, grow
+
+    def _kept_coords(self, min_count, max_moving_fraction):
+        """The voxel indices [V,3] i64 of the rows extract's filter keeps, from the keys and the two counts alone: no centroid, no other column."""
+        keys, acc, _ = self._cur
+        count, moving = acc[0, :self._n], acc[1, :self._n]
+        keep = count >= min_count
+        if max_moving_fraction is not None:
+            keep &= moving.double() / count.double() <= float(max_moving_fraction)
+        k = keys[:self._n][keep]
+        return torch.stack([(k >> 42) & 0x1fffff, (k >> 21) & 0x1fffff, k & 0x1fffff], 1) - native.ACCUM_IDX_BIAS
+
+    def _distance(self, dist2):
+        """Metres, f32: sqrt(dist2) * voxel_size in float64, inf where there is no result."""
+        metres = torch.sqrt(dist2.clamp(min=0).double()) * self.voxel_size
+        return torch.where(dist2 >= 0, metres, torch.full_like(metres, float('inf'))).float()
+
+    def distance_field(self, origin=None, shape=None, max_radius=32, planar=False, pad=True, min_count=1, max_moving_fraction=None):
+        """How far every voxel of a box is from the nearest voxel extract(min_count, max_moving_fraction) returns, exactly, up to max_radius voxels,
+        and which voxel that is (include/pcacc.h C19).  The map is not modified.  origin = (x0, y0, z0) and shape = (nx, ny, nz) in voxel indices;
+        None = the bounding box of the kept voxels (a min / max on the device and one read-back; (0, 0, 0) and (1, 1, 1) for an empty map).
+        max_radius in [1, 128] voxels.  planar: distances in (x, y) only, to any kept voxel with z inside [z0, z0 + nz): one plane, the clearance map
+        of a ground vehicle.  pad: the call runs on the box grown by max_radius on every side (x and y only when planar) and returns the inner part,
+        so that voxels just outside the box count; the counters are then those of the GROWN box, and the limit of 2^28 cells applies to it.
+        -> dict: dist2 [nx, ny, nz or 1] i32, the squared distance in voxels, -1 where nothing lies within max_radius; nearest, same shape, i32, the
+        row of extract() under the same filter that is nearest (ties go to the lowest row), -1 likewise; distance f32 = sqrt(dist2) * voxel_size in
+        metres, inf where -1; origin, shape, planar, max_radius, voxel_size; counters [4] i64: kept rows, sites (voxels inside the box; planar:
+        columns that hold one), cells with a result, cells without one."""
+        max_radius, min_count = self._field_args(origin, shape, max_radius, planar, pad, min_count, max_moving_fraction)
+        self._ensure()
+        if origin is None or shape is None:
+            coords = self._kept_coords(min_count, max_moving_fraction)
+            if coords.shape[0]:
+                lo, hi = torch.stack([coords.min(0).values, coords.max(0).values]).tolist()       # the one read-back
+            else:
+                lo, hi = [0, 0, 0], [0, 0, 0]
+            origin = tuple(lo) if origin is None else origin
+            if shape is None:
+                shape = tuple(h - int(o) + 1 for h, o in zip(hi, origin))
+                if min(shape) < 1:
+                    raise ValueError('the kept voxels end before origin %r: give a shape' % (tuple(origin),))
+        origin, shape = tuple(int(v) for v in origin), tuple(int(v) for v in shape)
+        box_origin, box_shape, grow = self._field_box(origin, shape, max_radius, planar, pad)
+        out = native.accum_field(self._cur, self._n, min_count, max_moving_fraction, box_origin, box_shape, max_radius, planar)
+        nz_out = 1 if planar else shape[2]
+        inner = tuple(slice(g, g + n) for g, n in zip(grow, (shape[0], shape[1], nz_out)))
+        dist2, nearest = out['dist2'][inner].contiguous(), out['nearest'][inner].contiguous()
+        return dict(dist2=dist2, nearest=nearest, distance=self._distance(dist2), origin=origin, shape=shape, planar=bool(planar), max_radius=max_radius,
+                    voxel_size=self.voxel_size, counters=out['counters'])
+
+    def clearance(self, points=None, coords=None, pose=None, field=None, **field_kw):
+        """The distance field at the voxels of a scan or at voxel index rows: exactly one of points [n,3] f32 (device; through pose [4,4], None =
+        identity) and coords [n,3] int32 / int64 (device).  field: a distance_field() dict to look up in; None = distance_field(**field_kw) first.
+        -> dict of device tensors, one row each: status [n] u8, a sum of native.FIELD_VALID (finite and inside the grid), FIELD_INSIDE (the voxel
+        lies in the field's box; planar: z inside [z0, z0 + nz)) and FIELD_NEAR (its cell has a result); dist2, row [n] i32, -1 unless NEAR;
+        distance [n] f32 in metres, inf unless NEAR; counters [4] i64: rows, valid, inside, near.  Nothing is read back."""
+        if (points is None) == (coords is None):
+            raise ValueError('clearance: exactly one of points and coords')
+        if points is not None:
+            _scan_points('clearance', 'points', points, native.ACCUM_MAX_POINTS)
+        else:
+            _scan_points('clearance', 'coords', coords, native.ACCUM_MAX_POINTS, 'rows')
+            if coords.dtype not in (torch.int32, torch.int64):
+                raise ValueError('coords must be int32 or int64 voxel indices, got %s' % coords.dtype)
+        pose = self._pose(pose)
+        if field is None:
+            field = self.distance_field(**field_kw)
+        elif field_kw:
+            raise ValueError('clearance: a field and arguments for a new one: %r' % sorted(field_kw))
+        self._ensure()
+        if points is not None:
+            points = points.detach().float().contiguous()
+        else:
+            if coords.dtype == torch.int64:                        # an index outside the grid stays outside after the cast
+                coords = coords.clamp(-native.ACCUM_IDX_BIAS - 1, native.ACCUM_IDX_BIAS)
+            coords = coords.to(torch.int32).contiguous()
+        out = native.accum_field_lookup(points, coords, pose, field['voxel_size'], field['origin'], field['shape'], field['planar'], field['dist2'],
+                                        field['nearest'])
+        out['distance'] = self._distance(out['dist2'])
+        return out
+
+    def inflate(self, radius_m, field=None, **field_kw):
+        """The cells of a distance field within radius_m metres of a voxel of the map, as a bool tensor of the field's shape: dist2 >= 0 and dist2 <=
+        floor(radius_m / voxel_size)^2.  With the planar field of what stands on the ground, ~inflate(r) is where a vehicle of radius r may be.
+        field: a distance_field() dict; None = distance_field(**field_kw).  The radius in voxels must not exceed the field's max_radius."""
+        radius_m = float(radius_m)
+        if not (radius_m >= 0.0 and np.isfinite(radius_m)):
+            raise ValueError('radius_m must be a finite number >= 0, got %r' % radius_m)
+        r = int(math.floor(radius_m / self.voxel_size))
+        if field is None:
+            field = self.distance_field(**field_kw)
+        elif field_kw:
+            raise ValueError('inflate: a field and arguments for a new one: %r' % sorted(field_kw))
+        if r > field['max_radius']:                               # the field knows nothing beyond its max_radius: such cells would pass for free
+            raise ValueError('radius_m is %d voxels: above the max_radius %d of the field' % (r, field['max_radius']))
+        return (field['dist2'] >= 0) & (field['dist2'] <= r * r)
 
     # ---- see through -------------------------------------------------------------------------------------------------------------------
     def see_through(self, points, origins, origin_index=None, pose=None, moving=None, stamp=None, margin=None, max_range=None, max_steps=4096):

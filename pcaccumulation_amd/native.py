@@ -1055,6 +1055,69 @@ def accum_bev(tables, m, min_count, max_moving_fraction, columns, x0, y0, width,
     return dict(out)
 
 
+FIELD_MAX_RADIUS, FIELD_MAX_CELLS, FIELD_MAX_ORIGIN = 128, 1 << 28, 1 << 31
+FIELD_COUNTERS, FIELD_LOOKUP_COUNTERS = 4, 4
+FIELD_N_ROWS, FIELD_N_SITES, FIELD_N_NEAR, FIELD_N_FAR = 0, 1, 2, 3
+FIELD_VALID, FIELD_INSIDE, FIELD_NEAR = 1, 2, 4
+FIELD_LOOKUP_ROWS, FIELD_LOOKUP_N_VALID, FIELD_LOOKUP_N_INSIDE, FIELD_LOOKUP_N_NEAR = 0, 1, 2, 3
+FIELD_LOOKUP_FIELDS = (('status', torch.uint8, ()), ('dist2', torch.int32, ()), ('row', torch.int32, ()))
+
+
+def _field_grid(origin, shape, planar):
+    """A box as the entry points of C19 take it -> (x0, y0, z0, nx, ny, nz, planar as 0 / 1, the shape of its grid)."""
+    x0, y0, z0 = (int(v) for v in origin)
+    nx, ny, nz = (int(v) for v in shape)
+    return x0, y0, z0, nx, ny, nz, 1 if planar else 0, (max(nx, 0), max(ny, 0), 1 if planar else max(nz, 0))
+
+
+def accum_field(tables, m, min_count, max_moving_fraction, origin, shape, max_radius, planar, out=None, counters=None):
+    """The exact squared distance, in voxels, of every cell of a box to the nearest kept voxel of the first m rows of a map within max_radius, and the
+    row of extract() that is it; see include/pcacc.h (C19).  origin (x0, y0, z0), shape (nx, ny, nz).  out: a dict of 'dist2' and 'nearest'
+    [nx, ny, nz or 1] i32 to write into (None = new ones), counters [4] i64 likewise.  -> {'dist2', 'nearest', 'counters'}; nothing is read back."""
+    keys, acc, _, cap = _accum_tables(tables, 'accum_field')
+    dev = tables[0].device
+    x0, y0, z0, nx, ny, nz, flat, grid = _field_grid(origin, shape, planar)
+    if out is None:
+        if not (0 < grid[0] * grid[1] * grid[2] <= FIELD_MAX_CELLS):
+            raise NativeError('accum_field failed: PCACC_E_ARG')                  # nothing to allocate for: the entry point would say the same
+        out = {name: torch.empty(grid, dtype=torch.int32, device=dev) for name in ('dist2', 'nearest')}
+    for name in ('dist2', 'nearest'):
+        _shaped('accum_field', 'out[%r]' % name, out[name], grid)
+    if counters is None:
+        counters = torch.empty((FIELD_COUNTERS,), dtype=torch.int64, device=dev)
+    _shaped('accum_field', 'counters', counters, (FIELD_COUNTERS,))
+    o_dist2, o_nearest = _dev(out['dist2'], torch.int32, 'dist2'), _dev(out['nearest'], torch.int32, 'nearest')
+    use_f, f = _fraction(max_moving_fraction)
+    ws = _workspace(lib().pcacc_accum_field_workspace_bytes, dev, int(m), grid[0] * grid[1] * grid[2])
+    _check(lib().pcacc_accum_field(keys, acc, cap, int(m), int(min_count), use_f, f, x0, y0, z0, nx, ny, nz, int(max_radius), flat, o_dist2, o_nearest,
+                                   _dev(counters, torch.int64, 'counters'), _dev(ws), ws.numel(), _stream()), 'accum_field')
+    return {'dist2': out['dist2'], 'nearest': out['nearest'], 'counters': counters}
+
+
+def accum_field_lookup(points, coords, pose, voxel_size, origin, shape, planar, dist2, nearest, out=None, counters=None):
+    """n rows against the two grids of an accum_field call on the box (origin, shape, planar); see include/pcacc.h (C19).  Exactly one of points [n,3]
+    f32 (through pose [4,4] f64 or None) and coords [n,3] i32 is given.  out: a dict of the FIELD_LOOKUP_FIELDS tensors [n] to write into (None = new
+    ones), counters [4] i64 likewise.  -> {'status', 'dist2', 'row', 'counters'} on the device; nothing is read back."""
+    if (points is None) == (coords is None):
+        raise NativeError('accum_field_lookup: exactly one of points and coords')
+    rows = points if points is not None else coords
+    _shaped('accum_field_lookup', 'points' if points is not None else 'coords', rows, ('n', 3))
+    _shaped('accum_field_lookup', 'pose', pose, (4, 4))
+    x0, y0, z0, nx, ny, nz, flat, grid = _field_grid(origin, shape, planar)
+    _shaped('accum_field_lookup', 'dist2', dist2, grid)
+    _shaped('accum_field_lookup', 'nearest', nearest, grid)
+    n, dev = rows.shape[0], dist2.device
+    src = _dev(rows, torch.float32 if points is not None else torch.int32, 'points' if points is not None else 'coords')
+    out, counters, (o_status, o_dist2, o_row) = _out_columns('accum_field_lookup', FIELD_LOOKUP_FIELDS, n, out, counters, FIELD_LOOKUP_COUNTERS, dev)
+    _check(lib().pcacc_accum_field_lookup(src if n and points is not None else None, src if n and coords is not None else None, n,
+                                          _opt(pose, torch.float64, 'pose'), float(voxel_size), x0, y0, z0, nx, ny, nz, flat,
+                                          _dev(dist2, torch.int32, 'dist2'), _dev(nearest, torch.int32, 'nearest'), o_status, o_dist2, o_row,
+                                          _dev(counters, torch.int64, 'counters'), _stream()), 'accum_field_lookup')
+    res = dict(out)
+    res.update(counters=counters)
+    return res
+
+
 COMPONENTS_COUNTERS, COMPONENTS_REMOVE_COUNTERS = 7, 4
 COMPONENTS_ROWS, COMPONENTS_PARTICIPATING, COMPONENTS_OUTSIDE, COMPONENTS_MASKED, COMPONENTS_K, COMPONENTS_LARGEST, COMPONENTS_STATUS = 0, 1, 2, 3, 4, 5, 6
 COMPONENTS_OK, COMPONENTS_BAD_MASK, COMPONENTS_GAVE_UP = 0, 1, 2
