@@ -42,8 +42,9 @@ const char *pcacc_target(void);
  * and pointers multiples of 16 bytes.  The decoder concatenations of models/unet.py:101-113. */
 int pcacc_cat2_rows(const void *a, int32_t a_row_bytes, const void *b, int32_t b_row_bytes, int64_t rows, void *out, void *stream);
 
-/* The launchers' A/B switches (PCACC_CONV_FRAME_MAJOR, PCACC_CONV_SWZ_OFF, PCACC_CONV_RES, PCACC_ROWS_FM_OFF, PCACC_CONV_PLAN: experiments and
- * the equality tests only) are read from the environment once per process; this reads them again.  Returns 0. */
+/* The launchers' switches (PCACC_CONV_FRAME_MAJOR, PCACC_CONV_SWZ_OFF, PCACC_CONV_RES, PCACC_ROWS_FM_OFF, PCACC_CONV_PLAN, PCACC_XCD_REMAP: the ones
+ * the equality tests set; the scatter-variant switches of rounds 5 and 6 are retired) are read from the environment once per process; this reads
+ * them again.  Returns 0. */
 int pcacc_reload_switches(void);
 
 /* ------------------------------------------------------------------------------------------------

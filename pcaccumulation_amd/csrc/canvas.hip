@@ -234,69 +234,20 @@ __global__ __launch_bounds__(256) void pillar_scatter_vec4(const float4 *__restr
 
 // bf16 feature rows -> bf16 canvas (the bf16 compute mode: the pillar encoder's last pooling already emits bf16 rows, so the kernel
 // moves C*2 B per occupied cell in and C*2 B per cell out -- SURVEY.md 8d's bytes with s = 2 on both sides, no fp32 [M,C] table in
-// between).  Two 16-byte pieces per lane and iteration, table words first, then the two row pieces, then the two stores.
-__global__ __launch_bounds__(256) void pillar_scatter_rows16(const uint4 *__restrict__ feats, const int32_t *__restrict__ c2p,
-                                                             int64_t n_pieces, int ppc /*16-byte pieces per cell*/, uint4 *__restrict__ canvas)
-{
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t e0 = (int64_t)blockIdx.x * 256 + threadIdx.x; e0 < n_pieces; e0 += 2 * stride) {
-        const int64_t e1 = e0 + stride;
-        const bool two = e1 < n_pieces;
-        const int64_t cell0 = e0 / ppc, cell1 = two ? e1 / ppc : cell0;
-        const int p0 = c2p[cell0], p1 = two ? c2p[cell1] : -1;
-        uint4 o0 = make_uint4(0u, 0u, 0u, 0u), o1 = o0;
-        if (p0 >= 0) o0 = feats[(int64_t)p0 * ppc + (e0 - cell0 * ppc)];
-        if (p1 >= 0) o1 = feats[(int64_t)p1 * ppc + (e1 - cell1 * ppc)];
-        canvas[e0] = o0;
-        if (two) canvas[e1] = o1;
-    }
-}
-
-// The same fill with K 16-byte pieces per lane and iteration -- K table words, then K row pieces, then K stores in flight per lane -- and, with NT,
-// the streaming cache policy on both sides (`nt` loads of the row table, `nt` stores of the canvas: every byte is touched once by this kernel).
+// between).  One 16-byte piece per lane and iteration with the streaming cache policy on both sides (`nt` loads of the table word and the row piece,
+// `nt` store of the canvas piece): the canvas is written once and read much later, the row table is read once.
+// Retired variants (round 5, profiles/r05_scatter_variants.txt and r05_cache_policy_ab.txt; code: see the parent of this commit): round 4's cached kernel with two
+// pieces per lane, 2 / 4 / 8 pieces per lane with and without the streaming policy, streaming stores with cached loads, other workgroup counts per CU.  Against
+// round 4's kernel this one took the fill from 35.4 to 32.7 us in the step (0.66 -> 0.71 of 8 TB/s), from 51 to 34 us behind 1 GiB of dirty lines, and the step
+// from 31.15 to 30.65 ms (two runs each); none of the others beat it.
 typedef uint32_t pcacc_u32x4 __attribute__((ext_vector_type(4)));
-template <int K, bool NT, bool NTL = NT>
 __global__ __launch_bounds__(256) void pillar_scatter_rows16_k(const pcacc_u32x4 *__restrict__ feats, const int32_t *__restrict__ c2p,
                                                                int64_t n_pieces, int ppc /*16-byte pieces per cell*/, pcacc_u32x4 *__restrict__ canvas)
-{
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t e0 = (int64_t)blockIdx.x * 256 + threadIdx.x; e0 < n_pieces; e0 += K * stride) {
-        int p[K];
-        int64_t src[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int64_t e = e0 + k * stride;
-            const bool in = e < n_pieces;
-            const int64_t cell = in ? e / ppc : 0;
-            p[k] = in ? (NTL ? __builtin_nontemporal_load(c2p + cell) : c2p[cell]) : -1;
-            src[k] = e - cell * ppc;
-        }
-        pcacc_u32x4 o[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            o[k] = (pcacc_u32x4){0u, 0u, 0u, 0u};
-            if (p[k] >= 0) o[k] = NTL ? __builtin_nontemporal_load(feats + (int64_t)p[k] * ppc + src[k]) : feats[(int64_t)p[k] * ppc + src[k]];
-        }
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int64_t e = e0 + k * stride;
-            if (e < n_pieces) {
-                if (NT) __builtin_nontemporal_store(o[k], canvas + e);
-                else canvas[e] = o[k];
-            }
-        }
-    }
-}
-
-// fp32 rows -> fp32 canvas with the streaming policy on both sides (the fp32 twin canvas of the 'mixed' / fp32x3 modes)
-typedef float pcacc_f32x4v __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void pillar_scatter_f32_nt(const pcacc_f32x4v *__restrict__ feats, const int32_t *__restrict__ c2p, int64_t n_pieces,
-                                                             int ppc, pcacc_f32x4v *__restrict__ canvas)
 {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n_pieces; e += (int64_t)gridDim.x * 256) {
         const int64_t cell = e / ppc;
         const int p = __builtin_nontemporal_load(c2p + cell);
-        pcacc_f32x4v o = {0.f, 0.f, 0.f, 0.f};
+        pcacc_u32x4 o = {0u, 0u, 0u, 0u};
         if (p >= 0) o = __builtin_nontemporal_load(feats + (int64_t)p * ppc + (e - cell * ppc));
         __builtin_nontemporal_store(o, canvas + e);
     }
@@ -327,35 +278,18 @@ static int pillar_scatter_launch(const void *feats, int feats_dtype, const int32
     if (feats_dtype != PCACC_F32 && !(feats_dtype == PCACC_BF16 && dtype == PCACC_BF16 && c % 8 == 0)) return PCACC_E_ARG;
     if (n_cells == 0) return PCACC_OK;
     int64_t n;
-    int width, per_lane = 1;
+    int width;
     const void *fn;
     if (feats_dtype == PCACC_BF16) {
         width = c / 8;
         n = n_cells * width;
-        // [r5] default: one piece per lane, streaming (`nt`) loads and stores -- the canvas is written once and read much later, the row table is read
-        // once: in the step 35.4 -> 32.7 us (0.66 -> 0.71 of 8 TB/s), behind 1 GiB of dirty lines 51 -> 34 us (0.46 -> 0.69), and the kernels that follow
-        // find their operands still cached (step 31.15 -> 30.65 ms, two runs each; profiles/r05_scatter_variants.txt).  '0' = round 4's kernel.
-        fn = reinterpret_cast<const void *>(pillar_scatter_rows16_k<1, true>);
-        per_lane = 1;
-        switch (pcacc_switches().scatter_variant) {               // A/B: PCACC_SCATTER_VARIANT
-        case '0': fn = reinterpret_cast<const void *>(pillar_scatter_rows16); per_lane = 2; break;
-        case '1': fn = reinterpret_cast<const void *>(pillar_scatter_rows16_k<4, true>); per_lane = 4; break;
-        case '2': fn = reinterpret_cast<const void *>(pillar_scatter_rows16_k<2, true>); per_lane = 2; break;
-        case '3': fn = reinterpret_cast<const void *>(pillar_scatter_rows16_k<4, false>); per_lane = 4; break;
-        case '4': fn = reinterpret_cast<const void *>(pillar_scatter_rows16_k<8, true>); per_lane = 8; break;
-        case '5': fn = reinterpret_cast<const void *>(pillar_scatter_rows16_k<1, true>); per_lane = 1; break;
-        case '6': fn = reinterpret_cast<const void *>(pillar_scatter_rows16_k<1, true, false>); per_lane = 1; break;     // streaming stores, cached loads
-        case '7': fn = reinterpret_cast<const void *>(pillar_scatter_rows16_k<2, true, false>); per_lane = 2; break;
-        default: break;
-        }
+        fn = reinterpret_cast<const void *>(pillar_scatter_rows16_k);
     } else if (dtype == PCACC_F32 ? (c % 4 == 0) : (c % 8 == 0)) {
         width = c / 4;
         n = dtype == PCACC_F32 ? n_cells * width : n_cells * (width / 2);
         fn = dtype == PCACC_F32 ? reinterpret_cast<const void *>(pillar_scatter_vec4<0>) : reinterpret_cast<const void *>(pillar_scatter_vec4<1>);
-        // the fp32 canvas is read by the first convolution right behind this fill: cached stores.  The streaming variant (PCACC_SCATTER_VARIANT=f) left the
-        // step where it was and slowed the bf16 fill that follows it in the 'mixed' mode from 32.7 to 41 us (profiles/r05_cache_policy_ab.txt)
-        if (dtype == PCACC_F32 && pcacc_switches().scatter_variant == 'f')
-            fn = reinterpret_cast<const void *>(pillar_scatter_f32_nt);
+        // the fp32 canvas is read by the first convolution right behind this fill: cached stores.  A streaming fp32 fill (retired; code: see the parent of
+        // this commit) left the step where it was and slowed the bf16 fill that follows it in the 'mixed' mode from 32.7 to 41 us (profiles/r05_cache_policy_ab.txt)
     } else {
         width = c;
         n = n_cells * c;
@@ -363,9 +297,7 @@ static int pillar_scatter_launch(const void *feats, int feats_dtype, const int32
     }
     // all kernel families take (features, cell2pillar, n, width, canvas)
     void *args[] = {(void *)&feats, (void *)&cell2pillar, (void *)&n, (void *)&width, (void *)&canvas};
-    const int64_t items = (n + per_lane - 1) / per_lane;
-    const int blocks_per_cu = pcacc_switches().scatter_blocks > 0 ? pcacc_switches().scatter_blocks : 8;
-    if (hipExtLaunchKernel(fn, dim3(pcacc_grid(items, 256, PCACC_CUS * blocks_per_cu)), dim3(256), args, 0, s, start, stop, 0) != hipSuccess) return PCACC_E_LAUNCH;
+    if (hipExtLaunchKernel(fn, dim3(pcacc_grid(n, 256, PCACC_CUS * 8)), dim3(256), args, 0, s, start, stop, 0) != hipSuccess) return PCACC_E_LAUNCH;
     PCACC_CHECK_LAUNCH();
     return PCACC_OK;
 }
@@ -511,10 +443,6 @@ static void switches_read()
     g_switches.conv_res = e ? e[0] : 0;
     const char *xr = getenv("PCACC_XCD_REMAP");
     g_switches.xcd_off = xr && xr[0] == '0';
-    const char *v = getenv("PCACC_SCATTER_VARIANT");
-    g_switches.scatter_variant = v ? v[0] : 0;
-    const char *b = getenv("PCACC_SCATTER_BLOCKS");
-    g_switches.scatter_blocks = b ? atoi(b) : 0;
     g_switches_read = true;
 }
 

@@ -23,32 +23,15 @@
 #include <cstdlib>
 
 
-// [r5] experiment (CSP_SHADOW_NT=1): the bf16 shadow of a forward result ('mixed' mode) is read by the BACKWARD pass, a whole forward later; stored
-// with the streaming policy it should not push the fp32 result out of the caches.  Measured the other way round: step 31.55 ms with streaming shadow
-// stores against 30.78 ms with plain ones (three interleaved pairs, profiles/r05_cache_policy_ab.txt) -- the 8-byte shadow pieces of a lane are
-// half a 16-byte fp32 piece's neighbours, and partial-line streaming writes cost more than they save.  Plain stores stay.
+// The bf16 shadow of a forward result ('mixed' mode): one plain 8-byte store per lane.  Retired experiments on the cache policy (round 5, three interleaved
+// pairs of the whole step each, profiles/r05_cache_policy_ab.txt; code: see the parent of this commit): streaming (nontemporal) shadow stores, step 31.55 ms
+// against 30.78 ms -- partial-line streaming writes cost more than they save; streaming loads of a forward layer's fp32 input, 31.04 - 32.19 ms against
+// 30.39 - 30.73 ms.  Plain loads and stores stay.
 typedef uint32_t csp_u32x2 __attribute__((ext_vector_type(2)));
-#ifndef CSP_SHADOW_NT
-#define CSP_SHADOW_NT 0
-#endif
-// experiment (CSP_IN_NT=1): the fp32 input of a forward layer is read once per layer -- streaming loads mark its lines for early eviction
-typedef float csp_f32x4v __attribute__((ext_vector_type(4)));
-#ifndef CSP_IN_NT
-#define CSP_IN_NT 0
-#endif
-__device__ __forceinline__ float4 csp_load_in4(const float *p)
-{
-    if (CSP_IN_NT) {
-        const csp_f32x4v v = __builtin_nontemporal_load(reinterpret_cast<const csp_f32x4v *>(p));
-        return make_float4(v.x, v.y, v.z, v.w);
-    }
-    return *reinterpret_cast<const float4 *>(p);
-}
 __device__ __forceinline__ void csp_store_shadow(uint16_t *p, uint32_t a, uint32_t b)
 {
     const csp_u32x2 v = {a, b};
-    if (CSP_SHADOW_NT) __builtin_nontemporal_store(v, reinterpret_cast<csp_u32x2 *>(p));
-    else *reinterpret_cast<csp_u32x2 *>(p) = v;
+    *reinterpret_cast<csp_u32x2 *>(p) = v;
 }
 
 #define CSP_THREADS 512
@@ -333,8 +316,8 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_kernel(const float 
         }
 #pragma unroll
         for (int q = 0; q < CSP_PCH; ++q) {
-            preg[q][0] = csp_load_in4(src + offs[q]);
-            preg[q][1] = csp_load_in4(src + offs[q] + 4);
+            preg[q][0] = *reinterpret_cast<const float4 *>(src + offs[q]);
+            preg[q][1] = *reinterpret_cast<const float4 *>(src + offs[q] + 4);
         }
         if constexpr (MASKED) {
 #pragma unroll
@@ -505,35 +488,13 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_kernel(const float 
 // registers during the current pass's MFMAs, the nine tap tiles of the pass's slice sit in LDS (re-staged only when the slice changes:
 // never for a one-slice layer), and the 9 x CS/16 steps of a pass run without a barrier, fragment reads two steps ahead of their MFMAs.
 // 8 waves along the pixels (NGW = 1); a wave owns MT pixel tiles x NW channel tiles.
-#ifndef CSR_EXP
-#define CSR_EXP 0                               // phase knock-outs for tools/exp_conv_res_phases.sh (1 MFMA loop, 2 patch staging, 4 stores, 8 patch loads, 16 weight staging)
-#endif
 #define CSR_WPT 9                               // 16-byte weight pieces a thread carries for the next slice (9 taps x 64 rows x 32 ch x 2 planes / 512)
-// [r6] experiment CSR_LINES = 1: whole-line stores (VERDICT round 5, item 1's second half).  As first written the weights were the MFMA's A operand and the pixels its B operand: a lane ended up with ONE pixel's
-// channels 8 g + 4 lh + 0..3 -- a store instruction wrote 32-byte pieces (two lanes) of 32 different lines, the shadow 16-byte pieces, four instructions to
-// complete a line (4 096 write requests per 512-pixel tile).  With the operands exchanged (the accumulator holds the transposed tile: same products, same
-// order of additions, bit-identical) a lane has one CHANNEL of pixels 8 g + 4 lh + 0..3; a 4 x 4 transpose inside each lane quad (two quad_perm exchanges)
-// gives quad lane k the pixel 8 g + 4 lh + k with channels 4 Q .. 4 Q + 3: eight quads write one pixel's 128-byte row, a store instruction eight whole lines
-// (the shadow: whole 64-byte rows, neighbours in memory) -- 1 024 requests per tile.
-// MEASURED (profiles/r06_conv_line_stores_ab.txt, two interleaved rounds alone + three interleaved pairs of the whole step, one box): bit-identical results;
-// alone 32 -> 32 182 vs 184 us, 64 -> 32 277 vs 284, 27 taps 316 vs 318, 32 -> 64 294 vs 320 us; in the step 30.12 / 30.05 / 30.00 ms against 29.87 / 29.87 /
-// 29.94 ms with the partial-line stores.  The write-request count is NOT what holds these layers at 3.5 TB/s (the L2 merges the pieces before they reach HBM:
-// counter traffic was 1.0 x before as well); the partial-line form stays the default, this one is kept behind the macro for the next reader of that idea.
-#ifndef CSR_LINES
-#define CSR_LINES 0
-#endif
-__device__ __forceinline__ float csr_quad_xchg1(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true)); }   // lane ^ 1
-__device__ __forceinline__ float csr_quad_xchg2(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true)); }   // lane ^ 2
-// quad lane k holds column k of a 4 x 4 block (a0 .. a3 = its rows 0 .. 3) -> row k of the block
-__device__ __forceinline__ float4 csr_quad_transpose(float a0, float a1, float a2, float a3, int k)
-{
-    const bool odd = k & 1, hi = k & 2;
-    const float r01 = csr_quad_xchg1(odd ? a0 : a1), r23 = csr_quad_xchg1(odd ? a2 : a3);
-    const float b0 = odd ? r01 : a0, b1 = odd ? a1 : r01;      // rows (k & 1) and 2 + (k & 1), columns (k & ~1), (k & ~1) + 1
-    const float b2 = odd ? r23 : a2, b3 = odd ? a3 : r23;
-    const float s0 = csr_quad_xchg2(hi ? b0 : b2), s1 = csr_quad_xchg2(hi ? b1 : b3);
-    return hi ? make_float4(s0, s1, b2, b3) : make_float4(b0, b1, s0, s1);
-}
+// The weights are the MFMA's A operand and the pixels its B operand: a lane ends up with one pixel's channels 8 g + 4 lh + 0..3, a store instruction writes 32-byte
+// pieces of 32 different lines.  Retired experiment (round 6, whole-line stores: operands exchanged, a 4 x 4 transpose inside each lane quad, a pixel-position table
+// in LDS; profiles/r06_conv_line_stores_ab.txt; code: see the parent of this commit): bit-identical results; alone 32 -> 32 182 vs 184 us, 64 -> 32 277 vs 284,
+// 27 taps 316 vs 318, 32 -> 64 294 vs 320 us; in the step 30.12 / 30.05 / 30.00 ms against 29.87 / 29.87 / 29.94 ms with these partial-line stores -- the L2 merges
+// the pieces before they reach HBM, the write-request count is not what holds these layers at 3.5 TB/s.  The phase knock-outs that timed the loop's parts (MFMA loop,
+// patch staging, stores, patch loads, weight staging) went with it.
 
 template <int CS, int NW, int MT, int PCH, bool RESTAGE, bool MASKED>          // MASKED: in_mask != NULL (a compile-time fact: a run-time branch behind the loads made the compiler copy -- and so wait for -- every loaded register at once)
 __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const float *__restrict__ in, const float *__restrict__ in_amax,
@@ -558,7 +519,6 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
     // memory for every (tile, channel group) and each of those loads was followed by s_waitcnt vmcnt(0) -- which also waits for every store issued before
     // it (loads and stores retire in order on one counter): 16 memory round trips per pass in series, and the stores never overlapped anything
     float *sb = reinterpret_cast<float *>(wl + 2 * WPL);       // [2][WROWS]: scale, bias
-    int *ptab = reinterpret_cast<int *>(sb + 2 * WROWS);       // [8 MT 32] (CSR_LINES): y << 16 | x of the tile's q-th pixel, -1 behind its last
 
     const int cog = blockIdx.x % co_groups, slot = blockIdx.x / co_groups;
     const int co0 = cog * WROWS;
@@ -573,8 +533,6 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
         sb[threadIdx.x] = wscale[blockIdx.x % co_groups * WROWS + threadIdx.x] * inv_sx;
         sb[WROWS + threadIdx.x] = (bias && relu != CSP_OUTMASK) ? bias[blockIdx.x % co_groups * WROWS + threadIdx.x] : 0.f;
     }
-    if (CSR_LINES)
-        for (int q = threadIdx.x; q < 8 * MT * 32; q += CSP_THREADS) ptab[q] = q < n_px ? ((q / bw) << 16 | (q % bw)) : -1;
 
     // slices of a tile that exist: frame taps f_lo .. f_hi (a missing frame contributes zeros), all channel slices of each
     // (tile coordinates come from the walker, frame tap f and channel slice cs of a slice s = f * nc + cs are carried along: no divisions per pass)
@@ -620,8 +578,8 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
         }
 #pragma unroll
         for (int q = 0; q < PCH; ++q) {
-            preg[q][0] = csp_load_in4(src + offs[q]);
-            preg[q][1] = csp_load_in4(src + offs[q] + 4);
+            preg[q][0] = *reinterpret_cast<const float4 *>(src + offs[q]);
+            preg[q][1] = *reinterpret_cast<const float4 *>(src + offs[q] + 4);
         }
         if constexpr (MASKED) {                                // the masked data gradient of the fp32x3 backward (not on the mixed mode's path)
 #pragma unroll
@@ -690,32 +648,9 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
     // written before, load burst, MFMA phase and store burst took turns (57 + 53 + 71 us of a 181 us layer, measured by knocking each out)
     constexpr bool DEFER = !RESTAGE;
     float4 pend[MT][NW][4];
-    int pend_pyx[MT], pend_img = 0, pend_y0 = 0, pend_x0 = 0;
+    int pend_pyx[MT], pend_img = 0;
     bool have_pend = false;
-    // the image position of the pixel this lane stores for pixel tile j, group g (CSR_LINES): -1 outside the tile or the image
-    auto line_pyx = [&](int j, int g, int y0, int x0) __attribute__((always_inline)) {
-        const int t = ptab[(wave + 8 * j) * 32 + 8 * g + 4 * lh + (lp & 3)];
-        const int y = y0 + (t >> 16), x = x0 + (t & 0xffff);
-        return (t >= 0 && y < h && x < w) ? (y << 16 | x) : -1;
-    };
     auto flush = [&]() __attribute__((always_inline)) {
-        if (CSR_LINES) {
-#pragma unroll
-            for (int j = 0; j < MT; ++j)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int yx = line_pyx(j, g, pend_y0, pend_x0);
-                    if (yx < 0) continue;
-                    const int64_t o = (((int64_t)pend_img * h + (yx >> 16)) * w + (yx & 0xffff)) * c_out + co0 + 4 * (lp >> 2);
-#pragma unroll
-                    for (int n = 0; n < NW; ++n) {
-                        const float4 v = pend[j][n][g];
-                        *reinterpret_cast<float4 *>(out + o + n * 32) = v;
-                        if (out16) csp_store_shadow(out16 + o + n * 32, pcacc_pack_bf16x2(v.x, v.y), pcacc_pack_bf16x2(v.z, v.w));
-                    }
-                }
-            return;
-        }
 #pragma unroll
         for (int j = 0; j < MT; ++j) {
             if (pend_pyx[j] < 0) continue;
@@ -741,8 +676,8 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
                     for (int r = 0; r < 16; ++r) acc[j][n][r] = 0.f;
         }
         __syncthreads();                                       // the previous pass is done with the patch and the weight tiles
-        if (!(CSR_EXP & 2)) write_patch();
-        if (RESTAGE && !(CSR_EXP & 16)) write_w();             // unconditionally (46 - 92 KB of LDS writes against ~1 MB of fragment reads per pass):
+        write_patch();
+        if (RESTAGE) write_w();                                // unconditionally (46 - 92 KB of LDS writes against ~1 MB of fragment reads per pass):
         __syncthreads();                                       // under a condition the compiler keeps the pieces in scratch memory
         // the next pass: its patch and its weight tiles in flight during this pass's MFMAs
         int nk = k, ns = s + 1, nf = f, ncs = cs + 1;
@@ -753,9 +688,9 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
             if (nk < n_mine) { nxt = walk.get(nk); ns = first_slice(nxt); nf = ns ? 1 : 0; ncs = 0; }
             else { ns = s; nf = f; ncs = cs; }
         }
-        if (nk < n_mine && !(CSR_EXP & 8)) fetch_patch(nxt, nf, ncs);
-        if (RESTAGE && !(CSR_EXP & 16)) fetch_w(nf, ncs);
-        if (have_pend && !(CSR_EXP & 4)) flush();
+        if (nk < n_mine) fetch_patch(nxt, nf, ncs);
+        if (RESTAGE) fetch_w(nf, ncs);
+        if (have_pend) flush();
         have_pend = false;
 
         // the lane's pixels of this tile
@@ -769,7 +704,7 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
             poff[j] = ok ? (y * pw + x) * PS : 0;
             pyx[j] = ok ? ((y0 + y) << 16 | (x0 + x)) : -1;
         }
-        if (!(CSR_EXP & 1)) {
+        {                                                      // the pass's MFMAs
             x3_f16x8 ah[AHEAD + 1][NW], al[AHEAD + 1][NW], bh[AHEAD + 1][MT], bl[AHEAD + 1][MT];
             const uint16_t *wa = wl + lp * PS + lh * 8;
             auto load = [&](int slt, int st) __attribute__((always_inline)) {
@@ -796,61 +731,21 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
                 for (int j = 0; j < MT; ++j)
 #pragma unroll
                     for (int n = 0; n < NW; ++n)
-                        acc[j][n] = CSR_LINES ? __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[c][j], ah[c][n], acc[j][n], 0, 0, 0)
-                                              : __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[c][n], bl[c][j], acc[j][n], 0, 0, 0);
+                        acc[j][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[c][n], bl[c][j], acc[j][n], 0, 0, 0);
 #pragma unroll
                 for (int j = 0; j < MT; ++j)
 #pragma unroll
                     for (int n = 0; n < NW; ++n)
-                        acc[j][n] = CSR_LINES ? __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[c][j], al[c][n], acc[j][n], 0, 0, 0)
-                                              : __builtin_amdgcn_mfma_f32_32x32x16_f16(al[c][n], bh[c][j], acc[j][n], 0, 0, 0);
+                        acc[j][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[c][n], bh[c][j], acc[j][n], 0, 0, 0);
 #pragma unroll
                 for (int j = 0; j < MT; ++j)
 #pragma unroll
                     for (int n = 0; n < NW; ++n)
-                        acc[j][n] = CSR_LINES ? __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[c][j], ah[c][n], acc[j][n], 0, 0, 0)
-                                              : __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[c][n], bh[c][j], acc[j][n], 0, 0, 0);
+                        acc[j][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[c][n], bh[c][j], acc[j][n], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if (nk != k && CSR_LINES) {                            // last slice of this tile: a lane holds channel lp of pixels 8 g + 4 lh + 0..3 -- scales off, bias, ReLU, then the quad transpose
-            pend_img = img;
-            pend_y0 = y0;
-            pend_x0 = x0;
-#pragma unroll
-            for (int n = 0; n < NW; ++n) {
-                const float sc = sb[n * 32 + lp], bv = sb[WROWS + n * 32 + lp];
-#pragma unroll
-                for (int j = 0; j < MT; ++j)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        float a[4];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            a[i] = acc[j][n][4 * g + i] * sc + bv;
-                            if (relu && relu != CSP_OUTMASK) a[i] = fmaxf(a[i], 0.f);
-                        }
-                        float4 v = csr_quad_transpose(a[0], a[1], a[2], a[3], lp & 3);
-                        bool ok = true;                        // a pixel outside the tile or the image repeats the tile's first pixel: it cannot raise the maximum ...
-                        if (relu == CSP_OUTMASK) {             // ... unless that pixel's own result is masked away
-                            const int yx = line_pyx(j, g, y0, x0);
-                            ok = yx >= 0;
-                            if (ok) v = x3_outmask4(v, *reinterpret_cast<const float4 *>(bias + (((int64_t)img * h + (yx >> 16)) * w + (yx & 0xffff)) * c_out + co0 + n * 32 + 4 * (lp >> 2)));
-                        }
-                        pend[j][n][g] = v;
-                        if (ok) {
-                            omax = fmaxf(fmaxf(omax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-                            if (!(v.x == v.x && v.y == v.y && v.z == v.z && v.w == v.w)) omax = __builtin_inff();
-                        }
-                    }
-            }
-            have_pend = true;
-            if (!DEFER) {
-                if (!(CSR_EXP & 4)) flush();
-                have_pend = false;
-            }
-        }
-        if (nk != k && !CSR_LINES) {                           // last slice of this tile: scales off, bias, ReLU -> the pending registers
+        if (nk != k) {                                         // last slice of this tile: scales off, bias, ReLU -> the pending registers
             pend_img = img;
 #pragma unroll
             for (int j = 0; j < MT; ++j) {
@@ -877,7 +772,7 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
             }
             have_pend = true;
             if (!DEFER) {                                      // the re-staging variants have no registers to spare for the delay
-                if (!(CSR_EXP & 4)) flush();
+                flush();
                 have_pend = false;
             }
         }
@@ -887,7 +782,7 @@ __global__ __launch_bounds__(CSP_THREADS) void conv3x3_split_res_kernel(const fl
         cs = ncs;
         cur = nxt;
     }
-    if (have_pend && !(CSR_EXP & 4)) flush();
+    if (have_pend) flush();
     if (out_amax) {
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) omax = fmaxf(omax, __shfl_xor(omax, d, 64));
@@ -910,8 +805,7 @@ static bool conv_res_fits(int cs, int nw, int mt, int rows, int bw, size_t *lds)
 {
     const int64_t pp = (int64_t)(rows + 2) * (bw + 2);
     const int wrows = 32 * nw, pch = conv_res_pch(cs, nw, mt);
-    *lds = (size_t)(2 * pp + 2 * 9 * wrows) * (cs + 8) * sizeof(uint16_t) + 2 * wrows * sizeof(float) +    // + scale / bias of the workgroup's channels
-           (CSR_LINES ? 8 * mt * 32 * sizeof(int) : 0);                                                      // + the tile's pixel positions
+    *lds = (size_t)(2 * pp + 2 * 9 * wrows) * (cs + 8) * sizeof(uint16_t) + 2 * wrows * sizeof(float);     // + scale / bias of the workgroup's channels
     return pch > 0 && pp * (cs / 8) <= CSP_THREADS * pch && *lds <= CSP_LDS_MAX && 2 * 9 * wrows * (cs / 8) <= CSP_THREADS * CSR_WPT &&
            rows + 2 < 0x7ff && bw + 2 < 0xfff;
 }

@@ -591,12 +591,9 @@ extern "C" int pcacc_segment_max_dual(const float *src, int c, const int32_t *se
 // c / 4 lanes per cell; pillars are numbered in cell order (ops.PillarIndex), so the winners' table is written front to back.
 // ---------------------------------------------------------------------------------------------------
 typedef uint32_t seg_u32x2 __attribute__((ext_vector_type(2)));
-typedef float seg_f32x4 __attribute__((ext_vector_type(4)));
-typedef int seg_i32x4 __attribute__((ext_vector_type(4)));
-// CPG cells per lane group and iteration: the chain cell table -> segment offsets -> order -> point rows is four dependent memory round trips per cell; with two
-// cells in flight per group every round trip carries twice the requests (rows of ~3 points per pillar: the kernel is bound by what it keeps in flight).
-// NT: the point rows and their order are read once, the winners are read a whole forward later: streaming policy for those; the fp32 canvas keeps cached stores.
-template <int LPP, int CPG, bool NT>
+// One cell per lane group and iteration, cached loads of the point rows.  The chain cell table -> segment offsets -> order -> point rows is four dependent memory
+// round trips per cell; the first four rows of a pillar are in flight together.
+template <int LPP>
 __global__ __launch_bounds__(256) void seg_max_canvas_kernel(const float4 *__restrict__ src, const int32_t *__restrict__ seg_offsets,
                                                              const int32_t *__restrict__ order, const int32_t *__restrict__ cell2pillar, int64_t n_cells,
                                                              float4 *__restrict__ canvas32, uint16_t *__restrict__ canvas16, int4 *__restrict__ arg)
@@ -604,76 +601,41 @@ __global__ __launch_bounds__(256) void seg_max_canvas_kernel(const float4 *__res
     const int sub = threadIdx.x % LPP;
     const int64_t per_block = 256 / LPP;
     const int64_t stride = (int64_t)gridDim.x * per_block;
-    auto ld_row = [&](int64_t i4) -> float4 {
-        if (NT) {
-            const seg_f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const seg_f32x4 *>(src) + i4);
-            return make_float4(v.x, v.y, v.z, v.w);
-        }
-        return src[i4];
-    };
-    for (int64_t cell0 = (int64_t)blockIdx.x * per_block + threadIdx.x / LPP; cell0 < n_cells; cell0 += stride * CPG) {
-        int s[CPG], b[CPG], e[CPG];
+    for (int64_t cell = (int64_t)blockIdx.x * per_block + threadIdx.x / LPP; cell < n_cells; cell += stride) {
+        const int s = cell2pillar[cell];
+        const int b = s >= 0 ? seg_offsets[s] : 0;
+        const int e = s >= 0 ? seg_offsets[s + 1] : 0;
+        float4 best = make_float4(0.f, 0.f, 0.f, 0.f);
+        int4 bi = make_int4(-1, -1, -1, -1);
+        int idx[4];
+        float4 rows[4];
 #pragma unroll
-        for (int u = 0; u < CPG; ++u) {
-            const int64_t cell = cell0 + u * stride;
-            s[u] = cell < n_cells ? cell2pillar[cell] : -1;
-        }
+        for (int j = 0; j < 4; ++j) idx[j] = b + j < e ? order[b + j] : -1;
 #pragma unroll
-        for (int u = 0; u < CPG; ++u) {
-            b[u] = s[u] >= 0 ? seg_offsets[s[u]] : 0;
-            e[u] = s[u] >= 0 ? seg_offsets[s[u] + 1] : 0;
-        }
-        float4 best[CPG];
-        int4 bi[CPG];
-        int idx[CPG][4];
-        float4 rows[CPG][4];
+        for (int j = 0; j < 4; ++j) rows[j] = idx[j] >= 0 ? src[(int64_t)idx[j] * LPP + sub] : make_float4(0.f, 0.f, 0.f, 0.f);
+        int k0 = b;
+        while (true) {                                                      // four rows at a time
 #pragma unroll
-        for (int u = 0; u < CPG; ++u) {
-            best[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            bi[u] = make_int4(-1, -1, -1, -1);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) idx[u][j] = b[u] + j < e[u] ? (NT ? __builtin_nontemporal_load(order + b[u] + j) : order[b[u] + j]) : -1;
-        }
-#pragma unroll
-        for (int u = 0; u < CPG; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) rows[u][j] = idx[u][j] >= 0 ? ld_row((int64_t)idx[u][j] * LPP + sub) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int u = 0; u < CPG; ++u) {
-            int k0 = b[u];
-            while (true) {                                                  // the first four rows of both cells are in flight together; longer pillars go on alone
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int i = idx[u][j];
-                    if (i < 0) continue;
-                    const float4 v = rows[u][j];
-                    if (bi[u].x < 0 || v.x > best[u].x || (v.x == best[u].x && i < bi[u].x)) { best[u].x = v.x; bi[u].x = i; }
-                    if (bi[u].y < 0 || v.y > best[u].y || (v.y == best[u].y && i < bi[u].y)) { best[u].y = v.y; bi[u].y = i; }
-                    if (bi[u].z < 0 || v.z > best[u].z || (v.z == best[u].z && i < bi[u].z)) { best[u].z = v.z; bi[u].z = i; }
-                    if (bi[u].w < 0 || v.w > best[u].w || (v.w == best[u].w && i < bi[u].w)) { best[u].w = v.w; bi[u].w = i; }
-                }
-                k0 += 4;
-                if (k0 >= e[u]) break;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) idx[u][j] = k0 + j < e[u] ? order[k0 + j] : -1;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) rows[u][j] = idx[u][j] >= 0 ? ld_row((int64_t)idx[u][j] * LPP + sub) : make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int j = 0; j < 4; ++j) {
+                const int i = idx[j];
+                if (i < 0) continue;
+                const float4 v = rows[j];
+                if (bi.x < 0 || v.x > best.x || (v.x == best.x && i < bi.x)) { best.x = v.x; bi.x = i; }
+                if (bi.y < 0 || v.y > best.y || (v.y == best.y && i < bi.y)) { best.y = v.y; bi.y = i; }
+                if (bi.z < 0 || v.z > best.z || (v.z == best.z && i < bi.z)) { best.z = v.z; bi.z = i; }
+                if (bi.w < 0 || v.w > best.w || (v.w == best.w && i < bi.w)) { best.w = v.w; bi.w = i; }
             }
-        }
+            k0 += 4;
+            if (k0 >= e) break;
 #pragma unroll
-        for (int u = 0; u < CPG; ++u) {
-            const int64_t cell = cell0 + u * stride;
-            if (cell >= n_cells) continue;
-            if (s[u] >= 0) {
-                if (NT) {
-                    const seg_i32x4 a = {bi[u].x, bi[u].y, bi[u].z, bi[u].w};
-                    __builtin_nontemporal_store(a, reinterpret_cast<seg_i32x4 *>(arg) + (int64_t)s[u] * LPP + sub);
-                } else arg[(int64_t)s[u] * LPP + sub] = bi[u];
-            }
-            canvas32[cell * LPP + sub] = best[u];
-            const seg_u32x2 pk = {pcacc_pack_bf16x2(best[u].x, best[u].y), pcacc_pack_bf16x2(best[u].z, best[u].w)};
-            __builtin_nontemporal_store(pk, reinterpret_cast<seg_u32x2 *>(canvas16) + cell * LPP + sub);
+            for (int j = 0; j < 4; ++j) idx[j] = k0 + j < e ? order[k0 + j] : -1;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) rows[j] = idx[j] >= 0 ? src[(int64_t)idx[j] * LPP + sub] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
+        if (s >= 0) arg[(int64_t)s * LPP + sub] = bi;
+        canvas32[cell * LPP + sub] = best;
+        const seg_u32x2 pk = {pcacc_pack_bf16x2(best.x, best.y), pcacc_pack_bf16x2(best.z, best.w)};
+        __builtin_nontemporal_store(pk, reinterpret_cast<seg_u32x2 *>(canvas16) + cell * LPP + sub);
     }
 }
 
@@ -690,31 +652,24 @@ extern "C" int pcacc_segment_max_canvas(const float *src, int c, const int32_t *
     if (!cell2pillar || !canvas32 || !canvas16 || (m > 0 && (!seg_offsets || !arg || (n > 0 && (!src || !order))))) return PCACC_E_ARG;
     if (seg_use_two_level(n, m)) return PCACC_E_ARG;              // long segments: the two-level pooling + the separate fills (the caller's fallback)
     const void *fn;
-    int cpg = 1;
-    // Measured (tools/bench_fused_canvas.py, profiles/r06_fused_canvas_variants.txt; alone, warm / behind 1 GiB of streamed lines): one cell per group with
-    // cached loads 208 / 222 us, with streaming loads 198 / 200 us, two cells in flight 199 / 215 us, four 229 / 237 us -- bound by the random 128-byte row
-    // reads themselves, not by how many of them a lane group keeps in flight.  INSIDE the step the rows were written by the layer in front and partly still
-    // sit in the Infinity Cache: cached loads 191 us, streaming loads 199 - 209 us (three bench runs each) -- cached loads are the default.
-    const char variant = pcacc_switches().scatter_variant;     // A/B (PCACC_SCATTER_VARIANT): 'c' streaming loads; 'b' two cells, cached loads; 'e' two cells, streaming; 'd' four
+    // Retired variants (round 6, tools/bench_fused_canvas.py, profiles/r06_fused_canvas_variants.txt; code: see the parent of this commit).  Alone, warm / behind
+    // 1 GiB of streamed lines: one cell per group with cached loads 208 / 222 us, with streaming loads 198 / 200 us, two cells in flight 199 / 215 us, four
+    // 229 / 237 us -- bound by the random 128-byte row reads themselves, not by how many of them a lane group keeps in flight.  INSIDE the step the rows were
+    // written by the layer in front and partly still sit in the Infinity Cache: cached loads 191 us, streaming loads 199 - 209 us (three bench runs each) --
+    // one cell per group with cached loads is the kernel.
     switch (c / 4) {
-        case 1: fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<1, 1, false>); break;
-        case 2: fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<2, 1, false>); break;
-        case 4: fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<4, 1, false>); break;
-        case 8:
-            fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<8, 1, false>);
-            if (variant == 'c') fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<8, 1, true>);
-            else if (variant == 'b') { fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<8, 2, false>); cpg = 2; }
-            else if (variant == 'e') { fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<8, 2, true>); cpg = 2; }
-            else if (variant == 'd') { fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<8, 4, true>); cpg = 4; }
-            break;
-        case 16: fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<16, 1, false>); break;
-        case 32: fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<32, 1, false>); break;
-        case 64: fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<64, 1, false>); break;
+        case 1: fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<1>); break;
+        case 2: fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<2>); break;
+        case 4: fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<4>); break;
+        case 8: fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<8>); break;
+        case 16: fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<16>); break;
+        case 32: fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<32>); break;
+        case 64: fn = reinterpret_cast<const void *>(seg_max_canvas_kernel<64>); break;
         default: return PCACC_E_ARG;
     }
     void *args[] = {(void *)&src, (void *)&seg_offsets, (void *)&order, (void *)&cell2pillar, (void *)&n_cells, (void *)&canvas32, (void *)&canvas16, (void *)&arg};
     // events attached to the dispatch itself (see pillar_scatter_launch, canvas.hip): bench.py times this kernel live for its roofline object
-    if (hipExtLaunchKernel(fn, dim3(pcacc_grid((n_cells + cpg - 1) / cpg * (c / 4), 256)), dim3(256), args, 0, pcacc_stream(stream), reinterpret_cast<hipEvent_t>(start_event),
+    if (hipExtLaunchKernel(fn, dim3(pcacc_grid(n_cells * (c / 4), 256)), dim3(256), args, 0, pcacc_stream(stream), reinterpret_cast<hipEvent_t>(start_event),
                            reinterpret_cast<hipEvent_t>(stop_event), 0) != hipSuccess)
         return PCACC_E_LAUNCH;
     PCACC_CHECK_LAUNCH();

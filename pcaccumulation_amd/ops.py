@@ -94,9 +94,6 @@ class PillarIndex(object):
 
 
 # ---------------------------------------------------------------------------------------------------
-_SEGMAX_DUAL = os.environ.get('PCACC_SEGMAX_DUAL', '1') != '0'      # A/B switch: '0' = the pooled rows' bf16 shadow by a conversion pass of its own (before round 5)
-
-
 class _SegmentMax(torch.autograd.Function):
     """scatter(net, p2v, dim=0, reduce='max') -- models/pillar_encoder.py:116,120."""
 
@@ -106,7 +103,9 @@ class _SegmentMax(torch.autograd.Function):
         mixed = _MIXED and src.dtype == torch.bfloat16 and twin(src, required=False) is not None
         if mixed:                                                  # shadow rows: maxima AND winners from the fp32 twin (a bf16 copy ties close values)
             s32 = twin(src)
-            if _SEGMAX_DUAL and s32.dtype == torch.float32 and s32.is_contiguous() and not native._seg_two_level(s32.shape[0], pidx.m):
+            # the shadow from the pooling's own store; a conversion pass of its own (before round 5, retired: see the parent of this commit) measured the
+            # same step within the noise -- p50 29.95 against 30.09 ms, profiles/r05_batched_loads_ab.txt -- and three passes more in the trace
+            if s32.dtype == torch.float32 and s32.is_contiguous() and not native._seg_two_level(s32.shape[0], pidx.m):
                 out, out16, arg = native.segment_max_dual(s32, pidx.seg_offsets, pidx.order, pidx.m)   # the shadow from the same store, not a pass of its own
                 out = shadow(carry_amax(s32, out), out16)
             else:
@@ -163,12 +162,11 @@ class _SegmentMaxCanvas(torch.autograd.Function):
         return native.segment_max_canvas_backward(g, arg, pidx.p2v, pidx.cell, pidx.n, out_dtype=torch.bfloat16), None
 
 
-_FUSED_CANVAS = os.environ.get('PCACC_FUSED_CANVAS', '1') != '0'      # A/B switch: '0' = pooling, then the two canvas fills (rounds 1-5)
-
-
 def segment_max_canvas_available(src, pidx):
-    """'mixed' mode on the GPU, bf16 shadow rows with a contiguous fp32 twin, a full pillar index (cell table), short segments."""
-    if not (_FUSED_CANVAS and _MIXED and src.is_cuda and src.dtype == torch.bfloat16 and src.dim() == 2 and src.shape[1] % 4 == 0 and src.is_contiguous()
+    """'mixed' mode on the GPU, bf16 shadow rows with a contiguous fp32 twin, a full pillar index (cell table), short segments.  Where it applies it is the
+    only path: pooling followed by the two canvas fills (rounds 1-5; the switch back to it is retired, see the parent of this commit) moved 1 338 MB in
+    three kernels and 249 us against 902 MB and 191 us here."""
+    if not (_MIXED and src.is_cuda and src.dtype == torch.bfloat16 and src.dim() == 2 and src.shape[1] % 4 == 0 and src.is_contiguous()
             and getattr(pidx, 'cell2pillar', None) is not None and getattr(pidx, 'cell', None) is not None and pidx.m > 0
             and not native._seg_two_level(src.shape[0], pidx.m)):
         return False
@@ -308,9 +306,8 @@ def gather_rows(src2d, idx):
 
 # [r6] A training step is bit-reproducible: every sum over rows runs in a fixed order or in integers (CSR ascending inside segments of any length, piece sums
 # added in piece order, partial-slot reductions in slot order, the offset centres and the few-row sums of the TubeNet in 64-bit fixed point).  The
-# neighbourhood sums of the sparse ego-head convolution's backward used Tensor.index_add_ (fp32 atomics in arrival order): with this switch on (default) they
-# take a CSR + the atomic-free segment sum instead.  PCACC_DETERMINISTIC=0 restores index_add_ (A/B only).
-DETERMINISTIC = os.environ.get('PCACC_DETERMINISTIC', '1') != '0'
+# neighbourhood sums of the sparse ego-head convolution's backward take a CSR + the atomic-free segment sum (_SparseConv3x3.backward); the Tensor.index_add_
+# they used before (fp32 atomics in arrival order) is retired -- what the fixed order costs: profiles/r06_determinism.txt; code: see the parent of this commit.
 
 
 class ScatterPlan(object):
@@ -708,8 +705,9 @@ def pfn_block(block, x, pooled=None, pidx=None, pool=False):
 
 def pfn_pool_block_available(block, x, pidx):
     """block(cat(x, segment_max(x)[p2v])) as one node: the fused block's conditions with a [m, 32] pooled half in the rows' type
-    (short segments: native.segment_max keeps the type)."""
-    return (x.shape[1] == 32 and x.is_cuda and not native._seg_two_level(x.shape[0], pidx.m) and os.environ.get('PCACC_PFN_POOL_NODE', '1') != '0'
+    (short segments: native.segment_max keeps the type).  Pooling and block as two nodes (the switch back is retired, see the parent of this commit) cost
+    0.27 ms of kernels more per step; whole-step A/B 29.55 against 29.19 ms."""
+    return (x.shape[1] == 32 and x.is_cuda and not native._seg_two_level(x.shape[0], pidx.m)
             and pfn_block_available(block, x, torch.empty((0, 32), dtype=x.dtype, device=x.device)))
 
 
@@ -969,9 +967,9 @@ class _Cat2(torch.autograd.Function):
 
 def _cat2(a, b, dim):
     """torch.cat((a, b), dim) -- through pcacc_cat2_rows when both are channels-last maps concatenated along the channels (dim 1 of NCHW) or plain
-    rows concatenated along their last dimension, on the GPU, with 16-byte row pieces."""
-    if a.is_cuda and a.dtype == b.dtype and a.dtype in (torch.float32, torch.bfloat16) and a.dim() == b.dim() \
-            and os.environ.get('PCACC_OWN_CAT', '1') != '0':
+    rows concatenated along their last dimension, on the GPU, with 16-byte row pieces (torch.cat on these shapes: 18 launches and 0.72 ms per step where this
+    kernel takes 10 and 0.29 ms; the switch back to torch.cat is retired)."""
+    if a.is_cuda and a.dtype == b.dtype and a.dtype in (torch.float32, torch.bfloat16) and a.dim() == b.dim():
         ar = None
         if a.dim() == 4 and dim == 1:
             ar, br = a.permute(0, 2, 3, 1), b.permute(0, 2, 3, 1)
@@ -1520,9 +1518,10 @@ class _Conv3x3CatMixed(_Conv3x3):
 
 def conv3x3_cat(a, b, conv, relu=False, premasked=False):
     """`relu?(conv(cat((a, b), 1)))` for a decoder stage.  'mixed' mode on the GPU: the fp32 forward reads the two twins in place, only the bf16
-    shadows are concatenated (for the bf16 backward); everything else: cat_maps + conv3x3."""
+    shadows are concatenated (for the bf16 backward); everything else: cat_maps + conv3x3.  (The switch that sent the 'mixed' mode through cat_maps too is
+    retired; DESIGN.md section 18 has the two-input kernel's numbers.)"""
     if (_MIXED and a.is_cuda and a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and a.dim() == 4 and a.shape[1] % 32 == 0
-            and b.shape[1] % 32 == 0 and os.environ.get('PCACC_CONV_CAT', '1') != '0' and conv3x3_native(a.new_empty((0, a.shape[1] + b.shape[1]) + tuple(a.shape[2:])), conv) == 'mixed'):
+            and b.shape[1] % 32 == 0 and conv3x3_native(a.new_empty((0, a.shape[1] + b.shape[1]) + tuple(a.shape[2:])), conv) == 'mixed'):
         ar, br = a.permute(0, 2, 3, 1), b.permute(0, 2, 3, 1)
         a32, b32 = twin(ar), twin(br)
         if ar.is_contiguous() and br.is_contiguous() and a32.is_contiguous() and b32.is_contiguous():
@@ -1567,11 +1566,13 @@ class _UpConv2x2Split(torch.autograd.Function):
 
 def _upconv_bf16_backward(ctx, gy, x_rows, weight):
     """Data, weight and bias gradient of the transposed 2 x 2 convolution from bf16 rows.  gy may be a channel slice of the decoder's concatenation
-    gradient (read in place through its pixel pitch).  Own kernels (csrc/upconv_bf16.hip) where the channel counts allow, else the library."""
+    gradient (read in place through its pixel pitch).  Own kernels (csrc/upconv_bf16.hip) where the channel counts allow, else the library (the switch that
+    forced the library everywhere is retired: forward 31 us, data gradient 26-40 us, weight gradient 24 + 13 us per layer with the own kernels, DESIGN.md
+    section 18)."""
     c_in, c_up = weight.shape[0], weight.shape[1]
     if gy.dtype != torch.bfloat16:
         gy = gy.to(torch.bfloat16)
-    if native.upconv2x2_bf16_supported(c_in, c_up) and weight.dtype == torch.float32 and os.environ.get('PCACC_UPCONV_BF16', '1') != '0':
+    if native.upconv2x2_bf16_supported(c_in, c_up) and weight.dtype == torch.float32:
         gx = native.upconv2x2_bf16(gy, prepared_upconv_weights_bf16(weight)[1], None, 1) if ctx.needs_input_grad[0] else None
         gw = gb = None
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
@@ -1625,63 +1626,9 @@ class _UpConv2x2Mixed(torch.autograd.Function):
         return _upconv_bf16_backward(ctx, gy, x_rows, weight)
 
 
-class _UpConvCatMixed(torch.autograd.Function):
-    """cat(upconv(x), skip) of a decoder stage (models/unet.py:101-113) in the 'mixed' mode: the transposed convolution writes its fp32 result and
-    the bf16 shadow straight into the first halves of the two concatenation buffers (pcacc_upconv2x2_split_dual with a pixel pitch); only the
-    skip halves are copied.  Backward: the up-sampled half of the buffer's gradient goes through the transposed convolution's bf16 backward, the
-    skip half is handed on as the channel slice it is (the encoder's pool tail reads it in place).  Opt-in (PCACC_UPCONV_CAT=1): measured neutral."""
-
-    @staticmethod
-    def forward(ctx, x_rows, skip_rows, weight, bias):
-        x32, s32 = twin(x_rows), twin(skip_rows)
-        n, h, w, _ = x_rows.shape
-        c_up, c_skip = weight.shape[1], skip_rows.shape[3]
-        if c_skip != c_up or tuple(skip_rows.shape[:3]) != (n, 2 * h, 2 * w):
-            raise native.NativeError('upconv + concatenation: the skip map must have the up-sampled map\'s shape')
-        buf32 = torch.empty((n, 2 * h, 2 * w, 2 * c_up), dtype=torch.float32, device=x_rows.device)
-        buf16 = torch.empty((n, 2 * h, 2 * w, 2 * c_up), dtype=torch.bfloat16, device=x_rows.device)
-        _, up_amax, _ = native.upconv2x2_split(x32, amax_of(x32), prepared_upconv_weights_split(weight)[0], bias.detach() if bias is not None else None, 0,
-                                               want_bf16=True, into=(buf32, buf16))
-        buf32[..., c_up:].copy_(s32)
-        if _POISON:
-            buf16.fill_(float('nan'))
-        else:
-            buf16[..., c_up:].copy_(skip_rows)
-        set_amax_tag(buf32, torch.maximum(up_amax, amax_of(s32)))
-        ctx.save_for_backward(x_rows, weight)
-        ctx.has_bias, ctx.c_up = bias is not None, c_up
-        return shadow(buf32, buf16)
-
-    @staticmethod
-    def backward(ctx, g):
-        x_rows, weight = ctx.saved_tensors
-        c_up = ctx.c_up
-        gy = g[..., :c_up].contiguous()
-        w16 = weight.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-        gx, gw, _ = torch.ops.aten.convolution_backward(
-            gy.permute(0, 3, 1, 2), x_rows.permute(0, 3, 1, 2), w16, None, [2, 2], [0, 0], [1, 1], True, [0, 0], 1,
-            [ctx.needs_input_grad[0], ctx.needs_input_grad[2], False])
-        gb = gy.reshape(-1, c_up).sum(0, dtype=torch.float32) if ctx.has_bias and ctx.needs_input_grad[3] else None
-        if gx is not None:
-            gx = gx.permute(0, 2, 3, 1).contiguous()
-        return (gx, g[..., c_up:] if ctx.needs_input_grad[1] else None,
-                gw.float().contiguous(memory_format=torch.channels_last) if gw is not None else None, gb)
-
-
-def upconv_cat(from_up, from_down, conv):
-    """cat((conv(from_up), from_down), 1) for a decoder stage.  PCACC_UPCONV_CAT=1 ('mixed' mode): without the copy of the up-sampled half
-    (_UpConvCatMixed) -- opt-in: measured neutral (36.2 / 36.2 / 39.1 ms without, 37.6 / 37.0 / 38.5 with: the strided copies of the skip halves cost
-    what the saved half of the concatenation cost)."""
-    if (_MIXED and from_up.is_cuda and from_up.dtype == torch.bfloat16 and from_down.dtype == torch.bfloat16
-            and conv.kernel_size == (2, 2) and conv.stride == (2, 2) and conv.padding == (0, 0) and conv.output_padding == (0, 0) and conv.groups == 1
-            and conv.dilation == (1, 1) and conv.weight.dtype == torch.float32 and conv.out_channels == from_down.shape[1]
-            and os.environ.get('PCACC_UPCONV_CAT', '0') == '1'):
-        xr, sr = from_up.permute(0, 2, 3, 1), from_down.permute(0, 2, 3, 1)
-        if xr.is_contiguous() and sr.is_contiguous() and native.upconv2x2_split_supported(from_up.shape[-2], from_up.shape[-1], conv.in_channels, conv.out_channels):
-            return _UpConvCatMixed.apply(xr, sr, conv.weight, conv.bias).permute(0, 3, 1, 2)
-    return cat_maps((upconv2x2(from_up, conv), from_down), 1)
-
-
+# Retired (round 4, 'mixed' mode; code: see the parent of this commit): the transposed convolution writing straight into the decoder's concatenation buffers
+# (pcacc_upconv2x2_split_dual with a pixel pitch -- the `into=` of native.upconv2x2_split, which stays).  Measured neutral: 36.2 / 36.2 / 39.1 ms without,
+# 37.6 / 37.0 / 38.5 ms with -- the strided copies of the skip halves cost what the saved half of the concatenation cost.
 def upconv2x2(x, conv):
     """`conv(x)` for the decoders' nn.ConvTranspose2d(kernel 2, stride 2) (models/unet.py:22-30): fp32 channels-last maps in the fp32x3 mode
     run the split kernels, everything else the module (library)."""
@@ -1700,7 +1647,7 @@ def upconv2x2(x, conv):
             y = _UpConv2x2Split.apply(xr, conv.weight, conv.bias)
             return carry_amax(y, y.permute(0, 3, 1, 2))
     if (x.is_cuda and plain and (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype('cuda') == torch.bfloat16))
-            and native.upconv2x2_bf16_supported(conv.in_channels, conv.out_channels) and os.environ.get('PCACC_UPCONV_BF16', '1') != '0'):
+            and native.upconv2x2_bf16_supported(conv.in_channels, conv.out_channels)):
         xr = x.permute(0, 2, 3, 1)                              # bf16 compute mode: own kernels, no library call, no layout copies
         if xr.is_contiguous():
             return _UpConv2x2Bf16.apply(xr if xr.dtype == torch.bfloat16 else xr.to(torch.bfloat16), conv.weight, conv.bias).permute(0, 3, 1, 2)
@@ -1798,9 +1745,10 @@ def conv3x3_native(x, conv):
 def conv_pair_fusable(x, conv1, conv2):
     """conv1 -> ReLU -> conv2 (models/unet.py:45-71) where the first ReLU's backward can ride in conv2's data-gradient epilogue: both layers on
     the bf16 MFMA kernels, or both on the fp32x3 kernels.  The caller then passes premasked=True to conv1 and input_relu=True to conv2 -- conv1's output must have no
-    other consumer."""
+    other consumer.  Measured against the unpaired layers (switch retired, see the parent of this commit): bf16 27.8 vs 28.1 ms over seven interleaved pairs,
+    fp32x3 43.7 -> 43.0 ms over four; kept because it removes seven full-map passes."""
     mode = conv3x3_native(x, conv1)
-    if mode not in ('bf16', 'split', 'mixed') or conv2.in_channels != conv1.out_channels or os.environ.get('PCACC_CONV_PAIR', '1') == '0':      # A/B switch
+    if mode not in ('bf16', 'split', 'mixed') or conv2.in_channels != conv1.out_channels:
         return False
     probe = torch.empty((0, conv1.out_channels, x.shape[-2], x.shape[-1]), dtype=torch.float32 if mode == 'split' else torch.bfloat16, device=x.device)
     return conv3x3_native(probe, conv2) == mode
@@ -1900,16 +1848,13 @@ class _SparseConv3x3(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             gp = (g @ w2.t()).view(-1, C)                                                      # [K * 9, C] rows of the neighbourhoods' gradients
             cells = n * H * W
-            if DETERMINISTIC and C % 4 == 0:
-                # overlapping neighbourhoods add up in ascending tap-row order: a CSR over the cells (taps outside the map go to an extra last cell that is
-                # dropped) + the atomic-free segment sum -- index_add_ adds with atomics, in arrival order
-                key = torch.where(idx >= 0, idx, cells).to(torch.int32)
-                offs, order = native.csr_build(key, cells + 1)
-                gh = native.segment_sum(gp.contiguous(), offs, order, cells + 1)[:cells].view(n, H, W, C)
-            else:
-                gh = torch.zeros((cells + 1, C), dtype=torch.float32, device=g.device)         # last row: where the taps outside the map add up (dropped)
-                gh.index_add_(0, torch.where(idx >= 0, idx, cells).long(), gp)                 # overlapping neighbourhoods add up
-                gh = gh[:cells].view(n, H, W, C)
+            if C % 4:
+                raise native.NativeError('_SparseConv3x3: the segment sum of the backward needs C % 4 == 0 (sparse_conv_available guarantees it)')
+            # overlapping neighbourhoods add up in ascending tap-row order: a CSR over the cells (taps outside the map go to an extra last cell that is
+            # dropped) + the atomic-free segment sum -- bit-reproducible, where an index_add_ adds with atomics, in arrival order
+            key = torch.where(idx >= 0, idx, cells).to(torch.int32)
+            offs, order = native.csr_build(key, cells + 1)
+            gh = native.segment_sum(gp.contiguous(), offs, order, cells + 1)[:cells].view(n, H, W, C)
         if ctx.needs_input_grad[1]:
             k = g.shape[0]
             if k % 16 == 0 and k >= 4096:

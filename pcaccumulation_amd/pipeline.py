@@ -6,7 +6,6 @@ see SURVEY.md 8b) so the model boundary does not change; only the voxeliser runs
 of numba on a DataLoader worker.
 """
 import os
-import time
 
 import torch
 
@@ -19,16 +18,6 @@ def sample_to_device(sample, device):
     # everything, including the per-instance motion table (the reference's collate keeps that one as a host list and every
     # consumer moves it with .to(device), models/alignnet.py:22, libs/loss.py:222: a blocking copy per sample per step)
     return {k: torch.from_numpy(v).to(device) for k, v in sample.items()}
-
-
-def _host_wait(event):
-    """Wait on the host for `event` (the voxel counts have reached pinned memory).  PCACC_PREFETCH_WAIT=poll: query the event in a sleep loop
-    instead of blocking inside the runtime's event wait (experiment for the two-ranks-on-one-GPU collapse of DESIGN.md section 6)."""
-    if os.environ.get('PCACC_PREFETCH_WAIT') == 'poll':
-        while not event.query():
-            time.sleep(20e-6)
-        return
-    event.synchronize()
 
 
 class _Pending(object):
@@ -136,7 +125,9 @@ class DeviceBatcher(object):
         arrived by then); finish() then only joins the streams."""
         if p.event is None or p.result is not None:
             return
-        _host_wait(p.event)
+        p.event.synchronize()                                        # the voxel counts have reached pinned memory (polling the event in a sleep loop instead
+                                                                     # was an experiment for the two-ranks-on-one-GPU collapse of DESIGN.md section 6;
+                                                                     # retired, code: see the parent of this commit)
         with torch.cuda.stream(p.stream):
             out = self._collate(p, p.counts.tolist())
             if prepare is not None:
@@ -154,7 +145,7 @@ class DeviceBatcher(object):
             share_with_stream(main, p.result, [x for l in p.launched for x in l[:2]])     # allocated there, consumed here
             return p.result
         if p.event is not None:
-            _host_wait(p.event)                                          # long past when the batch was started a step ago
+            p.event.synchronize()                                        # long past when the batch was started a step ago
             main = torch.cuda.current_stream(dev)
             main.wait_event(p.event)
             for t in [x for l in p.launched for x in l[:2]] + list(p.static.values()):

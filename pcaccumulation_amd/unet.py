@@ -6,7 +6,6 @@ package's own MFMA kernels (pcaccumulation_amd.ops: 3x3 / 3x3x3, the 2x2 transpo
 channels-last tensors; the library (MIOpen through PyTorch-ROCm) is the fallback for shapes they do not take and the CPU
 path.  DESIGN.md sections 3, 15, 16 and 18: why the C <= 64 full-resolution layers are HBM-bound and what is fused around them.
 """
-import os
 
 import torch
 import torch.nn as nn
@@ -52,16 +51,13 @@ class UpConv(nn.Module):
         self.conv2 = conv3x3(out_channels, out_channels)
 
     def forward(self, from_down, from_up):
-        if self.merge_mode == 'concat' and os.environ.get('PCACC_UPCONV_CAT', '0') != '1':
+        if self.merge_mode == 'concat':
             up = ops.upconv2x2(from_up, self.upconv)                  # fp32x3 / mixed: the 1-tap split kernels; bf16: csrc/upconv_bf16.hip; else the library
             probe = up.new_empty((0, self.conv1.in_channels) + tuple(up.shape[2:]))
             pair = ops.conv_pair_fusable(probe, self.conv1, self.conv2)
             x = ops.conv3x3_cat(up, from_down, self.conv1, relu=True, premasked=pair)      # mixed: conv1 reads the two fp32 maps in place, no fp32 concatenation
             return ops.conv3x3(x, self.conv2, relu=True, input_relu=pair)
-        if self.merge_mode == 'concat':
-            x = ops.upconv_cat(from_up, from_down, self.upconv)        # opt-in experiment: the transposed convolution writes into the concatenation buffers
-        else:
-            x = ops.upconv2x2(from_up, self.upconv) + from_down
+        x = ops.upconv2x2(from_up, self.upconv) + from_down
         pair = ops.conv_pair_fusable(x, self.conv1, self.conv2)
         return ops.conv3x3(ops.conv3x3(x, self.conv1, relu=True, premasked=pair), self.conv2, relu=True, input_relu=pair)
 

@@ -313,6 +313,52 @@ def test_pooling_into_the_canvas_is_pooling_then_scatter(native, dev, golden, si
         assert torch.equal(got, want)
 
 
+@pytest.mark.parametrize('c', [4, 8, 16, 32, 64, 128, 256])
+def test_pooling_into_the_canvas_every_width(native, dev, c):
+    """The contract of test_pooling_into_the_canvas_is_pooling_then_scatter at every channel count pcacc_segment_max_canvas is instantiated for (c / 4 = 1 .. 64
+    lanes per cell), on shapes the large test does not reach: 37 cells, 11 of them occupied in cell order, pillars of 1, 3, 4, 5, 8, 9 and 13 points (both
+    sides of the reduction loop's four-row batches), exact ties between rows.  fp32 canvas, bf16 canvas and winners bit for bit equal to pcacc_segment_max
+    followed by the two pcacc_pillar_scatter calls; empty cells zero."""
+    rng = np.random.RandomState(c)
+    n_cells, sizes = 37, np.array([1, 3, 4, 5, 8, 9, 13, 4, 1, 5, 8])
+    m, n = sizes.size, int(sizes.sum())
+    cells = np.sort(rng.choice(n_cells, m, replace=False))
+    c2p_np = np.full(n_cells, -1, np.int32)
+    c2p_np[cells] = np.arange(m, dtype=np.int32)
+    p2v_np = np.repeat(np.arange(m), sizes).astype(np.int32)
+    rng.shuffle(p2v_np)
+    src = rng.randn(n, c).astype(np.float32)
+    src[rng.randint(0, n, 12)] = src[rng.randint(0, n, 12)]                              # exact ties across points
+    src, p2v, c2p = torch.from_numpy(src).to(dev), torch.from_numpy(p2v_np).to(dev), torch.from_numpy(c2p_np).to(dev)
+    offs, order = native.csr_build(p2v, m)
+    assert sorted((offs[1:] - offs[:-1]).tolist()) == sorted(sizes.tolist())
+    pooled, arg = native.segment_max(src, offs, order, m)
+    want32 = native.pillar_scatter(pooled, c2p)
+    want16 = native.pillar_scatter(pooled.to(torch.bfloat16) if c % 8 == 0 else pooled, c2p, torch.bfloat16)      # bf16 rows go in as 16-byte pieces: c % 8
+    got32, got16, got_arg = native.segment_max_canvas(src, offs, order, m, c2p)
+    assert torch.equal(got32, want32) and torch.equal(got16, want16) and torch.equal(got_arg, arg)
+    empty = c2p < 0
+    assert int(empty.sum()) == n_cells - m
+    assert float(got32[empty].abs().max()) == 0.0 and float(got16[empty].float().abs().max()) == 0.0
+
+
+@pytest.mark.parametrize('c', [8, 24, 32])
+@pytest.mark.parametrize('n_cells', [1, 5, 300])
+def test_pillar_scatter_bf16_rows_small_shapes(native, dev, c, n_cells):
+    """bf16 rows -> bf16 canvas (one 16-byte piece per lane) bit-equal to the dense scatter built on the host, about a third of the cells occupied: 1 piece,
+    fewer than 256 pieces, piece counts that are no multiple of 256, and (300 cells of 24 and 32 channels) more pieces than one workgroup has lanes."""
+    rng = np.random.RandomState(c * 1000 + n_cells)
+    m = (n_cells + 2) // 3
+    cells = np.sort(rng.choice(n_cells, m, replace=False))
+    c2p_np = np.full(n_cells, -1, np.int32)
+    c2p_np[cells] = np.arange(m, dtype=np.int32)
+    feats = torch.from_numpy(rng.randn(m, c).astype(np.float32)).to(torch.bfloat16)
+    want = torch.zeros((n_cells, c), dtype=torch.bfloat16)
+    want[torch.from_numpy(cells)] = feats
+    got = native.pillar_scatter(feats.to(dev), torch.from_numpy(c2p_np).to(dev), torch.bfloat16)
+    assert got.dtype == torch.bfloat16 and torch.equal(got.cpu().view(torch.int16), want.view(torch.int16))
+
+
 def test_pillar_scatter_full_size_roundtrip(native, dev):
     """c3-size property test: scatter then gather is the identity on pillars; empty cells are zero."""
     nx = ny = 288
@@ -333,7 +379,7 @@ def test_pillar_scatter_full_size_roundtrip(native, dev):
         assert float(cv.float().abs().sum(1).gt(0).sum()) <= occ.size
         assert abs(float(cv.double().sum()) - float(feats.to(dt).double().sum())) < 1e-3
     # bf16 rows in (what the bf16 compute mode feeds): bit-identical canvas to the f32 -> bf16 launch on pre-rounded rows, odd
-    # piece counts (the kernel moves two pieces per lane and iteration)
+    # piece counts
     f16 = feats.to(torch.bfloat16)
     assert torch.equal(native.pillar_scatter(f16, c2p, torch.bfloat16), native.pillar_scatter(f16.float(), c2p, torch.bfloat16))
     for cells, c in ((7, 8), (1, 32), (333, 24)):

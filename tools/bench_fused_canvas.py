@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""pcacc_segment_max_canvas (pooling + pillar scatter in one pass) at the step's size: variants (PCACC_SCATTER_VARIANT: cells in flight per lane group, cache
-policy of the row loads) on uniform and on LiDAR-shaped pillar sizes (a few crowded pillars, two thirds of the cells empty), warm and behind 1 GiB of
-streamed lines; results compared bit for bit with the default.  Usage: python tools/bench_fused_canvas.py"""
+"""pcacc_segment_max_canvas (pooling + pillar scatter in one pass) at the step's size, on uniform and on LiDAR-shaped pillar sizes (a few crowded pillars, two
+thirds of the cells empty), warm and behind 1 GiB of streamed lines.  (The variants this tool once compared -- cells in flight per lane group, cache policy of the
+row loads -- are retired: profiles/r06_fused_canvas_variants.txt.)  Usage: python tools/bench_fused_canvas.py"""
 import os
 import sys
 
@@ -37,33 +37,20 @@ def main():
     for kind in ('uniform', 'lidar'):
         src, offs, order, m, c2p, n_cells, c, n = case(kind, dev)
         alg = bench.fused_alg_bytes(n_cells, c, m, n)
-        ref = None
-        for variant in ('', 'c', 'b', 'e', 'd'):
-            if variant:
-                os.environ['PCACC_SCATTER_VARIANT'] = variant
-            else:
-                os.environ.pop('PCACC_SCATTER_VARIANT', None)
-            native.reload_switches()
-            out = native.segment_max_canvas(src, offs, order, m, c2p)
-            if ref is None:
-                ref = out
-            same = all(torch.equal(a, b) for a, b in zip(out, ref))
-            res = {}
-            for cold in (False, True):
-                native.scatter_timer = []
-                for _ in range(10):
-                    if cold:
-                        flush.add_(1.0)
-                    native.segment_max_canvas(src, offs, order, m, c2p)
-                torch.cuda.synchronize()
-                us = sorted(t[0].elapsed_us() for t in native.scatter_timer)
-                native.scatter_timer = None
-                res['cold' if cold else 'warm'] = us[len(us) // 2]
-            print('%-8s variant %-7s warm %6.1f us (%.3f of 8 TB/s)  cold %6.1f us (%.3f)  %s' % (
-                kind, repr(variant) if variant else 'default', res['warm'], alg / res['warm'] / 1e3 / 8000.0, res['cold'], alg / res['cold'] / 1e3 / 8000.0,
-                'identical' if same else 'RESULTS DIFFER'), flush=True)
-    os.environ.pop('PCACC_SCATTER_VARIANT', None)
-    native.reload_switches()
+        native.segment_max_canvas(src, offs, order, m, c2p)
+        res = {}
+        for cold in (False, True):
+            native.scatter_timer = []
+            for _ in range(10):
+                if cold:
+                    flush.add_(1.0)
+                native.segment_max_canvas(src, offs, order, m, c2p)
+            torch.cuda.synchronize()
+            us = sorted(t[0].elapsed_us() for t in native.scatter_timer)
+            native.scatter_timer = None
+            res['cold' if cold else 'warm'] = us[len(us) // 2]
+        print('%-8s warm %6.1f us (%.3f of 8 TB/s)  cold %6.1f us (%.3f)' % (
+            kind, res['warm'], alg / res['warm'] / 1e3 / 8000.0, res['cold'], alg / res['cold'] / 1e3 / 8000.0), flush=True)
 
 
 if __name__ == '__main__':

@@ -156,7 +156,7 @@ c2p6[torch.randperm(n_cells6, device=dev)[:m].sort().values] = torch.arange(m, d
 offs6, order6 = native.csr_build(p2v6, m)
 rows6 = f32(rows, 32)
 for _ in range(3):
-    native.segment_max_canvas(rows6, offs6, order6, m, c2p6)                        # seg_max_canvas_kernel<8, 1, false>
+    native.segment_max_canvas(rows6, offs6, order6, m, c2p6)                        # seg_max_canvas_kernel<8>
     native.segment_max_dual(rows6, offs6, order6, m)                                # seg_max_kernel<8>
 slot6 = torch.randint(0, 400, (320_000,), device=dev, dtype=torch.int32)
 v16 = f32(320_000, 16)
