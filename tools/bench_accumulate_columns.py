@@ -10,60 +10,34 @@ does without it: the copy of the records to the host, np.unique over the column 
 The windows of this scene are independent random clouds: the scene gives the sizes and the memory behaviour of a real sequence.  Results go to --out.
 Nothing is gated on them.
 Usage: python tools/bench_accumulate_columns.py [--windows 40] [--repeat 5] [--no-baseline] [--out profiles/accum_columns_bench.txt]"""
-import argparse
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
+from accum_bench import Report, header, parser, scene, timed_repeat
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--windows', type=int, default=40)
-    ap.add_argument('--frames', type=int, default=5)
-    ap.add_argument('--pts-per-frame', type=int, default=160000)
-    ap.add_argument('--voxel', type=float, default=0.1)
-    ap.add_argument('--repeat', type=int, default=5)
-    ap.add_argument('--no-baseline', action='store_true')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'accum_columns_bench.txt'))
-    a = ap.parse_args()
+def parse_args(argv=None):
+    return parser('accum_columns_bench.txt', repeat=5).parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     import torch
-    from bench_accumulate import drift
-    from bench_accumulate_query import timed
     from pcaccumulation_amd import native
     from pcaccumulation_amd.accumulate import AccumulatedCloud
-    from pcaccumulation_amd.config import default_config
-    from pcaccumulation_amd.synthetic import make_sequence
     dev = torch.device('cuda:0')
-    cfg = default_config('waymo', 'test', n_sweeps=a.frames)
-    lines = ['tools/bench_accumulate_columns.py --windows %d --frames %d --pts-per-frame %d --voxel %g --repeat %d   (%s; GPU: device events around each call, '
-             'one warm-up, median of %d; host: perf_counter, once)' % (a.windows, a.frames, a.pts_per_frame, a.voxel, a.repeat, torch.cuda.get_device_name(0),
-                                                                       a.repeat)]
-
-    def emit(line):
-        lines.append(line)
-        print(line, flush=True)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:                                              # rewritten line by line: a run that is cut short leaves what it measured
-            f.write('\n'.join(lines) + '\n')
-
-    rng = np.random.RandomState(0)
+    emit = Report(a.out, header(__file__, a, '--repeat %d' % a.repeat,
+                                'GPU: device events around each call, one warm-up, median of %d; host: perf_counter, once' % a.repeat)).emit
     m = AccumulatedCloud(a.voxel, dev, 1 << 20)
-    for k in range(a.windows):
-        s = make_sequence(500 + k, a.frames, a.pts_per_frame, cfg, mode='lidar_scan')
-        pts = torch.from_numpy(np.ascontiguousarray(s['input_points'][:, :3], np.float32)).to(dev)
-        m.add(pts, drift(k), torch.from_numpy(rng.rand(pts.shape[0]) < 0.1).to(dev), k)
+    for k, pts, mv, T in scene(a, dev):
+        m.add(pts, T, mv, k)
         if k % 10 == 9:
             print('window %d: %d voxels' % (k, m.num_voxels), flush=True)
     names = ('rows', 'columns', 'ground rows', 'rows in the band', 'columns with a borrowed ground')
 
     def report(what, fn, counters=lambda res: res['counters']):
-        res, ms = timed(torch, fn, a.repeat)
+        res, ms = timed_repeat(fn, a.repeat)
         counts = ', '.join('%s %d' % (k, v) for k, v in zip(names, counters(res).tolist()))
         emit('  GPU %s: median %.3f ms, min %.3f, max %.3f; %s' % (what, float(np.median(ms)), min(ms), max(ms), counts))
         return res, float(np.median(ms))
@@ -81,7 +55,7 @@ def main():
     x0, y0 = image['origin']
     emit('  the bounding box: origin (%d, %d), %d x %d = %d pixels, %d of them columns' % (x0, y0, H, W, H * W, int((image['column'] >= 0).sum())))
     out = {name: torch.empty((H, W), dtype=dtype, device=dev) for name, dtype, _ in native.BEV_FIELDS}
-    _, ms = timed(torch, lambda: native.accum_bev(m._cur, m.num_voxels, 1, None, cols, x0, y0, W, H, out=out), a.repeat)
+    _, ms = timed_repeat(lambda: native.accum_bev(m._cur, m.num_voxels, 1, None, cols, x0, y0, W, H, out=out), a.repeat)
     emit('  GPU the raster alone (native.accum_bev into given images: pass 1 of C5 and the pixel kernel): median %.3f ms, min %.3f, max %.3f'
          % (float(np.median(ms)), min(ms), max(ms)))
     if not a.no_baseline:

@@ -8,17 +8,12 @@ records() of both maps to the host with a numpy searchsorted join there.
           included; the median of --repeats calls.
 The host join's SAME / HELD counts are compared with compare's counters (equality).  Results go to --out.  Nothing is gated on them.
 Usage: timeout -k 10 900 python tools/bench_accumulate_compare.py [--windows 40] [--repeats 5] [--no-baseline] [--out profiles/accum_compare_bench.txt]"""
-import argparse
-import os
-import sys
+import itertools
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-from bench_accumulate import drift  # noqa: E402
+from accum_bench import Report, drift, header, parser, scene, timed
 
 
 def host_join(a, b):
@@ -28,33 +23,17 @@ def host_join(a, b):
     return int((kb[q] == ka).sum())
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--windows', type=int, default=40)
-    ap.add_argument('--frames', type=int, default=5)
-    ap.add_argument('--pts-per-frame', type=int, default=160000)
-    ap.add_argument('--voxel', type=float, default=0.1)
-    ap.add_argument('--capacity', type=int, default=1 << 20)
-    ap.add_argument('--repeats', type=int, default=5)
-    ap.add_argument('--no-baseline', action='store_true')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'accum_compare_bench.txt'))
-    a = ap.parse_args()
+def parse_args(argv=None):
+    return parser('accum_compare_bench.txt', capacity=True, repeats=5).parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     import torch
     from pcaccumulation_amd.accumulate import AccumulatedCloud
-    from pcaccumulation_amd.config import default_config
-    from pcaccumulation_amd.synthetic import make_sequence
     dev = torch.device('cuda:0')
-    cfg = default_config('waymo', 'test', n_sweeps=a.frames)
-    lines = ['tools/bench_accumulate_compare.py --windows %d --frames %d --pts-per-frame %d --voxel %g --capacity %d --repeats %d   (%s; GPU: device events '
-             'around each call; host: perf_counter)' % (a.windows, a.frames, a.pts_per_frame, a.voxel, a.capacity, a.repeats, torch.cuda.get_device_name(0))]
-
-    def timed(call):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = call()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1), out
+    emit = Report(a.out, header(__file__, a, '--capacity %d --repeats %d' % (a.capacity, a.repeats),
+                                'GPU: device events around each call; host: perf_counter')).emit
 
     def leg(name, call, what):
         times, out = [], None
@@ -62,19 +41,16 @@ def main():
             torch.cuda.synchronize()
             t, out = timed(call)
             times.append(t)
-        lines.append('GPU: %-44s median %.2f ms = %.2f x the median add (%s) %s' % (name, float(np.median(times)), float(np.median(times)) / add_ms,
-                                                                                ' '.join('%.2f' % t for t in times), what(out)))
+        emit('GPU: %-44s median %.2f ms = %.2f x the median add (%s) %s' % (name, float(np.median(times)), float(np.median(times)) / add_ms,
+                                                                        ' '.join('%.2f' % t for t in times), what(out)))
         return out
 
-    rng = np.random.RandomState(0)
     half = a.windows // 2
+    windows = scene(a, dev)                                                      # one generator for both maps: B's windows follow A's
     maps, adds = [], []
-    for lo, hi in ((0, half), (half, a.windows)):
+    for n in (half, a.windows - half):
         m, times = AccumulatedCloud(a.voxel, dev, a.capacity), []
-        for k in range(lo, hi):
-            s = make_sequence(500 + k, a.frames, a.pts_per_frame, cfg, mode='lidar_scan')
-            pts = torch.from_numpy(np.ascontiguousarray(s['input_points'][:, :3], np.float32)).to(dev)
-            mv = torch.from_numpy(rng.rand(pts.shape[0]) < 0.1).to(dev)
+        for k, pts, mv, _ in itertools.islice(windows, n):
             if k == 0:                                                           # warm-up: code objects, allocator
                 AccumulatedCloud(a.voxel, dev, a.capacity).add(pts, drift(k), mv, k).extract()
                 torch.cuda.synchronize()
@@ -84,10 +60,10 @@ def main():
     A, B = maps
     tail = [t for t, _ in adds[0][-max(1, half // 4):]]                          # the adds that met a map of about A's final size
     add_ms = float(np.median(tail))
-    lines.append('maps: A = windows 0-%d, %d voxels (capacity %d); B = windows %d-%d, %d voxels; yardstick: median add of the last %d windows of A '
-                 '(map %d -> %d voxels, %d points each) %.2f ms' % (half - 1, A.num_voxels, A.capacity, half, a.windows - 1, B.num_voxels, len(tail),
-                                                                     adds[0][-len(tail) - 1][1] if len(adds[0]) > len(tail) else 0, A.num_voxels,
-                                                                     a.frames * a.pts_per_frame, add_ms))
+    emit('maps: A = windows 0-%d, %d voxels (capacity %d); B = windows %d-%d, %d voxels; yardstick: median add of the last %d windows of A '
+         '(map %d -> %d voxels, %d points each) %.2f ms' % (half - 1, A.num_voxels, A.capacity, half, a.windows - 1, B.num_voxels, len(tail),
+                                                             adds[0][-len(tail) - 1][1] if len(adds[0]) > len(tail) else 0, A.num_voxels,
+                                                             a.frames * a.pts_per_frame, add_ms))
     small = AccumulatedCloud(a.voxel, dev, 64).add(pts[:1000], None, None, 0)    # warm-up of the new code objects and of query's
     small.difference(small)
     small.query(small.extract()['points'])
@@ -105,12 +81,8 @@ def main():
             shared = host_join(A, B)
             host.append((time.perf_counter() - t0) * 1e3)
         same = all(counters[s][k] == shared for s in ('self', 'other') for k in ('same', 'held'))
-        lines.append('host: records() of both + numpy searchsorted join: median %.0f ms (%s); %d keys in both maps; SAME and HELD of both sides equal it: %s'
-                     % (float(np.median(host)), ' '.join('%.0f' % t for t in host), shared, same))
-    print('\n'.join(lines), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as f:
-        f.write('\n'.join(lines) + '\n')
+        emit('host: records() of both + numpy searchsorted join: median %.0f ms (%s); %d keys in both maps; SAME and HELD of both sides equal it: %s'
+             % (float(np.median(host)), ' '.join('%.0f' % t for t in host), shared, same))
 
 
 if __name__ == '__main__':

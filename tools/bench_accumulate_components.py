@@ -11,32 +11,12 @@ figures give sizes and memory behaviour, not the component structure of a real d
 Results go to --out.  Nothing is gated on them.
 Usage: python tools/bench_accumulate_components.py [--windows 40] [--repeat 5] [--min-voxels 10] [--host-rows 1000000] [--no-baseline]
        [--out profiles/accum_components_bench.txt]"""
-import argparse
 import io
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-
-BIAS = 1 << 20
-
-
-def timed(torch, fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1), out
-
-
-def stats(t):
-    return 'median %.2f ms, min %.2f, max %.2f' % (float(np.median(t)), min(t), max(t))
+from accum_bench import BIAS, Report, header, parser, scene, stats, timed, voxel_coords
 
 
 def host_labels(keys, radius):
@@ -45,7 +25,7 @@ def host_labels(keys, radius):
     from scipy.sparse import coo_matrix
     from scipy.sparse.csgraph import connected_components
     n = keys.shape[0]
-    c = [((keys >> 42) & 0x1fffff) - BIAS, ((keys >> 21) & 0x1fffff) - BIAS, (keys & 0x1fffff) - BIAS]
+    c = voxel_coords(keys)
     src, dst = [], []
     for dx in range(-radius, radius + 1):
         for dy in range(-radius, radius + 1):
@@ -69,43 +49,25 @@ def host_labels(keys, radius):
     return order[lab].astype(np.int32), k, src.shape[0]
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--windows', type=int, default=40)
-    ap.add_argument('--frames', type=int, default=5)
-    ap.add_argument('--pts-per-frame', type=int, default=160000)
-    ap.add_argument('--voxel', type=float, default=0.1)
-    ap.add_argument('--repeat', type=int, default=5)
+def parse_args(argv=None):
+    ap = parser('accum_components_bench.txt', repeat=5)
     ap.add_argument('--min-voxels', type=int, default=10)
     ap.add_argument('--host-rows', type=int, default=1000000)
-    ap.add_argument('--no-baseline', action='store_true')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'accum_components_bench.txt'))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     import torch
-    from bench_accumulate import drift
     from pcaccumulation_amd import native
     from pcaccumulation_amd.accumulate import AccumulatedCloud
-    from pcaccumulation_amd.config import default_config
-    from pcaccumulation_amd.synthetic import make_sequence
     dev = torch.device('cuda:0')
-    cfg = default_config('waymo', 'test', n_sweeps=a.frames)
-    lines = ['tools/bench_accumulate_components.py --windows %d --frames %d --pts-per-frame %d --voxel %g --repeat %d --min-voxels %d   (%s; GPU: device events '
-             'around each call, counter read-back included, one warm-up, median of %d; host: perf_counter)'
-             % (a.windows, a.frames, a.pts_per_frame, a.voxel, a.repeat, a.min_voxels, torch.cuda.get_device_name(0), a.repeat)]
-
-    def emit(line):
-        lines.append(line)
-        print(line, flush=True)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:                                              # rewritten line by line: a run that is cut short leaves what it measured
-            f.write('\n'.join(lines) + '\n')
-
-    rng = np.random.RandomState(0)
+    emit = Report(a.out, header(__file__, a, '--repeat %d --min-voxels %d' % (a.repeat, a.min_voxels),
+                                'GPU: device events around each call, counter read-back included, one warm-up, median of %d; host: perf_counter'
+                                % a.repeat)).emit
     m = AccumulatedCloud(a.voxel, dev, 1 << 20)
-    for k in range(a.windows):
-        s = make_sequence(500 + k, a.frames, a.pts_per_frame, cfg, mode='lidar_scan')
-        pts = torch.from_numpy(np.ascontiguousarray(s['input_points'][:, :3], np.float32)).to(dev)
-        m.add(pts, drift(k), torch.from_numpy(rng.rand(pts.shape[0]) < 0.1).to(dev), k)
+    for k, pts, mv, T in scene(a, dev):
+        m.add(pts, T, mv, k)
     total = m.num_voxels
     tables, state = tuple(t.clone() for t in m._cur), m._state.clone()
     emit('the map: %d voxels in tables of %d rows after %d windows' % (total, m.capacity, a.windows))
@@ -120,7 +82,7 @@ def main():
                      ('r = 2, min_count=2, max_moving_fraction=0.0', dict(radius=2, min_count=2, max_moving_fraction=0.0))):
         t = []
         for rep in range(a.repeat + 1):                                          # the first call is the warm-up
-            ms, res = timed(torch, lambda: m.components(**kw))
+            ms, res = timed(lambda: m.components(**kw))
             t.append(ms)
         c = res['counters'].tolist()
         emit('GPU components(%s): %s; %d rows take part, K %d, largest component %d voxels' % (name, stats(t[1:]), c[native.COMPONENTS_PARTICIPATING],
@@ -131,7 +93,7 @@ def main():
             for rep in range(a.repeat + 1):
                 restore()
                 torch.cuda.synchronize()
-                ms, res = timed(torch, lambda: m.remove_components(min_voxels=a.min_voxels, dry_run=dry, **kw))
+                ms, res = timed(lambda: m.remove_components(min_voxels=a.min_voxels, dry_run=dry, **kw))
                 t.append(ms)
             emit('GPU remove_components(min_voxels=%d, %s%s): %s; kept %d, small %d, components removed %d, kept %d, largest %d'
                  % (a.min_voxels, name, ', dry_run' if dry else '', stats(t[1:]), res['kept'], res['small'], res['components_removed'], res['components_kept'],
@@ -155,7 +117,7 @@ def main():
             part = AccumulatedCloud.load(buf, dev)
             t = []
             for rep in range(a.repeat + 1):
-                ms, res = timed(torch, lambda: part.components(radius=radius))
+                ms, res = timed(lambda: part.components(radius=radius))
                 t.append(ms)
             same = np.array_equal(res['label'].cpu().numpy(), lab) and k == int(res['counters'][native.COMPONENTS_K])
             assert same, 'the labels of the host baseline and of the GPU differ at r = %d' % radius

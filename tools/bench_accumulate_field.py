@@ -10,55 +10,30 @@ the records to the host and scipy.ndimage.distance_transform_edt of the same box
 The windows of this scene are independent random clouds: the scene gives the sizes and the memory behaviour of a real sequence.  Results go to --out.
 Nothing is gated on the times.
 Usage: python tools/bench_accumulate_field.py [--windows 40] [--repeat 5] [--no-baseline] [--out profiles/accum_field_bench.txt]"""
-import argparse
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
+from accum_bench import Report, header, parser, scene, timed_repeat, voxel_coords
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--windows', type=int, default=40)
-    ap.add_argument('--frames', type=int, default=5)
-    ap.add_argument('--pts-per-frame', type=int, default=160000)
-    ap.add_argument('--voxel', type=float, default=0.1)
-    ap.add_argument('--repeat', type=int, default=5)
+def parse_args(argv=None):
+    ap = parser('accum_field_bench.txt', repeat=5)
     ap.add_argument('--box', type=int, nargs=3, default=(512, 512, 64))
     ap.add_argument('--points', type=int, default=800000)
-    ap.add_argument('--no-baseline', action='store_true')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'accum_field_bench.txt'))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     import torch
-    from bench_accumulate import drift
-    from bench_accumulate_query import timed
     from pcaccumulation_amd.accumulate import AccumulatedCloud
-    from pcaccumulation_amd.config import default_config
-    from pcaccumulation_amd.synthetic import make_sequence
     dev = torch.device('cuda:0')
-    cfg = default_config('waymo', 'test', n_sweeps=a.frames)
-    lines = ['tools/bench_accumulate_field.py --windows %d --frames %d --pts-per-frame %d --voxel %g --repeat %d --box %d %d %d   (%s; GPU: device events around '
-             'each call, one warm-up, median of %d; host: perf_counter, once)' % ((a.windows, a.frames, a.pts_per_frame, a.voxel, a.repeat) + tuple(a.box)
-                                                                                  + (torch.cuda.get_device_name(0), a.repeat))]
-
-    def emit(line):
-        lines.append(line)
-        print(line, flush=True)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:                                              # rewritten line by line: a run that is cut short leaves what it measured
-            f.write('\n'.join(lines) + '\n')
-
-    rng = np.random.RandomState(0)
+    emit = Report(a.out, header(__file__, a, '--repeat %d --box %d %d %d' % ((a.repeat,) + tuple(a.box)),
+                                'GPU: device events around each call, one warm-up, median of %d; host: perf_counter, once' % a.repeat)).emit
     m = AccumulatedCloud(a.voxel, dev, 1 << 20)
-    for k in range(a.windows):
-        s = make_sequence(500 + k, a.frames, a.pts_per_frame, cfg, mode='lidar_scan')
-        pts = torch.from_numpy(np.ascontiguousarray(s['input_points'][:, :3], np.float32)).to(dev)
-        m.add(pts, drift(k), torch.from_numpy(rng.rand(pts.shape[0]) < 0.1).to(dev), k)
+    for k, pts, mv, T in scene(a, dev):
+        m.add(pts, T, mv, k)
     coords = m.extract()['coords']
     centre = coords.median(0).values.tolist()
     shape = tuple(a.box)
@@ -73,7 +48,7 @@ def main():
                 f = m.distance_field(origin, shape, R, planar, pad=False)
                 f['counts'] = f['counters'].tolist()                             # the read-back
                 return f
-            fields[(planar, R)], ms = timed(torch, call, a.repeat)
+            fields[(planar, R)], ms = timed_repeat(call, a.repeat)
             emit('  GPU distance_field(max_radius=%d, planar=%s): median %.3f ms, min %.3f, max %.3f; %s'
                  % (R, planar, float(np.median(ms)), min(ms), max(ms), ', '.join('%s %d' % (k, v) for k, v in zip(names, fields[(planar, R)]['counts']))))
     lo = torch.tensor(origin, dtype=torch.float64) * a.voxel
@@ -83,7 +58,7 @@ def main():
             out = m.clearance(points=pts, field=fields[(planar, 32)])
             out['counts'] = out['counters'].tolist()
             return out
-        out, ms = timed(torch, look, a.repeat)
+        out, ms = timed_repeat(look, a.repeat)
         emit('  GPU clearance of %d points against the field of R = 32, planar=%s, the read-back of the counters included: median %.3f ms, min %.3f, max %.3f; '
              'rows %d, valid %d, inside %d, near %d' % ((a.points, planar, float(np.median(ms)), min(ms), max(ms)) + tuple(out['counts'])))
     if not a.no_baseline:
@@ -92,7 +67,7 @@ def main():
         keys, _, _ = m.records()
         t_copy = time.perf_counter() - t0
         t0 = time.perf_counter()
-        c = np.stack([(keys >> 42) & 0x1fffff, (keys >> 21) & 0x1fffff, keys & 0x1fffff], 1) - (1 << 20) - np.array(origin)
+        c = np.stack(voxel_coords(keys), 1) - np.array(origin)
         c = c[np.all((c >= 0) & (c < np.array(shape)), 1)]
         occ = np.zeros(shape, bool)
         occ[tuple(c.T)] = True

@@ -9,64 +9,38 @@ The windows of this scene are independent random clouds: the scene gives the siz
 Nothing is gated on them.  An A/B of two builds of the library runs this tool alternately with PCACC_LIB naming the other build (the appendix of
 profiles/accum_knn_bench.txt was made that way, with --no-baseline).
 Usage: python tools/bench_accumulate_knn.py [--windows 40] [--box 50] [--repeat 5] [--no-baseline] [--out profiles/accum_knn_bench.txt]"""
-import argparse
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
+from accum_bench import Report, drift, header, parser, scene, timed_repeat, window_points
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--windows', type=int, default=40)
-    ap.add_argument('--frames', type=int, default=5)
-    ap.add_argument('--pts-per-frame', type=int, default=160000)
-    ap.add_argument('--voxel', type=float, default=0.1)
+def parse_args(argv=None):
+    ap = parser('accum_knn_bench.txt', repeat=5)
     ap.add_argument('--box', type=float, default=50.0)
-    ap.add_argument('--repeat', type=int, default=5)
-    ap.add_argument('--no-baseline', action='store_true')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'accum_knn_bench.txt'))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     import torch
-    from bench_accumulate import drift
-    from bench_accumulate_query import timed
     from pcaccumulation_amd.accumulate import AccumulatedCloud
-    from pcaccumulation_amd.config import default_config
-    from pcaccumulation_amd.synthetic import make_sequence
     dev = torch.device('cuda:0')
-    cfg = default_config('waymo', 'test', n_sweeps=a.frames)
-    lines = ['tools/bench_accumulate_knn.py --windows %d --frames %d --pts-per-frame %d --voxel %g --box %g --repeat %d   (%s; GPU: device events around each '
-             'call, one warm-up, median of %d; host: perf_counter)' % (a.windows, a.frames, a.pts_per_frame, a.voxel, a.box, a.repeat,
-                                                                         torch.cuda.get_device_name(0), a.repeat)]
-
-    def emit(line):
-        lines.append(line)
-        print(line, flush=True)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:                                              # rewritten line by line: a run that is cut short leaves what it measured
-            f.write('\n'.join(lines) + '\n')
-
-    rng = np.random.RandomState(0)
+    emit = Report(a.out, header(__file__, a, '--box %g --repeat %d' % (a.box, a.repeat),
+                                'GPU: device events around each call, one warm-up, median of %d; host: perf_counter' % a.repeat)).emit
     m = AccumulatedCloud(a.voxel, dev, 1 << 20)
-    for k in range(a.windows):
-        s = make_sequence(500 + k, a.frames, a.pts_per_frame, cfg, mode='lidar_scan')
-        pts = torch.from_numpy(np.ascontiguousarray(s['input_points'][:, :3], np.float32)).to(dev)
-        m.add(pts, drift(k), torch.from_numpy(rng.rand(pts.shape[0]) < 0.1).to(dev), k)
+    for k, pts, mv, T in scene(a, dev):
+        m.add(pts, T, mv, k)
         if k % 10 == 9:
             print('window %d: %d voxels' % (k, m.num_voxels), flush=True)
-    s = make_sequence(500 + a.windows, a.frames, a.pts_per_frame, cfg, mode='lidar_scan')
-    scan = torch.from_numpy(np.ascontiguousarray(s['input_points'][:, :3], np.float32)).to(dev)
+    scan = window_points(a, a.windows, dev)                                      # a fresh window: the one after the scene's last
     pose = drift(a.windows - 1)
     n = scan.shape[0]
     names = ('queries', 'invalid', 'found', 'full', 'neighbours')
 
     def report(what, fn):
-        res, ms = timed(torch, fn, a.repeat)
+        res, ms = timed_repeat(fn, a.repeat)
         counts = ', '.join('%s %d' % (k, v) for k, v in zip(names, res['counters'].tolist())) if res['counters'].numel() == 5 else \
             'matched %d' % int(res['counters'][4])
         emit('  GPU %s: median %.3f ms, min %.3f, max %.3f; %s' % (what, float(np.median(ms)), min(ms), max(ms), counts))

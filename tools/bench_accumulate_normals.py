@@ -7,34 +7,15 @@ the host and a vectorised numpy PCA there (np.searchsorted on the copied keys fo
              host -- with the GPU timed on the same sub-map; neighbour counts are compared for equality, normals up to sign.
 Results go to --out.  Nothing is gated on them.
 Usage: python tools/bench_accumulate_normals.py [--windows 40] [--baseline-rows 1000000] [--no-baseline] [--out profiles/accum_normals_bench.txt]"""
-import argparse
 import os
-import sys
 import tempfile
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
+from accum_bench import BIAS, Report, drift, header, parser, scene, timed_repeat, voxel_coords
 
-BIAS = 1 << 20
 FILTERS = (('no filter', dict()), ('min_count=2, max_moving_fraction=0.0', dict(min_count=2, max_moving_fraction=0.0)))
-
-
-def gpu_time(torch, fn, repeats=5):
-    fn()                                                                         # warm-up: code objects, allocator
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return float(np.median(times)), times, out
 
 
 def host_normals(keys, acc, radius, min_neighbors, min_count=1, max_moving_fraction=None):
@@ -45,7 +26,7 @@ def host_normals(keys, acc, radius, min_neighbors, min_count=1, max_moving_fract
     k = keys[keep]
     cent = (acc[2:5, keep].T.astype(np.float64) / acc[0, keep].astype(np.float64)[:, None]) * 2.0 ** -16
     v = k.shape[0]
-    c = [((k >> s) & 0x1fffff) - BIAS for s in (42, 21, 0)]
+    c = voxel_coords(k)
     n = np.zeros(v, np.int32)
     s1, s2 = np.zeros((v, 3)), np.zeros((v, 6))
     rng = range(-radius, radius + 1)
@@ -75,50 +56,32 @@ def host_normals(keys, acc, radius, min_neighbors, min_count=1, max_moving_fract
     return n, flags, vec[:, :, 0], gap
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--windows', type=int, default=40)
-    ap.add_argument('--frames', type=int, default=5)
-    ap.add_argument('--pts-per-frame', type=int, default=160000)
-    ap.add_argument('--voxel', type=float, default=0.1)
+def parse_args(argv=None):
+    ap = parser('accum_normals_bench.txt')
     ap.add_argument('--baseline-rows', type=int, default=1000000)
-    ap.add_argument('--no-baseline', action='store_true')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'accum_normals_bench.txt'))
-    a = ap.parse_args()
-    import torch
-    from bench_accumulate import drift
-    from pcaccumulation_amd.accumulate import AccumulatedCloud
-    from pcaccumulation_amd.config import default_config
-    from pcaccumulation_amd.synthetic import make_sequence
-    dev = torch.device('cuda:0')
-    cfg = default_config('waymo', 'test', n_sweeps=a.frames)
-    lines = ['tools/bench_accumulate_normals.py --windows %d --frames %d --pts-per-frame %d --voxel %g --baseline-rows %d   (%s; GPU: device events '
-             'around each call, median of 5 after one warm-up; host: perf_counter)'
-             % (a.windows, a.frames, a.pts_per_frame, a.voxel, a.baseline_rows, torch.cuda.get_device_name(0))]
-    def emit():
-        print(lines[-1], flush=True)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:                                              # rewritten line by line: a run that is cut short leaves what it measured
-            f.write('\n'.join(lines) + '\n')
+    return ap.parse_args(argv)
 
-    rng = np.random.RandomState(0)
+
+def main(argv=None):
+    a = parse_args(argv)
+    import torch
+    from pcaccumulation_amd.accumulate import AccumulatedCloud
+    dev = torch.device('cuda:0')
+    emit = Report(a.out, header(__file__, a, '--baseline-rows %d' % a.baseline_rows,
+                                'GPU: device events around each call, median of 5 after one warm-up; host: perf_counter')).emit
     m = AccumulatedCloud(a.voxel, dev, 1 << 20)
-    for k in range(a.windows):
-        s = make_sequence(500 + k, a.frames, a.pts_per_frame, cfg, mode='lidar_scan')
-        pts = np.ascontiguousarray(s['input_points'][:, :3], np.float32)
-        m.add(torch.from_numpy(pts).to(dev), drift(k), torch.from_numpy(rng.rand(pts.shape[0]) < 0.1).to(dev), k)
+    for k, pts, mv, T in scene(a, dev):
+        m.add(pts, T, mv, k)
     viewpoints = torch.from_numpy(np.stack([drift(k)[:3, 3] for k in range(a.windows)])).to(dev)
-    lines.append('map: %d windows -> %d voxels (capacity %d)' % (a.windows, m.num_voxels, m.capacity))
-    emit()
+    emit('map: %d windows -> %d voxels (capacity %d)' % (a.windows, m.num_voxels, m.capacity))
 
     def report(cloud, what):
         for fname, f in FILTERS:
             for radius in (1, 2):
-                med, times, out = gpu_time(torch, lambda: cloud.normals(radius=radius, viewpoints=viewpoints, **f))
-                lines.append('GPU %s, %s, r = %d: %d rows, %d valid, mean k %.1f; median %.2f ms (%s)'
-                             % (what, fname, radius, out['flags'].shape[0], int(out['valid'].sum()), float(out['neighbors'].float().mean()),
-                                med, ' '.join('%.2f' % t for t in times)))
-                emit()
+                out, times = timed_repeat(lambda: cloud.normals(radius=radius, viewpoints=viewpoints, **f), 5)
+                emit('GPU %s, %s, r = %d: %d rows, %d valid, mean k %.1f; median %.2f ms (%s)'
+                     % (what, fname, radius, out['flags'].shape[0], int(out['valid'].sum()), float(out['neighbors'].float().mean()),
+                        float(np.median(times)), ' '.join('%.2f' % t for t in times)))
 
     report(m, 'full map')
     if not a.no_baseline and m.num_voxels:
@@ -143,11 +106,10 @@ def main():
                 clear = (flags == 0) & (gap >= 1e-3)
                 g_nrm = got['normals'].cpu().numpy().astype(np.float64)[clear]
                 diff = np.abs(np.abs((g_nrm * nrm[clear]).sum(1)) - 1.0).max() if clear.any() else 0.0
-                lines.append('host sub-map, %s, r = %d: copy + numpy (searchsorted per offset, eigh) %.1f s for %d rows; neighbours equal: %s; '
-                             'flags equal: %s; largest |1 - |n_gpu . n_host|| on the %d valid rows with gap >= 1e-3: %.2g'
-                             % (fname, radius, t_host, n.shape[0], bool(np.array_equal(n, g_n)), bool(np.array_equal(flags, g_flags & 3)),
-                                int(clear.sum()), diff))
-                emit()
+                emit('host sub-map, %s, r = %d: copy + numpy (searchsorted per offset, eigh) %.1f s for %d rows; neighbours equal: %s; '
+                     'flags equal: %s; largest |1 - |n_gpu . n_host|| on the %d valid rows with gap >= 1e-3: %.2g'
+                     % (fname, radius, t_host, n.shape[0], bool(np.array_equal(n, g_n)), bool(np.array_equal(flags, g_flags & 3)),
+                        int(clear.sum()), diff))
 
 
 if __name__ == '__main__':

@@ -8,67 +8,29 @@ The windows of this scene are INDEPENDENT random clouds (synthetic.make_sequence
 figures give sizes and memory behaviour, not a free-space rate (tests/test_accumulate_observe.py has the scene with a known answer).
 Results go to --out.  Nothing is gated on them.
 Usage: python tools/bench_accumulate_observe.py [--windows 40] [--voxel 0.1] [--coarse 0.4] [--out profiles/accum_observe_bench.txt]"""
-import argparse
-import os
-import sys
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-
-SENSOR = np.array([[0.0, 0.0, 1.8]])                                             # synthetic.make_sequence: the beams start here
+from accum_bench import SENSOR, Report, header, parser, scene, stats, timed
 
 
-def timed(torch, fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1), out
-
-
-def stats(t):
-    return 'median %.2f ms, min %.2f, max %.2f' % (float(np.median(t)), min(t), max(t))
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--windows', type=int, default=40)
-    ap.add_argument('--frames', type=int, default=5)
-    ap.add_argument('--pts-per-frame', type=int, default=160000)
-    ap.add_argument('--voxel', type=float, default=0.1)
+def parse_args(argv=None):
+    ap = parser('accum_observe_bench.txt', repeats=10, baseline=False)
     ap.add_argument('--coarse', type=float, default=0.4)
     ap.add_argument('--max-steps', type=int, default=4096)
-    ap.add_argument('--repeats', type=int, default=10)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'accum_observe_bench.txt'))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     import torch
-    from bench_accumulate import drift
     from pcaccumulation_amd import native
     from pcaccumulation_amd.accumulate import AccumulatedCloud, ObservedSpace, _observe_chunks
-    from pcaccumulation_amd.config import default_config
-    from pcaccumulation_amd.synthetic import make_sequence
     dev = torch.device('cuda:0')
-    cfg = default_config('waymo', 'test', n_sweeps=a.frames)
-    lines = ['tools/bench_accumulate_observe.py --windows %d --frames %d --pts-per-frame %d --voxel %g --coarse %g --max-steps %d   (%s; device events around '
-             'each call, one warm-up)' % (a.windows, a.frames, a.pts_per_frame, a.voxel, a.coarse, a.max_steps, torch.cuda.get_device_name(0))]
-
-    def emit(line):
-        lines.append(line)
-        print(line, flush=True)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:                                              # rewritten line by line: a run that is cut short leaves what it measured
-            f.write('\n'.join(lines) + '\n')
-
-    rng = np.random.RandomState(0)
+    emit = Report(a.out, header(__file__, a, '--coarse %g --max-steps %d' % (a.coarse, a.max_steps),
+                                'device events around each call, one warm-up')).emit
     windows = []
-    for k in range(a.windows):
-        s = make_sequence(500 + k, a.frames, a.pts_per_frame, cfg, mode='lidar_scan')
-        pts = np.ascontiguousarray(s['input_points'][:, :3], np.float32)
-        windows.append((torch.from_numpy(pts).to(dev), torch.from_numpy(rng.rand(pts.shape[0]) < 0.1).to(dev), drift(k)))
+    for k, pts, mv, T in scene(a, dev):
+        windows.append((pts, mv, T))
         if k % 10 == 9:
             print('scene: %d windows built' % (k + 1), flush=True)
     n = windows[0][0].shape[0]
@@ -92,12 +54,12 @@ def main():
         t_obs, t_see, visits, splits, sizes, caps = [], [], [], [], [], []
         for k, (pts, mv, T) in enumerate(windows):
             v0, s0 = sp.counters['visits'], sp.splits
-            t_obs.append(timed(torch, lambda: sp.observe(pts, SENSOR, pose=T, moving=mv, stamp=k, max_steps=a.max_steps))[0])
+            t_obs.append(timed(lambda: sp.observe(pts, SENSOR, pose=T, moving=mv, stamp=k, max_steps=a.max_steps))[0])
             visits.append(sp.counters['visits'] - v0)
             splits.append(sp.splits - s0)
             sizes.append(sp.num_voxels)
             caps.append(sp.capacity)
-            t_see.append(timed(torch, lambda: cloud.see_through(pts, SENSOR, pose=T, moving=mv, stamp=k, max_steps=a.max_steps))[0])
+            t_see.append(timed(lambda: cloud.see_through(pts, SENSOR, pose=T, moving=mv, stamp=k, max_steps=a.max_steps))[0])
             cloud.add(pts, T, mv, k)
         c = sp.counters
         grew = [k for k in range(1, len(caps)) if caps[k] != caps[k - 1]]
@@ -114,7 +76,7 @@ def main():
             emit('  windows %2d-%2d: table -> %9d voxels, observe median %.2f ms (max %.2f), V median %d, see_through median %.2f ms'
                  % (lo, hi - 1, sizes[hi - 1], float(np.median(t_obs[lo:hi])), max(t_obs[lo:hi]), int(np.median(visits[lo:hi])), float(np.median(t_see[lo:hi]))))
         pts, _, T = windows[-1]
-        t_look = [timed(torch, lambda: sp.lookup(pts, T))[0] for _ in range(a.repeats)]
+        t_look = [timed(lambda: sp.lookup(pts, T))[0] for _ in range(a.repeats)]
         res = sp.lookup(pts, T)
         emit('  lookup of %d points in the table of %d voxels: %s; counters rows, valid, seen, enough = %s'
              % (n, sp.num_voxels, stats(t_look[1:] or t_look), res['counters'].tolist()))

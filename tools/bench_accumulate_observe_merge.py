@@ -8,19 +8,11 @@ contract's order), and the columns written back to device tables -- a host clock
 asserted equal, column for column.
 The windows of this scene are INDEPENDENT random clouds: the figures give sizes and memory behaviour.  Results go to --out.  Nothing is gated on them.
 Usage: python tools/bench_accumulate_observe_merge.py [--windows 40] [--voxel 0.1] [--out profiles/accum_observe_merge_bench.txt]"""
-import argparse
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-
-SENSOR = np.array([[0.0, 0.0, 1.8]])                                             # synthetic.make_sequence: the beams start here
-BIAS = 1 << 20
+from accum_bench import BIAS, SENSOR, Report, header, parser, scene, stats, timed, voxel_coords
 
 
 def session_pose():
@@ -54,7 +46,7 @@ def host_regrid(table, pose, in_voxel_size, out_voxel_size):
     maximum ray count, the minimum first and the maximum last stamp -> (the columns, rows dropped)."""
     keys, rays, stamps = table
     T = np.eye(4) if pose is None else np.asarray(pose, np.float64)
-    c = np.stack([(keys >> 42) - BIAS, ((keys >> 21) & 0x1fffff) - BIAS, (keys & 0x1fffff) - BIAS], 1)
+    c = np.stack(voxel_coords(keys), 1)
     p = (c.astype(np.float64) + 0.5) * np.float64(in_voxel_size)
     valid = np.ones(keys.shape[0], bool)
     out_key = np.zeros(keys.shape[0], np.int64)
@@ -73,55 +65,23 @@ def host_regrid(table, pose, in_voxel_size, out_voxel_size):
     return (k[heads], np.maximum.reduceat(r, heads), np.stack([np.minimum.reduceat(s0, heads), np.maximum.reduceat(s1, heads)])), int((~valid).sum())
 
 
-def timed(torch, fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1), out
-
-
-def stats(t):
-    return 'median %.2f ms, min %.2f, max %.2f' % (float(np.median(t)), min(t), max(t))
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--windows', type=int, default=40)
-    ap.add_argument('--frames', type=int, default=5)
-    ap.add_argument('--pts-per-frame', type=int, default=160000)
-    ap.add_argument('--voxel', type=float, default=0.1)
+def parse_args(argv=None):
+    ap = parser('accum_observe_merge_bench.txt', repeats=5, baseline=False)
     ap.add_argument('--max-steps', type=int, default=4096)
-    ap.add_argument('--repeats', type=int, default=5)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'accum_observe_merge_bench.txt'))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     import torch
-    from bench_accumulate import drift
     from pcaccumulation_amd.accumulate import ObservedSpace
-    from pcaccumulation_amd.config import default_config
-    from pcaccumulation_amd.synthetic import make_sequence
     dev = torch.device('cuda:0')
-    cfg = default_config('waymo', 'test', n_sweeps=a.frames)
-    lines = ['tools/bench_accumulate_observe_merge.py --windows %d --frames %d --pts-per-frame %d --voxel %g --max-steps %d --repeats %d   (%s; device events '
-             'around each call, one warm-up; the host route by a host clock that ends in a synchronise)'
-             % (a.windows, a.frames, a.pts_per_frame, a.voxel, a.max_steps, a.repeats, torch.cuda.get_device_name(0))]
-
-    def emit(line):
-        lines.append(line)
-        print(line, flush=True)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:                                              # rewritten line by line: a run that is cut short leaves what it measured
-            f.write('\n'.join(lines) + '\n')
-
-    rng = np.random.RandomState(0)
+    emit = Report(a.out, header(__file__, a, '--max-steps %d --repeats %d' % (a.max_steps, a.repeats),
+                                'device events around each call, one warm-up; the host route by a host clock that ends in a synchronise')).emit
     half = a.windows // 2
     spaces = [ObservedSpace(a.voxel, dev), ObservedSpace(a.voxel, dev)]
-    for k in range(a.windows):
-        s = make_sequence(500 + k, a.frames, a.pts_per_frame, cfg, mode='lidar_scan')
-        pts = torch.from_numpy(np.ascontiguousarray(s['input_points'][:, :3], np.float32)).to(dev)
-        moving = torch.from_numpy(rng.rand(pts.shape[0]) < 0.1).to(dev)
-        spaces[k >= half].observe(pts, SENSOR, pose=drift(k), moving=moving, stamp=k, max_steps=a.max_steps)
+    for k, pts, moving, T in scene(a, dev):
+        spaces[k >= half].observe(pts, SENSOR, pose=T, moving=moving, stamp=k, max_steps=a.max_steps)
         if k % 10 == 9:
             print('scene: %d windows observed' % (k + 1), flush=True)
     A, B = spaces
@@ -164,7 +124,7 @@ def main():
             if into_copy:
                 c._alt = tuple(torch.empty_like(t) for t in c._cur)              # the second set of tables, as a space that has observed holds it
             torch.cuda.synchronize()
-            t, res = timed(torch, lambda: device_fn(c))
+            t, res = timed(lambda: device_fn(c))
             times.append(t)
             out = c if into_copy else res
             del c, res

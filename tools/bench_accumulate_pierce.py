@@ -11,70 +11,29 @@ The windows of this scene are INDEPENDENT random clouds (synthetic.make_sequence
 figures give sizes and memory behaviour, not a ghost-removal rate (tests/test_accumulate_pierce.py has the scene with a known ghost).
 Results go to --out.  Nothing is gated on them.
 Usage: python tools/bench_accumulate_pierce.py [--windows 40] [--max-range 30] [--sample 2000] [--no-baseline] [--out profiles/accum_pierce_bench.txt]"""
-import argparse
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-sys.path.insert(0, os.path.join(ROOT, 'tests'))
-
-SENSOR = np.array([[0.0, 0.0, 1.8]])                                             # synthetic.make_sequence: the beams start here
+from accum_bench import SENSOR, Report, header, parser, scene, stats, timed
 
 
-def timed(torch, fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1), out
-
-
-def stats(t):
-    return 'median %.2f ms, min %.2f, max %.2f' % (float(np.median(t)), min(t), max(t))
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--windows', type=int, default=40)
-    ap.add_argument('--frames', type=int, default=5)
-    ap.add_argument('--pts-per-frame', type=int, default=160000)
-    ap.add_argument('--voxel', type=float, default=0.1)
+def parse_args(argv=None):
+    ap = parser('accum_pierce_bench.txt')
     ap.add_argument('--max-range', type=float, default=30.0)
     ap.add_argument('--max-steps', type=int, default=4096)
     ap.add_argument('--sample', type=int, default=2000)
-    ap.add_argument('--no-baseline', action='store_true')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'accum_pierce_bench.txt'))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     import torch
-    from bench_accumulate import drift
     from pcaccumulation_amd.accumulate import AccumulatedCloud
-    from pcaccumulation_amd.config import default_config
-    from pcaccumulation_amd.synthetic import make_sequence
     dev = torch.device('cuda:0')
-    cfg = default_config('waymo', 'test', n_sweeps=a.frames)
-    lines = ['tools/bench_accumulate_pierce.py --windows %d --frames %d --pts-per-frame %d --voxel %g --max-range %g --max-steps %d   (%s; GPU: device events '
-             'around each call, one warm-up; host: perf_counter)' % (a.windows, a.frames, a.pts_per_frame, a.voxel, a.max_range, a.max_steps,
-                                                                      torch.cuda.get_device_name(0))]
-
-    def emit(line):
-        lines.append(line)
-        print(line, flush=True)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:                                              # rewritten line by line: a run that is cut short leaves what it measured
-            f.write('\n'.join(lines) + '\n')
-
-    rng = np.random.RandomState(0)
-    windows = []
-    for k in range(a.windows):
-        s = make_sequence(500 + k, a.frames, a.pts_per_frame, cfg, mode='lidar_scan')
-        pts = np.ascontiguousarray(s['input_points'][:, :3], np.float32)
-        windows.append((torch.from_numpy(pts).to(dev), torch.from_numpy(rng.rand(pts.shape[0]) < 0.1).to(dev), drift(k)))
+    emit = Report(a.out, header(__file__, a, '--max-range %g --max-steps %d' % (a.max_range, a.max_steps),
+                                'GPU: device events around each call, one warm-up; host: perf_counter')).emit
+    windows = [(pts, mv, T) for _, pts, mv, T in scene(a, dev)]
     n = windows[0][0].shape[0]
     warm = AccumulatedCloud(a.voxel, dev, 1 << 20)                               # warm-up: code objects, allocator
     warm.add(windows[0][0], windows[0][2], windows[0][1], 0)
@@ -85,7 +44,7 @@ def main():
 
     # add alone: no sidecar, the code path of the revision before C7
     plain = AccumulatedCloud(a.voxel, dev, 1 << 20)
-    t_add_plain = [timed(torch, lambda: plain.add(pts, T, mv, k))[0] for k, (pts, mv, T) in enumerate(windows)]
+    t_add_plain = [timed(lambda: plain.add(pts, T, mv, k))[0] for k, (pts, mv, T) in enumerate(windows)]
     del plain
     last = None
     for max_range in (None, a.max_range):
@@ -93,8 +52,8 @@ def main():
         t_see, t_add, sizes = [], [], []
         for k, (pts, mv, T) in enumerate(windows):
             sizes.append(m.num_voxels)
-            t_see.append(timed(torch, lambda: m.see_through(pts, SENSOR, pose=T, moving=mv, stamp=k, max_range=max_range, max_steps=a.max_steps))[0])
-            t_add.append(timed(torch, lambda: m.add(pts, T, mv, k))[0])
+            t_see.append(timed(lambda: m.see_through(pts, SENSOR, pose=T, moving=mv, stamp=k, max_range=max_range, max_steps=a.max_steps))[0])
+            t_add.append(timed(lambda: m.add(pts, T, mv, k))[0])
         c = m._pierce_counters.tolist()
         emit('GPU, max_range %s: %d see_through calls of %d rays against a map of %d .. %d voxels: %s; rays walked %d, dropped %d, skipped %d, truncated %d, '
              'hits %d (%.2f per walked ray); voxels with a count >= 1: %d of %d'
@@ -140,7 +99,7 @@ def baseline(a, torch, m, window, emit):
     t_host = time.perf_counter() - t0
     before = m._pierce_counters.clone()
     sel = torch.from_numpy(pick).to(pts.device)
-    t_gpu, after = timed(torch, lambda: m.see_through(pts[sel], SENSOR, pose=T, moving=mv[sel], max_steps=a.max_steps))
+    t_gpu, after = timed(lambda: m.see_through(pts[sel], SENSOR, pose=T, moving=mv[sel], max_steps=a.max_steps))
     got = (after - before).tolist()
     emit('host, a sub-sample of %d rays of the last window (%d walked): copy of the scan (%d points) and of %d keys %.2f s; the walk in plain Python and '
          'np.searchsorted %.2f s = %.2f ms per ray (%.0f s for the whole window at that rate); %.1f visits per walked ray, %d hits; the kernel on the same '

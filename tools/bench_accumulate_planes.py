@@ -11,20 +11,13 @@ The windows of this scene are INDEPENDENT random clouds (synthetic.make_sequence
 figures give sizes and memory behaviour, not the segment structure of a real drive; few rows are flat, so max_variation 1 (no gate) is timed as well.
 Results go to --out.  Nothing is gated on them.
 Usage: python tools/bench_accumulate_planes.py [--windows 40] [--repeat 5] [--host-rows 1000000] [--no-baseline] [--out profiles/accum_planes_bench.txt]"""
-import argparse
 import io
 import math
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-
-BIAS = 1 << 20
+from accum_bench import BIAS, Report, header, parser, scene, timed_repeat, voxel_coords
 
 
 def host_labels(keys, acc, normals, eigenvalues, flags, cos_angle, max_offset, max_variation):
@@ -37,7 +30,7 @@ def host_labels(keys, acc, normals, eigenvalues, flags, cos_angle, max_offset, m
     part = ((flags & 3) == 0) & (e[:, 2] <= np.float64(max_variation) * ((e[:, 0] + e[:, 1]) + e[:, 2]))
     nrm = normals.astype(np.float64)
     cen = (acc[2:5].T.astype(np.float64) / acc[0].astype(np.float64)[:, None]) * np.float64(2.0 ** -16)
-    c = [((keys >> 42) & 0x1fffff) - BIAS, ((keys >> 21) & 0x1fffff) - BIAS, (keys & 0x1fffff) - BIAS]
+    c = voxel_coords(keys)
     src, dst = [], []
     for dx in (-1, 0, 1):
         for dy in (-1, 0, 1):
@@ -68,55 +61,36 @@ def host_labels(keys, acc, normals, eigenvalues, flags, cos_angle, max_offset, m
     return np.where(part, order[np.maximum(lab, 0)], -1).astype(np.int32), uniq.shape[0], src.shape[0]
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--windows', type=int, default=40)
-    ap.add_argument('--frames', type=int, default=5)
-    ap.add_argument('--pts-per-frame', type=int, default=160000)
-    ap.add_argument('--voxel', type=float, default=0.1)
-    ap.add_argument('--repeat', type=int, default=5)
+def parse_args(argv=None):
+    ap = parser('accum_planes_bench.txt', repeat=5)
     ap.add_argument('--host-rows', type=int, default=1000000)
-    ap.add_argument('--no-baseline', action='store_true')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'accum_planes_bench.txt'))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     import torch
-    from bench_accumulate import drift
-    from bench_accumulate_query import timed
     from pcaccumulation_amd import native
     from pcaccumulation_amd.accumulate import AccumulatedCloud
-    from pcaccumulation_amd.config import default_config
-    from pcaccumulation_amd.synthetic import make_sequence
     dev = torch.device('cuda:0')
-    cfg = default_config('waymo', 'test', n_sweeps=a.frames)
-    lines = ['tools/bench_accumulate_planes.py --windows %d --frames %d --pts-per-frame %d --voxel %g --repeat %d   (%s; GPU: device events around each call, '
-             'counter read-back included, one warm-up, median of %d; host: perf_counter, once)'
-             % (a.windows, a.frames, a.pts_per_frame, a.voxel, a.repeat, torch.cuda.get_device_name(0), a.repeat)]
-
-    def emit(line):
-        lines.append(line)
-        print(line, flush=True)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:                                              # rewritten line by line: a run that is cut short leaves what it measured
-            f.write('\n'.join(lines) + '\n')
-
-    rng = np.random.RandomState(0)
+    emit = Report(a.out, header(__file__, a, '--repeat %d' % a.repeat,
+                                'GPU: device events around each call, counter read-back included, one warm-up, median of %d; host: perf_counter, once'
+                                % a.repeat)).emit
     m = AccumulatedCloud(a.voxel, dev, 1 << 20)
-    for k in range(a.windows):
-        s = make_sequence(500 + k, a.frames, a.pts_per_frame, cfg, mode='lidar_scan')
-        pts = torch.from_numpy(np.ascontiguousarray(s['input_points'][:, :3], np.float32)).to(dev)
-        m.add(pts, drift(k), torch.from_numpy(rng.rand(pts.shape[0]) < 0.1).to(dev), k)
+    for k, pts, mv, T in scene(a, dev):
+        m.add(pts, T, mv, k)
         if k % 10 == 9:
             print('window %d: %d voxels' % (k, m.num_voxels), flush=True)
     emit('the map: %d voxels in tables of %d rows after %d windows; normals at radius 2, min_neighbors 5' % (m.num_voxels, m.capacity, a.windows))
     names = ('rows', 'take part', 'outside', 'masked', 'no valid normal', 'not flat', 'K', 'largest', 'status')
 
     def report(what, fn, counters=lambda res: res['counters']):
-        res, ms = timed(torch, fn, a.repeat)
+        res, ms = timed_repeat(fn, a.repeat)
         counts = '' if counters is None else '; ' + ', '.join('%s %d' % (k, v) for k, v in zip(names, counters(res).tolist()))
         emit('  GPU %s: median %.3f ms, min %.3f, max %.3f%s' % (what, float(np.median(ms)), min(ms), max(ms), counts))
         return res
 
-    nrm, ms = timed(torch, lambda: m.normals(radius=2, min_neighbors=5), a.repeat)
+    nrm, ms = timed_repeat(lambda: m.normals(radius=2, min_neighbors=5), a.repeat)
     emit('  GPU normals(radius=2) alone, for scale: median %.3f ms, min %.3f, max %.3f' % (float(np.median(ms)), min(ms), max(ms)))
     for mv in (0.01, 1.0):
         report('planes(max_variation=%g) with given normals' % mv, lambda: m.planes(max_variation=mv, normals=nrm))
@@ -146,7 +120,7 @@ def main():
             t0 = time.perf_counter()
             lab, k, n_edges = host_labels(keys[:rows], acc[:, :rows], arrays[0], arrays[1], arrays[2], cos_angle, max_offset, mv)
             t_host = time.perf_counter() - t0
-            got, ms = timed(torch, lambda: part.planes(max_variation=mv, normals=part_n), a.repeat)
+            got, ms = timed_repeat(lambda: part.planes(max_variation=mv, normals=part_n), a.repeat)
             same = np.array_equal(got['label'].cpu().numpy(), lab) and k == int(got['counters'][native.PLANES_K])
             assert same, 'the labels of the host baseline and of the GPU differ at max_variation %g' % mv
             emit('host max_variation=%g, the first %d rows: 13 searchsorted calls, the gate and scipy connected_components over %d edges %.2f s, K %d; the GPU '

@@ -11,35 +11,14 @@ The windows of this scene are INDEPENDENT random clouds (synthetic.make_sequence
 figures give sizes and memory behaviour, not a removal rate of real ghosts.
 Results go to --out.  Nothing is gated on them.
 Usage: python tools/bench_accumulate_prune.py [--windows 40] [--box 50] [--repeat 5] [--neighbour-rows 1000000] [--no-baseline] [--out profiles/accum_prune_bench.txt]"""
-import argparse
 import io
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
+from accum_bench import BIAS, HBM_GBS, SENSOR, Report, drift, header, parser, scene, stats, timed, voxel_coords
 
-SENSOR = np.array([[0.0, 0.0, 1.8]])                                             # synthetic.make_sequence: the beams start here
-BIAS = 1 << 20
 NAMES = ('kept', 'filter', 'stale', 'box', 'pierced', 'isolated')
-HBM_GBS = 8000.0                                                                 # MI355X: 8 TB/s peak
-
-
-def timed(torch, fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1), out
-
-
-def stats(t):
-    return 'median %.2f ms, min %.2f, max %.2f' % (float(np.median(t)), min(t), max(t))
 
 
 class Snapshot(object):
@@ -70,7 +49,7 @@ def host_keep(acc, min_count, max_moving_fraction):
 
 def host_neighbours(keys, radius):
     """k of every row of the ascending keys: one np.searchsorted per offset; offsets that leave the grid are masked before the key is formed."""
-    c = [((keys >> 42) & 0x1fffff) - BIAS, ((keys >> 21) & 0x1fffff) - BIAS, (keys & 0x1fffff) - BIAS]
+    c = voxel_coords(keys)
     k = np.zeros(keys.shape[0], np.int32)
     for dx in range(-radius, radius + 1):
         for dy in range(-radius, radius + 1):
@@ -85,46 +64,27 @@ def host_neighbours(keys, radius):
     return k
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--windows', type=int, default=40)
-    ap.add_argument('--frames', type=int, default=5)
-    ap.add_argument('--pts-per-frame', type=int, default=160000)
-    ap.add_argument('--voxel', type=float, default=0.1)
+def parse_args(argv=None):
+    ap = parser('accum_prune_bench.txt', repeat=5)
     ap.add_argument('--box', type=float, default=50.0)
-    ap.add_argument('--repeat', type=int, default=5)
     ap.add_argument('--neighbour-rows', type=int, default=1000000)
-    ap.add_argument('--no-baseline', action='store_true')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'accum_prune_bench.txt'))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     import torch
-    from bench_accumulate import drift
     from pcaccumulation_amd.accumulate import AccumulatedCloud
-    from pcaccumulation_amd.config import default_config
-    from pcaccumulation_amd.synthetic import make_sequence
     dev = torch.device('cuda:0')
-    cfg = default_config('waymo', 'test', n_sweeps=a.frames)
-    lines = ['tools/bench_accumulate_prune.py --windows %d --frames %d --pts-per-frame %d --voxel %g --box %g --repeat %d   (%s; GPU: device events around each '
-             'prune() call, counter read-back included, one warm-up, median of %d; host: perf_counter)'
-             % (a.windows, a.frames, a.pts_per_frame, a.voxel, a.box, a.repeat, torch.cuda.get_device_name(0), a.repeat)]
-
-    def emit(line):
-        lines.append(line)
-        print(line, flush=True)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:                                              # rewritten line by line: a run that is cut short leaves what it measured
-            f.write('\n'.join(lines) + '\n')
-
-    rng = np.random.RandomState(0)
+    emit = Report(a.out, header(__file__, a, '--box %g --repeat %d' % (a.box, a.repeat),
+                                'GPU: device events around each prune() call, counter read-back included, one warm-up, median of %d; '
+                                'host: perf_counter' % a.repeat)).emit
     m = AccumulatedCloud(a.voxel, dev, 1 << 20)
     last = None
-    for k in range(a.windows):
-        s = make_sequence(500 + k, a.frames, a.pts_per_frame, cfg, mode='lidar_scan')
-        pts = torch.from_numpy(np.ascontiguousarray(s['input_points'][:, :3], np.float32)).to(dev)
-        mv = torch.from_numpy(rng.rand(pts.shape[0]) < 0.1).to(dev)
-        m.see_through(pts, SENSOR, pose=drift(k), moving=mv, stamp=k)
-        m.add(pts, drift(k), mv, k)
-        last = (pts, mv, drift(k))
+    for k, pts, mv, T in scene(a, dev):
+        m.see_through(pts, SENSOR, pose=T, moving=mv, stamp=k)
+        m.add(pts, T, mv, k)
+        last = (pts, mv, T)
     snap = Snapshot(m)
     total = snap.n
     centre = drift(a.windows - 1)[:3, 3]
@@ -151,7 +111,7 @@ def main():
             for rep in range(a.repeat + 1):                                      # the first call is the warm-up
                 snap.restore(m)
                 torch.cuda.synchronize()
-                ms, res = timed(torch, lambda: m.prune(dry_run=dry, **kw))
+                ms, res = timed(lambda: m.prune(dry_run=dry, **kw))
                 t.append(ms)
             gpu[(name, dry)] = res
             emit('GPU %s%s: %s; %s' % (name, ', dry_run' if dry else '', stats(t[1:]), ', '.join('%s %d' % (f, res[f]) for f in NAMES)))
@@ -171,7 +131,7 @@ def main():
                 m.prune(**kw)
             size = m.num_voxels
             torch.cuda.synchronize()
-            t.append(timed(torch, lambda: m.add(pts, T, mv, a.windows))[0])
+            t.append(timed(lambda: m.add(pts, T, mv, a.windows))[0])
         emit('GPU add of the last window (%d points, with the sidecar carry) on %s (%d voxels): %s' % (pts.shape[0], name, size, stats(t[1:])))
 
     if not a.no_baseline:
@@ -188,9 +148,8 @@ def baseline(a, torch, m, snap, box, gpu, cases, emit):
     pierced = m._pierced[:m.num_voxels].cpu().numpy()
     t_copy = time.perf_counter() - t0
     lo, hi = m._box_indices(box)
-    coords = [((keys >> 42) & 0x1fffff) - BIAS, ((keys >> 21) & 0x1fffff) - BIAS, (keys & 0x1fffff) - BIAS]
     inside = np.ones(keys.shape[0], bool)
-    for c, l, h in zip(coords, lo, hi):
+    for c, l, h in zip(voxel_coords(keys), lo, hi):
         inside &= (c >= l) & (c <= h)
     masks = {cases[1][0]: lambda: host_keep(acc, 2, 0.0), cases[2][0]: lambda: stamps[1] >= a.windows // 2, cases[3][0]: lambda: inside.copy(),
              cases[4][0]: lambda: pierced < 2,
@@ -226,7 +185,7 @@ def baseline(a, torch, m, snap, box, gpu, cases, emit):
         part = AccumulatedCloud.load(buf, m.device)
         t = []
         for rep in range(a.repeat + 1):
-            t.append(timed(torch, lambda: part.prune(min_neighbors=least, radius=radius, dry_run=True))[0])
+            t.append(timed(lambda: part.prune(min_neighbors=least, radius=radius, dry_run=True))[0])
         res = part.prune(min_neighbors=least, radius=radius)
         same = res['kept'] == int((k >= least).sum()) and np.array_equal(part.records()[0], keys[:rows][k >= least])
         emit('host isolated, r = %d (min_neighbors=%d), the first %d rows: %d searchsorted calls %.2f s; the GPU on the same rows (dry_run): %s; kept %d on the '

@@ -14,35 +14,13 @@ The windows of this scene are INDEPENDENT random clouds (synthetic.make_sequence
 figures give sizes and memory behaviour, not what a street looks like.  Results go to --out.  Nothing is gated on them.
 Usage: python tools/bench_accumulate_raycast.py [--windows 40] [--max-range 30] [--min-range 2] [--box 50] [--sample 2000] [--repeat 5] [--no-baseline]
        [--out profiles/accum_raycast_bench.txt]"""
-import argparse
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-sys.path.insert(0, os.path.join(ROOT, 'tests'))
+from accum_bench import BIAS, SENSOR, Report, drift, header, parser, scene, timed_repeat
 
-SENSOR = np.array([[0.0, 0.0, 1.8]])                                             # synthetic.make_sequence: the beams start here
-BIAS = 1 << 20
 NAMES = ('rays', 'dropped', 'skipped', 'hit', 'missed', 'truncated', 'visits')
-
-
-def timed(torch, fn, repeat):
-    fn()                                                                         # warm-up: code objects, allocator
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeat):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        res = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return res, ms
 
 
 class SortedKeys(object):
@@ -60,46 +38,27 @@ class SortedKeys(object):
         return p, [(float(self.acc[2 + a, p]) / n) * (1.0 / 65536.0) for a in range(3)]
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--windows', type=int, default=40)
-    ap.add_argument('--frames', type=int, default=5)
-    ap.add_argument('--pts-per-frame', type=int, default=160000)
-    ap.add_argument('--voxel', type=float, default=0.1)
+def parse_args(argv=None):
+    ap = parser('accum_raycast_bench.txt', repeat=5)
     ap.add_argument('--max-range', type=float, default=30.0)
     ap.add_argument('--min-range', type=float, default=2.0)
     ap.add_argument('--box', type=float, default=50.0)
     ap.add_argument('--sample', type=int, default=2000)
-    ap.add_argument('--repeat', type=int, default=5)
-    ap.add_argument('--no-baseline', action='store_true')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'accum_raycast_bench.txt'))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     import torch
-    from bench_accumulate import drift
     from pcaccumulation_amd import native
     from pcaccumulation_amd.accumulate import AccumulatedCloud
-    from pcaccumulation_amd.config import default_config
-    from pcaccumulation_amd.synthetic import make_sequence
     dev = torch.device('cuda:0')
-    cfg = default_config('waymo', 'test', n_sweeps=a.frames)
-    lines = ['tools/bench_accumulate_raycast.py --windows %d --frames %d --pts-per-frame %d --voxel %g --max-range %g --min-range %g --box %g --repeat %d   (%s; GPU: device '
-             'events around each call, one warm-up, median of %d; host: perf_counter)'
-             % (a.windows, a.frames, a.pts_per_frame, a.voxel, a.max_range, a.min_range, a.box, a.repeat, torch.cuda.get_device_name(0), a.repeat)]
-
-    def emit(line):
-        lines.append(line)
-        print(line, flush=True)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:                                              # rewritten line by line: a run that is cut short leaves what it measured
-            f.write('\n'.join(lines) + '\n')
-
-    rng = np.random.RandomState(0)
+    emit = Report(a.out, header(__file__, a, '--max-range %g --min-range %g --box %g --repeat %d' % (a.max_range, a.min_range, a.box, a.repeat),
+                                'GPU: device events around each call, one warm-up, median of %d; host: perf_counter' % a.repeat)).emit
     m = AccumulatedCloud(a.voxel, dev, 1 << 20)
     scan = None
-    for k in range(a.windows):
-        s = make_sequence(500 + k, a.frames, a.pts_per_frame, cfg, mode='lidar_scan')
-        scan = torch.from_numpy(np.ascontiguousarray(s['input_points'][:, :3], np.float32)).to(dev)
-        m.add(scan, drift(k), torch.from_numpy(rng.rand(scan.shape[0]) < 0.1).to(dev), k)
+    for k, scan, mv, T in scene(a, dev):
+        m.add(scan, T, mv, k)
         if k % 10 == 9:
             print('window %d: %d voxels' % (k, m.num_voxels), flush=True)
     pose = drift(a.windows - 1)
@@ -122,8 +81,8 @@ def main():
     legs.append(('raycast to the target, margin %g, a filter that keeps nothing (the walk that nothing stops: see_through\'s visits)' % margin,
                  dict(margin=margin, min_count=1 << 40)))
     for what, args in legs:
-        report(what, *timed(torch, lambda: m.raycast(scan, SENSOR, pose=pose, **args), a.repeat))
-    _, ms = timed(torch, lambda: m.see_through(scan, SENSOR, pose=pose, margin=margin), a.repeat)
+        report(what, *timed_repeat(lambda: m.raycast(scan, SENSOR, pose=pose, **args), a.repeat))
+    _, ms = timed_repeat(lambda: m.see_through(scan, SENSOR, pose=pose, margin=margin), a.repeat)
     c = m._pierce_counters.tolist()
     emit('  GPU see_through of the same rays, margin %g, no stamp (beside it, a distance and not a target: it never stops and adds to a sidecar): median '
          '%.3f ms, min %.3f, max %.3f; per call walked %d, hits %d' % (margin, float(np.median(ms)), min(ms), max(ms), c[0] // (a.repeat + 1), c[4] // (a.repeat + 1)))
@@ -145,7 +104,7 @@ def main():
         hits = sum(r['status'] == yref.HIT for r in status)
         visits = sum(r['visits'] for r in status)
         sel = torch.from_numpy(pick).to(dev)
-        res, ms = timed(torch, lambda: m.raycast(scan[sel], SENSOR, pose=pose, max_range=a.max_range, min_range=a.min_range), a.repeat)
+        res, ms = timed_repeat(lambda: m.raycast(scan[sel], SENSOR, pose=pose, max_range=a.max_range, min_range=a.min_range), a.repeat)
         got = res['counters'].tolist()
         emit('(iii) host, a sub-sample of %d rays of (i), max_range %g, min_range %g, no filter: copy of the records (%d voxels) and the scan %.2f s; the walk in plain Python '
              'with np.searchsorted %.2f s = %.2f ms per ray (%.0f s for the whole window at that rate); hits %d, visits %d; the kernel on the same rays: hits %d, '
@@ -163,7 +122,7 @@ def main():
         emit('(ii) %s: %d voxels; render_range_image 64 x 2048, vertical field +3 .. -25 degrees, from the last pose' % (tag, m.num_voxels))
         for max_range in (30.0, 80.0):
             for near in (0.0, a.min_range):
-                res, ms = timed(torch, lambda: m.render_range_image(sensor_pose, 64, 2048, np.deg2rad(3.0), np.deg2rad(-25.0), max_range, min_range=near), a.repeat)
+                res, ms = timed_repeat(lambda: m.render_range_image(sensor_pose, 64, 2048, np.deg2rad(3.0), np.deg2rad(-25.0), max_range, min_range=near), a.repeat)
                 report('max_range %g, min_range %g, no filter (the host-side directions and their copy are inside the events)' % (max_range, near), res, ms)
 
     images('the full map')

@@ -12,17 +12,11 @@ scene gives the sizes and the memory behaviour of a real sequence, not a geometr
 whether the voxel count drops says nothing about accuracy here (tests/test_accumulate_register.py has the scenes with a known pose).
 Results go to --out.  Nothing is gated on them.
 Usage: python tools/bench_accumulate_register.py [--windows 40] [--max-iter 30] [--no-baseline] [--out profiles/accum_register_bench.txt]"""
-import argparse
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-sys.path.insert(0, os.path.join(ROOT, 'tests'))
+from accum_bench import Report, drift, header, parser, scene, timed
 
 
 def host_icp(tree, cent, nrm, pts, init, max_distance, max_iter):
@@ -48,54 +42,31 @@ def host_icp(tree, cent, nrm, pts, init, max_distance, max_iter):
     return T, max_iter, fit, rmse
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--windows', type=int, default=40)
-    ap.add_argument('--frames', type=int, default=5)
-    ap.add_argument('--pts-per-frame', type=int, default=160000)
-    ap.add_argument('--voxel', type=float, default=0.1)
+def parse_args(argv=None):
+    ap = parser('accum_register_bench.txt')
     ap.add_argument('--max-iter', type=int, default=30)
-    ap.add_argument('--no-baseline', action='store_true')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'accum_register_bench.txt'))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     import torch
-    from bench_accumulate import drift
     from pcaccumulation_amd import native
     from pcaccumulation_amd.accumulate import AccumulatedCloud
-    from pcaccumulation_amd.config import default_config
-    from pcaccumulation_amd.synthetic import make_sequence
     dev = torch.device('cuda:0')
-    cfg = default_config('waymo', 'test', n_sweeps=a.frames)
-    lines = ['tools/bench_accumulate_register.py --windows %d --frames %d --pts-per-frame %d --voxel %g --max-iter %d   (%s; GPU: device events around '
-             'each register call, one warm-up; host: perf_counter)' % (a.windows, a.frames, a.pts_per_frame, a.voxel, a.max_iter, torch.cuda.get_device_name(0))]
-
-    def emit(line):
-        lines.append(line)
-        print(line, flush=True)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:                                              # rewritten line by line: a run that is cut short leaves what it measured
-            f.write('\n'.join(lines) + '\n')
-
-    rng = np.random.RandomState(0)
+    emit = Report(a.out, header(__file__, a, '--max-iter %d' % a.max_iter,
+                                'GPU: device events around each register call, one warm-up; host: perf_counter')).emit
     plain, reg = AccumulatedCloud(a.voxel, dev, 1 << 20), AccumulatedCloud(a.voxel, dev, 1 << 20)
     times, rows = [], []
     usable = native.REGISTER_MAX_ITER                                            # a pose that stopped at max_iter is still the best one there is
-    for k in range(a.windows):
-        s = make_sequence(500 + k, a.frames, a.pts_per_frame, cfg, mode='lidar_scan')
-        pts = torch.from_numpy(np.ascontiguousarray(s['input_points'][:, :3], np.float32)).to(dev)
-        mv = torch.from_numpy(rng.rand(pts.shape[0]) < 0.1).to(dev)
-        plain.add(pts, drift(k), mv, k)
-        pose = drift(k)
+    for k, pts, mv, pose in scene(a, dev):
+        plain.add(pts, pose, mv, k)
         if k:
             if k == 1:
                 reg.register(pts, drift(k), mv, max_iter=a.max_iter)             # warm-up: code objects, allocator
                 torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            res = reg.register(pts, drift(k), mv, max_iter=a.max_iter)
-            e1.record()
-            torch.cuda.synchronize()
-            times.append(e0.elapsed_time(e1))
+            ms, res = timed(lambda: reg.register(pts, drift(k), mv, max_iter=a.max_iter))
+            times.append(ms)
             status = int(res['status'])
             rows.append((k, reg.num_voxels, times[-1], int(res['iterations']), status, float(res['fitness']), float(res['rmse'])))
             if not status & ~usable:
