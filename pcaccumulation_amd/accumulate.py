@@ -97,10 +97,14 @@ def _scan_rows(what, name, t, n):
             raise ValueError('%s must be [n], got %s' % (name, tuple(t.shape)))
 
 
+def _f64(a):
+    """A pose, origins or viewpoints: a tensor as it is, an array (or nested lists) as a float64 tensor on the host."""
+    return a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+
+
 def _origins(origins):
     """[3] or [S,3], tensor or array -> tensor [S,3], S >= 1."""
-    if not torch.is_tensor(origins):
-        origins = torch.from_numpy(np.ascontiguousarray(origins, dtype=np.float64))
+    origins = _f64(origins)
     if origins.dim() == 1:
         origins = origins.reshape(1, -1)
     if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape[0] < 1:
@@ -160,8 +164,80 @@ def _bad_mask(rows):
     return ValueError('mask must have one entry per row of extract() under the same filter (%d rows)' % rows)
 
 
-class AccumulatedCloud(object):
-    def __init__(self, voxel_size, device='cuda', capacity=1 << 20):
+# ---- the argument checks that several methods make: one copy of each condition and of each message ---------------------------------------------
+def _max_distance(max_distance, voxel_size):
+    """None = voxel_size -> the float."""
+    max_distance = voxel_size if max_distance is None else float(max_distance)
+    if not 0.0 < max_distance <= voxel_size:
+        raise ValueError('max_distance must lie in (0, voxel_size = %r], got %r' % (voxel_size, max_distance))
+    return max_distance
+
+
+def _margin(margin):
+    if not (margin >= 0.0 and np.isfinite(margin)):
+        raise ValueError('margin must be a finite number >= 0, got %r' % margin)
+
+
+def _max_range(max_range):
+    if max_range is not None and not float(max_range) >= 0.0:
+        raise ValueError('max_range must be >= 0 or None, got %r' % max_range)
+
+
+def _max_steps(max_steps, limit):
+    if not 1 <= int(max_steps) <= limit:
+        raise ValueError('max_steps must lie in [1, 2^16], got %r' % max_steps)
+
+
+def _radius3(radius):
+    if not 1 <= int(radius) <= 3:
+        raise ValueError('radius must be 1, 2 or 3 voxels, got %r' % radius)
+
+
+def _min_neighbors3(min_neighbors):
+    if int(min_neighbors) < 3:
+        raise ValueError('min_neighbors must be at least 3, got %r' % min_neighbors)
+
+
+def _moving_fraction(max_moving_fraction):
+    if max_moving_fraction is not None and np.isnan(float(max_moving_fraction)):
+        raise ValueError('max_moving_fraction must be a number or None')
+
+
+def _stamp32(name, stamp):
+    if not -0x80000000 <= int(stamp) <= 0x7fffffff:
+        raise ValueError('%s must fit 32 bits, got %r' % (name, stamp))
+
+
+# ---- voxel keys and boxes of voxel indices ------------------------------------------------------------------------------------------------------
+def _voxel_keys(coords):
+    """coords [V,3] integers, every index in [-2^20, 2^20) -> C4's keys [V] i64."""
+    c = coords.to(torch.int64)
+    return ((c[:, 0] + native.ACCUM_IDX_BIAS) << 42) | ((c[:, 1] + native.ACCUM_IDX_BIAS) << 21) | (c[:, 2] + native.ACCUM_IDX_BIAS)
+
+
+def _voxel_coords(keys):
+    """The inverse of _voxel_keys: keys [V] i64 -> coords [V,3] i64."""
+    return torch.stack([(keys >> 42) & 0x1fffff, (keys >> 21) & 0x1fffff, keys & 0x1fffff], 1) - native.ACCUM_IDX_BIAS
+
+
+def _bounding_box(coords, origin):
+    """The default window of bev() and distance_field(): index rows [V,k] on the device and the caller's origin or None -> (origin, hi), where a
+    None origin becomes the lowest index of every axis and hi is the highest.  A min / max on the device and one read-back; zeros without a row."""
+    if coords.shape[0]:
+        lo, hi = torch.stack([coords.min(0).values, coords.max(0).values]).tolist()
+    else:
+        lo = hi = [0] * coords.shape[1]
+    return (tuple(lo) if origin is None else origin), hi
+
+
+class _VoxelTable(object):
+    """What AccumulatedCloud and ObservedSpace share: three sorted tables of `capacity` rows on the device, of which the first _n are in use, and
+    the protocol by which a call rewrites them.  _cur holds the rows; a call writes its result into _alt, taken at the capacity it needs, and the
+    two change places when it has fitted, so that what was there before the call stays in _alt until the next call overwrites it.
+    A class sets: _tables(capacity, device) -> the three tensors, keys first; _state_words, the length of _state; _noun, what messages call it."""
+    _tables = _state_words = _noun = None
+
+    def __init__(self, voxel_size, device, capacity):
         voxel_size = float(voxel_size)
         if not (voxel_size > 0.0 and np.isfinite(voxel_size)):
             raise ValueError('voxel_size must be a positive finite number, got %r' % voxel_size)
@@ -170,27 +246,155 @@ class AccumulatedCloud(object):
         self.voxel_size = voxel_size
         self.device = torch.device(device)
         self.capacity = int(capacity)
-        self._cur = self._alt = self._state = None           # device memory is taken at the first add
+        self._cur = self._alt = self._state = None           # device memory is taken at the first call that needs it
         self._n = 0
+
+    @property
+    def num_voxels(self):
+        return self._n
+
+    def _ensure(self):
+        if self.device.type != 'cuda':
+            raise native.NativeError('%s lives on the GPU (got device %s); the HIP path has no CPU fallback' % (type(self).__name__, self.device))
+        if self._cur is None:
+            self._cur = self._tables(self.capacity, self.device)
+            self._state = torch.zeros((self._state_words,), dtype=torch.int64, device=self.device)
+
+    def _pose(self, pose):
+        if pose is None:
+            return None
+        pose = _f64(pose)
+        if tuple(pose.shape) != (4, 4):
+            raise ValueError('pose must be [4,4], got %s' % (tuple(pose.shape),))
+        return pose.to(device=self.device, dtype=torch.float64).contiguous()
+
+    def _box_indices(self, box):
+        """(lo [3], hi [3]) in metres of the world frame -> inclusive voxel indices floor(bound / voxel_size), float64 (the map's own division),
+        clamped into the grid."""
+        try:
+            lo, hi = box
+            lo, hi = [float(v) for v in lo], [float(v) for v in hi]
+        except (TypeError, ValueError):
+            raise ValueError('box must be (lo [3], hi [3]) in metres, got %r' % (box,))
+        if len(lo) != 3 or len(hi) != 3:
+            raise ValueError('box must be (lo [3], hi [3]) in metres, got %r' % (box,))
+        if not all(np.isfinite(v) for v in lo + hi):
+            raise ValueError('box: every bound must be finite, got %r' % (box,))
+        if any(l > h for l, h in zip(lo, hi)):
+            raise ValueError('box: lo must not lie above hi, got %r' % (box,))
+        grid_lo, grid_hi = float(-native.ACCUM_IDX_BIAS), float(native.ACCUM_IDX_BIAS - 1)
+        index = lambda v: int(min(max(np.floor(np.float64(v) / np.float64(self.voxel_size)), grid_lo), grid_hi))
+        return [index(v) for v in lo], [index(v) for v in hi]
+
+    # ---- the two sets of tables ----------------------------------------------------------------------------------------------------------
+    def _stage(self, capacity):
+        """-> self._alt as tables of `capacity` rows: the ones that are there if they have that many, else new ones."""
+        if self._alt is None or self._alt[0].shape[0] != capacity:
+            self._alt = None                                       # release before taking the other tables
+            self._alt = self._tables(capacity, self.device)
+        return self._alt
+
+    def _swap(self):
+        self._cur, self._alt = self._alt, self._cur                # what was there before the call stays in self._alt, which the next call overwrites
+
+    def _grow(self, what, attempt, described=None, leave=()):
+        """A call whose result may have more rows than the capacity: attempt(capacity) launches it from self._cur into self._alt, which has that many
+        rows, does its one read-back and returns (status, the rows the result needs, the words it read, with whatever else its caller wants back).
+        Until the status is ACCUM_OK the capacity doubles up to what is needed and the attempt is made again; self._cur is untouched by an attempt
+        that does not fit.  Then the tables change places and the capacity is the new one.  A status in `leave` ends the call as it stands,
+        without either.  -> (status, what the attempt returned third)."""
+        capacity = self.capacity
+        while True:
+            self._stage(capacity)
+            status, need, host = attempt(capacity)
+            if status == native.ACCUM_OK:
+                break
+            if status in leave:
+                return status, host
+            if status != native.ACCUM_TOO_SMALL:
+                raise native.NativeError('%s: the state words do not describe the %s (status %d)' % (what, described or self._noun, status))
+            if need > native.ACCUM_MAX_CAPACITY:
+                raise native.NativeError('%s: the %s would take %d voxels, more than 2^30' % (what, self._noun, need))
+            while capacity < need:                                 # growth by doubling
+                capacity = min(2 * capacity, native.ACCUM_MAX_CAPACITY)
+        self._swap()
+        self.capacity = capacity
+        return status, host
+
+    # ---- what copy, regrid, select, merge and load share ---------------------------------------------------------------------------------------
+    def _copy_rows(self, c):
+        """The rows in use and the state words into `c`, a new object of this capacity -> c."""
+        c._n = self._n
+        if self._cur is not None:
+            c._ensure()
+            for dst, src in zip(c._cur, self._cur):
+                dst[..., :self._n].copy_(src[..., :self._n])
+            c._state.copy_(self._state)
+        return c
+
+    def _room(self, capacity):
+        """The capacity of a result that never has more rows than this one: None = this one's."""
+        capacity = self.capacity if capacity is None else int(capacity)
+        if capacity < max(self._n, 1):
+            raise ValueError('capacity must be at least the %d rows of the %s (the result never has more), got %r' % (self._n, self._noun, capacity))
+        return capacity
+
+    def _regrid_args(self, pose, voxel_size, capacity):
+        if pose is None and voxel_size is None:
+            raise ValueError('regrid needs a pose, a voxel_size or both')
+        return self.voxel_size if voxel_size is None else float(voxel_size), self._room(capacity)
+
+    def _peer(self, what, other, kind):
+        """`other` is a `kind` on this device."""
+        if not isinstance(other, kind):
+            raise TypeError('%s takes an %s, got %s' % (what, kind.__name__, type(other).__name__))
+        if _device_key(other.device) != _device_key(self.device):
+            raise ValueError('%s: the maps live on %s and %s; save() / load() carries a map across' % (what, self.device, other.device))
+
+    def _merge_args(self, other, pose, kind):
+        self._peer('merge', other, kind)
+        if pose is None and other.voxel_size != self.voxel_size:
+            raise ValueError('merge: voxel sizes %r and %r differ; give pose= (np.eye(4) keeps the frame) or regrid() the other map first'
+                             % (self.voxel_size, other.voxel_size))
+
+    def _records(self):
+        tables = self._tables(0, 'cpu') if self._cur is None or self._n == 0 else self._cur
+        return tuple(t[..., :self._n].cpu().numpy() for t in tables)
+
+    @staticmethod
+    def _ascending(path, keys):
+        if keys.shape[0] and (np.any(keys[1:] <= keys[:-1]) or keys[0] < 0):
+            raise ValueError('%s: the keys are not ascending' % path)
+
+    @classmethod
+    def _from_records(cls, columns, voxel_size, device):
+        """load(): an object whose capacity is 64 doubled until the rows fit, with the host arrays `columns`, keys first, as its rows."""
+        m = columns[0].shape[0]
+        capacity = 64
+        while capacity < m:
+            capacity *= 2
+        self = cls(voxel_size, device, capacity)
+        self._ensure()
+        if m:
+            for dst, src in zip(self._cur, columns):
+                dst[..., :m] = torch.from_numpy(src).to(self.device)
+        self._n = m
+        return self
+
+
+class AccumulatedCloud(_VoxelTable):
+    _tables, _state_words, _noun = staticmethod(_tables), native.ACCUM_STATE_WORDS, 'map'
+
+    def __init__(self, voxel_size, device='cuda', capacity=1 << 20):
+        super(AccumulatedCloud, self).__init__(voxel_size, device, capacity)
         self._dropped = 0
         self._pierced = self._pierce_counters = None          # the sidecar of see_through: taken at its first call
 
     # ---- state -------------------------------------------------------------------------------------------------------------------------
     @property
-    def num_voxels(self):
-        return self._n
-
-    @property
     def dropped(self):
         """Points that were not accumulated: a non-finite coordinate, |coordinate| >= 32768 or a voxel index outside +-2^20."""
         return self._dropped
-
-    def _ensure(self):
-        if self.device.type != 'cuda':
-            raise native.NativeError('AccumulatedCloud lives on the GPU (got device %s); the HIP path has no CPU fallback' % self.device)
-        if self._cur is None:
-            self._cur = _tables(self.capacity, self.device)
-            self._state = torch.zeros((native.ACCUM_STATE_WORDS,), dtype=torch.int64, device=self.device)
 
     def clear(self):
         self._n = self._dropped = 0
@@ -199,15 +403,6 @@ class AccumulatedCloud(object):
             self._state.zero_()
 
     # ---- add ---------------------------------------------------------------------------------------------------------------------------
-    def _pose(self, pose):
-        if pose is None:
-            return None
-        if not torch.is_tensor(pose):
-            pose = torch.from_numpy(np.ascontiguousarray(pose, dtype=np.float64))
-        if tuple(pose.shape) != (4, 4):
-            raise ValueError('pose must be [4,4], got %s' % (tuple(pose.shape),))
-        return pose.to(device=self.device, dtype=torch.float64).contiguous()
-
     def add(self, points, pose=None, moving=None, stamp=0):
         """points [n,3] f32 (device), pose [4,4] window-to-world (tensor or array; None = identity), moving [n] bool / integer (non-zero = predicted
         moving; None = none), stamp: one integer for the call.  Only the map's eight state words are read back."""
@@ -219,25 +414,12 @@ class AccumulatedCloud(object):
         pts = points.detach().float().contiguous()
         mv = (moving != 0).to(torch.uint8).contiguous() if moving is not None else None
         pose = self._pose(pose)
-        out_cap = self.capacity
-        while True:
-            if self._alt is None or self._alt[0].shape[0] != out_cap:
-                self._alt = None                                   # release before taking the larger tables
-                self._alt = _tables(out_cap, self.device)
+
+        def attempt(capacity):
             native.accum_add(pts, pose, mv, int(stamp), self.voxel_size, self._cur, self._alt, self._state)
             state = self._state.tolist()                           # the one read-back of an add
-            status = state[native.ACCUM_STATUS]
-            if status == native.ACCUM_OK:
-                break
-            if status != native.ACCUM_TOO_SMALL:
-                raise native.NativeError('accum_add: the state words do not describe the map (status %d)' % status)
-            need = state[native.ACCUM_NEEDED]
-            if need > native.ACCUM_MAX_CAPACITY:
-                raise native.NativeError('accum_add: the map would take %d voxels, more than 2^30' % need)
-            while out_cap < need:                                  # growth by doubling; the map so far is untouched
-                out_cap = min(2 * out_cap, native.ACCUM_MAX_CAPACITY)
-        self._cur, self._alt = self._alt, self._cur
-        self.capacity = out_cap
+            return state[native.ACCUM_STATUS], state[native.ACCUM_NEEDED], state
+        state = self._grow('accum_add', attempt)[1]
         if self._pierced is not None:                              # carry the sidecar: the old map sits untouched in self._alt
             self._pierced = self._carry(self._pierced, self._alt[0], self._n, self._cur[0], state[native.ACCUM_NUM_VOXELS])
         self._n = state[native.ACCUM_NUM_VOXELS]
@@ -249,8 +431,8 @@ class AccumulatedCloud(object):
         (results['mos_est'].argmax(1) == 1).  One sample per batch, or one pose per sample ([B,4,4])."""
         points = results['rec_est']
         moving = results['mos_est'].argmax(1) == 1
-        if pose is not None and not torch.is_tensor(pose):
-            pose = torch.from_numpy(np.ascontiguousarray(pose, dtype=np.float64))
+        if pose is not None:
+            pose = _f64(pose)
         if pose is not None and pose.dim() == 3:
             batch = input_dict['time_indice'][:, 0]
             for b in range(pose.shape[0]):
@@ -289,13 +471,10 @@ class AccumulatedCloud(object):
         viewpoints [S,3] (tensor or array): the sensor position of stamp stamp_base + s; a voxel whose first stamp has a row there gets the normal
         that faces it, every other voxel the normal whose first non-zero of (n_z, n_y, n_x) is positive.  Only the kept count is read back."""
         radius, min_neighbors = int(radius), int(min_neighbors)
-        if not 1 <= radius <= 3:
-            raise ValueError('radius must be 1, 2 or 3 voxels, got %r' % radius)
-        if min_neighbors < 3:
-            raise ValueError('min_neighbors must be at least 3, got %r' % min_neighbors)
+        _radius3(radius)
+        _min_neighbors3(min_neighbors)
         if viewpoints is not None:
-            if not torch.is_tensor(viewpoints):
-                viewpoints = torch.from_numpy(np.ascontiguousarray(viewpoints, dtype=np.float64))
+            viewpoints = _f64(viewpoints)
             if viewpoints.dim() != 2 or viewpoints.shape[1] != 3:
                 raise ValueError('viewpoints must be [S,3], got %s' % (tuple(viewpoints.shape),))
         self._ensure()
@@ -323,9 +502,7 @@ class AccumulatedCloud(object):
         2 ms per round at 800 k points against 2 - 8 M voxels).  Only the kept count that normals() reads is read back."""
         n = _scan_points('register', 'points', points, native.REGISTER_MAX_POINTS)
         _scan_rows('register', 'moving', moving, n)
-        max_distance = self.voxel_size if max_distance is None else float(max_distance)
-        if not 0.0 < max_distance <= self.voxel_size:
-            raise ValueError('max_distance must lie in (0, voxel_size = %r], got %r' % (self.voxel_size, max_distance))
+        max_distance = _max_distance(max_distance, self.voxel_size)
         if not 0 <= int(max_iter) <= native.REGISTER_MAX_ITERATIONS:
             raise ValueError('max_iter must lie in [0, %d], got %r' % (native.REGISTER_MAX_ITERATIONS, max_iter))
         init = self._pose(init_pose)
@@ -359,13 +536,9 @@ class AccumulatedCloud(object):
         counters [7] i64: points, invalid, occupied, kept, matched, with a normal, and native.QUERY_BAD_TABLE (always 0 from here).
         Nothing is read back beyond the kept count normals() reads when normals=True."""
         _scan_points('query', 'points', points, native.QUERY_MAX_POINTS)
-        max_distance = self.voxel_size if max_distance is None else float(max_distance)
-        if not 0.0 < max_distance <= self.voxel_size:
-            raise ValueError('max_distance must lie in (0, voxel_size = %r], got %r' % (self.voxel_size, max_distance))
-        if not 1 <= int(radius) <= 3:
-            raise ValueError('radius must be 1, 2 or 3 voxels, got %r' % radius)
-        if int(min_neighbors) < 3:
-            raise ValueError('min_neighbors must be at least 3, got %r' % min_neighbors)
+        max_distance = _max_distance(max_distance, self.voxel_size)
+        _radius3(radius)
+        _min_neighbors3(min_neighbors)
         if require_normal and not normals:
             raise ValueError('require_normal=True needs normals=True')
         pose = self._pose(pose)
@@ -506,11 +679,7 @@ class AccumulatedCloud(object):
         cols = self.columns(**column_kw)
         f = {a: column_kw[a] for a in ('min_count', 'max_moving_fraction') if a in column_kw}
         if origin is None or shape is None:
-            if cols['xy'].shape[0]:
-                lo, hi = torch.stack([cols['xy'].min(0).values, cols['xy'].max(0).values]).tolist()       # the one more read-back
-            else:
-                lo, hi = [0, 0], [0, 0]
-            origin = tuple(lo) if origin is None else origin
+            origin, hi = _bounding_box(cols['xy'], origin)          # the one more read-back
             if shape is None:
                 shape = (hi[1] - int(origin[1]) + 1, hi[0] - int(origin[0]) + 1)
                 if shape[0] < 1 or shape[1] < 1 or shape[0] * shape[1] > native.BEV_MAX_PIXELS:
@@ -555,8 +724,7 @@ class AccumulatedCloud(object):
         keep = count >= min_count
         if max_moving_fraction is not None:
             keep &= moving.double() / count.double() <= float(max_moving_fraction)
-        k = keys[:self._n][keep]
-        return torch.stack([(k >> 42) & 0x1fffff, (k >> 21) & 0x1fffff, k & 0x1fffff], 1) - native.ACCUM_IDX_BIAS
+        return _voxel_coords(keys[:self._n][keep])
 
     def _distance(self, dist2):
         """Metres, f32: sqrt(dist2) * voxel_size in float64, inf where there is no result."""
@@ -577,12 +745,7 @@ class AccumulatedCloud(object):
         max_radius, min_count = self._field_args(origin, shape, max_radius, planar, pad, min_count, max_moving_fraction)
         self._ensure()
         if origin is None or shape is None:
-            coords = self._kept_coords(min_count, max_moving_fraction)
-            if coords.shape[0]:
-                lo, hi = torch.stack([coords.min(0).values, coords.max(0).values]).tolist()       # the one read-back
-            else:
-                lo, hi = [0, 0, 0], [0, 0, 0]
-            origin = tuple(lo) if origin is None else origin
+            origin, hi = _bounding_box(self._kept_coords(min_count, max_moving_fraction), origin)       # the one read-back
             if shape is None:
                 shape = tuple(h - int(o) + 1 for h, o in zip(hi, origin))
                 if min(shape) < 1:
@@ -659,12 +822,9 @@ class AccumulatedCloud(object):
         _scan_rows('see_through', 'origin_index', origin_index, n)
         origins = _origins(origins)
         margin = 2.0 * self.voxel_size if margin is None else float(margin)
-        if not (margin >= 0.0 and np.isfinite(margin)):
-            raise ValueError('margin must be a finite number >= 0, got %r' % margin)
-        if max_range is not None and not float(max_range) >= 0.0:
-            raise ValueError('max_range must be >= 0 or None, got %r' % max_range)
-        if not 1 <= int(max_steps) <= native.PIERCE_MAX_STEPS:
-            raise ValueError('max_steps must lie in [1, 2^16], got %r' % max_steps)
+        _margin(margin)
+        _max_range(max_range)
+        _max_steps(max_steps, native.PIERCE_MAX_STEPS)
         pose = self._pose(pose)
         self._ensure()
         if self._pierced is None:
@@ -705,16 +865,13 @@ class AccumulatedCloud(object):
         min_range, margin = float(min_range), float(margin)
         if not (min_range >= 0.0 and np.isfinite(min_range)):
             raise ValueError('min_range must be a finite number >= 0, got %r' % min_range)
-        if not (margin >= 0.0 and np.isfinite(margin)):
-            raise ValueError('margin must be a finite number >= 0, got %r' % margin)
+        _margin(margin)
         if max_range is not None:
             max_range = float(max_range)
-            if not max_range >= 0.0:
-                raise ValueError('max_range must be >= 0 or None, got %r' % max_range)
+            _max_range(max_range)
             if margin != 0.0:
                 raise ValueError('margin is measured from the target: it cannot be combined with a max_range')
-        if not 1 <= int(max_steps) <= native.RAYCAST_MAX_STEPS:
-            raise ValueError('max_steps must lie in [1, 2^16], got %r' % max_steps)
+        _max_steps(max_steps, native.RAYCAST_MAX_STEPS)
         pose = self._pose(pose)
         self._ensure()
         return native.accum_raycast(targets.detach().float().contiguous(), origins.to(device=self.device, dtype=torch.float64).contiguous(),
@@ -753,30 +910,28 @@ class AccumulatedCloud(object):
     def pierced(self, min_count=1, max_moving_fraction=None):
         """[V] int32: the rays see_through counted through every voxel that extract(min_count, max_moving_fraction) returns, row for row; all zeros before
         any see_through.  A key join: extract's coords -> keys -> their rows in the map."""
-        coords = self.extract(min_count, max_moving_fraction)['coords'].to(torch.int64)
+        coords = self.extract(min_count, max_moving_fraction)['coords']
         if self._pierced is None or coords.shape[0] == 0:
             return torch.zeros((coords.shape[0],), dtype=torch.int32, device=self.device)
-        keys = ((coords[:, 0] + native.ACCUM_IDX_BIAS) << 42) | ((coords[:, 1] + native.ACCUM_IDX_BIAS) << 21) | (coords[:, 2] + native.ACCUM_IDX_BIAS)
-        return self._pierced[torch.searchsorted(self._cur[0][:self._n], keys)]
+        return self._pierced[torch.searchsorted(self._cur[0][:self._n], _voxel_keys(coords))]
 
     # ---- prune -------------------------------------------------------------------------------------------------------------------------
-    def _box_indices(self, box):
-        """(lo [3], hi [3]) in metres of the world frame -> inclusive voxel indices floor(bound / voxel_size), float64 (the map's own division),
-        clamped into the grid."""
-        try:
-            lo, hi = box
-            lo, hi = [float(v) for v in lo], [float(v) for v in hi]
-        except (TypeError, ValueError):
-            raise ValueError('box must be (lo [3], hi [3]) in metres, got %r' % (box,))
-        if len(lo) != 3 or len(hi) != 3:
-            raise ValueError('box must be (lo [3], hi [3]) in metres, got %r' % (box,))
-        if not all(np.isfinite(v) for v in lo + hi):
-            raise ValueError('box: every bound must be finite, got %r' % (box,))
-        if any(l > h for l, h in zip(lo, hi)):
-            raise ValueError('box: lo must not lie above hi, got %r' % (box,))
-        grid_lo, grid_hi = float(-native.ACCUM_IDX_BIAS), float(native.ACCUM_IDX_BIAS - 1)
-        index = lambda v: int(min(max(np.floor(np.float64(v) / np.float64(self.voxel_size)), grid_lo), grid_hi))
-        return [index(v) for v in lo], [index(v) for v in hi]
+    def _rewrite(self, dry_run, launch):
+        """What prune() and remove_components() share: a call that leaves rows out at the present capacity.  launch(tables_out, pierced_out, state)
+        -- all None when dry_run -- runs it and -> its counters as a dict with 'kept'.  Afterwards the tables change places, the ray counts are
+        the new ones and 'kept' rows are in use."""
+        out = pierced_out = None
+        if not dry_run:
+            out = self._stage(self.capacity)
+            if self._pierced is not None:
+                pierced_out = torch.zeros((self.capacity,), dtype=torch.int32, device=self.device)
+        res = launch(out, pierced_out, None if dry_run else self._state)
+        if not dry_run and self._n:                                # the map before the call stays in self._alt, which the next add overwrites
+            self._swap()
+            if self._pierced is not None:
+                self._pierced = pierced_out
+            self._n = res['kept']
+        return res
 
     def prune(self, min_pierced=None, pierced_ratio=None, before_stamp=None, min_count=1, max_moving_fraction=None, box=None, min_neighbors=None,
               radius=1, dry_run=False):
@@ -799,43 +954,29 @@ class AccumulatedCloud(object):
                 raise ValueError('pierced_ratio needs min_pierced >= 1')
             if not float(pierced_ratio) >= 0.0:
                 raise ValueError('pierced_ratio must be >= 0, got %r' % pierced_ratio)
-        if before_stamp is not None and not -0x80000000 <= int(before_stamp) <= 0x7fffffff:
-            raise ValueError('before_stamp must fit 32 bits, got %r' % before_stamp)
-        if max_moving_fraction is not None and np.isnan(float(max_moving_fraction)):
-            raise ValueError('max_moving_fraction must be a number or None')
+        if before_stamp is not None:
+            _stamp32('before_stamp', before_stamp)
+        _moving_fraction(max_moving_fraction)
         if not 0 <= min_neighbors <= native.PRUNE_MAX_NEIGHBORS:
             raise ValueError('min_neighbors must be None or lie in [0, %d], got %r' % (native.PRUNE_MAX_NEIGHBORS, min_neighbors))
-        if min_neighbors and not 1 <= radius <= 3:
-            raise ValueError('radius must be 1, 2 or 3 voxels, got %r' % radius)
+        if min_neighbors:
+            _radius3(radius)
         if box is not None:
             box = self._box_indices(box)
         self._ensure()
         counters = torch.empty((native.PRUNE_COUNTERS,), dtype=torch.int64, device=self.device)
-        out = pierced_out = None
-        if not dry_run:
-            if self._alt is None or self._alt[0].shape[0] != self.capacity:
-                self._alt = None                                   # release before taking the tables
-                self._alt = _tables(self.capacity, self.device)
-            out = self._alt
-            if self._pierced is not None:
-                pierced_out = torch.zeros((self.capacity,), dtype=torch.int32, device=self.device)
-        native.accum_prune(self._cur, self._n, self._pierced, min_count, max_moving_fraction, before_stamp, box, min_pierced, pierced_ratio,
-                           min_neighbors, radius, dry_run, out, pierced_out, counters, None if dry_run else self._state)
-        res = dict(zip(_PRUNE_FIELDS, counters.tolist()))          # the one read-back of a prune
-        if not dry_run and self._n:                                # the map before the prune stays in self._alt, which the next add overwrites
-            self._cur, self._alt = self._alt, self._cur
-            if self._pierced is not None:
-                self._pierced = pierced_out
-            self._n = res['kept']
-        return res
+
+        def launch(out, pierced_out, state):
+            native.accum_prune(self._cur, self._n, self._pierced, min_count, max_moving_fraction, before_stamp, box, min_pierced, pierced_ratio,
+                               min_neighbors, radius, dry_run, out, pierced_out, counters, state)
+            return dict(zip(_PRUNE_FIELDS, counters.tolist()))     # the one read-back of a prune
+        return self._rewrite(dry_run, launch)
 
     # ---- connected components ----------------------------------------------------------------------------------------------------------
     def _components_args(self, what, radius, min_count, max_moving_fraction, mask):
         radius, min_count = int(radius), int(min_count)
-        if not 1 <= radius <= 3:
-            raise ValueError('radius must be 1, 2 or 3 voxels, got %r' % radius)
-        if max_moving_fraction is not None and np.isnan(float(max_moving_fraction)):
-            raise ValueError('max_moving_fraction must be a number or None')
+        _radius3(radius)
+        _moving_fraction(max_moving_fraction)
         return radius, min_count, _row_mask(what, mask)
 
     @staticmethod
@@ -880,25 +1021,14 @@ class AccumulatedCloud(object):
         self._ensure()
         counters = torch.empty((native.COMPONENTS_COUNTERS + native.COMPONENTS_REMOVE_COUNTERS,), dtype=torch.int64, device=self.device)
         first = native.accum_components(self._cur, self._n, min_count, max_moving_fraction, mask, radius, counters=counters[:native.COMPONENTS_COUNTERS])
-        out = pierced_out = None
-        if not dry_run:
-            if self._alt is None or self._alt[0].shape[0] != self.capacity:
-                self._alt = None                                   # release before taking the tables
-                self._alt = _tables(self.capacity, self.device)
-            out = self._alt
-            if self._pierced is not None:
-                pierced_out = torch.zeros((self.capacity,), dtype=torch.int32, device=self.device)
-        native.accum_remove_components(self._cur, self._n, self._pierced, min_count, max_moving_fraction, first, min_voxels, min_points, dry_run, out,
-                                       pierced_out, counters[native.COMPONENTS_COUNTERS:], None if dry_run else self._state)
-        host = counters.tolist()                                   # the one read-back, of both stages
-        self._components_status(host)                              # a stage that did not end OK has left the tables and the state word alone
-        res = dict(zip(_REMOVE_FIELDS, host[native.COMPONENTS_COUNTERS:] + host[:native.COMPONENTS_STATUS]))
-        if not dry_run and self._n:                                # the map before the call stays in self._alt, which the next add overwrites
-            self._cur, self._alt = self._alt, self._cur
-            if self._pierced is not None:
-                self._pierced = pierced_out
-            self._n = res['kept']
-        return res
+
+        def launch(out, pierced_out, state):
+            native.accum_remove_components(self._cur, self._n, self._pierced, min_count, max_moving_fraction, first, min_voxels, min_points, dry_run,
+                                           out, pierced_out, counters[native.COMPONENTS_COUNTERS:], state)
+            host = counters.tolist()                               # the one read-back, of both stages
+            self._components_status(host)                          # a stage that did not end OK has left the tables and the state word alone
+            return dict(zip(_REMOVE_FIELDS, host[native.COMPONENTS_COUNTERS:] + host[:native.COMPONENTS_STATUS]))
+        return self._rewrite(dry_run, launch)
 
     # ---- planar segments ---------------------------------------------------------------------------------------------------------------
     def planes(self, angle=15.0, max_offset=None, max_variation=0.01, radius=1, normal_radius=2, min_neighbors=5, min_count=1,
@@ -967,35 +1097,28 @@ class AccumulatedCloud(object):
     def copy(self):
         """An independent clone: device copies of the rows in use, of the ray counts and of the state words.  merge() mutates its map, so
         `c = a.copy(); c.merge(b)` keeps a."""
-        c = AccumulatedCloud(self.voxel_size, self.device, self.capacity)
-        c._n, c._dropped = self._n, self._dropped
-        if self._cur is not None:
-            c._ensure()
-            n = self._n
-            for dst, src in zip(c._cur, self._cur):
-                dst[..., :n].copy_(src[..., :n])
-            c._state.copy_(self._state)
-            if self._pierced is not None:
-                c._pierced = torch.zeros((self.capacity,), dtype=torch.int32, device=self.device)
-                c._pierced[:n].copy_(self._pierced[:n])
-                c._pierce_counters = self._pierce_counters.clone()
+        c = self._copy_rows(self._like(self.voxel_size, self.capacity))
+        c._dropped = self._dropped
+        if self._pierced is not None:
+            c._pierced[:self._n].copy_(self._pierced[:self._n])
         return c
 
-    def _regrid(self, pose, voxel_size, capacity):
-        """-> (the new map, the counters of the call as Python integers: the one read-back)."""
-        if pose is None and voxel_size is None:
-            raise ValueError('regrid needs a pose, a voxel_size or both')
-        voxel_size = self.voxel_size if voxel_size is None else float(voxel_size)
-        capacity = self.capacity if capacity is None else int(capacity)
-        if capacity < max(self._n, 1):
-            raise ValueError('capacity must be at least the %d rows of the map (the result never has more), got %r' % (self._n, capacity))
-        new = AccumulatedCloud(voxel_size, self.device, capacity)              # checks voxel_size and capacity
-        pose = self._pose(pose)
-        self._ensure()
-        new._ensure()
+    def _like(self, voxel_size, capacity):
+        """A new, empty map on this device, with ray counts (all 0) and this map's see_through counters if this map has them.  The constructor
+        checks voxel_size and capacity; device memory for the tables is taken by the caller's _ensure()."""
+        new = AccumulatedCloud(voxel_size, self.device, capacity)
         if self._pierced is not None:
             new._pierced = torch.zeros((capacity,), dtype=torch.int32, device=self.device)
             new._pierce_counters = self._pierce_counters.clone()
+        return new
+
+    def _regrid(self, pose, voxel_size, capacity):
+        """-> (the new map, the counters of the call as Python integers: the one read-back)."""
+        voxel_size, capacity = self._regrid_args(pose, voxel_size, capacity)
+        new = self._like(voxel_size, capacity)
+        pose = self._pose(pose)
+        self._ensure()
+        new._ensure()
         counters = torch.empty((native.REGRID_COUNTERS,), dtype=torch.int64, device=self.device)
         native.accum_regrid(self._cur, self._n, self._pierced, pose, voxel_size, self._dropped, new._cur, new._pierced, counters, new._state)
         host = counters.tolist()                                   # the one read-back of a regrid
@@ -1020,13 +1143,7 @@ class AccumulatedCloud(object):
         The capacity grows as in add().  -> {'rows', 'shared', 'new', 'dropped_rows', 'dropped_points', 'saturated'}: rows of this map after the call,
         voxels both maps held, voxels only `other` held, rows / points the regrid dropped, ray counts that were clamped -- Python integers, one
         read-back of the counters per attempt.  An empty `other` changes nothing."""
-        if not isinstance(other, AccumulatedCloud):
-            raise TypeError('merge takes an AccumulatedCloud, got %s' % type(other).__name__)
-        if _device_key(other.device) != _device_key(self.device):
-            raise ValueError('merge: the maps live on %s and %s; save() / load() carries a map across' % (self.device, other.device))
-        if pose is None and other.voxel_size != self.voxel_size:
-            raise ValueError('merge: voxel sizes %r and %r differ; give pose= (np.eye(4) keeps the frame) or regrid() the other map first'
-                             % (self.voxel_size, other.voxel_size))
+        self._merge_args(other, pose, AccumulatedCloud)
         self._ensure()
         other._ensure()
         res = dict(rows=self._n, shared=0, new=0, dropped_rows=0, dropped_points=0, saturated=0)
@@ -1038,24 +1155,15 @@ class AccumulatedCloud(object):
             res['saturated'] = host[native.REGRID_SATURATED]
         sidecar = self._pierced is not None or other._pierced is not None
         counters = torch.empty((native.MERGE_COUNTERS,), dtype=torch.int64, device=self.device)
-        out_cap = self.capacity
-        while True:
-            if self._alt is None or self._alt[0].shape[0] != out_cap:
-                self._alt = None                                   # release before taking the larger tables
-                self._alt = _tables(out_cap, self.device)
-            pierced_out = torch.zeros((out_cap,), dtype=torch.int32, device=self.device) if sidecar else None
+
+        def attempt(capacity):
+            pierced_out = torch.zeros((capacity,), dtype=torch.int32, device=self.device) if sidecar else None
             native.accum_merge(self._cur, self._n, self._pierced, other._cur, other._n, other._pierced, other._dropped, self._alt, pierced_out, counters,
                                self._state)
             host = counters.tolist()                               # the one read-back of an attempt
-            if host[native.MERGE_STATUS] == native.ACCUM_OK:
-                break
-            need = host[native.MERGE_NEEDED]
-            if need > native.ACCUM_MAX_CAPACITY:
-                raise native.NativeError('accum_merge: the map would take %d voxels, more than 2^30' % need)
-            while out_cap < need:                                  # growth by doubling; both maps are untouched
-                out_cap = min(2 * out_cap, native.ACCUM_MAX_CAPACITY)
-        self._cur, self._alt = self._alt, self._cur                # the map before the merge stays in self._alt, which the next add overwrites
-        self.capacity = out_cap
+            ok = host[native.MERGE_STATUS] == native.ACCUM_OK      # the entry point has one other status: the result needs more rows
+            return native.ACCUM_OK if ok else native.ACCUM_TOO_SMALL, host[native.MERGE_NEEDED], (host, pierced_out)
+        host, pierced_out = self._grow('accum_merge', attempt)[1]
         if sidecar:
             if self._pierce_counters is None:
                 self._pierce_counters = other._pierce_counters.clone()
@@ -1072,8 +1180,7 @@ class AccumulatedCloud(object):
         min_count = int(min_count)
         if min_count < 1:
             raise ValueError('min_count must be at least 1, got %r' % min_count)
-        if max_moving_fraction is not None and np.isnan(float(max_moving_fraction)):
-            raise ValueError('max_moving_fraction must be a number or None')
+        _moving_fraction(max_moving_fraction)
         return min_count
 
     def compare(self, other, max_distance=None, min_count=1, max_moving_fraction=None):
@@ -1090,15 +1197,10 @@ class AccumulatedCloud(object):
         next add, prune or merge of the map they index.
         counters: per side {'rows', 'kept', 'same', 'held', 'near', 'only'}, Python integers -- the one read-back; `only` counts kept rows with
         neither SAME nor NEAR."""
-        if not isinstance(other, AccumulatedCloud):
-            raise TypeError('compare takes an AccumulatedCloud, got %s' % type(other).__name__)
-        if _device_key(other.device) != _device_key(self.device):
-            raise ValueError('compare: the maps live on %s and %s; save() / load() carries a map across' % (self.device, other.device))
+        self._peer('compare', other, AccumulatedCloud)
         if other.voxel_size != self.voxel_size:
             raise ValueError('compare: voxel sizes %r and %r differ; regrid() one map onto the other\'s grid first' % (self.voxel_size, other.voxel_size))
-        max_distance = self.voxel_size if max_distance is None else float(max_distance)
-        if not 0.0 < max_distance <= self.voxel_size:
-            raise ValueError('max_distance must lie in (0, voxel_size = %r], got %r' % (self.voxel_size, max_distance))
+        max_distance = _max_distance(max_distance, self.voxel_size)
         min_count = self._filter_args(min_count, max_moving_fraction)
         self._ensure()
         other._ensure()
@@ -1121,15 +1223,9 @@ class AccumulatedCloud(object):
             raise ValueError('select needs a mask over the rows of extract()')
         mask = _row_mask('select', mask)
         min_count = self._filter_args(min_count, max_moving_fraction)
-        capacity = self.capacity if capacity is None else int(capacity)
-        if capacity < max(self._n, 1):
-            raise ValueError('capacity must be at least the %d rows of the map (the result never has more), got %r' % (self._n, capacity))
-        new = AccumulatedCloud(self.voxel_size, self.device, capacity)         # checks the capacity
+        new = self._like(self.voxel_size, self._room(capacity))
         self._ensure()
         new._ensure()
-        if self._pierced is not None:
-            new._pierced = torch.zeros((capacity,), dtype=torch.int32, device=self.device)
-            new._pierce_counters = self._pierce_counters.clone()
         counters = torch.empty((native.SELECT_COUNTERS,), dtype=torch.int64, device=self.device)
         native.accum_select(self._cur, self._n, self._pierced, min_count, max_moving_fraction, mask, bool(invert), new._cur, new._pierced, counters,
                             new._state)
@@ -1158,10 +1254,7 @@ class AccumulatedCloud(object):
     # ---- persistence -------------------------------------------------------------------------------------------------------------------
     def records(self):
         """The integer records of the map as host arrays: keys [M] i64, acc [5,M] i64 (count, moving, sum q_x, sum q_y, sum q_z), stamps [2,M] i32."""
-        if self._cur is None or self._n == 0:
-            return (np.zeros((0,), np.int64), np.zeros((native.ACCUM_FIELDS, 0), np.int64), np.zeros((2, 0), np.int32))
-        keys, acc, stamps = self._cur
-        return keys[:self._n].cpu().numpy(), acc[:, :self._n].cpu().numpy(), stamps[:, :self._n].cpu().numpy()
+        return self._records()
 
     def save(self, path):
         keys, acc, stamps = self.records()
@@ -1181,26 +1274,17 @@ class AccumulatedCloud(object):
         m = keys.shape[0]
         if keys.dtype != np.int64 or acc.dtype != np.int64 or stamps.dtype != np.int32 or acc.shape != (native.ACCUM_FIELDS, m) or stamps.shape != (2, m):
             raise ValueError('%s does not hold the records of an AccumulatedCloud' % path)
-        if m and (np.any(keys[1:] <= keys[:-1]) or keys[0] < 0):
-            raise ValueError('%s: the keys are not ascending' % path)
+        cls._ascending(path, keys)
         if (pierced is None) != (counters is None) or (pierced is not None and (pierced.dtype != np.int32 or pierced.shape != (m,) or counters.dtype != np.int64
                                                                                  or counters.shape != (native.PIERCE_COUNTERS,))):
             raise ValueError('%s does not hold the ray counts of an AccumulatedCloud' % path)
-        capacity = 64
-        while capacity < m:
-            capacity *= 2
-        self = cls(voxel_size, device, capacity)
-        self._ensure()
-        if m:
-            self._cur[0][:m] = torch.from_numpy(keys).to(self.device)
-            self._cur[1][:, :m] = torch.from_numpy(acc).to(self.device)
-            self._cur[2][:, :m] = torch.from_numpy(stamps).to(self.device)
+        self = cls._from_records((keys, acc, stamps), voxel_size, device)
         host = [0] * native.ACCUM_STATE_WORDS
         host[native.ACCUM_NUM_VOXELS], host[native.ACCUM_DROPPED] = m, dropped
         self._state.copy_(torch.tensor(host, dtype=torch.int64))
-        self._n, self._dropped = m, dropped
+        self._dropped = dropped
         if pierced is not None:
-            self._pierced = torch.zeros((capacity,), dtype=torch.int32, device=self.device)
+            self._pierced = torch.zeros((self.capacity,), dtype=torch.int32, device=self.device)
             self._pierced[:m] = torch.from_numpy(pierced).to(self.device)
             self._pierce_counters = torch.from_numpy(counters).to(self.device)
         return self
@@ -1217,56 +1301,32 @@ def _observed_tables(capacity, device):
             torch.empty((2, capacity), dtype=torch.int32, device=device))
 
 
-def _voxel_keys(coords):
-    """coords [V,3] integers, every index in [-2^20, 2^20) -> C4's keys [V] i64."""
-    c = coords.to(torch.int64)
-    return ((c[:, 0] + native.ACCUM_IDX_BIAS) << 42) | ((c[:, 1] + native.ACCUM_IDX_BIAS) << 21) | (c[:, 2] + native.ACCUM_IDX_BIAS)
-
-
 _OBSERVE_COUNTERS = ('walked', 'dropped', 'skipped', 'truncated', 'visits')
 UNKNOWN, FREE, OCCUPIED = 0, 1, 2                                  # occupancy()'s three states
 
 
-class ObservedSpace(object):
+class ObservedSpace(_VoxelTable):
     """Where the sensor looked and found nothing: the voxels that measured rays crossed, as a second sorted table on the device (include/pcacc.h C14,
     DESIGN.md section 9n).  Per voxel the number of rays that crossed it and the first / last stamp of the calls in which one did.  With an
     AccumulatedCloud on the same grid a voxel is OCCUPIED, FREE or UNKNOWN (occupancy()); its own lookup() works at any voxel size, so free space may
     be kept coarser than the cloud.  All integers: the table is a function of the set of (ray, stamp) pairs it was given.  No CPU path."""
 
+    _tables, _state_words, _noun = staticmethod(_observed_tables), native.OBSERVE_STATE_WORDS, 'table'
+
     def __init__(self, voxel_size, device='cuda', capacity=1 << 20, visit_budget=1 << 26):
-        voxel_size = float(voxel_size)
-        if not (voxel_size > 0.0 and np.isfinite(voxel_size)):
-            raise ValueError('voxel_size must be a positive finite number, got %r' % voxel_size)
-        if not 1 <= int(capacity) <= native.ACCUM_MAX_CAPACITY:
-            raise ValueError('capacity must lie in [1, 2^30], got %r' % capacity)
+        super(ObservedSpace, self).__init__(voxel_size, device, capacity)
         if not 1 <= int(visit_budget) < native.OBSERVE_MAX_VISITS:
             raise ValueError('visit_budget must lie in [1, 2^31), got %r' % visit_budget)
-        self.voxel_size = voxel_size
-        self.device = torch.device(device)
-        self.capacity = int(capacity)
         self.visit_budget = int(visit_budget)
-        self._cur = self._alt = self._state = None           # device memory is taken at the first observe
-        self._n = 0
         self._counters = [0] * len(_OBSERVE_COUNTERS)
         self.splits = 0                                      # times a call's rays had to be cut for the visit budget, since clear()
         self.dropped_rows = 0                                # of a table that regrid() made: the rows that left the grid under the pose
 
     # ---- state -------------------------------------------------------------------------------------------------------------------------
     @property
-    def num_voxels(self):
-        return self._n
-
-    @property
     def counters(self):
         """{'walked', 'dropped', 'skipped', 'truncated', 'visits'}: rays and visited voxels of every observe since clear(), Python integers."""
         return dict(zip(_OBSERVE_COUNTERS, self._counters))
-
-    def _ensure(self):
-        if self.device.type != 'cuda':
-            raise native.NativeError('ObservedSpace lives on the GPU (got device %s); the HIP path has no CPU fallback' % self.device)
-        if self._cur is None:
-            self._cur = _observed_tables(self.capacity, self.device)
-            self._state = torch.zeros((native.OBSERVE_STATE_WORDS,), dtype=torch.int64, device=self.device)
 
     def _write_state(self):
         host = [0] * native.OBSERVE_STATE_WORDS
@@ -1280,8 +1340,6 @@ class ObservedSpace(object):
         self.splits = 0
         if self._state is not None:
             self._state.zero_()
-
-    _pose = AccumulatedCloud._pose
 
     # ---- observe -----------------------------------------------------------------------------------------------------------------------
     def observe(self, points, origins, origin_index=None, pose=None, moving=None, stamp=0, margin=None, max_range=None, max_steps=4096):
@@ -1297,17 +1355,13 @@ class ObservedSpace(object):
         _scan_rows('observe', 'origin_index', origin_index, n)
         origins = _origins(origins)
         margin = 2.0 * self.voxel_size if margin is None else float(margin)
-        if not (margin >= 0.0 and np.isfinite(margin)):
-            raise ValueError('margin must be a finite number >= 0, got %r' % margin)
-        if max_range is not None and not float(max_range) >= 0.0:
-            raise ValueError('max_range must be >= 0 or None, got %r' % max_range)
+        _margin(margin)
+        _max_range(max_range)
         max_steps = int(max_steps)
-        if not 1 <= max_steps <= native.PIERCE_MAX_STEPS:
-            raise ValueError('max_steps must lie in [1, 2^16], got %r' % max_steps)
+        _max_steps(max_steps, native.PIERCE_MAX_STEPS)
         if self.visit_budget < max_steps:
             raise ValueError('visit_budget %d is below max_steps %d: a single ray must fit' % (self.visit_budget, max_steps))
-        if not -0x80000000 <= int(stamp) <= 0x7fffffff:
-            raise ValueError('stamp must fit 32 bits, got %r' % stamp)
+        _stamp32('stamp', stamp)
         pose = self._pose(pose)
         if n == 0:
             return self
@@ -1333,28 +1387,15 @@ class ObservedSpace(object):
     def _observe_rows(self, pts, mv, org, idx, pose, stamp, margin, max_range, max_steps):
         """One run of rays through the double-the-tables loop of add().  -> 0, or the visits of a run that exceeds the budget (nothing has changed)."""
         visit_capacity = min(self.visit_budget, pts.shape[0] * max_steps)
-        out_cap = self.capacity
-        while True:
-            if self._alt is None or self._alt[0].shape[0] != out_cap:
-                self._alt = None                                   # release before taking the larger tables
-                self._alt = _observed_tables(out_cap, self.device)
+
+        def attempt(capacity):
             native.accum_observe(pts, mv, org, idx, pose, stamp, self.voxel_size, margin, max_range, max_steps, visit_capacity, self._cur, self._n, self._alt,
                                  self._state)
             state = self._state.tolist()                           # the one read-back of an attempt
-            status = state[native.OBSERVE_STATUS]
-            if status == native.ACCUM_OK:
-                break
-            if status == native.OBSERVE_TOO_MANY:
-                return state[native.OBSERVE_NEEDED_VISITS]
-            if status != native.ACCUM_TOO_SMALL:
-                raise native.NativeError('accum_observe: the state words do not describe the table (status %d)' % status)
-            need = state[native.OBSERVE_NEEDED]
-            if need > native.ACCUM_MAX_CAPACITY:
-                raise native.NativeError('accum_observe: the table would take %d voxels, more than 2^30' % need)
-            while out_cap < need:                                  # growth by doubling; the table so far is untouched
-                out_cap = min(2 * out_cap, native.ACCUM_MAX_CAPACITY)
-        self._cur, self._alt = self._alt, self._cur
-        self.capacity = out_cap
+            return state[native.OBSERVE_STATUS], state[native.OBSERVE_NEEDED], state
+        status, state = self._grow('accum_observe', attempt, leave=(native.OBSERVE_TOO_MANY,))
+        if status == native.OBSERVE_TOO_MANY:
+            return state[native.OBSERVE_NEEDED_VISITS]
         self._n = state[native.OBSERVE_NUM_VOXELS]
         self._counters = state[native.OBSERVE_WALKED:native.OBSERVE_WALKED + len(_OBSERVE_COUNTERS)]
         return 0
@@ -1382,8 +1423,7 @@ class ObservedSpace(object):
         self._ensure()
         keys, rays, stamps = (t[..., :self._n] for t in self._cur)
         keep = rays >= min_rays
-        keys = keys[keep]
-        coords = torch.stack([(keys >> 42) & 0x1fffff, (keys >> 21) & 0x1fffff, keys & 0x1fffff], 1) - native.ACCUM_IDX_BIAS
+        coords = _voxel_coords(keys[keep])
         centers = ((coords.to(torch.float64) + 0.5) * self.voxel_size).to(torch.float32)
         return {'coords': coords.to(torch.int32), 'centers': centers, 'rays': rays[keep], 't_first': stamps[0][keep], 't_last': stamps[1][keep]}
 
@@ -1434,10 +1474,10 @@ class ObservedSpace(object):
     def forget(self, before_stamp=None, box=None):
         """Rows leave the table: those whose last stamp is below before_stamp and those whose voxel lies outside box = (lo [3], hi [3]), metres, both
         faces' voxels included (prune()'s rule).  The order of the rows that stay is preserved.  -> the number kept."""
-        if before_stamp is not None and not -0x80000000 <= int(before_stamp) <= 0x7fffffff:
-            raise ValueError('before_stamp must fit 32 bits, got %r' % before_stamp)
+        if before_stamp is not None:
+            _stamp32('before_stamp', before_stamp)
         if box is not None:
-            box = AccumulatedCloud._box_indices(self, box)
+            box = self._box_indices(box)
         self._ensure()
         n = self._n
         keys, rays, stamps = self._cur
@@ -1445,10 +1485,9 @@ class ObservedSpace(object):
         if before_stamp is not None:
             keep &= stamps[1, :n] >= int(before_stamp)
         if box is not None:
-            k = keys[:n]
-            for shift, lo, hi in zip((42, 21, 0), box[0], box[1]):
-                c = ((k >> shift) & 0x1fffff) - native.ACCUM_IDX_BIAS
-                keep &= (c >= lo) & (c <= hi)
+            coords = _voxel_coords(keys[:n])
+            for axis, (lo, hi) in enumerate(zip(*box)):
+                keep &= (coords[:, axis] >= lo) & (coords[:, axis] <= hi)
         kept = int(keep.sum())                                     # the one read-back
         if kept != n:
             keys[:kept], rays[:kept] = keys[:n][keep], rays[:n][keep]
@@ -1461,23 +1500,12 @@ class ObservedSpace(object):
     def copy(self):
         """An independent clone: device copies of the rows in use and of the state words, the counters and visit_budget; its `splits` start at 0.
         merge() mutates its space, so `c = a.copy(); c.merge(b)` keeps a."""
-        c = ObservedSpace(self.voxel_size, self.device, self.capacity, self.visit_budget)
-        c._n, c._counters = self._n, list(self._counters)
-        if self._cur is not None:
-            c._ensure()
-            n = self._n
-            for dst, src in zip(c._cur, self._cur):
-                dst[..., :n].copy_(src[..., :n])
-            c._state.copy_(self._state)
+        c = self._copy_rows(ObservedSpace(self.voxel_size, self.device, self.capacity, self.visit_budget))
+        c._counters = list(self._counters)
         return c
 
     def _regrid(self, pose, voxel_size, capacity):
-        if pose is None and voxel_size is None:
-            raise ValueError('regrid needs a pose, a voxel_size or both')
-        voxel_size = self.voxel_size if voxel_size is None else float(voxel_size)
-        capacity = self.capacity if capacity is None else int(capacity)
-        if capacity < max(self._n, 1):
-            raise ValueError('capacity must be at least the %d rows of the table (the result never has more), got %r' % (self._n, capacity))
+        voxel_size, capacity = self._regrid_args(pose, voxel_size, capacity)
         new = ObservedSpace(voxel_size, self.device, capacity, self.visit_budget)      # checks voxel_size and capacity
         pose = self._pose(pose)
         self._ensure()
@@ -1513,13 +1541,7 @@ class ObservedSpace(object):
         The capacity grows as in observe().  -> {'rows', 'shared', 'new', 'dropped_rows'}: rows of this table after the call, voxels both held,
         voxels only `other` held, rows the regrid dropped -- Python integers, one read-back of the counters per attempt.  An empty `other` changes
         nothing."""
-        if not isinstance(other, ObservedSpace):
-            raise TypeError('merge takes an ObservedSpace, got %s' % type(other).__name__)
-        if _device_key(other.device) != _device_key(self.device):
-            raise ValueError('merge: the maps live on %s and %s; save() / load() carries a map across' % (self.device, other.device))
-        if pose is None and other.voxel_size != self.voxel_size:
-            raise ValueError('merge: voxel sizes %r and %r differ; give pose= (np.eye(4) keeps the frame) or regrid() the other map first'
-                             % (self.voxel_size, other.voxel_size))
+        self._merge_args(other, pose, ObservedSpace)
         pose = self._pose(pose)
         self._ensure()
         other._ensure()
@@ -1530,25 +1552,12 @@ class ObservedSpace(object):
             other = other._regrid(pose, self.voxel_size, None)
             res['dropped_rows'] = other.dropped_rows
         counters = torch.empty((native.OBSERVED_MERGE_COUNTERS,), dtype=torch.int64, device=self.device)
-        out_cap = self.capacity
-        while True:
-            if self._alt is None or self._alt[0].shape[0] != out_cap:
-                self._alt = None                                   # release before taking the larger tables
-                self._alt = _observed_tables(out_cap, self.device)
+
+        def attempt(capacity):
             native.accum_observed_merge(self._cur, self._n, other._cur, other._n, other._state, self._alt, counters, self._state)
             host = counters.tolist()                               # the one read-back of an attempt
-            status = host[native.OBSERVED_MERGE_STATUS]
-            if status == native.ACCUM_OK:
-                break
-            if status != native.ACCUM_TOO_SMALL:
-                raise native.NativeError('accum_observed_merge: the state words do not describe the tables (status %d)' % status)
-            need = host[native.OBSERVED_MERGE_NEEDED]
-            if need > native.ACCUM_MAX_CAPACITY:
-                raise native.NativeError('accum_observed_merge: the table would take %d voxels, more than 2^30' % need)
-            while out_cap < need:                                  # growth by doubling; both tables are untouched
-                out_cap = min(2 * out_cap, native.ACCUM_MAX_CAPACITY)
-        self._cur, self._alt = self._alt, self._cur                # the table before the merge stays in self._alt, which the next observe overwrites
-        self.capacity = out_cap
+            return host[native.OBSERVED_MERGE_STATUS], host[native.OBSERVED_MERGE_NEEDED], host
+        host = self._grow('accum_observed_merge', attempt, described='tables')[1]
         self._n = host[native.OBSERVED_MERGE_NEEDED]
         self._counters = [a + b for a, b in zip(self._counters, other._counters)]
         res.update(rows=self._n, shared=host[native.OBSERVED_MERGE_SHARED], new=host[native.OBSERVED_MERGE_NEW])
@@ -1557,10 +1566,7 @@ class ObservedSpace(object):
     # ---- persistence -------------------------------------------------------------------------------------------------------------------
     def records(self):
         """The integer columns as host arrays: keys [M] i64, rays [M] i64, stamps [2,M] i32."""
-        if self._cur is None or self._n == 0:
-            return np.zeros((0,), np.int64), np.zeros((0,), np.int64), np.zeros((2, 0), np.int32)
-        keys, rays, stamps = self._cur
-        return keys[:self._n].cpu().numpy(), rays[:self._n].cpu().numpy(), stamps[:, :self._n].cpu().numpy()
+        return self._records()
 
     def save(self, path):
         keys, rays, stamps = self.records()
@@ -1575,18 +1581,9 @@ class ObservedSpace(object):
         if keys.dtype != np.int64 or rays.dtype != np.int64 or stamps.dtype != np.int32 or counters.dtype != np.int64 or keys.ndim != 1 \
                 or rays.shape != (m,) or stamps.shape != (2, m) or counters.shape != (len(_OBSERVE_COUNTERS),):
             raise ValueError('%s does not hold the columns of an ObservedSpace' % path)
-        if m and (np.any(keys[1:] <= keys[:-1]) or keys[0] < 0):
-            raise ValueError('%s: the keys are not ascending' % path)
-        capacity = 64
-        while capacity < m:
-            capacity *= 2
-        self = cls(voxel_size, device, capacity)
-        self._ensure()
-        if m:
-            self._cur[0][:m] = torch.from_numpy(keys).to(self.device)
-            self._cur[1][:m] = torch.from_numpy(rays).to(self.device)
-            self._cur[2][:, :m] = torch.from_numpy(stamps).to(self.device)
-        self._n, self._counters = m, [int(v) for v in counters]
+        cls._ascending(path, keys)
+        self = cls._from_records((keys, rays, stamps), voxel_size, device)
+        self._counters = [int(v) for v in counters]
         self._write_state()
         return self
 
